@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- walker-steps/s of the stretch-move ensemble step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[1], SURVEY.md 8d "C2"): 16 384 walkers x 32 dims, correlated Gaussian
 log-posterior (Sigma_ij = 0.5^|i-j|, dense 32x32 precision matrix), fp64, StretchMove, seed = rank.
@@ -10,6 +10,10 @@ slicing interval 100, stored steps downloaded to the host inside the timed regio
 resident in HBM).  For N > 1 every rank runs its own independent chain of the same size on its own GPU
 (BASELINE.json configs[3]: no data-path collective; weak scaling); the value is the sum over ranks
 divided by the slowest rank's time.
+
+A plain run sets up, warms up, times the K steps and prints the line; with --dump-outputs DIR it also writes what the
+last timed step returned (see dump_outputs).  Everything below that takes runs of its own (cpu_baseline, secondary, the
+live counter passes of roofline.traffic, the split leg of several ranks) is measured only with --full.
 
 The JSON line also carries
   roofline      achieved HBM bytes/s of the dominant kernel: algorithmic bytes per step-kernel launch
@@ -199,7 +203,7 @@ def live_counter_traffic(kernel_sub, seconds_per_pass=60.0):
             for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
                 env.pop(k, None)
             cmd = [prof, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", out, "--", sys.executable, os.path.abspath(__file__),
-                   "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-secondary", "--no-live-counters"]
+                   "--steps", "2", "--warmup", "1"]
             child = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
             try:
                 rc = child.wait(timeout=seconds_per_pass)
@@ -494,6 +498,29 @@ def bench_split(args, rank, local_rank, world, dist, torch, capi):
         dist.destroy_process_group()
 
 
+DUMP_BYTES = 60 * 2**20  # --dump-outputs: the files together stay below 64 MB
+
+
+def dump_outputs(directory, chain, acc):
+    """--dump-outputs: what the last timed step returned to its caller, as float64 .npy files: the accepted count of every
+    ensemble step (accepted.npy) and the stored steps (chain.npy, [stored step][walker][param]).  When the stored steps
+    exceed the size limit, chain.npy holds a fixed sample of walkers (seed 0, ascending) and chain_walkers.npy lists them."""
+    os.makedirs(directory, exist_ok=True)
+    budget = DUMP_BYTES
+    if acc is not None:
+        acc = np.asarray(acc, dtype=np.float64)
+        np.save(os.path.join(directory, "accepted.npy"), acc)
+        budget -= acc.nbytes
+    if chain is not None:
+        n_saved, W, D = chain.shape
+        keep = min(W, budget // (n_saved * D * 8 + 8))
+        if keep < W:
+            walkers = np.sort(np.random.default_rng(0).choice(W, size=keep, replace=False))
+            np.save(os.path.join(directory, "chain_walkers.npy"), walkers.astype(np.float64))
+            chain = chain[:, walkers, :]
+        np.save(os.path.join(directory, "chain.npy"), np.asarray(chain, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -536,9 +563,21 @@ def main():
     ap.add_argument("--split-leg-seconds", type=float, default=45.0, help="several ranks: time limit of that measurement")
     ap.add_argument("--calc", default="dense", choices=["dense", "iso", "rosenbrock"],
                     help="experiments only: the headline workload is the dense (correlated) Gaussian")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline, the secondary configurations, the live counter "
+                         "passes and, with several ranks, the split leg (each still subject to its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (rank 0) as DIR/<name>.npy in float64")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 20 if args.mode == "split" else 500
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.mode != "chains":
+        ap.error("--dump-outputs: --mode chains only")
+    if not args.full:
+        # a plain run measures the headline only
+        args.no_cpu_baseline = args.no_secondary = args.no_live_counters = args.no_split_leg = True
 
     if args.loopback_ranks > 0 or os.environ.get("MCMCPP_BENCH_SPLIT_LEG") == "loopback":
         # (before the library binds its collectives, i.e. before the first handle with a communicator)
@@ -633,13 +672,15 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        _, acc = bench_step()
+        chain, acc = bench_step()
         accepted += int(acc.sum()) if acc is not None else 0
         ms, nl = sampler.last_run_timing()
         gpu_ms += ms
         launches += nl
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, chain, acc)
 
     from mcmcpp_amd import distributed as md
     walker_steps = float(W) * args.batch * args.steps

@@ -71,3 +71,26 @@ def test_numa_binding_helper(tmp_path, monkeypatch):
     (dev / "numa_node").write_text("-1\n")
     assert "no NUMA node" in bench.bind_to_gpu_numa_node(Torch, 0, sysfs=str(tmp_path))
     assert bench.bind_to_gpu_numa_node(Torch, 0, sysfs=str(tmp_path / "nowhere")).startswith("unchanged")
+
+
+def test_dump_outputs(tmp_path):
+    """--dump-outputs on the headline's shapes: float64 files below 64 MB in all, the same walker sample every time, and
+    every walker of a chain that fits."""
+    import numpy as np
+    chain = np.arange(20 * 16384 * 32, dtype=np.float64).reshape(20, 16384, 32)
+    acc = np.arange(2000, dtype=np.uint32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), chain, acc)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["accepted.npy", "chain.npy", "chain_walkers.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64e6
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    walkers = np.load(tmp_path / "a" / "chain_walkers.npy").astype(np.int64)
+    assert np.all(np.diff(walkers) > 0) and walkers[0] >= 0 and walkers[-1] < 16384
+    assert np.array_equal(np.load(tmp_path / "a" / "chain.npy"), chain[:, walkers, :])
+    assert np.array_equal(np.load(tmp_path / "a" / "accepted.npy"), acc)
+    bench.dump_outputs(str(tmp_path / "c"), chain[:, :64], None)
+    assert os.listdir(tmp_path / "c") == ["chain.npy"]
+    assert np.array_equal(np.load(tmp_path / "c" / "chain.npy"), chain[:, :64])

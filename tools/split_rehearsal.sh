@@ -18,10 +18,10 @@ python bench.py --no-live-counters --mode split --loopback-ranks 2 --split-walke
 find /tmp/prof_split -name "*kernel_stats.csv" -exec cp {} $OUT/r03_split_loopback8_kernel_stats.csv \;
 for N in 2 4; do
   MCMCPP_BENCH_BACKEND=gloo MCMCPP_BENCH_SPLIT_LEG=loopback MCMCPP_BENCH_NUMA_BIND=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-    --master-addr 127.0.0.1 --master-port 2961$N bench.py --gpus $N --steps 20 --warmup 2 > $OUT/r03_rehearsal_chains_plus_split_gloo_N$N.json 2> $OUT/r03_rehearsal_N$N.err
+    --master-addr 127.0.0.1 --master-port 2961$N bench.py --full --gpus $N --steps 20 --warmup 2 > $OUT/r03_rehearsal_chains_plus_split_gloo_N$N.json 2> $OUT/r03_rehearsal_N$N.err
 done
 MCMCPP_BENCH_BACKEND=gloo MCMCPP_BENCH_NUMA_BIND=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29617 bench.py --gpus 2 --steps 20 --warmup 2 > $OUT/r03_rehearsal_children_fail_N2.json 2> $OUT/r03_rehearsal_children_fail_N2.err
+    --master-addr 127.0.0.1 --master-port 29617 bench.py --full --gpus 2 --steps 20 --warmup 2 > $OUT/r03_rehearsal_children_fail_N2.json 2> $OUT/r03_rehearsal_children_fail_N2.err
 # (the id's bootstrap listener lives in the process that made the id: the parent stays alive while its child joins, as in bench.py)
 python - > $OUT/r03_split_child_rank.json 2> $OUT/r03_split_child_rank.err <<'PY'
 import subprocess, sys
