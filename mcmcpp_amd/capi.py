@@ -44,7 +44,7 @@ COMM_ID_BYTES = 128
 
 
 def library_path():
-    # MCMCPP_HIP_LIB: diagnostics only (e.g. the in-kernel-stamp build libmcmcpp_hip_stamps.so)
+    # MCMCPP_HIP_LIB: load another build of the library instead (e.g. to compare two builds in one job)
     return os.environ.get("MCMCPP_HIP_LIB") or os.path.join(_HERE, "libmcmcpp_hip.so")
 
 

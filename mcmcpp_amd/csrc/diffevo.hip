@@ -31,6 +31,7 @@ public:
 
     int init(const mcmcpp_hip_config& c)
     {
+        const Knobs knobs = Knobs::from_environment();
         W = c.num_walkers;
         D = c.num_params;
         n = W / 2;
@@ -49,13 +50,11 @@ public:
         walkers_per_block = (64 / lpw) * kWavesPerBlock;
         {
             // the dense Gaussian's product on the matrix cores (de_update_mfma_kernel): fp64, even D, 8 walkers per wavefront
-            const char* v = std::getenv("MCMCPP_HIP_MATRIX_CORE_MIN_WALKERS");
-            const long mc_min = (v && *v) ? std::strtol(v, nullptr, 10) : 0;
+            const long mc_min = knobs.matrix_core_min_walkers;
             if (table->de_update_mc[0][lpw_log][epl_shift] && c.calc_id == MCMCPP_HIP_CALC_DENSE_GAUSSIAN && D % 2 == 0 && D <= 32 && mc_min >= 0 && n >= mc_min)
             {
                 // 16 walkers per wavefront once the chip is full (as the stretch kernels: MCMCPP_HIP_MATRIX_CORE_4PASS_WALKERS)
-                const char* v4 = std::getenv("MCMCPP_HIP_MATRIX_CORE_4PASS_WALKERS");
-                const long four_pass = (v4 && *v4) ? std::strtol(v4, nullptr, 10) : 32768;
+                const long four_pass = knobs.matrix_core_4pass.value_or(32768);
                 const int big = n >= four_pass ? 1 : 0;
                 update_fn = table->de_update_mc[big][lpw_log][epl_shift];
                 walkers_per_block = (big ? 16 : 8) * kWavesPerBlock;
@@ -85,20 +84,9 @@ public:
             own_stream = true;
         }
 
-        {
-            const char* v = std::getenv("MCMCPP_HIP_DE_SCAN_RUN");  // stream positions one scanning lane steps through
-            scan_run = (v && *v) ? (int)std::strtol(v, nullptr, 10) : kDeScanRun;
-            if (scan_run < 1) scan_run = 1;
-            v = std::getenv("MCMCPP_HIP_DE_BATCH");  // half-steps planned together
-            batch_max = (v && *v) ? (int)std::strtol(v, nullptr, 10) : kDeBatchMax;
-#ifdef MCMCPP_DE_TIMING_DIAGNOSTICS
-            // Experiment builds only (make VARIANT=detiming EXTRA=-DMCMCPP_DE_TIMING_DIAGNOSTICS): launches left out to time
-            // the others -- THE CHAIN IS WRONG: 1 = the update launches alone, 2 = the planning launches alone, 3 / 4 / 5 = the
-            // boundary without its records / resolve / scan.  The library that ships has no such switch.
-            v = std::getenv("MCMCPP_HIP_DE_DEBUG");
-            knob_debug = (v && *v) ? (int)std::strtol(v, nullptr, 10) : 0;
-#endif
-        }
+        scan_run = (int)knobs.de_scan_run.value_or(kDeScanRun);
+        if (scan_run < 1) scan_run = 1;
+        batch_max = (int)knobs.de_batch.value_or(kDeBatchMax);
         // the batch: as many half-steps as the position counters (32 bits), the resolver's lists and a sensible amount of
         // record memory (256 MiB) allow
         const unsigned per = (unsigned)D + 3u;
@@ -441,12 +429,7 @@ public:
             const uint64_t h = h0 + (uint64_t)i;
             const uint64_t b = h / (uint64_t)batch_max;
             const int j = (int)(h % (uint64_t)batch_max);
-            if (j == 0 && knob_debug != 1)
-            {
-                // (timing diagnostics 3 / 4 / 5: the boundary without its records / without its resolve / without its scan)
-                launch_boundary(knob_debug == 4 ? -1 : (long long)b + 1, knob_debug == 3 ? -1 : (long long)b, knob_debug == 5 ? -1 : (long long)b + 2);
-            }
-            if (knob_debug >= 2) continue;
+            if (j == 0) launch_boundary((long long)b + 1, (long long)b, (long long)b + 2);
             l.recs = d_recs + (size_t)j * (size_t)n;
             l.color = (int)(h & 1);
             l.step = i >> 1;
@@ -628,7 +611,6 @@ public:
         HIP_TRY(hipStreamSynchronize(stream));
         return MCMCPP_HIP_OK;
     }
-    int debug_stamps(unsigned long long*) override { return unsupported("debug_stamps"); }
 
 private:
     int unsupported(const char* what) { return fail(MCMCPP_HIP_E_UNSUPPORTED, "%s: not available with the differential-evolution mover", what); }
@@ -670,7 +652,7 @@ private:
     DeRec<T>* d_recs = nullptr;
     DeRunInfo* d_run = nullptr;
     DeArgs<T> args;
-    int update_blocks = 0, partial_waves = 0, graph_steps = 128, replay_steps_max = 128, knob_debug = 0;
+    int update_blocks = 0, partial_waves = 0, graph_steps = 128, replay_steps_max = 128;
     int resolve_capacity = 0, scan_blocks = 0;
     bool primed = false;    // batches 0 and 1 planned behind the last set_state
     Affine128 batch_jump;   // (D+3) * n * batch_max draws

@@ -34,10 +34,7 @@ namespace mcmcpp
 {
 
 constexpr uint32_t kRowMovedBit = 0x80000000u;  // in n_accept[w]: the walker's row in the other position buffer is out of date
-#ifndef MCMCPP_FULL_DRAW_WAVES
-#define MCMCPP_FULL_DRAW_WAVES 4
-#endif
-constexpr int kFullDrawWaves = MCMCPP_FULL_DRAW_WAVES;  // extra wavefronts of a full-step workgroup: 4 = next red draws (2), next black draws (2); 2 = one per colour
+constexpr int kFullDrawWaves = 4;  // extra wavefronts of a full-step workgroup: next red draws (2), next black draws (2)
 
 // Hands the random stream and the step counters to the next full-step launch (one lane of the whole grid).
 template <class T>
@@ -66,8 +63,8 @@ __device__ __forceinline__ void full_step_draw_wave(const HalfStepArgs<T>& a, co
                                                     bool block_barrier, DrawRec<T>* dn_red, int n, int sh_begin, int sh_count, int wpb, int which, int lane,
                                                     int run_behind_ctl = -1, int ctl_chain = 0)
 {
-    const int black = kFullDrawWaves == 4 ? which >> 1 : which, half = kFullDrawWaves == 4 ? (which & 1) : 0;
-    const int h0 = kFullDrawWaves == 4 ? (wpb + 1) / 2 : wpb;  // walkers of the first half
+    const int black = which >> 1, half = which & 1;
+    const int h0 = (wpb + 1) / 2;  // walkers of the first half
     DrawRec<T>* const dst = black ? dn_red + n : dn_red;
     // (the first of them also forwards this launch's slice of the last stored step: trickle_stored_step)
     draw_wave_body<T, 1>(a, tab, ctl_ptr, block_barrier, dst, dst, 1, sh_begin, sh_count, blockIdx.x * wpb + half * h0, half ? wpb - h0 : h0, lane, black != 0,
@@ -135,12 +132,6 @@ stretch_full_step_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b, T* h
     T* sh_stage = reinterpret_cast<T*>(smem + LdsLayout<T, Calc, EPL>::stage_offset());
     T* sh_block = reinterpret_cast<T*>(smem + LdsLayout<T, Calc, EPL>::block_offset());
 
-#ifdef MCMCPP_STAMPS
-    unsigned long long stamp_val[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    stamp_val[6] = __builtin_amdgcn_s_memrealtime();
-#endif
-    MCMCPP_STAMP(0);
-    MCMCPP_STAMP_BLOCK(0);
     const int lane = threadIdx.x & 63;
     const int wib = threadIdx.x >> 6;
     if (wib >= kWavesPerBlock)
@@ -204,7 +195,6 @@ stretch_full_step_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b, T* h
         load_slice_as<T, EPL, false>(pin + (size_t)jx * h_dims, i0, h_dims, active, own_x);
         load_slice_as<T, EPL, false>(pin + (size_t)(h_n + (int)rec_b.partner2) * h_dims, i0, h_dims, active, par_x);
     }
-    MCMCPP_STAMP(1);  // first round trip landed, second issued
     // Every scalar miss of this wavefront is taken here, in one batch whose wait overlaps the second round trip: the
     // control and run records (preloaded pointers) and all lines of the launch description (cold misses of the order of
     // a microsecond each; issued one by one where first needed they delayed the calculator by about that much).
@@ -251,7 +241,6 @@ stretch_full_step_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b, T* h
             compute_draw<T>(a, c ? base_b : ctl.state2, j_a, j_b, direct, k, (c ? dn_blk : dn_red) + i, c != 0, ctl.state2);
         }
     }
-    MCMCPP_STAMP(2);
 
     // One StretchMove::updateWalker (StretchMove.h:100-123) in two parts: the proposal, then calculator + accept test.
     auto propose = [&](const T (&own)[EPL], const T (&par)[EPL], const DrawRec<T>& rec, T (&prop)[EPL]) {
@@ -309,25 +298,14 @@ stretch_full_step_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b, T* h
     T new_x[EPL], fin[EPL];
     T lp_x_new, lp_fin;
     finish(own_x, prop_x, rec_x, lp_x, false, new_x, lp_x_new);
-    MCMCPP_STAMP(3);  // second round trip landed, partner's update repeated
     T prop_b[EPL];
     propose(own_b, new_x, rec_b, prop_b);
     // ---- the group's red walker: its row goes out now and drains while the black update computes ----
     const bool acc_r = finish(own_r, prop_r, rec_r, lp_r, true, fin, lp_fin) && active;
     commit(ir, fin, lp_fin, acc_r, nacc_r);
-    MCMCPP_STAMP(4);  // red update done, its stores issued
     const bool acc_b = finish(own_b, prop_b, rec_b, lp_b, true, fin, lp_fin) && active;
     commit(h_n + ir, fin, lp_fin, acc_b, nacc_b);
 
-    MCMCPP_STAMP(5);
-    MCMCPP_STAMP_BLOCK(1);
-#ifdef MCMCPP_STAMPS
-    if (a.stamps != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
-    {
-        stamp_val[7] = __builtin_amdgcn_s_memrealtime();
-        for (int k = 0; k < 8; ++k) a.stamps[k] = stamp_val[k];
-    }
-#endif
     const unsigned acc_red = (unsigned)__popcll(__ballot(acc_r && sub == 0));
     const unsigned acc_blk = (unsigned)__popcll(__ballot(acc_b && sub == 0));
     if (a.partials != nullptr && run.accepted_per_step != nullptr && lane == 0)
@@ -392,12 +370,6 @@ stretch_full_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b,
     T* sh_x = reinterpret_cast<T*>(smem) + (threadIdx.x >> 6) * ((2 * NW + kSecondTileRows) * kMcXS);
 
     const HalfStepArgs<T>& a = rest;
-#ifdef MCMCPP_STAMPS
-    unsigned long long stamp_val[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    stamp_val[6] = __builtin_amdgcn_s_memrealtime();
-#endif
-    MCMCPP_STAMP(0);
-    MCMCPP_STAMP_BLOCK(0);
     const int h_n = hot_n;
     const int h_dims = (int)(hot_bits & 0xFFFu);
     // chain blockIdx.y of (hot_bits >> 28) + 1 (ChainGeometry): every per-chain array at its fixed stride
@@ -501,25 +473,12 @@ stretch_full_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b,
 #pragma unroll
     for (int q = 0; q < 2; ++q)
     {
-#if defined(MCMCPP_EXP_PUSH) && (MCMCPP_EXP_PUSH & 1)
-        // EXPERIMENT 3i (timing only, THE CHAIN IS WRONG): what a push scheme would read -- the rows the records point to
-        // at addresses that follow from the walker's own index (an inbox of three rows per red/black pair), so that they
-        // go out with the first round trip instead of behind it
-        const uint32_t bx = (3u * ir[q]) & (un - 1u);
-        load_row(un + bx, par_r[q]);
-        const uint32_t jx = (bx + 1u) & (un - 1u);
-        rec_x[q] = load_rec(drr_b, jx);
-        load_row(jx, own_x[q]);
-        lp_x[q] = load_lp(jx);
-        load_row(un + ((bx + 2u) & (un - 1u)), par_x[q]);
-#else
         load_row(un + rec_r[q].partner, par_r[q]);
         const uint32_t jx = rec_b[q].partner;
         rec_x[q] = load_rec(drr_b, jx);
         load_row(jx, own_x[q]);
         lp_x[q] = load_lp(jx);
         load_row(un + rec_b[q].partner2, par_x[q]);
-#endif
     }
     // The wavefront's share of P^T: 8 x 16 bytes per lane, the same 8 KiB for every wavefront (L2 hits), through a preloaded
     // pointer (no kernarg miss in front).  Behind the second trip's loads on purpose: issued with the first trip they
@@ -527,7 +486,6 @@ stretch_full_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b,
     asm volatile("" ::: "memory");
     McB<T> matB;
     mc_load_b(hot_matrix, sub, grp, matB);
-    MCMCPP_STAMP(1);
     // every scalar miss of this wavefront in one batch whose wait overlaps the second round trip (see the plain kernel)
     StepCtl ctl;
     RunInfo run;
@@ -587,7 +545,6 @@ stretch_full_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b,
             prop4[2 + q][e] = par_r[q][e] + zdr;
         }
     mc_eval<4>(matB, sh_x, sub, grp, h_dims, prop4, lp4);
-    MCMCPP_STAMP(2);  // second round trip landed, first tile done
 
     // ---- the black walkers against their partners' results ----
     T prop_b[2][2], lp_b_new[2], new_x[2], lp_dummy;
@@ -611,39 +568,16 @@ stretch_full_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b,
     {
         const bool accr = decide(q, own_r[q], prop4[2 + q], rec_r[q], lp_r[q], lp4[2 + q], true, fin, lp_fin) && active[q];
         commit(q, ir[q], fin, lp_fin, accr, nacc_r[q]);
-#if defined(MCMCPP_EXP_PUSH) && (MCMCPP_EXP_PUSH & 2)
-        // EXPERIMENT 3i: the red walker's final row pushed to the one consumer it has on average (a scattered inbox slot)
-        if (a.stamps != nullptr && col_ok) store_row_piece(reinterpret_cast<T*>(a.stamps) + (size_t)(3 * rec_r[q].partner + 1) * h_dims + i0, fin[0], fin[1]);
-#endif
         acc_red += (unsigned)__popcll(__ballot(accr && sub == 0));
     }
-    MCMCPP_STAMP(3);  // red rows decided, their stores issued
     mc_eval<2>(matB, sh_x + 2 * NW * kMcXS, sub, grp, h_dims, prop_b, lp_b_new);
-    MCMCPP_STAMP(4);  // second tile done
 #pragma unroll
     for (int q = 0; q < 2; ++q)
     {
         const bool accb = decide(q, own_b[q], prop_b[q], rec_b[q], lp_b[q], lp_b_new[q], true, fin, lp_fin) && active[q];
         commit(q, un + ir[q], fin, lp_fin, accb, nacc_b[q]);
-#if defined(MCMCPP_EXP_PUSH) && (MCMCPP_EXP_PUSH & 2)
-        // EXPERIMENT 3i: the black walker's final row pushed to the two consumers it has on average
-        if (a.stamps != nullptr && col_ok)
-        {
-            store_row_piece(reinterpret_cast<T*>(a.stamps) + (size_t)(3 * rec_b[q].partner) * h_dims + i0, fin[0], fin[1]);
-            store_row_piece(reinterpret_cast<T*>(a.stamps) + (size_t)(3 * rec_b[q].partner2 + 2) * h_dims + i0, fin[0], fin[1]);
-        }
-#endif
         acc_blk += (unsigned)__popcll(__ballot(accb && sub == 0));
     }
-    MCMCPP_STAMP(5);
-    MCMCPP_STAMP_BLOCK(1);
-#ifdef MCMCPP_STAMPS
-    if (a.stamps != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
-    {
-        stamp_val[7] = __builtin_amdgcn_s_memrealtime();
-        for (int k = 0; k < 8; ++k) a.stamps[k] = stamp_val[k];
-    }
-#endif
     if (a.partials != nullptr && run.accepted_per_step != nullptr && lane == 0)
     {
         uint32_t* p = a.partials + ((size_t)chain * (size_t)a.partial_slots + (size_t)ctl.partial_slot) * 2 * (size_t)a.partial_waves;

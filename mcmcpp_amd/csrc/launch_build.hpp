@@ -91,7 +91,7 @@ void launch_full_mfma(const HalfStepArgs<T>& a, unsigned grid, hipStream_t st)
                           ((uint32_t)(chains - 1) << 28);
     // (logp_alt == logp + W, n_accept == logp + 2 W and the run record kRunBehindCtlBytes behind the control records: the
     //  kernel derives them and takes the padded matrix and the shard bounds as preloaded arguments instead)
-    if (chains > 1 || a.chains < 0)  // (a.chains < 0: experiments -- the several-chains instantiation for one ensemble)
+    if (chains > 1)
         hipLaunchKernelGGL((stretch_full_step_mfma_kernel<T, Calc, EPL, LPW, true>), dim3(grid, chains), dim3(64 * (kWavesPerBlock + extra_waves)), lds, st, a.draws,
                            a.pos, a.pos_alt, a.logp, a.calc_params_padded, a.shard_begin, a.shard_count, a.n, bits, a.ctl_in, a);
     else

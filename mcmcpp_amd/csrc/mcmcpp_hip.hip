@@ -69,72 +69,6 @@ void parallel_memcpy(char* dst, const char* src, size_t bytes)
     for (int k = 1; k < pieces; ++k) helpers[k - 1].join();
 }
 
-long env_long(const char* name, long fallback)
-{
-    const char* v = std::getenv(name);
-    return (v && *v) ? std::strtol(v, nullptr, 10) : fallback;
-}
-
-// The library's tuning and diagnostic knobs (environment variables, DESIGN.md section 9 lists them).  Read ONCE, when a
-// handle is created; nothing on the launch path touches the environment.  Negative "unset" values mean "library default".
-struct Knobs
-{
-    long passes;                  // MCMCPP_HIP_PASSES                   walkers-per-wavefront rounds of the half-step kernels (0: chosen from the size)
-    long waves_per_simd;          // MCMCPP_HIP_WAVES_PER_SIMD           wavefronts per SIMD to reach before a wavefront takes more walkers (2)
-    long matrix_core_min_walkers; // MCMCPP_HIP_MATRIX_CORE_MIN_WALKERS  smallest shard stepped by the matrix-core kernels (0; -1: never)
-    long matrix_core_4pass;       // MCMCPP_HIP_MATRIX_CORE_4PASS_WALKERS from this many updates per launch on: 16 walkers per wavefront (18432)
-    long matrix_core_late;        // MCMCPP_HIP_MATRIX_CORE_LATE_DRAWS    from this many updates per launch on: the 16-walker wavefronts make their next draws behind the accept, four to a SIMD (49152; -1: never)
-    long full_step;               // MCMCPP_HIP_FULL_STEP                1: one launch per ensemble step for small ensembles (1)
-    long full_step_max_walkers;   // MCMCPP_HIP_FULL_STEP_MAX_WALKERS    largest ensemble stepped that way (-1: 32768; 32767 where the matrix-core
-                                  //                                     half-step kernel is the alternative)
-    long task_table_mb;           // MCMCPP_HIP_TASK_TABLE_MB            size limit of the one-entry-per-draw jump table (16)
-    long chain_subchunk_mb;       // MCMCPP_HIP_CHAIN_SUBCHUNK_MB        device chain staging per sub-chunk / ring budget (32)
-    long graph_steps;             // MCMCPP_HIP_GRAPH_STEPS              ensemble steps per hipGraph replay (-1 here: 300 up to 32768 walkers, else 128)
-    long debug_timing;            // MCMCPP_HIP_DEBUG_TIMING             1: run() prints its host-side phases to stderr
-    long trickle;                 // MCMCPP_HIP_TRICKLE                  1: stored steps forwarded to pinned memory by the launches (1)
-    long no_draw_wave;            // MCMCPP_HIP_NO_DRAW_WAVE             1: no extra draw wavefronts (0)
-    long batch_draws;             // MCMCPP_HIP_BATCH_DRAWS              ensemble steps whose draw records one launch makes ahead of the matrix-core full-step launches; 0: the launches make them themselves; -1: as many as a graph replays (-1)
-    long fill_branch;             // MCMCPP_HIP_FILL_BRANCH              > 0: the records of the NEXT graph replay are made beside this replay's step launches, in that many pieces on a parallel branch of the graph (0: one launch in line at the head of each replay)
-    long copy_stream;             // MCMCPP_HIP_COPY_STREAM              1: chain downloads on a second stream (0)
-    long pinned_direct;           // MCMCPP_HIP_PINNED_DIRECT            1: stored steps forwarded straight into a pinned chain_out (1)
-    long comm_full_step;          // MCMCPP_HIP_COMM_FULL_STEP           split ensembles: 1 = one exchange per ensemble step (1), 0 = one per half-step
-    long comm_compact;            // MCMCPP_HIP_COMM_COMPACT             split ensembles of more than one rank: 1 = exchange only the rows that moved (1), 0 = all-gather the slices
-    long comm_compact_cap;        // MCMCPP_HIP_COMM_COMPACT_CAP         slots of an exchange block (0: learned from the run; a bound that is too small costs
-                                  //                                     a repeated chunk, never a wrong chain)
-    long comm_compact_chunk;      // MCMCPP_HIP_COMM_COMPACT_CHUNK       ensemble steps between two looks at the overflow flag (256)
-    long force_multi_chain_kernels; // MCMCPP_HIP_FORCE_MC                experiments: single ensembles stepped by the several-chains instantiations (0)
-    static Knobs from_environment()
-    {
-        Knobs k;
-        k.passes = env_long("MCMCPP_HIP_PASSES", 0);
-        k.waves_per_simd = env_long("MCMCPP_HIP_WAVES_PER_SIMD", 2);
-        k.matrix_core_min_walkers = env_long("MCMCPP_HIP_MATRIX_CORE_MIN_WALKERS", 0);
-        // (measured after the round-3 rework, us per launch with 8 / 16 walkers per wavefront: 16 384 updates 5.04 / 5.23,
-        //  20 480: 7.37 / 6.57, 24 576: 7.54 / 6.63, 28 672: 9.97 / 6.72, 32 768: 10.02 / 6.78 -- profiles/r03_mc_p2_p4.txt)
-        k.matrix_core_4pass = env_long("MCMCPP_HIP_MATRIX_CORE_4PASS_WALKERS", 18432);
-        k.matrix_core_late = env_long("MCMCPP_HIP_MATRIX_CORE_LATE_DRAWS", 49152);
-        k.full_step = env_long("MCMCPP_HIP_FULL_STEP", 1);
-        k.full_step_max_walkers = env_long("MCMCPP_HIP_FULL_STEP_MAX_WALKERS", -1);
-        k.task_table_mb = env_long("MCMCPP_HIP_TASK_TABLE_MB", 16);
-        k.chain_subchunk_mb = env_long("MCMCPP_HIP_CHAIN_SUBCHUNK_MB", 32);
-        k.graph_steps = env_long("MCMCPP_HIP_GRAPH_STEPS", -1);
-        k.debug_timing = env_long("MCMCPP_HIP_DEBUG_TIMING", 0);
-        k.trickle = env_long("MCMCPP_HIP_TRICKLE", 1);
-        k.no_draw_wave = env_long("MCMCPP_HIP_NO_DRAW_WAVE", 0);
-        k.batch_draws = env_long("MCMCPP_HIP_BATCH_DRAWS", -1);
-        k.fill_branch = env_long("MCMCPP_HIP_FILL_BRANCH", 0);
-        k.copy_stream = env_long("MCMCPP_HIP_COPY_STREAM", 0);
-        k.pinned_direct = env_long("MCMCPP_HIP_PINNED_DIRECT", 1);
-        k.comm_full_step = env_long("MCMCPP_HIP_COMM_FULL_STEP", 1);
-        k.force_multi_chain_kernels = env_long("MCMCPP_HIP_FORCE_MC", 0);
-        k.comm_compact = env_long("MCMCPP_HIP_COMM_COMPACT", 1);
-        k.comm_compact_cap = env_long("MCMCPP_HIP_COMM_COMPACT_CAP", 0);
-        k.comm_compact_chunk = env_long("MCMCPP_HIP_COMM_COMPACT_CHUNK", 256);
-        if (k.comm_compact_chunk < 1) k.comm_compact_chunk = 1;
-        return k;
-    }
-};
-
 struct RegisteredCalc
 {
     const void* f64;
@@ -216,15 +150,30 @@ void launch_fill_draws_batch(const HalfStepArgs<float>& a, const StepCtl* ctl, c
     hipLaunchKernelGGL(fill_draws_batch_kernel<float>, dim3(grid, (unsigned)(2 * steps)), dim3(192), 0, stream, a, ctl, step_jump, out);
 }
 void launch_accepted_reduce(const uint32_t* partials, int partial_slots, int partial_waves, int count,
-                            const StepCtl* ctl_after, const RunInfo* run, hipStream_t stream, int chains, StepCtl* ctl_keep)
+                            const StepCtl* ctl_after, const RunInfo* run, hipStream_t stream, int chains)
 {
     hipLaunchKernelGGL(accepted_reduce_kernel, dim3((unsigned)count, (unsigned)(chains > 1 ? chains : 1)), dim3(256), 0, stream, partials, partial_slots,
-                       partial_waves, count, ctl_after, run, ctl_keep);
+                       partial_waves, count, ctl_after, run);
 }
 }  // namespace mcmcpp
 
 namespace
 {
+// The host's pinned scratch of one handle: records on their way to the device and status words on their way back.  The
+// host rewrites a slot only once the asynchronous copies that read it have been ordered (synchronised, or in the case of
+// the run records four sub-chunks of launches later: the sub-chunk loop rotates over them).
+struct PinnedScratch
+{
+    uint64_t status_out[6];                         // agree_on_status: the words every rank all-reduces
+    uint64_t status_back[6];                        // ... and what comes back
+    XStats xstats;                                  // split ensembles: the exchange statistics of the chunk in hand
+    alignas(64) StepCtl ctl;                        // write_ctl, one chain
+    alignas(64) RunInfo run[4];                     // one chain: a run's sub-chunks in turn (the split path uses [0])
+    alignas(64) StepCtl chain_ctl[kMaxChains];      // write_ctl, several chains
+    alignas(64) RunInfo chain_run[4][kMaxChains];   // several chains: [sub-chunk % 4][chain] (the trickle path uses [0], also for one chain)
+};
+static_assert(sizeof(StepCtl) <= 64 && sizeof(RunInfo) <= 64, "a control or run record is uploaded as one 64-byte line");
+
 template <class T>
 class Sampler final : public mcmcpp_hip_sampler
 {
@@ -346,7 +295,9 @@ public:
             c.calc_id == MCMCPP_HIP_CALC_DENSE_GAUSSIAN &&     // (they read the padded matrix this file prepares)
             (size_t)W * (size_t)D * sizeof(T) < (1ull << 32))  // (and address a chain's arrays with 32-bit byte offsets)
         {
-            mc_level = launch_walkers >= knobs.matrix_core_4pass ? 1 : 0;
+            // (measured after the round-3 rework, us per launch with 8 / 16 walkers per wavefront: 16 384 updates 5.04 / 5.23,
+            //  20 480: 7.37 / 6.57, 24 576: 7.54 / 6.63, 28 672: 9.97 / 6.72, 32 768: 10.02 / 6.78 -- profiles/r03_mc_p2_p4.txt)
+            mc_level = launch_walkers >= knobs.matrix_core_4pass.value_or(18432) ? 1 : 0;
             // (about as many updates as one round of wavefront slots holds at three wavefronts per SIMD, or more: four per SIMD,
             //  draws behind the accept -- profiles/r03_mc_threshold.txt)
             if (mc_level == 1 && knobs.matrix_core_late >= 0 && launch_walkers >= knobs.matrix_core_late && table->half_step_mc[2][lpw_log][epl_shift]) mc_level = 2;
@@ -467,20 +418,10 @@ public:
             d_jump_lo = reinterpret_cast<Affine128*>(piece + tables_offset_lo(n, have_task_table, K));
         }
         HIP_TRY(hipMemset(d_draws, 0, sizeof(DrawRec<T>) * (size_t)W * 2 * K));
-#if defined(MCMCPP_EXP_PUSH) && !defined(MCMCPP_STAMPS)
-        // experiment 3i (a variant build, never the library that ships): the scratch "inboxes" the pushed rows are written to
-        HIP_TRY(hipMalloc(&d_stamps, sizeof(T) * (size_t)3 * (size_t)n * (size_t)D + 4096));
-#endif
-#ifdef MCMCPP_STAMPS
-        HIP_TRY(hipMalloc(&d_stamps, kStampWords * sizeof(unsigned long long)));  // [8 stamps][2 alternating launches][start, end of 4096 workgroups | end of their draw wavefronts]
-        HIP_TRY(hipMemset(d_stamps, 0, kStampWords * sizeof(unsigned long long)));
-#endif
         HIP_TRY(hipMemset(d_logp, 0, logp_chain_stride_bytes<T>(n) * (size_t)K));
         HIP_TRY(hipMemset(d_diag, 0, sizeof(Diag)));
         HIP_TRY(hipMemset(d_ctl, 0, (size_t)kCtlChainStride * (size_t)K));
-        // pinned scratch of the host: [0, 512) as before (control record at 128, four run records from 256 on);
-        // per-chain control records from 1024, per-chain run records from 1024 + 64 * kMaxChains on
-        HIP_TRY(hipHostMalloc(&h_pinned, 1024 + 64 * kMaxChains + 4 * 64 * kMaxChains, hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc(&h_pinned, sizeof(PinnedScratch), hipHostMallocDefault));
 
         // calculator parameters (the dense Gaussian's matrix goes over transposed: see DenseGaussianFn)
         if (c.calc_params_len > 0)
@@ -551,19 +492,7 @@ public:
             batch_draws = (int)(want > 512 ? 512 : want);
             HIP_TRY(hipMalloc(&d_draws_batch, sizeof(DrawRec<T>) * (size_t)batch_draws * 2 * (size_t)n));
             HIP_TRY(hipMemset(d_draws_batch, 0, sizeof(DrawRec<T>) * (size_t)batch_draws * 2 * (size_t)n));  // (partner indices a kernel may follow)
-            // Records of the NEXT replay made beside this replay's launches (fill_pieces > 0): piece k, forked off the launch
-            // sequence behind the last step that read its record sets, refills them for the same steps of the next replay
-            // from the control record the previous replay left in d_ctl_keep (step_jump[batch_draws + j]).
-            if (knobs.fill_branch > 0 && batch_draws == graph_steps && batch_draws >= 2)
-            {
-                fill_pieces = (int)(knobs.fill_branch < batch_draws ? knobs.fill_branch : batch_draws);
-                HIP_TRY(hipStreamCreateWithFlags(&fill_stream, hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&ev_fill_fork, hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&ev_fill_join, hipEventDisableTiming));
-                HIP_TRY(hipMalloc(&d_ctl_keep, sizeof(StepCtl)));
-                HIP_TRY(hipMemset(d_ctl_keep, 0, sizeof(StepCtl)));
-            }
-            std::vector<Affine128> sj((size_t)batch_draws * (fill_pieces > 0 ? 2 : 1));
+            std::vector<Affine128> sj((size_t)batch_draws);
             for (size_t j = 0; j < sj.size(); ++j) sj[j] = pcg_jump(inc, (unsigned __int128)6 * (unsigned)n * (unsigned __int128)j);
             HIP_TRY(hipMalloc(&d_step_jump, sizeof(Affine128) * sj.size()));
             HIP_TRY(hipMemcpy(d_step_jump, sj.data(), sizeof(Affine128) * sj.size(), hipMemcpyHostToDevice));
@@ -610,7 +539,6 @@ public:
         half_steps = 0;
         steps_since_reset = 0;
         records_valid = false;
-        records_ahead_of = kNoStep;
         int rc = write_ctl(0);
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(stream));
@@ -658,7 +586,6 @@ public:
         (void)hipGetLastError();
         have_state = false;
         records_valid = false;
-        records_ahead_of = kNoStep;
         error = keep + " (the walker state on the device is no longer consistent: call set_state again)";
     }
 
@@ -673,7 +600,6 @@ public:
         last_ms = 0.0;
         last_launches = 0;
         if (total == 0) return MCMCPP_HIP_OK;
-        const bool dbg = knobs.debug_timing != 0;
         const auto tp0 = std::chrono::steady_clock::now();
 
         const size_t step_bytes = sizeof(T) * (size_t)W * D;
@@ -742,9 +668,7 @@ public:
             for (int k = 0; k < K; ++k)
             {
                 // (several chains: one record each; the upload slots rotate per sub-chunk as for one chain)
-                RunInfo* ri = K > 1 ? reinterpret_cast<RunInfo*>((char*)h_pinned + 1024 + 64 * kMaxChains + 64 * k + 64 * kMaxChains * (c % 4))
-                                    : reinterpret_cast<RunInfo*>((char*)h_pinned + 256 + 64 * (c % 4));
-                static_assert(sizeof(RunInfo) <= 64, "the pinned upload slots are 64 bytes apart");
+                RunInfo* ri = K > 1 ? &h_pinned->chain_run[c % 4][k] : &h_pinned->run[c % 4];
                 // chain k's stored steps of this sub-chunk: the k-th run of sub_saved steps of the device half
                 ri->chain = chain_out ? (void*)((char*)d_chain[buf] + step_bytes * (size_t)sub_saved * (size_t)k) : nullptr;
                 ri->accepted_per_step = accepted_per_step ? d_acc + (size_t)k * (size_t)total : nullptr;
@@ -773,19 +697,8 @@ public:
                 // the staging buffer is free: its previous content (sub-chunk c-2) was copied out below
                 // (the whole device half in one copy: with several chains, chain k's steps sit sub_saved steps apart)
                 const size_t half_used = K > 1 ? step_bytes * (size_t)sub_saved * (size_t)(K - 1) + step_bytes * (size_t)now : step_bytes * (size_t)now;
-                if (copy_stream)
-                {
-                    // the download runs beside the next sub-chunk's launches (which fill the other device half)
-                    HIP_TRY(hipEventRecord(ev_filled[buf], stream));
-                    HIP_TRY(hipStreamWaitEvent(copy_stream, ev_filled[buf], 0));
-                    HIP_TRY(hipMemcpyAsync(h_stage[buf], d_chain[buf], half_used, hipMemcpyDeviceToHost, copy_stream));
-                    HIP_TRY(hipEventRecord(ev_copied[buf], copy_stream));
-                }
-                else
-                {
-                    HIP_TRY(hipMemcpyAsync(h_stage[buf], d_chain[buf], half_used, hipMemcpyDeviceToHost, stream));
-                    HIP_TRY(hipEventRecord(ev_copied[buf], stream));
-                }
+                HIP_TRY(hipMemcpyAsync(h_stage[buf], d_chain[buf], half_used, hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipEventRecord(ev_copied[buf], stream));
                 if (pending_first >= 0)
                 {
                     HIP_TRY(hipEventSynchronize(ev_copied[pending_buf]));
@@ -841,15 +754,6 @@ public:
         host_wall_ms = std::chrono::duration<double, std::milli>(tp3 - tp0).count();
         exchange_us_per_step = 0.0;
         // (the device-side RunInfo still points to run-scoped buffers; half_step_async replaces it before it launches)
-        if (dbg)
-        {
-            const auto tp4 = std::chrono::steady_clock::now();
-            auto us = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) {
-                return std::chrono::duration<double, std::micro>(y - x).count();
-            };
-            std::fprintf(stderr, "[mcmcpp_hip] run: setup %.0f us, enqueue %.0f us, drain %.0f us, idle-info %.0f us, gpu launches %.0f us\n",
-                         us(tp0, tp1), us(tp1, tp2), us(tp2, tp3), us(tp3, tp4), last_ms * 1e3);
-        }
         return rc;
     }
 
@@ -934,28 +838,29 @@ public:
     // in their first all-gather for good.  One small all-reduce and one stream synchronisation per run.
     int agree_on_status(int local_rc, int64_t total, int32_t interval, bool stores, bool* any_rank_stores)
     {
-        uint64_t* hs = reinterpret_cast<uint64_t*>(h_pinned);  // [0, 64): words out, [64, 128): words back
-        hs[0] = (uint64_t)local_rc;
-        hs[1] = (uint64_t)total;
-        hs[2] = ~(uint64_t)total;
-        hs[3] = (uint64_t)(uint32_t)interval;
-        hs[4] = ~(uint64_t)(uint32_t)interval;
-        hs[5] = stores ? 1u : 0u;  // (stored steps are handed out a staging buffer at a time: where the chunks of the run end)
+        uint64_t* out = h_pinned->status_out;
+        const uint64_t* back = h_pinned->status_back;
+        out[0] = (uint64_t)local_rc;
+        out[1] = (uint64_t)total;
+        out[2] = ~(uint64_t)total;
+        out[3] = (uint64_t)(uint32_t)interval;
+        out[4] = ~(uint64_t)(uint32_t)interval;
+        out[5] = stores ? 1u : 0u;  // (stored steps are handed out a staging buffer at a time: where the chunks of the run end)
         const std::string mine = error;
         HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipMemcpyAsync(d_status, hs, 6 * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(d_status, out, 6 * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
         NCCL_TRY(rccl->AllReduce(d_status, d_status, 6, ncclUint64, ncclMax, comm, stream));
-        HIP_TRY(hipMemcpyAsync(hs + 8, d_status, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(h_pinned->status_back, d_status, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         if (local_rc != MCMCPP_HIP_OK)
         {
             error = mine;
             return local_rc;
         }
-        if (hs[8] != 0) return fail((int)hs[8], "run: the preparation of another rank of the split ensemble failed (code %d); nothing was launched", (int)hs[8]);
-        if (hs[9] != ~hs[10] || hs[11] != ~hs[12])
+        if (back[0] != 0) return fail((int)back[0], "run: the preparation of another rank of the split ensemble failed (code %d); nothing was launched", (int)back[0]);
+        if (back[1] != ~back[2] || back[3] != ~back[4])
             return fail(MCMCPP_HIP_E_ARG, "run: the ranks of the split ensemble were asked for different numbers of steps or intervals; nothing was launched");
-        *any_rank_stores = hs[13] != 0;
+        *any_rank_stores = back[5] != 0;
         return MCMCPP_HIP_OK;
     }
 
@@ -1024,7 +929,7 @@ public:
         records_valid = false;
         run_info_idle = false;
         {
-            RunInfo* ri = reinterpret_cast<RunInfo*>((char*)h_pinned + 256);
+            RunInfo* ri = &h_pinned->run[0];
             ri->chain = nullptr;  // (stored steps are copied from the replica after the exchange)
             ri->accepted_per_step = d_acc;
             ri->interval = interval;
@@ -1165,7 +1070,7 @@ public:
             const bool more = s0 + len < total;
             if (compact)
             {
-                XStats* hx = reinterpret_cast<XStats*>((char*)h_pinned + 112);  // (behind the status words agree_on_status reads back)
+                XStats* hx = &h_pinned->xstats;
                 HIP_TRY(hipMemcpyAsync(hx, d_xstats, sizeof(XStats), hipMemcpyDeviceToHost, stream));
                 HIP_TRY(hipStreamSynchronize(stream));
                 if (hx->overflow)
@@ -1284,7 +1189,7 @@ public:
         const size_t ring_bytes = step_bytes * (size_t)ring, out_bytes = step_bytes * (size_t)n_saved;
         for (int k = 0; k < K; ++k)
         {
-            RunInfo* ri = reinterpret_cast<RunInfo*>((char*)h_pinned + 1024 + 64 * kMaxChains + 64 * k);
+            RunInfo* ri = &h_pinned->chain_run[0][k];
             ri->chain = (char*)d_ring + ring_bytes * (size_t)k;
             ri->accepted_per_step = want_accepted ? d_acc + (size_t)k * (size_t)total : nullptr;
             ri->interval = interval;
@@ -1418,7 +1323,6 @@ public:
         HIP_TRY(hipSetDevice(device));
         half_steps = 2 * steps_done;
         records_valid = false;
-        records_ahead_of = kNoStep;
         return write_ctl(0);  // repositions the stream and re-primes the draw records of the next two half-steps
     }
 
@@ -1539,14 +1443,6 @@ public:
         return MCMCPP_HIP_OK;
     }
 
-    int debug_stamps(unsigned long long* out8) override
-    {
-        if (!d_stamps) return fail(MCMCPP_HIP_E_UNSUPPORTED, "not a diagnostic build");
-        HIP_TRY(hipStreamSynchronize(stream));
-        HIP_TRY(hipMemcpy(out8, d_stamps, kStampWords * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        return MCMCPP_HIP_OK;
-    }
-
     int synchronize() override
     {
         HIP_TRY(hipSetDevice(device));
@@ -1644,13 +1540,12 @@ private:
         a.partial_waves = partial_waves;
         a.direct_save_slot = -1;
         a.use_ctl_save = 1;
-        a.stamps = d_stamps;
         a.draw_parity = 0;
         a.pos_alt = d_pos_alt;
         a.logp_alt = d_logp + W;
         a.pos_parity = 0;
         a.calc_params_padded = d_params_padded;
-        a.chains = (K == 1 && knobs.force_multi_chain_kernels != 0) ? -1 : K;
+        a.chains = K;
         // a fifth wavefront per workgroup computes the next draws when that is at most two rounds of 64 draws
         a.draw_wave = (3 * kWavesPerBlock * (64 / step_lpw) * passes <= 128 && knobs.no_draw_wave == 0) ? 1 : 0;
         return a;
@@ -1666,7 +1561,7 @@ private:
         const bool refill = !(records_valid && records_step == (half_steps >> 1) && (!full_fn || records_partner2));
         for (int k = 0; k < K; ++k)
         {
-            StepCtl* c = K > 1 ? (StepCtl*)((char*)h_pinned + 1024 + 64 * k) : (StepCtl*)((char*)h_pinned + 128);
+            StepCtl* c = K > 1 ? &h_pinned->chain_ctl[k] : &h_pinned->ctl;
             c->state = apply(j, state0_of[k]);
             const U128 state1 = apply(half_jump, c->state);
             c->state2 = apply(half_jump, state1);
@@ -1676,7 +1571,6 @@ private:
             c->save_phase = (uint32_t)(step_in_run % (uint64_t)interval);
             c->partial_slot = (uint32_t)(step_in_run % (uint64_t)partial_slots);
             HIP_TRY(hipMemcpyAsync(ctl_of(k) + (half_steps & 1), c, sizeof(StepCtl), hipMemcpyHostToDevice, stream));
-            if (d_ctl_keep) HIP_TRY(hipMemcpyAsync(d_ctl_keep, c, sizeof(StepCtl), hipMemcpyHostToDevice, stream));
             if (refill)
             {
                 const int parity = (int)((half_steps >> 1) & 1);  // the buffer the coming ensemble step reads
@@ -1710,7 +1604,7 @@ private:
             a.ctl_out = d_ctl + (1 - pos_parity);
             a.partial_waves = partial_waves;
             // the next draws by four extra wavefronts (two per colour) when that is one round of 64 draws each
-            a.draw_wave = (3 * (kFullDrawWaves == 4 ? (full_wpb + 1) / 2 : full_wpb) <= 64 && knobs.no_draw_wave == 0) ? 1 : 0;
+            a.draw_wave = (3 * ((full_wpb + 1) / 2) <= 64 && knobs.no_draw_wave == 0) ? 1 : 0;
             if (batch_slot >= 0)
             {
                 a.draw_wave = 2;
@@ -1736,63 +1630,34 @@ private:
         launch_fill_draws_batch(a, d_ctl + pos_parity, d_step_jump, d_draws_batch, count, stream);
     }
 
-    // record sets [first, first + count) for the same steps of the NEXT replay, on the parallel branch (stream capture:
-    // the fork is the event, the join comes before the accepted-count reduction)
-    int fork_fill_of_next_replay(int first, int count)
-    {
-        HalfStepArgs<T> a = args_red;
-        a.draws = d_draws;
-        HIP_TRY(hipEventRecord(ev_fill_fork, stream));
-        HIP_TRY(hipStreamWaitEvent(fill_stream, ev_fill_fork, 0));
-        launch_fill_draws_batch(a, d_ctl_keep, d_step_jump + batch_draws + first, d_draws_batch + (size_t)first * 2 * (size_t)n, count, fill_stream);
-        return MCMCPP_HIP_OK;
-    }
-
     // `steps` ensemble steps from record-buffer parity start_parity / position-buffer parity pos_parity on
-    // records_ahead: the batch records of these steps are in place (the replay before made them on its branch);
-    // fill_next: make the next replay's on a branch of this one
-    int enqueue_step_sequence(int steps, int start_parity, int pos_parity, bool records_ahead = false, bool fill_next = false)
+    void enqueue_step_sequence(int steps, int start_parity, int pos_parity)
     {
-        int piece_first = 0, piece = 0;
         for (int s = 0; s < steps; ++s)
         {
             if (batch_draws > 0)
             {
-                if (s % batch_draws == 0 && !(s == 0 && records_ahead)) fill_batch((pos_parity + s) & 1, steps - s < batch_draws ? steps - s : batch_draws);
+                if (s % batch_draws == 0) fill_batch((pos_parity + s) & 1, steps - s < batch_draws ? steps - s : batch_draws);
                 enqueue_step(0, (pos_parity + s) & 1, s % batch_draws);
-                if (fill_next && (s + 1 == (int)(((int64_t)steps * (piece + 1)) / fill_pieces)))
-                {
-                    if (int rc = fork_fill_of_next_replay(piece_first, s + 1 - piece_first)) return rc;
-                    piece_first = s + 1;
-                    ++piece;
-                }
             }
             else
                 enqueue_step((start_parity + s) & 1, (pos_parity + s) & 1);
         }
-        if (fill_next)
-        {
-            HIP_TRY(hipEventRecord(ev_fill_join, fill_stream));
-            HIP_TRY(hipStreamWaitEvent(stream, ev_fill_join, 0));
-        }
-        return MCMCPP_HIP_OK;
     }
 
     // hipGraph of `steps` ensemble steps followed by the accepted-count reduction (cached per step count:
     // graph_steps for the bulk, one graph per distinct remainder)
     // (the record-buffer parity of every node is frozen into the graph, hence one graph per starting parity)
-    // (with records made a replay ahead: a replay of graph_steps steps always makes the next replay's on its branch, and
-    //  one graph per "the records of my own steps are in place already")
-    int graph_for(int steps, int start_parity, int pos_parity, hipGraphExec_t* out, bool records_ahead = false)
+    int graph_for(int steps, int start_parity, int pos_parity, hipGraphExec_t* out)
     {
-        const size_t key = ((size_t)steps * 2 + (records_ahead ? 1 : 0)) * 4 + (size_t)start_parity * 2 + (size_t)pos_parity;
+        const size_t key = (size_t)steps * 4 + (size_t)start_parity * 2 + (size_t)pos_parity;
         if (graph_cache.size() <= key) graph_cache.resize(key + 1, nullptr);
         if (!graph_cache[key])
         {
             hipGraph_t g = nullptr;
             HIP_TRY(hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed));
-            if (int rc = enqueue_step_sequence(steps, start_parity, pos_parity, records_ahead, fill_pieces > 0 && steps == graph_steps)) return rc;
-            launch_accepted_reduce(d_partials, partial_slots, partial_waves, steps, ctl_after(pos_parity + steps), d_run, stream, K, d_ctl_keep);
+            enqueue_step_sequence(steps, start_parity, pos_parity);
+            launch_accepted_reduce(d_partials, partial_slots, partial_waves, steps, ctl_after(pos_parity + steps), d_run, stream, K);
             HIP_TRY(hipStreamEndCapture(stream, &g));
             hipGraphExec_t ex = nullptr;
             HIP_TRY(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
@@ -1807,7 +1672,7 @@ private:
     {
         if (graph_steps < 1) return MCMCPP_HIP_OK;
         hipGraphExec_t ex;
-        return graph_for(graph_steps, (int)(enq_step & 1), 0, &ex, fill_pieces > 0 && records_ahead_of == enq_step);
+        return graph_for(graph_steps, (int)(enq_step & 1), 0, &ex);
     }
 
     // the control record the last launch of a step sequence leaves behind: the half-step pair always ends in [0],
@@ -1824,31 +1689,28 @@ private:
             hipGraphExec_t ex = nullptr;
             while (left >= graph_steps)
             {
-                int rc = graph_for(graph_steps, (int)(enq_step & 1), (int)(run_step & 1), &ex, fill_pieces > 0 && records_ahead_of == enq_step);
+                int rc = graph_for(graph_steps, (int)(enq_step & 1), (int)(run_step & 1), &ex);
                 if (rc) return rc;
                 HIP_TRY(hipGraphLaunch(ex, stream));
                 left -= graph_steps;
                 enq_step += (uint64_t)graph_steps;
                 run_step += (uint64_t)graph_steps;
-                records_ahead_of = fill_pieces > 0 ? enq_step : kNoStep;
             }
             if (left > 0)
             {
-                // one replay for the remainder (it may use records made ahead, it makes none: the record sets would no
-                // longer line up with the steps of a whole replay)
-                int rc = graph_for((int)left, (int)(enq_step & 1), (int)(run_step & 1), &ex, fill_pieces > 0 && records_ahead_of == enq_step);
+                // one replay for the remainder
+                int rc = graph_for((int)left, (int)(enq_step & 1), (int)(run_step & 1), &ex);
                 if (rc) return rc;
                 HIP_TRY(hipGraphLaunch(ex, stream));
                 enq_step += (uint64_t)left;
                 run_step += (uint64_t)left;
-                records_ahead_of = kNoStep;
             }
         }
         else
         {
             for (; left > 0; --left)
             {
-                (void)enqueue_step_sequence(1, (int)(enq_step & 1), (int)(run_step & 1));
+                enqueue_step_sequence(1, (int)(enq_step & 1), (int)(run_step & 1));
                 launch_accepted_reduce(d_partials, partial_slots, partial_waves, 1, ctl_after((int64_t)run_step + 1), d_run, stream, K);
                 enq_step += 1;
                 run_step += 1;
@@ -1893,8 +1755,6 @@ private:
         if (half_bytes > 0 && ev_copied[0] == nullptr)
         {
             for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreateWithFlags(&ev_copied[k], hipEventDisableTiming));
-            for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreateWithFlags(&ev_filled[k], hipEventDisableTiming));
-            if (knobs.copy_stream != 0) HIP_TRY(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
         }
         if (half_bytes > chain_half_capacity)
         {
@@ -1931,16 +1791,11 @@ private:
         if (d_acc) hipFree(d_acc);
         if (d_draws_batch) hipFree(d_draws_batch);
         if (d_step_jump) hipFree(d_step_jump);
-        if (d_ctl_keep) hipFree(d_ctl_keep);
-        if (fill_stream) hipStreamDestroy(fill_stream);
-        if (ev_fill_fork) hipEventDestroy(ev_fill_fork);
-        if (ev_fill_join) hipEventDestroy(ev_fill_join);
         for (int k = 0; k < 2; ++k)
         {
             if (d_chain[k]) hipFree(d_chain[k]);
             if (h_stage[k]) hipHostFree(h_stage[k]);
             if (ev_copied[k]) hipEventDestroy(ev_copied[k]);
-            if (ev_filled[k]) hipEventDestroy(ev_filled[k]);
         }
         if (d_ring) hipFree(d_ring);
         if (h_ring) hipHostFree(h_ring);
@@ -1950,11 +1805,6 @@ private:
         {
             if (ev_t0[k]) hipEventDestroy(ev_t0[k]);
             if (ev_t1[k]) hipEventDestroy(ev_t1[k]);
-        }
-        if (copy_stream)
-        {
-            hipStreamSynchronize(copy_stream);
-            hipStreamDestroy(copy_stream);
         }
         if (d_xblocks) hipFree(d_xblocks);
         if (d_seen) hipFree(d_seen);
@@ -1991,12 +1841,11 @@ private:
     int W = 0, D = 0, n = 0, lpw = 1, epl = 1, step_lpw = 1, passes = 1, vec_ok = 0, num_cus = 256;
     int shard_begin = 0, shard_count = 0, device = -1, graph_steps = 32;
     size_t chain_subchunk_bytes = 0, chain_half_capacity = 0, acc_capacity = 0;
-    hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_filled[2] = {nullptr, nullptr};
+    hipEvent_t ev_copied[2] = {nullptr, nullptr};
     void* arena = nullptr;  // one device allocation holding everything a step launch touches (see carve)
     size_t arena_bytes = 0, arena_used = 0;
     void *d_ring = nullptr, *h_ring = nullptr;  // full-step chain path: device ring of stored steps and its pinned host twin
     size_t ring_capacity = 0, host_ring_capacity = 0;
-    hipStream_t copy_stream = nullptr;  // experiment (MCMCPP_HIP_COPY_STREAM=1): chain downloads beside the launches
     T* d_chain[2] = {nullptr, nullptr};
     void* h_stage[2] = {nullptr, nullptr};
     uint32_t* d_acc = nullptr;
@@ -2013,14 +1862,6 @@ private:
     DrawRec<T>* d_draws_batch = nullptr;  // [batch_draws][2][n]: records made ahead of the matrix-core full-step launches
     Affine128* d_step_jump = nullptr;     // [batch_draws]
     int batch_draws = 0;                  // 0: the step launches make their own next records
-    int fill_pieces = 0;                  // > 0: a whole replay makes the next replay's records on a parallel branch, in that many pieces
-    hipStream_t fill_stream = nullptr;    // (capture only: the branch)
-    hipEvent_t ev_fill_fork = nullptr, ev_fill_join = nullptr;
-    StepCtl* d_ctl_keep = nullptr;        // the control record at the head of the coming replay (write_ctl, accepted_reduce_kernel)
-    static constexpr uint64_t kNoStep = ~0ULL;
-    uint64_t records_ahead_of = kNoStep;  // the ensemble step (since set_state) whose records sit in record set 0, made ahead by a branch
-    static constexpr size_t kStampWords = 8 + 2 * 3 * 4096 + 8;
-    unsigned long long* d_stamps = nullptr;  // diagnostic build only
     uint32_t* d_partials = nullptr;
     int partial_slots = 1, partial_waves = 0;
     Affine128 *d_jump_lo = nullptr, *d_jump_hi = nullptr, *d_task_jump = nullptr;  // behind d_draws: see JumpTables
@@ -2028,7 +1869,7 @@ private:
     // which ensemble step the draw records on the device belong to, if known, and whether the black ones carry partner2
     bool records_valid = false, records_partner2 = false, run_info_idle = false;
     uint64_t records_step = 0;
-    void* h_pinned = nullptr;
+    PinnedScratch* h_pinned = nullptr;
     U128 state0, inc;
     U128 state0_of[kMaxChains];  // per chain (seed + k)
     int K = 1;                   // independent ensembles stepped by one launch
@@ -2100,15 +1941,6 @@ int check_config(const mcmcpp_hip_config* c, std::string& err)
 extern "C"
 {
 int mcmcpp_hip_abi_version(void) { return MCMCPP_HIP_ABI_VERSION; }
-
-#ifdef MCMCPP_STAMPS
-// diagnostic build only: shader-clock stamps of the last half-step launch (not part of the ABI)
-int mcmcpp_hip_debug_stamps(mcmcpp_hip_sampler* h, unsigned long long* out8)
-{
-    if (!h || !out8) return MCMCPP_HIP_E_ARG;
-    return h->debug_stamps(out8);
-}
-#endif
 
 int mcmcpp_hip_register_calculator(int32_t calc_id, const void* table_f64, const void* table_f32, int32_t params_len)
 {

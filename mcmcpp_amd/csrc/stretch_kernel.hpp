@@ -24,6 +24,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <type_traits>
@@ -99,11 +100,7 @@ struct Diag
 // An accept decision within a few ulp of a tie (include/mcmcpp_hip.h: near_ties).
 __device__ __forceinline__ void count_near_tie(Diag* diag)
 {
-#ifndef MCMCPP_EXP_NO_TIE_ATOMIC
     atomicAdd(&diag->near_ties, 1ULL);
-#else
-    (void)diag;
-#endif
 }
 
 // The jump tables live right behind the draw records, at offsets that follow from the number of walkers per colour
@@ -178,10 +175,9 @@ struct alignas(64) HalfStepArgs
     int color;                  // 0 red = walkers [0,n), 1 black = [n,2n)
     int shard_begin;            // first walker (index inside the half) updated by this launch
     int shard_count;            // number of walkers updated by this launch
-    // ---- lines 2-3: two-level jump tables only; diagnostics ----
+    // ---- lines 2-3: two-level jump tables only ----
     alignas(64) Affine128 draw_jump[3];  // maps of 1, 2, 3 draws: a walker's base state -> the state behind draw k
     U128 inc;                   // pcg stream increment
-    unsigned long long* stamps; // diagnostic build only (MCMCPP_STAMPS): shader-clock stamps
     // ---- the updating wavefronts ----
     alignas(64) T* pos;         // [W][D]
     T* logp;                    // [W]
@@ -208,6 +204,9 @@ struct alignas(64) HalfStepArgs
     int pos_parity;             // full-step kernels: 0: read pos/logp, write pos_alt/logp_alt; 1: the reverse
     int chains;                 // independent ensembles stepped by this launch (grid.y), 1..kMaxChains
 };
+// the line layout above is what the kernels are tuned to: the updating wavefronts' fields start on line 4
+static_assert(offsetof(HalfStepArgs<double>, pos) == 256 && sizeof(HalfStepArgs<double>) == 448, "HalfStepArgs<double> layout moved");
+static_assert(offsetof(HalfStepArgs<float>, pos) == 256 && sizeof(HalfStepArgs<float>) == 448, "HalfStepArgs<float> layout moved");
 
 // This lane's EPL elements of a walker row; cells beyond D (and everything when !active) are +0.  Branch-free on
 // purpose: the address is clamped to a valid one, the load is unconditional and unwanted data is masked off bitwise.
@@ -346,46 +345,7 @@ __device__ __forceinline__ float dev_log(float x) { return logf(x); }
 __device__ __forceinline__ double dev_abs(double x) { return fabs(x); }
 __device__ __forceinline__ float dev_abs(float x) { return fabsf(x); }
 
-#ifndef MCMCPP_WAVES_PER_BLOCK  // (experiment builds: make VARIANT=... EXTRA=-DMCMCPP_WAVES_PER_BLOCK=2)
-#define MCMCPP_WAVES_PER_BLOCK 4
-#endif
-constexpr int kWavesPerBlock = MCMCPP_WAVES_PER_BLOCK;
-
-// Diagnostic build only (make STAMPS=1 -> libmcmcpp_hip_stamps.so): wavefront 0 of workgroup 0 drains its
-// memory counters and records the shader clock at a few points; the product build compiles none of it.
-#ifdef MCMCPP_STAMPS
-#ifdef MCMCPP_STAMPS_DRAIN  // attribute waits to the segment that issued the memory operations
-#define MCMCPP_STAMP_DRAIN "s_waitcnt vmcnt(0) lgkmcnt(0)\n\t"
-#else  // leave the kernel's own overlap intact: only read the clock
-#define MCMCPP_STAMP_DRAIN ""
-#endif
-#define MCMCPP_STAMP(k)                                                                     \
-    do                                                                                      \
-    {                                                                                       \
-        if (a.stamps != nullptr && blockIdx.x == 0 && threadIdx.x < 64)                     \
-        {                                                                                   \
-            unsigned long long t_;                                                          \
-            asm volatile(MCMCPP_STAMP_DRAIN "s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory"); \
-            if (threadIdx.x == 0) stamp_val[k] = t_;                                        \
-        }                                                                                   \
-    } while (0)
-// start / end of every workgroup's first wavefront on the chip-wide 100 MHz clock
-#define MCMCPP_STAMP_BLOCK(which)                                                                               \
-    do                                                                                                          \
-    {                                                                                                           \
-        if (a.stamps != nullptr && threadIdx.x == 0 && blockIdx.x < 4096)                                       \
-            a.stamps[8 + (a.pos_parity | a.color) * 3 * 4096 + 2 * blockIdx.x + (which)] = __builtin_amdgcn_s_memrealtime(); \
-    } while (0)
-#else
-#define MCMCPP_STAMP(k) \
-    do                  \
-    {                   \
-    } while (0)
-#define MCMCPP_STAMP_BLOCK(which) \
-    do                            \
-    {                             \
-    } while (0)
-#endif
+constexpr int kWavesPerBlock = 4;  // updating wavefronts per workgroup
 
 // dynamic LDS of one workgroup: [proposal stage (if the calculator wants it)][calculator tables]
 template <class T, class Calc, int EPL>
@@ -610,21 +570,6 @@ __device__ __forceinline__ void draw_wave_body(const HalfStepArgs<T>& a, const J
                                                int group_first, int group_walkers, int lane, bool black_only = false,
                                                const RunInfo* trickle_run = nullptr, int run_behind_ctl = -1, int ctl_chain = 0)
 {
-#ifdef MCMCPP_STAMPS
-    unsigned long long dstamp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define MCMCPP_DSTAMP(k, drain)                                                                             \
-    do                                                                                                      \
-    {                                                                                                       \
-        if (drain) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                              \
-        dstamp[k] = __builtin_amdgcn_s_memrealtime();                                                       \
-    } while (0)
-#else
-#define MCMCPP_DSTAMP(k, drain) \
-    do                          \
-    {                           \
-    } while (0)
-#endif
-    MCMCPP_DSTAMP(0, false);
     const bool direct = tab.task != nullptr;
     const int per_colour = 3 * group_walkers;
     const int tasks = colours * per_colour;
@@ -661,9 +606,7 @@ __device__ __forceinline__ void draw_wave_body(const HalfStepArgs<T>& a, const J
                                           trickle_run != nullptr ? 0u : ctl_off, ctl, run);
         if (wants_run) trickle_stored_step(run, ctl, lane);
     }
-    MCMCPP_DSTAMP(1, true);
     if (block_barrier) __syncthreads();  // keep the workgroup barrier count whole
-    MCMCPP_DSTAMP(2, false);
     // black_only: the full-step kernels' second draw wavefront (black records of the next step, with partner2)
     const bool with_p2 = colours > 1 || black_only;
     const U128 base1 = with_p2 ? apply(a.half_jump, ctl.state2) : ctl.state2;
@@ -686,28 +629,12 @@ __device__ __forceinline__ void draw_wave_body(const HalfStepArgs<T>& a, const J
         j_a[r] = *(direct ? tab.task + 3 * (size_t)jj : tab.hi + (jj >> 8));  // branch-free: one pointer, one load
         j_b[r] = tab.lo[direct ? 0u : (jj & 255u)];
     }
-    MCMCPP_DSTAMP(5, false);  // raw outputs computed, gathers issued
 #pragma unroll
     for (int r = 0; r < MAXR; ++r)
         if (ok[r]) draw_store<T>(a, kk[r], raw[r], (cc[r] ? write1 : write0) + wi[r]);
-    MCMCPP_DSTAMP(6, false);  // record fields computed and stored
-    MCMCPP_DSTAMP(7, true);   // gathers landed
 #pragma unroll
     for (int r = 0; r < MAXR; ++r)
         if (p2[r]) ((cc[r] ? write1 : write0) + wi[r])->partner2 = draw_partner2<T>(a, ctl.state2, j_a[r], j_b[r], direct);
-    MCMCPP_DSTAMP(3, false);
-#ifdef MCMCPP_STAMPS
-    if (a.stamps != nullptr && lane == 0 && blockIdx.x < 4096)
-    {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (blockIdx.x == 0)
-        {
-            dstamp[4] = __builtin_amdgcn_s_memrealtime();
-            for (int k = 0; k < 8; ++k) a.stamps[8 + 2 * 3 * 4096 + k] = dstamp[k];
-        }
-        a.stamps[8 + (a.pos_parity | a.color) * 3 * 4096 + 2 * 4096 + blockIdx.x] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
 }
 
 // DW: built with the extra draw wavefront (HalfStepArgs::draw_wave) or without it.  Two instantiations on purpose: the
@@ -761,13 +688,6 @@ stretch_half_step_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, uint32_
     T* sh_stage = reinterpret_cast<T*>(smem + LdsLayout<T, Calc, EPL>::stage_offset());
     T* sh_block = reinterpret_cast<T*>(smem + LdsLayout<T, Calc, EPL>::block_offset());
 
-#ifdef MCMCPP_STAMPS
-    unsigned long long stamp_val[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-    MCMCPP_STAMP(0);
-#ifdef MCMCPP_STAMPS
-    stamp_val[6] = __builtin_amdgcn_s_memrealtime();
-#endif
     const int lane = threadIdx.x & 63;
     const int wib = threadIdx.x >> 6;
     const int nw = WPP * h_passes;
@@ -849,7 +769,6 @@ stretch_half_step_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, uint32_
     T par[EPL];
     load_slice<T, EPL>(h_pos + (size_t)(other_base + (int)rec.partner) * h_dims, i0, h_dims, vec_ok,
                        wave_active && first + grp < h_shard_count, par);
-    MCMCPP_STAMP(1);  // records landed, partner gather issued (diagnostic build: also landed)
 
     // ---- in its shadow: the calculator's tables, the hand-over to the next launch, the next draws -----------
     const bool has_block_scratch = Calc::block_scratch_elems(h_dims) != 0;
@@ -898,7 +817,6 @@ stretch_half_step_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, uint32_
             }
         }
     };
-    MCMCPP_STAMP(2);
 
     // ---------------- the update: LPW lanes per walker ------------------------------------------------------
     unsigned accepted_here = 0;
@@ -926,7 +844,6 @@ stretch_half_step_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, uint32_
         }
         if (q > 0)
             load_slice<T, EPL>(h_pos + (size_t)(other_base + (int)rec.partner) * h_dims, i0, h_dims, vec_ok, active, par);
-        if (q == 0) MCMCPP_STAMP(3);  // partner rows landed
 
         // StretchMove.h:105-108  proposal = sel + z*(cur - sel); padded cells stay +0
         T prop[EPL];
@@ -938,7 +855,6 @@ stretch_half_step_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, uint32_
             prop[e] = par[e] + zd;
         }
         const T lp_new = Calc::template eval<EPL, LPW>(ctx, a.calc_params, cregs, prop);
-        if (q == 0) MCMCPP_STAMP(4);  // calculator done
 
         // StretchMove.h:112-113  accept iff lnU < (probScaling + newProb) - oldProb
         const T zs = rec.zs, ln_u = rec.ln_u;
@@ -982,14 +898,6 @@ stretch_half_step_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, uint32_
     // gather they lift the kernel from 64 to 85 VGPRs and cost occupancy (7 % at 1 M walkers).  The record buffers
     // alternate, so the order against the update loop is free as far as correctness goes.
     if (!h_draw_wave) next_draws();
-    MCMCPP_STAMP(5);  // all stores of this wavefront acknowledged
-#ifdef MCMCPP_STAMPS
-    if (a.stamps != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
-    {
-        stamp_val[7] = __builtin_amdgcn_s_memrealtime();  // 100 MHz constant clock, with [6] taken at entry
-        for (int k = 0; k < 8; ++k) a.stamps[k] = stamp_val[k];
-    }
-#endif
     // per-wavefront accepted count of this half-step; summed per ensemble step by accepted_reduce_kernel
     // (one plain store per wavefront: thousands of same-address atomics would serialise for ~12 ns each)
     if (a.partials != nullptr && run.accepted_per_step != nullptr && lane == 0)
@@ -1173,12 +1081,6 @@ stretch_half_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, ui
     T* sh_x = reinterpret_cast<T*>(smem) + (threadIdx.x >> 6) * (kStageRows * XS);
 
     const HalfStepArgs<T>& a = rest;
-#ifdef MCMCPP_STAMPS
-    unsigned long long stamp_val[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    stamp_val[6] = __builtin_amdgcn_s_memrealtime();
-#endif
-    MCMCPP_STAMP(0);
-    MCMCPP_STAMP_BLOCK(0);
     // chain blockIdx.y of (hot_bits >> 28) + 1 (ChainGeometry), as in the kernel above
         // (MC: built for several chains per launch; the single-ensemble instantiation carries none of it -- measured 2 % of a
     //  65 536-walker launch otherwise)
@@ -1327,7 +1229,6 @@ stretch_half_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, ui
         mpiece = *reinterpret_cast<const V4*>(hot_matrix + 4 * threadIdx.x);
     else
         mc_load_b(hot_matrix, sub, grp, matB);
-    MCMCPP_STAMP(1);  // records landed, partner gather issued
 
     // ---- in its shadow: hand-over to the next launch, the walkers' next draws ------------------------------------------
     // one lane of the grid hands the stream and the counters to the next launch (in the shadow of its gather wait;
@@ -1340,7 +1241,6 @@ stretch_half_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, ui
     else if (h_use_ctl_save && run.chain != nullptr && ctl.save_phase + 1u == (uint32_t)run.interval)
         save_slot = run.chain_slot_base + ctl.chain_slot;
     if constexpr (!DW && !LATE) MCMCPP_MAKE_NEXT_DRAWS();
-    MCMCPP_STAMP(2);  // next draws done
 
     // ---- proposals (StretchMove.h:105-108) -----------------------------------------------------------------------
     T prop[P][2];
@@ -1355,7 +1255,6 @@ stretch_half_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, ui
             prop[q][e] = par[q][e] + zd;
         }
     }
-    MCMCPP_STAMP(3);  // partner rows landed
 
     // ---- Y = X * P^T on the matrix cores, products and the canonical tree ------------------------------------------
     T lp_new[P];
@@ -1375,7 +1274,6 @@ stretch_half_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, ui
         return;
     }
     mc_eval<P>(matB, sh_x, sub, grp, h_dims, prop, lp_new);
-    MCMCPP_STAMP(4);  // calculator done
     if constexpr (LATE) MCMCPP_LOAD_DRAW_JUMPS();
 
     // ---- Metropolis accept in place, chain store, counters ------------------------------------------------------------
@@ -1417,15 +1315,6 @@ stretch_half_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, ui
     if constexpr (LATE) MCMCPP_MAKE_NEXT_DRAWS();
 #undef MCMCPP_LOAD_DRAW_JUMPS
 #undef MCMCPP_MAKE_NEXT_DRAWS
-    MCMCPP_STAMP(5);
-    MCMCPP_STAMP_BLOCK(1);
-#ifdef MCMCPP_STAMPS
-    if (a.stamps != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
-    {
-        stamp_val[7] = __builtin_amdgcn_s_memrealtime();
-        for (int k = 0; k < 8; ++k) a.stamps[k] = stamp_val[k];
-    }
-#endif
     if (a.partials != nullptr && run.accepted_per_step != nullptr && lane == 0)
         a.partials[(((size_t)chain * (size_t)a.partial_slots + (size_t)ctl.partial_slot) * 2 + (size_t)h_color) * (size_t)a.partial_waves + (size_t)wave] = accepted_here;
 }
@@ -1446,11 +1335,9 @@ __global__ void __launch_bounds__(256) mark_rows_moved_kernel(uint32_t* n_accept
 #ifdef MCMCPP_DEFINE_REDUCE_KERNEL  // one definition, in mcmcpp_hip.hip
 __global__ void __launch_bounds__(256)
 accepted_reduce_kernel(const uint32_t* partials, int partial_slots, int partial_waves, int count, const StepCtl* ctl_after,
-                       const RunInfo* run_ptr, StepCtl* ctl_keep)
+                       const RunInfo* run_ptr)
 {
     __shared__ unsigned sums[4];
-    // (one chain, records made a replay ahead: the control record at the head of the next replay, out of the step launches' way)
-    if (ctl_keep != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *ctl_keep = *ctl_after;
     // (blockIdx.y: the chain, see ChainGeometry)
     partials += (size_t)blockIdx.y * (size_t)partial_slots * 2 * (size_t)partial_waves;
     ctl_after = reinterpret_cast<const StepCtl*>(reinterpret_cast<const char*>(ctl_after) + (size_t)blockIdx.y * kCtlChainStride);

@@ -273,13 +273,10 @@ def test_draw_records_made_ahead_in_batches_of_any_length(monkeypatch, batch):
     _assert_same_state(orc, hip)
 
 
-@pytest.mark.parametrize("pieces", ["1", "3", "8"])
-def test_draw_records_of_the_next_replay_made_on_a_branch_of_this_one(monkeypatch, pieces):
-    """MCMCPP_HIP_FILL_BRANCH = p: a whole graph replay makes the NEXT replay's draw records beside its own step launches, in
-    p pieces on a parallel branch of the graph (piece k forked off behind the last step that read its record sets).  Whole
-    replays, remainders that use records made ahead, remainders that make their own, runs that store steps and runs that do
-    not, a seek in between: the chain and the accepted counts are the oracle's."""
-    monkeypatch.setenv("MCMCPP_HIP_FILL_BRANCH", pieces)
+def test_draw_records_made_at_the_head_of_each_replay(monkeypatch):
+    """The matrix-core full-step path makes a graph replay's draw records in one launch at its head.  Whole replays,
+    remainders, runs that store steps and runs that do not, a seek in between: the chain and the accepted counts are the
+    oracle's."""
     monkeypatch.setenv("MCMCPP_HIP_GRAPH_STEPS", "8")
     orc, hip = _oracle_and_hip(2048 + 6, 32, po.CALC_DENSE_GAUSSIAN, po.F64, seed=5, steps=0)
     oc, oa = orc.run(104, interval=1, mode=po.MODE_COUNTER, threads=4)
@@ -292,7 +289,7 @@ def test_draw_records_of_the_next_replay_made_on_a_branch_of_this_one(monkeypatc
         at += steps
     assert at == 104
     _assert_same_state(orc, hip)
-    # back to step 40 with the walkers as they stand: records made ahead for another step must not be used
+    # back to step 40 with the walkers as they stand: records made for another step must not be used
     hip.seek(40)
     orc.seek(40)
     oc2, oa2 = orc.run(20, interval=1, mode=po.MODE_COUNTER, threads=4)
@@ -329,11 +326,11 @@ def test_wave_mapping_and_chunking_do_not_change_results(monkeypatch):
                 {"MCMCPP_HIP_FULL_STEP": "0", "MCMCPP_HIP_NO_DRAW_WAVE": "1"},
                 {"MCMCPP_HIP_NO_DRAW_WAVE": "1"},                          # the updating wavefronts make the next draws
                 {"MCMCPP_HIP_MATRIX_CORE_MIN_WALKERS": "-1"},              # generic kernels for the dense target
-                {"MCMCPP_HIP_COPY_STREAM": "1", "MCMCPP_HIP_CHAIN_SUBCHUNK_MB": "1", "MCMCPP_HIP_TRICKLE": "0"},
+                {"MCMCPP_HIP_CHAIN_SUBCHUNK_MB": "1", "MCMCPP_HIP_TRICKLE": "0"},
                 {"MCMCPP_HIP_TRICKLE": "0"},                               # stored steps by device-to-host copies
                 {"MCMCPP_HIP_CHAIN_SUBCHUNK_MB": "1"}]:                    # the smallest ring of stored steps
         for k in ("MCMCPP_HIP_PASSES", "MCMCPP_HIP_CHAIN_SUBCHUNK_MB", "MCMCPP_HIP_GRAPH_STEPS", "MCMCPP_HIP_TASK_TABLE_MB",
-                  "MCMCPP_HIP_MATRIX_CORE_MIN_WALKERS", "MCMCPP_HIP_FULL_STEP", "MCMCPP_HIP_NO_DRAW_WAVE", "MCMCPP_HIP_COPY_STREAM",
+                  "MCMCPP_HIP_MATRIX_CORE_MIN_WALKERS", "MCMCPP_HIP_FULL_STEP", "MCMCPP_HIP_NO_DRAW_WAVE",
                   "MCMCPP_HIP_TRICKLE"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
