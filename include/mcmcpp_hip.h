@@ -291,6 +291,36 @@ int mcmcpp_hip_autocorr_times_device(int32_t dtype, int32_t device, const void* 
                                      int32_t num_params, int32_t walkers_to_use, int32_t window_scaling, void* times, void* functions);
 const char* mcmcpp_hip_autocorr_last_error(void);
 
+/* Analysis::CornerHistograms and Analysis::PercentileAndMaximumFinder (reference MCMCpp/Analysis/CornerHistograms.h,
+ * PercentileAndMaximumFinder.h): the 1-D histogram of every parameter and, with with_pairs, the 2-D histogram of every
+ * parameter pair, over the selected stored steps.  Binning is the reference's, in the chain's element type: per parameter
+ * the minimum and maximum of the samples used (start values numeric_limits<T>::max() / ::min(), strict comparisons), the
+ * reference's tweak of the two bounds, width = (hi - lo) / bins, bin = int((x - lo) / width).  Every sample the reference
+ * bins in range lands in the reference's bin.  A bin outside [0, bins) (the reference writes outside its arrays there) is
+ * clamped into bin 0 or bins - 1 and counted in `clamped`.  Counts are 64-bit integer sums: bit-reproducible.
+ *   create          dtype MCMCPP_HIP_F64 / _F32 = the chain's ParamType; device -1 = current; bins >= 2;
+ *                   1 <= num_params <= 65535.  MCMCPP_HIP_E_NOMEM (with a message) when the 64-bit result arrays cannot be
+ *                   allocated.  MCMCPP_HIP_HIST_CHUNK_MB (read here, default 1024) sizes the chunks host chains are
+ *                   uploaded in.
+ *   compute         n_steps pointers to the steps to use (host memory, the caller has applied sliceInterval); steps that
+ *                   are contiguous in memory are uploaded in one copy.  Replaces the previous result.  A NaN sample fails
+ *                   the call with MCMCPP_HIP_E_ARG; the handle stays usable.
+ *   compute_device  n_steps contiguous steps [n][W][P] in device memory (e.g. a device chain bound with
+ *                   mcmcpp_hip_bind_device_chain); every slice_interval-th from the first is used; no upload.
+ *   result          bounds [P][2] = (low edge, bin width) in T, as the reference's paramBounds after findBinning;
+ *                   single [P][bins]; pairs [P(P-1)/2][bins][bins] (pair i > j at i(i-1)/2 + j, element [bin_i][bin_j]) or
+ *                   NULL; clamped [P]; *num_points = samples used.  Any pointer may be NULL. */
+typedef struct mcmcpp_hip_histograms mcmcpp_hip_histograms;
+int mcmcpp_hip_histograms_create(int32_t dtype, int32_t device, int32_t num_walkers, int32_t num_params, int32_t bins,
+                                 int32_t with_pairs, mcmcpp_hip_histograms** out);
+void mcmcpp_hip_histograms_destroy(mcmcpp_hip_histograms* h);
+int mcmcpp_hip_histograms_compute(mcmcpp_hip_histograms* h, const void* const* steps, int64_t n_steps);
+int mcmcpp_hip_histograms_compute_device(mcmcpp_hip_histograms* h, const void* device_steps, int64_t n_steps,
+                                         int64_t slice_interval);
+int mcmcpp_hip_histograms_result(const mcmcpp_hip_histograms* h, int64_t* num_points, void* bounds, int64_t* single,
+                                 int64_t* pairs, int64_t* clamped);
+const char* mcmcpp_hip_histograms_last_error(const mcmcpp_hip_histograms* h);
+
 int mcmcpp_hip_abi_version(void);
 
 #ifdef __cplusplus

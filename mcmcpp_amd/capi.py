@@ -26,6 +26,8 @@ EXPORTS = [
     "mcmcpp_hip_moments_create", "mcmcpp_hip_moments_destroy", "mcmcpp_hip_moments_reset", "mcmcpp_hip_moments_add_steps",
     "mcmcpp_hip_moments_add_device_steps", "mcmcpp_hip_moments_finish", "mcmcpp_hip_moments_last_error",
     "mcmcpp_hip_autocorr_times", "mcmcpp_hip_autocorr_times_device", "mcmcpp_hip_autocorr_last_error",
+    "mcmcpp_hip_histograms_create", "mcmcpp_hip_histograms_destroy", "mcmcpp_hip_histograms_compute",
+    "mcmcpp_hip_histograms_compute_device", "mcmcpp_hip_histograms_result", "mcmcpp_hip_histograms_last_error",
 ]
 
 
@@ -116,6 +118,15 @@ def lib():
             L.mcmcpp_hip_autocorr_times_device.argtypes = [i32, i32, vp, i64, i32, i32, i32, i32, vp, vp]
             L.mcmcpp_hip_autocorr_last_error.argtypes = []
             L.mcmcpp_hip_autocorr_last_error.restype = C.c_char_p
+        if hasattr(L, "mcmcpp_hip_histograms_create"):
+            L.mcmcpp_hip_histograms_create.argtypes = [i32, i32, i32, i32, i32, i32, C.POINTER(vp)]
+            L.mcmcpp_hip_histograms_destroy.argtypes = [vp]
+            L.mcmcpp_hip_histograms_destroy.restype = None
+            L.mcmcpp_hip_histograms_compute.argtypes = [vp, C.POINTER(vp), i64]
+            L.mcmcpp_hip_histograms_compute_device.argtypes = [vp, vp, i64, i64]
+            L.mcmcpp_hip_histograms_result.argtypes = [vp, C.POINTER(i64), vp, vp, vp, vp]
+            L.mcmcpp_hip_histograms_last_error.argtypes = [vp]
+            L.mcmcpp_hip_histograms_last_error.restype = C.c_char_p
         _lib = L
     return _lib
 
@@ -320,6 +331,61 @@ class HipMoments:
     def close(self):
         if self.h:
             lib().mcmcpp_hip_moments_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HipHistograms:
+    """Device-side Analysis::CornerHistograms / PercentileAndMaximumFinder (include/mcmcpp_hip.h, mcmcpp_hip_histograms_*)."""
+
+    def __init__(self, num_walkers, num_params, bins, with_pairs=True, dtype=F64, device=-1):
+        self.W, self.P, self.bins, self.with_pairs, self.dtype = num_walkers, num_params, bins, bool(with_pairs), dtype
+        self.h = C.c_void_p()
+        rc = lib().mcmcpp_hip_histograms_create(dtype, device, num_walkers, num_params, bins, 1 if with_pairs else 0, C.byref(self.h))
+        if rc != OK:
+            self.h = C.c_void_p()
+            raise HipError(rc, (lib().mcmcpp_hip_histograms_last_error(None) or b"").decode())
+
+    def _check(self, rc):
+        if rc != OK:
+            raise HipError(rc, (lib().mcmcpp_hip_histograms_last_error(self.h) or b"").decode())
+
+    def compute(self, steps, slice_interval=1):
+        """steps: array [(n, W, P)] or a sequence of arrays [(W, P)]; every slice_interval-th step is used, starting with the first."""
+        if isinstance(steps, np.ndarray):
+            steps = np.ascontiguousarray(steps, dtype=np_dtype(self.dtype))
+            assert steps.ndim == 3 and steps.shape[1:] == (self.W, self.P)
+            blocks = [steps[k] for k in range(0, steps.shape[0], slice_interval)]
+        else:
+            blocks = [np.ascontiguousarray(b, dtype=np_dtype(self.dtype)) for b in list(steps)[::slice_interval]]
+            assert all(b.shape == (self.W, self.P) for b in blocks)
+        ptrs = (C.c_void_p * max(1, len(blocks)))(*[b.ctypes.data for b in blocks])
+        self._keep = blocks
+        self._check(lib().mcmcpp_hip_histograms_compute(self.h, ptrs, len(blocks)))
+
+    def compute_device(self, device_ptr, n_steps, slice_interval=1):
+        """n_steps contiguous stored steps in device memory (an integer address, e.g. torch.Tensor.data_ptr())."""
+        self._check(lib().mcmcpp_hip_histograms_compute_device(self.h, C.c_void_p(device_ptr), n_steps, slice_interval))
+
+    def result(self, want_pairs=None):
+        """(num_points, bounds[(P, 2)] in the chain's type, single[(P, bins)], pairs[(P(P-1)/2, bins, bins)] or None, clamped[P])"""
+        want_pairs = self.with_pairs if want_pairs is None else want_pairs
+        n = C.c_int64(0)
+        bounds = np.zeros((self.P, 2), np_dtype(self.dtype))
+        single = np.zeros((self.P, self.bins), np.int64)
+        pairs = np.zeros((self.P * (self.P - 1) // 2, self.bins, self.bins), np.int64) if want_pairs else None
+        clamped = np.zeros(self.P, np.int64)
+        self._check(lib().mcmcpp_hip_histograms_result(self.h, C.byref(n), _ptr(bounds), _ptr(single), _ptr(pairs), _ptr(clamped)))
+        return n.value, bounds, single, pairs, clamped
+
+    def close(self):
+        if self.h:
+            lib().mcmcpp_hip_histograms_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

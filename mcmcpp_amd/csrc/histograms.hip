@@ -1,0 +1,654 @@
+// histograms.hip -- 1-D histograms of every parameter and 2-D histograms of every parameter pair of stored chain steps:
+// the device side of Analysis::CornerHistograms and Analysis::PercentileAndMaximumFinder (reference:
+// MCMCpp/Analysis/CornerHistograms.h, PercentileAndMaximumFinder.h).
+//
+// Both reference classes bin the same way: per parameter the minimum and maximum of the samples used (start values
+// numeric_limits<T>::max() / ::min(), strict comparisons), a small tweak of the two bounds, width = (hi - lo) / bins,
+// and bin = int((x - lo) / width), all in T.  Here:
+//   * bounds pass: per-block minimum / maximum of every parameter (strict comparisons, the reference's start values),
+//     combined on the host; min and max are exact in any order.  A NaN sample fails the call.
+//   * the tweak and the width are computed on the host in T (this file is built with -ffp-contract=off);
+//   * bin pass: every selected sample's bin of every parameter, (x - lo) / width as a correctly rounded division in T,
+//     truncated toward zero, written as a column-major index array [P][n] of u8 / u16 / u32.  A bin outside [0, bins)
+//     (the reference's upper-bound tweak puts every positive maximum above the range; its behaviour there is undefined)
+//     is clamped into bin 0 or bins - 1 and counted per parameter;
+//   * 1-D histograms: one block per (slice of samples, parameter), counters privatised in LDS (u32), flushed with
+//     64-bit integer atomics; global 64-bit atomics where the bins do not fit;
+//   * 2-D histograms: one block per (slice of samples, tile of pairs), the tile's pair histograms privatised in LDS,
+//     fed from the two index columns of each pair, flushed with 64-bit integer atomics; global 64-bit atomics where one
+//     pair histogram does not fit.
+// Every count is an integer sum: results are bit-reproducible and independent of scheduling and chunking.
+// Host chains are uploaded in chunks of MCMCPP_HIP_HIST_CHUNK_MB (read at create, default 1024); a selection that fits
+// in one chunk is uploaded once and serves both passes, a larger one is uploaded twice.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/mcmcpp_hip.h"
+
+namespace
+{
+constexpr int kHistThreads = 256;
+
+template <class T>
+__device__ __forceinline__ const T* sample_row(const T* base, long long step_stride, unsigned W, int P, unsigned s)
+{
+    return base + (size_t)(s / W) * (size_t)step_stride + (size_t)(s % W) * (size_t)P;
+}
+
+// per-block minimum / maximum of every parameter over samples [blockIdx.x * per, ...): part[block][P][2]
+template <class T>
+__global__ void __launch_bounds__(kHistThreads)
+hist_bounds_kernel(const T* base, long long step_stride, unsigned W, int P, unsigned n, unsigned per, T* part, int* nan_flag)
+{
+    __shared__ T s_lo[kHistThreads], s_hi[kHistThreads];
+    const unsigned s0 = blockIdx.x * per;
+    const unsigned s1 = (n - s0 < per) ? n : s0 + per;
+    const int tid = threadIdx.x;
+    bool nan = false;
+    for (int p0 = 0; p0 < P; p0 += kHistThreads)
+    {
+        const int pt = (P - p0 < kHistThreads) ? P - p0 : kHistThreads;
+        const int rows = kHistThreads / pt;
+        T lo = std::numeric_limits<T>::max(), hi = std::numeric_limits<T>::min();
+        if (tid < rows * pt)
+        {
+            const int p = p0 + tid % pt;
+            for (unsigned s = s0 + tid / pt; s < s1; s += rows)
+            {
+                const T x = sample_row(base, step_stride, W, P, s)[p];
+                nan |= (x != x);
+                if (x < lo) lo = x;
+                if (x > hi) hi = x;
+            }
+        }
+        __syncthreads();
+        s_lo[tid] = lo;
+        s_hi[tid] = hi;
+        __syncthreads();
+        if (tid < pt)
+        {
+            for (int r = 1; r < rows; ++r)
+            {
+                if (s_lo[r * pt + tid] < lo) lo = s_lo[r * pt + tid];
+                if (s_hi[r * pt + tid] > hi) hi = s_hi[r * pt + tid];
+            }
+            T* o = part + ((size_t)blockIdx.x * P + p0 + tid) * 2;
+            o[0] = lo;
+            o[1] = hi;
+        }
+    }
+    if (nan) atomicOr(nan_flag, 1);
+}
+
+// bin of every (sample, parameter): idx[p * col + s]; out-of-range bins clamped and counted
+template <class T, class I>
+__global__ void __launch_bounds__(kHistThreads)
+hist_bin_kernel(const T* base, long long step_stride, unsigned W, int P, unsigned n, const T* edges, int bins, I* idx, size_t col,
+                unsigned long long* clamped)
+{
+    const double top = (double)bins;
+    for (unsigned s = blockIdx.x * kHistThreads + threadIdx.x; s < n; s += gridDim.x * kHistThreads)
+    {
+        const T* row = sample_row(base, step_stride, W, P, s);
+        for (int p = 0; p < P; ++p)
+        {
+            const T q = (row[p] - edges[2 * p]) / edges[2 * p + 1];
+            const double qd = (double)q;
+            int b;
+            if (qd >= top)
+                b = bins - 1;
+            else if (!(qd > -1.0))
+                b = 0;
+            else
+                b = -1;
+            if (b >= 0)
+                atomicAdd(&clamped[p], 1ull);
+            else
+                b = (int)q;  // in (-1, bins): truncation toward zero lands in [0, bins)
+            idx[(size_t)p * col + s] = (I)b;
+        }
+    }
+}
+
+// 1-D histograms: block (slice, p); LDS counters when `lds` (dynamic size bins * 4), else global atomics
+template <class I>
+__global__ void __launch_bounds__(kHistThreads)
+hist_single_kernel(const I* idx, size_t col, unsigned n, unsigned per, int bins, int lds, unsigned long long* single)
+{
+    extern __shared__ unsigned s_cnt[];
+    const int p = blockIdx.y;
+    const unsigned s0 = blockIdx.x * per;
+    const unsigned s1 = (n - s0 < per) ? n : s0 + per;
+    const I* c = idx + (size_t)p * col;
+    unsigned long long* out = single + (size_t)p * bins;
+    if (lds)
+    {
+        for (int b = threadIdx.x; b < bins; b += kHistThreads) s_cnt[b] = 0;
+        __syncthreads();
+        for (unsigned s = s0 + threadIdx.x; s < s1; s += kHistThreads) atomicAdd(&s_cnt[c[s]], 1u);
+        __syncthreads();
+        for (int b = threadIdx.x; b < bins; b += kHistThreads)
+            if (s_cnt[b]) atomicAdd(&out[b], (unsigned long long)s_cnt[b]);
+    }
+    else
+        for (unsigned s = s0 + threadIdx.x; s < s1; s += kHistThreads) atomicAdd(&out[c[s]], 1ull);
+}
+
+// 2-D histograms: block (slice, tile of `tile` pairs); pair q = (i, j) from ij[2q], ij[2q+1]; element [bin_i][bin_j]
+template <class I>
+__global__ void __launch_bounds__(kHistThreads)
+hist_pairs_kernel(const I* idx, size_t col, unsigned n, unsigned per, int bins, const int* ij, long long npairs, int tile, int lds,
+                  unsigned long long* pairs)
+{
+    extern __shared__ unsigned s_cnt[];
+    const unsigned s0 = blockIdx.x * per;
+    const unsigned s1 = (n - s0 < per) ? n : s0 + per;
+    const long long q0 = (long long)blockIdx.y * tile;
+    const int count = (npairs - q0 < tile) ? (int)(npairs - q0) : tile;
+    const size_t b2 = (size_t)bins * bins;
+    if (lds)
+    {
+        const int cells = count * (int)b2;
+        for (int e = threadIdx.x; e < cells; e += kHistThreads) s_cnt[e] = 0;
+        __syncthreads();
+        for (int k = 0; k < count; ++k)
+        {
+            const I* ci = idx + (size_t)ij[2 * (q0 + k)] * col;
+            const I* cj = idx + (size_t)ij[2 * (q0 + k) + 1] * col;
+            unsigned* h = s_cnt + (size_t)k * b2;
+            for (unsigned s = s0 + threadIdx.x; s < s1; s += kHistThreads) atomicAdd(&h[(unsigned)ci[s] * bins + cj[s]], 1u);
+        }
+        __syncthreads();
+        unsigned long long* out = pairs + (size_t)q0 * b2;
+        for (int e = threadIdx.x; e < cells; e += kHistThreads)
+            if (s_cnt[e]) atomicAdd(&out[e], (unsigned long long)s_cnt[e]);
+    }
+    else
+        for (int k = 0; k < count; ++k)
+        {
+            const I* ci = idx + (size_t)ij[2 * (q0 + k)] * col;
+            const I* cj = idx + (size_t)ij[2 * (q0 + k) + 1] * col;
+            unsigned long long* out = pairs + (size_t)(q0 + k) * b2;
+            for (unsigned s = s0 + threadIdx.x; s < s1; s += kHistThreads) atomicAdd(&out[(size_t)ci[s] * bins + cj[s]], 1ull);
+        }
+}
+}  // namespace
+
+struct mcmcpp_hip_histograms
+{
+    std::string error;
+    int dtype = 0, device = 0, W = 0, P = 0, bins = 0, cus = 0;
+    bool with_pairs = false;
+    long long npairs = 0;
+    size_t chunk_bytes = 0;        // MCMCPP_HIP_HIST_CHUNK_MB
+    size_t lds_limit = 0;          // dynamic LDS per block for the counters
+    int idx_bytes = 1;             // 1 / 2 / 4 (bins <= 256 / <= 65536 / more)
+    unsigned long long *d_single = nullptr, *d_pairs = nullptr, *d_clamped = nullptr;
+    int* d_ij = nullptr;           // [npairs][2]
+    int* d_nan = nullptr;
+    void* d_edges = nullptr;       // [P][2] (low edge, width) in T
+    void* d_part = nullptr;        // bounds partials
+    size_t part_cap = 0;
+    void* d_chunk = nullptr;       // host path upload buffer
+    size_t chunk_cap = 0;
+    void* d_idx = nullptr;         // bin indices [P][col]
+    size_t idx_cap = 0;
+    hipStream_t stream = nullptr;
+    bool have_result = false;
+    long long points = 0;
+    std::vector<unsigned char> bounds;  // [P][2] in T
+};
+
+namespace
+{
+thread_local std::string g_hist_error;
+
+int fail(mcmcpp_hip_histograms* h, int code, const std::string& msg, hipError_t e = hipSuccess)
+{
+    std::string m = msg;
+    if (e != hipSuccess) m += std::string(": ") + hipGetErrorString(e);
+    if (h)
+        h->error = m;
+    else
+        g_hist_error = m;
+    return code;
+}
+
+#define HIST_TRY(expr)                                                     \
+    do                                                                     \
+    {                                                                      \
+        hipError_t e_ = (expr);                                            \
+        if (e_ != hipSuccess) return fail(h, MCMCPP_HIP_E_HIP, #expr, e_); \
+    } while (0)
+
+int ensure(mcmcpp_hip_histograms* h, void** buf, size_t* cap, size_t bytes, const char* what)
+{
+    if (*cap >= bytes) return MCMCPP_HIP_OK;
+    HIST_TRY(hipStreamSynchronize(h->stream));
+    if (*buf) hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    if (hipMalloc(buf, bytes) != hipSuccess)
+    {
+        *buf = nullptr;
+        return fail(h, MCMCPP_HIP_E_NOMEM, std::string("histograms: cannot allocate ") + what + " (" + std::to_string(bytes) + " bytes)");
+    }
+    *cap = bytes;
+    return MCMCPP_HIP_OK;
+}
+
+// A source of selected samples: n_steps steps of W*P elements, step k at base + k * step_stride (elements)
+template <class T>
+struct Span
+{
+    const T* base;
+    long long step_stride;
+    long long n_steps;
+};
+
+template <class T>
+int bounds_pass(mcmcpp_hip_histograms* h, const Span<T>& sp, std::vector<T>& lo, std::vector<T>& hi)
+{
+    const unsigned n = (unsigned)(sp.n_steps * h->W);
+    if (n == 0) return MCMCPP_HIP_OK;
+    unsigned blocks = (unsigned)h->cus * 2;
+    if (blocks > (n + 255) / 256) blocks = (n + 255) / 256;
+    const unsigned per = (n + blocks - 1) / blocks;
+    blocks = (n + per - 1) / per;
+    const size_t pbytes = sizeof(T) * 2 * (size_t)blocks * h->P;
+    int rc = ensure(h, &h->d_part, &h->part_cap, pbytes, "the bounds partials");
+    if (rc) return rc;
+    hipLaunchKernelGGL((hist_bounds_kernel<T>), dim3(blocks), dim3(kHistThreads), 0, h->stream, sp.base, sp.step_stride, (unsigned)h->W, h->P,
+                       n, per, (T*)h->d_part, h->d_nan);
+    HIST_TRY(hipGetLastError());
+    std::vector<T> part(2 * (size_t)blocks * h->P);
+    HIST_TRY(hipMemcpyAsync(part.data(), h->d_part, pbytes, hipMemcpyDeviceToHost, h->stream));
+    HIST_TRY(hipStreamSynchronize(h->stream));
+    for (unsigned b = 0; b < blocks; ++b)
+        for (int p = 0; p < h->P; ++p)
+        {
+            const T l = part[((size_t)b * h->P + p) * 2], u = part[((size_t)b * h->P + p) * 2 + 1];
+            if (l < lo[p]) lo[p] = l;
+            if (u > hi[p]) hi[p] = u;
+        }
+    return MCMCPP_HIP_OK;
+}
+
+template <class T, class I>
+int count_pass_t(mcmcpp_hip_histograms* h, const Span<T>& sp)
+{
+    const unsigned n = (unsigned)(sp.n_steps * h->W);
+    if (n == 0) return MCMCPP_HIP_OK;
+    const size_t col = ((size_t)n + 15) & ~(size_t)15;
+    int rc = ensure(h, &h->d_idx, &h->idx_cap, sizeof(I) * col * h->P, "the bin index buffer");
+    if (rc) return rc;
+    I* idx = (I*)h->d_idx;
+    const int bins = h->bins;
+    {
+        unsigned blocks = (n + kHistThreads - 1) / kHistThreads;
+        if (blocks > (unsigned)h->cus * 8) blocks = (unsigned)h->cus * 8;
+        hipLaunchKernelGGL((hist_bin_kernel<T, I>), dim3(blocks), dim3(kHistThreads), 0, h->stream, sp.base, sp.step_stride, (unsigned)h->W,
+                           h->P, n, (const T*)h->d_edges, bins, idx, col, h->d_clamped);
+        HIST_TRY(hipGetLastError());
+    }
+    // slices of samples: enough blocks to fill the device, each slice long enough to amortise its flush
+    auto slices_for = [&](long long columns, long long flush_cells) {
+        long long want = ((long long)h->cus * 4 + columns - 1) / columns;
+        const long long most = (long long)n / (flush_cells * 4 > 1024 ? flush_cells * 4 : 1024);
+        if (want > most) want = most;
+        if (want < 1) want = 1;
+        return (unsigned)want;
+    };
+    {
+        const int lds = (size_t)bins * 4 <= h->lds_limit;
+        const unsigned slices = slices_for(h->P, lds ? bins : 1);
+        const unsigned per = (n + slices - 1) / slices;
+        hipLaunchKernelGGL((hist_single_kernel<I>), dim3((n + per - 1) / per, h->P), dim3(kHistThreads), lds ? (size_t)bins * 4 : 0, h->stream,
+                           idx, col, n, per, bins, lds, h->d_single);
+        HIST_TRY(hipGetLastError());
+    }
+    if (h->with_pairs && h->npairs > 0)
+    {
+        const size_t b2 = (size_t)bins * bins;
+        const int lds = b2 * 4 <= h->lds_limit;
+        int tile = lds ? (int)(h->lds_limit / (b2 * 4)) : 1;
+        if (tile > 64) tile = 64;
+        // keep enough tiles to fill the device
+        while (tile > 1 && (h->npairs + tile - 1) / tile < (long long)h->cus * 2) tile /= 2;
+        const long long tiles = (h->npairs + tile - 1) / tile;
+        const unsigned slices = slices_for(tiles, lds ? (long long)(tile * b2) : 1);
+        const unsigned per = (n + slices - 1) / slices;
+        for (long long t0 = 0; t0 < tiles; t0 += 65535)  // grid.y limit
+        {
+            const long long now = (tiles - t0 < 65535) ? tiles - t0 : 65535;
+            const long long q0 = t0 * tile;
+            hipLaunchKernelGGL((hist_pairs_kernel<I>), dim3((n + per - 1) / per, (unsigned)now), dim3(kHistThreads), lds ? (size_t)tile * b2 * 4 : 0,
+                               h->stream, idx, col, n, per, bins, h->d_ij + 2 * q0, h->npairs - q0, tile, lds, h->d_pairs + (size_t)q0 * b2);
+            HIST_TRY(hipGetLastError());
+        }
+    }
+    return MCMCPP_HIP_OK;
+}
+
+template <class T>
+int count_pass(mcmcpp_hip_histograms* h, const Span<T>& sp)
+{
+    switch (h->idx_bytes)
+    {
+    case 1: return count_pass_t<T, uint8_t>(h, sp);
+    case 2: return count_pass_t<T, uint16_t>(h, sp);
+    default: return count_pass_t<T, uint32_t>(h, sp);
+    }
+}
+
+template <class T>
+int sign_of(T v)
+{
+    return (T(0) < v) - (v < T(0));
+}
+
+// the reference's findBinning after its extremum search (CornerHistograms.h / PercentileAndMaximumFinder.h): bound tweak,
+// then the width; in T, operation for operation
+template <class T>
+void finish_bounds(mcmcpp_hip_histograms* h, const std::vector<T>& lo_in, const std::vector<T>& hi_in)
+{
+    const T expand = static_cast<T>(1.001), contract = static_cast<T>(0.999), minSize = static_cast<T>(0.001);
+    h->bounds.assign(sizeof(T) * 2 * (size_t)h->P, 0);
+    T* b = (T*)h->bounds.data();
+    for (int p = 0; p < h->P; ++p)
+    {
+        T lo = lo_in[p], hi = hi_in[p];
+        if (lo == hi)
+        {
+            if (lo != T(0))
+            {
+                if (sign_of(lo) == 1)
+                {
+                    lo *= contract;
+                    hi *= expand;
+                }
+                else
+                {
+                    lo *= expand;
+                    hi *= contract;
+                }
+            }
+            else
+            {
+                lo = -minSize;
+                hi = minSize;
+            }
+        }
+        else
+        {
+            int s = sign_of(lo);
+            if (s == -1)
+                lo *= expand;
+            else if (s == 0)
+                lo = -minSize;
+            else
+                lo *= contract;
+            s = sign_of(hi);
+            if (s == -1)
+                hi *= expand;
+            else if (s == 0)
+                hi = minSize;
+            else
+                hi *= contract;
+        }
+        b[2 * p] = lo;
+        b[2 * p + 1] = (hi - lo) / static_cast<T>(h->bins);
+    }
+}
+
+int reset_counts(mcmcpp_hip_histograms* h)
+{
+    h->have_result = false;
+    HIST_TRY(hipMemsetAsync(h->d_single, 0, sizeof(unsigned long long) * (size_t)h->P * h->bins, h->stream));
+    if (h->d_pairs) HIST_TRY(hipMemsetAsync(h->d_pairs, 0, sizeof(unsigned long long) * (size_t)h->npairs * h->bins * h->bins, h->stream));
+    HIST_TRY(hipMemsetAsync(h->d_clamped, 0, sizeof(unsigned long long) * h->P, h->stream));
+    HIST_TRY(hipMemsetAsync(h->d_nan, 0, sizeof(int), h->stream));
+    return MCMCPP_HIP_OK;
+}
+
+template <class T>
+int after_bounds(mcmcpp_hip_histograms* h, const std::vector<T>& lo, const std::vector<T>& hi)
+{
+    int nan = 0;
+    HIST_TRY(hipMemcpyAsync(&nan, h->d_nan, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIST_TRY(hipStreamSynchronize(h->stream));
+    if (nan) return fail(h, MCMCPP_HIP_E_ARG, "histograms: the selected samples contain a NaN (the reference would index with int(NaN))");
+    finish_bounds<T>(h, lo, hi);
+    HIST_TRY(hipMemcpyAsync(h->d_edges, h->bounds.data(), h->bounds.size(), hipMemcpyHostToDevice, h->stream));
+    return MCMCPP_HIP_OK;
+}
+
+// samples per pass-2 chunk: bounded by the chunk size (through the index buffer) and by 32-bit sample indexing
+long long steps_per_chunk(const mcmcpp_hip_histograms* h, size_t step_bytes)
+{
+    long long k = (long long)(h->chunk_bytes / step_bytes);
+    const long long cap = ((long long)1 << 31) / h->W - 1;
+    if (k > cap) k = cap;
+    return k < 1 ? 1 : k;
+}
+
+template <class T>
+int compute_host(mcmcpp_hip_histograms* h, const void* const* steps, int64_t n_steps)
+{
+    const size_t step_elems = (size_t)h->W * h->P, step_bytes = sizeof(T) * step_elems;
+    const long long per = steps_per_chunk(h, step_bytes);
+    const long long first_chunk = n_steps < per ? n_steps : per;
+    int rc = ensure(h, &h->d_chunk, &h->chunk_cap, step_bytes * (size_t)(first_chunk > 0 ? first_chunk : 1), "the upload buffer");
+    if (rc) return rc;
+    auto upload = [&](long long k0, long long now) -> int {
+        HIST_TRY(hipStreamSynchronize(h->stream));  // the previous chunk's kernels have read the buffer
+        for (long long k = 0; k < now;)
+        {
+            // a run of steps that are contiguous in host memory goes in one copy
+            const char* src = (const char*)steps[k0 + k];
+            long long run = 1;
+            while (k + run < now && (const char*)steps[k0 + k + run] == src + step_bytes * (size_t)run) ++run;
+            HIST_TRY(hipMemcpyAsync((char*)h->d_chunk + step_bytes * (size_t)k, src, step_bytes * (size_t)run, hipMemcpyHostToDevice, h->stream));
+            k += run;
+        }
+        return MCMCPP_HIP_OK;
+    };
+    std::vector<T> lo(h->P, std::numeric_limits<T>::max()), hi(h->P, std::numeric_limits<T>::min());
+    const Span<T> whole{(const T*)h->d_chunk, (long long)step_elems, 0};
+    for (long long k0 = 0; k0 < n_steps; k0 += per)
+    {
+        const long long now = (n_steps - k0 < per) ? n_steps - k0 : per;
+        if ((rc = upload(k0, now))) return rc;
+        Span<T> sp = whole;
+        sp.n_steps = now;
+        if ((rc = bounds_pass<T>(h, sp, lo, hi))) return rc;
+    }
+    if ((rc = after_bounds<T>(h, lo, hi))) return rc;
+    for (long long k0 = 0; k0 < n_steps; k0 += per)
+    {
+        const long long now = (n_steps - k0 < per) ? n_steps - k0 : per;
+        if (n_steps > per && (rc = upload(k0, now))) return rc;  // one chunk: still resident from the bounds pass
+        Span<T> sp = whole;
+        sp.n_steps = now;
+        if ((rc = count_pass<T>(h, sp))) return rc;
+    }
+    HIST_TRY(hipStreamSynchronize(h->stream));
+    h->points = (long long)n_steps * h->W;
+    h->have_result = true;
+    return MCMCPP_HIP_OK;
+}
+
+template <class T>
+int compute_device(mcmcpp_hip_histograms* h, const T* d, int64_t n_steps, int64_t slice)
+{
+    const size_t step_elems = (size_t)h->W * h->P;
+    const long long used = (n_steps + slice - 1) / slice;
+    const long long per = steps_per_chunk(h, sizeof(T) * step_elems);
+    std::vector<T> lo(h->P, std::numeric_limits<T>::max()), hi(h->P, std::numeric_limits<T>::min());
+    int rc;
+    for (int pass = 0; pass < 2; ++pass)
+    {
+        for (long long k0 = 0; k0 < used; k0 += per)
+        {
+            const long long now = (used - k0 < per) ? used - k0 : per;
+            const Span<T> sp{d + (size_t)(k0 * slice) * step_elems, (long long)(slice * (long long)step_elems), now};
+            if ((rc = pass == 0 ? bounds_pass<T>(h, sp, lo, hi) : count_pass<T>(h, sp))) return rc;
+        }
+        if (pass == 0 && (rc = after_bounds<T>(h, lo, hi))) return rc;
+    }
+    HIST_TRY(hipStreamSynchronize(h->stream));
+    h->points = (long long)used * h->W;
+    h->have_result = true;
+    return MCMCPP_HIP_OK;
+}
+}  // namespace
+
+extern "C"
+{
+const char* mcmcpp_hip_histograms_last_error(const mcmcpp_hip_histograms* h) { return h ? h->error.c_str() : g_hist_error.c_str(); }
+
+int mcmcpp_hip_histograms_create(int32_t dtype, int32_t device, int32_t num_walkers, int32_t num_params, int32_t bins, int32_t with_pairs,
+                                 mcmcpp_hip_histograms** out)
+{
+    mcmcpp_hip_histograms* h = nullptr;
+    if (!out) return fail(h, MCMCPP_HIP_E_ARG, "histograms_create: out is NULL");
+    *out = nullptr;
+    if ((dtype != MCMCPP_HIP_F64 && dtype != MCMCPP_HIP_F32) || num_walkers < 1 || num_params < 1 || num_params > 65535 || bins < 2)
+        return fail(h, MCMCPP_HIP_E_ARG, "histograms_create: dtype must be F64/F32, num_walkers >= 1, 1 <= num_params <= 65535, bins >= 2");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(h, MCMCPP_HIP_E_NO_DEVICE, "no HIP device visible to this process");
+    if (device >= ndev) return fail(h, MCMCPP_HIP_E_NO_DEVICE, "histograms_create: device out of range");
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) return fail(h, MCMCPP_HIP_E_HIP, "hipGetDevice failed");
+    hipDeviceProp_t prop;
+    if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess)
+        return fail(h, MCMCPP_HIP_E_HIP, "histograms_create: cannot select the device");
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(h, MCMCPP_HIP_E_NO_DEVICE, "this library is built for gfx950 only");
+    const long long npairs = with_pairs ? (long long)num_params * (num_params - 1) / 2 : 0;
+    // the 64-bit result arrays; refuse what cannot be addressed before asking the allocator
+    const double pair_bytes = (double)npairs * (double)bins * (double)bins * 8.0;
+    const double single_bytes = (double)num_params * (double)bins * 8.0;
+    if (pair_bytes > (double)((size_t)1 << 50) || single_bytes > (double)((size_t)1 << 50))
+    {
+        char msg[200];
+        std::snprintf(msg, sizeof msg, "histograms_create: the 64-bit result arrays would take %.3g bytes", pair_bytes + single_bytes);
+        return fail(h, MCMCPP_HIP_E_NOMEM, msg);
+    }
+    h = new (std::nothrow) mcmcpp_hip_histograms();
+    if (!h) return fail(nullptr, MCMCPP_HIP_E_NOMEM, "histograms_create: out of host memory");
+    h->dtype = dtype;
+    h->device = device;
+    h->W = num_walkers;
+    h->P = num_params;
+    h->bins = bins;
+    h->with_pairs = with_pairs != 0;
+    h->npairs = npairs;
+    h->cus = prop.multiProcessorCount;
+    h->lds_limit = prop.sharedMemPerBlock < (size_t)65536 ? prop.sharedMemPerBlock : (size_t)65536;
+    h->idx_bytes = bins <= 256 ? 1 : (bins <= 65536 ? 2 : 4);
+    size_t mb = 1024;
+    if (const char* env = std::getenv("MCMCPP_HIP_HIST_CHUNK_MB"))
+    {
+        const long long v = std::atoll(env);
+        if (v >= 1) mb = (size_t)v;
+    }
+    h->chunk_bytes = mb << 20;
+    const size_t esize = dtype == MCMCPP_HIP_F64 ? 8 : 4;
+    auto bad = [&](int code, const std::string& what) {
+        g_hist_error = what;
+        mcmcpp_hip_histograms_destroy(h);
+        return code;
+    };
+    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bad(MCMCPP_HIP_E_HIP, "histograms_create: cannot create a stream");
+    if (hipMalloc(&h->d_single, (size_t)single_bytes) != hipSuccess || hipMalloc(&h->d_clamped, 8 * (size_t)num_params) != hipSuccess ||
+        hipMalloc(&h->d_nan, sizeof(int)) != hipSuccess || hipMalloc(&h->d_edges, 2 * esize * (size_t)num_params) != hipSuccess)
+        return bad(MCMCPP_HIP_E_NOMEM, "histograms_create: cannot allocate device memory");
+    if (npairs > 0)
+    {
+        if (hipMalloc(&h->d_pairs, (size_t)pair_bytes) != hipSuccess)
+        {
+            h->d_pairs = nullptr;
+            (void)hipGetLastError();
+            return bad(MCMCPP_HIP_E_NOMEM, "histograms_create: cannot allocate the " + std::to_string((size_t)pair_bytes) +
+                                               "-byte 64-bit pair histograms (" + std::to_string(npairs) + " pairs of " + std::to_string(bins) +
+                                               " x " + std::to_string(bins) + " bins)");
+        }
+        std::vector<int> ij(2 * (size_t)npairs);
+        size_t q = 0;
+        for (int i = 1; i < num_params; ++i)
+            for (int j = 0; j < i; ++j, ++q)
+            {
+                ij[2 * q] = i;
+                ij[2 * q + 1] = j;
+            }
+        if (hipMalloc(&h->d_ij, sizeof(int) * ij.size()) != hipSuccess) return bad(MCMCPP_HIP_E_NOMEM, "histograms_create: cannot allocate the pair table");
+        if (hipMemcpy(h->d_ij, ij.data(), sizeof(int) * ij.size(), hipMemcpyHostToDevice) != hipSuccess)
+            return bad(MCMCPP_HIP_E_HIP, "histograms_create: cannot upload the pair table");
+    }
+    *out = h;
+    return MCMCPP_HIP_OK;
+}
+
+void mcmcpp_hip_histograms_destroy(mcmcpp_hip_histograms* h)
+{
+    if (!h) return;
+    hipSetDevice(h->device);
+    if (h->stream) hipStreamSynchronize(h->stream);
+    for (void* p : {(void*)h->d_single, (void*)h->d_pairs, (void*)h->d_clamped, (void*)h->d_ij, (void*)h->d_nan, h->d_edges, h->d_part, h->d_chunk,
+                    h->d_idx})
+        if (p) hipFree(p);
+    if (h->stream) hipStreamDestroy(h->stream);
+    delete h;
+}
+
+int mcmcpp_hip_histograms_compute(mcmcpp_hip_histograms* h, const void* const* steps, int64_t n_steps)
+{
+    if (!h) return MCMCPP_HIP_E_ARG;
+    h->have_result = false;
+    if (n_steps < 0 || (n_steps > 0 && !steps)) return fail(h, MCMCPP_HIP_E_ARG, "histograms_compute: bad arguments");
+    for (int64_t k = 0; k < n_steps; ++k)
+        if (!steps[k]) return fail(h, MCMCPP_HIP_E_ARG, "histograms_compute: a step pointer is NULL");
+    HIST_TRY(hipSetDevice(h->device));
+    int rc = reset_counts(h);
+    if (rc) return rc;
+    return h->dtype == MCMCPP_HIP_F64 ? compute_host<double>(h, steps, n_steps) : compute_host<float>(h, steps, n_steps);
+}
+
+int mcmcpp_hip_histograms_compute_device(mcmcpp_hip_histograms* h, const void* device_steps, int64_t n_steps, int64_t slice_interval)
+{
+    if (!h) return MCMCPP_HIP_E_ARG;
+    h->have_result = false;
+    if (n_steps < 0 || slice_interval < 1 || (n_steps > 0 && !device_steps))
+        return fail(h, MCMCPP_HIP_E_ARG, "histograms_compute_device: bad arguments");
+    HIST_TRY(hipSetDevice(h->device));
+    int rc = reset_counts(h);
+    if (rc) return rc;
+    return h->dtype == MCMCPP_HIP_F64 ? compute_device<double>(h, (const double*)device_steps, n_steps, slice_interval)
+                                      : compute_device<float>(h, (const float*)device_steps, n_steps, slice_interval);
+}
+
+int mcmcpp_hip_histograms_result(const mcmcpp_hip_histograms* hc, int64_t* num_points, void* bounds, int64_t* single, int64_t* pairs,
+                                 int64_t* clamped)
+{
+    mcmcpp_hip_histograms* h = const_cast<mcmcpp_hip_histograms*>(hc);
+    if (!h) return MCMCPP_HIP_E_ARG;
+    if (!h->have_result) return fail(h, MCMCPP_HIP_E_STATE, "histograms_result: no successful compute since creation or the last failure");
+    if (pairs && !h->with_pairs) return fail(h, MCMCPP_HIP_E_ARG, "histograms_result: this handle was created without pair histograms");
+    HIST_TRY(hipSetDevice(h->device));
+    if (single) HIST_TRY(hipMemcpyAsync(single, h->d_single, 8 * (size_t)h->P * h->bins, hipMemcpyDeviceToHost, h->stream));
+    if (pairs && h->npairs > 0)
+        HIST_TRY(hipMemcpyAsync(pairs, h->d_pairs, 8 * (size_t)h->npairs * h->bins * h->bins, hipMemcpyDeviceToHost, h->stream));
+    if (clamped) HIST_TRY(hipMemcpyAsync(clamped, h->d_clamped, 8 * (size_t)h->P, hipMemcpyDeviceToHost, h->stream));
+    HIST_TRY(hipStreamSynchronize(h->stream));
+    if (bounds) std::memcpy(bounds, h->bounds.data(), h->bounds.size());
+    if (num_points) *num_points = h->points;
+    return MCMCPP_HIP_OK;
+}
+}
