@@ -40,8 +40,10 @@ namespace MCMC
 namespace Device
 {
 
-/// Identifiers of the device functors built into libmcmcpp_hip.so (values = MCMCPP_HIP_CALC_*).
-enum CalcId : int { IsoGaussianId = 0, DenseGaussianId = 1, RosenbrockId = 2, SkewedGaussian2DId = 3 };
+/// Identifiers of the device functors built into libmcmcpp_hip.so (values = MCMCPP_HIP_CALC_*).  BatchCalcId names no
+/// functor: a Calculator with that id evaluates whole half-steps of proposals itself (hipBatchLogPostProb, see
+/// Utility::CheckBatchCalculator and INTEGRATION.md, "Batch targets").
+enum CalcId : int { IsoGaussianId = 0, DenseGaussianId = 1, RosenbrockId = 2, SkewedGaussian2DId = 3, BatchCalcId = 4 };
 
 namespace Detail
 {

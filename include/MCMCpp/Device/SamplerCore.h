@@ -27,12 +27,43 @@
 #include "../Chain/Chain.h"
 #include "../Utility/NoAction.h"
 #include "../Utility/UserOjbectsTest.h"
+#include "Calculators.h"
 #include "HipBackend.h"
 
 namespace MCMC
 {
 namespace Device
 {
+
+namespace Detail
+{
+/// How a Calculator reaches the device: a device functor named by hipCalcId with a parameter blob (the default), or a
+/// batch target whose hipBatchLogPostProb the library calls back once per half-step (MCMCPP_HIP_CALC_BATCH).
+template <class Calc, class ParamType, bool Batch = Utility::CheckBatchCalculator<Calc, ParamType>::value>
+struct CalcBinding
+{
+    static const ParamType* params(const Calc& c) { return c.hipParams(); }
+    static int paramCount(const Calc& c) { return c.hipParamCount(); }
+    static void bind(const HipHandle&, Calc&) {}
+};
+template <class Calc, class ParamType>
+struct CalcBinding<Calc, ParamType, true>
+{
+    static_assert(Calc::hipCalcId == BatchCalcId, "a Calculator with hipBatchLogPostProb declares hipCalcId = MCMC::Device::BatchCalcId");
+    static const ParamType* params(const Calc&) { return nullptr; }
+    static int paramCount(const Calc&) { return 0; }
+    static int call(void* user, const void* proposals, void* logpOut, std::int64_t count, std::int32_t numParams, void* hipStream)
+    {
+        return static_cast<Calc*>(user)->hipBatchLogPostProb(static_cast<const ParamType*>(proposals), static_cast<long long>(count),
+                                                             static_cast<int>(numParams), static_cast<ParamType*>(logpOut), hipStream);
+    }
+    /// the sampler's own copy of the Calculator (inside its Mover) is the callback's user pointer
+    static void bind(const HipHandle& h, Calc& c)
+    {
+        h.check("mcmcpp_hip_set_batch_calculator", mcmcpp_hip_set_batch_calculator(h.get(), &call, &c, nullptr, nullptr));
+    }
+};
+}  // namespace Detail
 
 template <class ParamType, class Mover, class PostStepAction>
 class SamplerCore
@@ -62,8 +93,9 @@ public:
         cfg.num_walkers = numWalkers;
         cfg.num_params = numParams;
         cfg.calc_id = Mover::CalculatorType::hipCalcId;
-        cfg.calc_params = moveProposer.getCalculator().hipParams();
-        cfg.calc_params_len = moveProposer.getCalculator().hipParamCount();
+        typedef Detail::CalcBinding<typename Mover::CalculatorType, ParamType> Binding;
+        cfg.calc_params = Binding::params(moveProposer.getCalculator());
+        cfg.calc_params_len = Binding::paramCount(moveProposer.getCalculator());
         cfg.seed = static_cast<std::uint64_t>(static_cast<long long>(randSeed));  // sign-extends like MultiSampler::setPrng
         cfg.stream = static_cast<std::uint64_t>(stream);
         cfg.gw_alpha_num = Mover::DistributionType::Numerator;
@@ -75,6 +107,7 @@ public:
         {
             cfg.device = where.device(0);
             ranks[0].create(cfg);
+            Binding::bind(ranks[0], moveProposer.getCalculator());
             return;
         }
         // One ensemble split over G devices: one handle per device, all ranks of one RCCL communicator.  The communicator's

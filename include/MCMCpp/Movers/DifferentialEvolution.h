@@ -40,7 +40,7 @@ public:
     static_assert(Utility::CheckCalcLogPostProb<Calculator, ParamType, ParamType*>::value,
                   "DifferentialEvolution: the Calculator needs 'ParamType calcLogPostProb(ParamType* paramSet)'");
     static_assert(std::is_copy_constructible<Calculator>::value, "DifferentialEvolution: the Calculator must be copy constructible");
-    static_assert(Utility::CheckDeviceCalculator<Calculator>::value,
+    static_assert(Utility::CheckDeviceCalculator<Calculator>::value || Utility::CheckBatchCalculator<Calculator, ParamType>::value,
                   "DifferentialEvolution (MI355X): the Calculator must also name its device functor -- hipCalcId, hipParams(), "
                   "hipParamCount() -- see MCMCpp/Device/Calculators.h; arbitrary host code cannot run inside the GPU kernel");
 

@@ -47,7 +47,7 @@ public:
     static_assert(Utility::CheckCalcLogPostProb<Calculator, ParamType, ParamType*>::value,
                   "StretchMove: the Calculator needs 'ParamType calcLogPostProb(ParamType* paramSet)'");
     static_assert(std::is_copy_constructible<Calculator>::value, "StretchMove: the Calculator must be copy constructible");
-    static_assert(Utility::CheckDeviceCalculator<Calculator>::value,
+    static_assert(Utility::CheckDeviceCalculator<Calculator>::value || Utility::CheckBatchCalculator<Calculator, ParamType>::value,
                   "StretchMove (MI355X): the Calculator must also name its device functor -- hipCalcId, hipParams(), "
                   "hipParamCount() -- see MCMCpp/Device/Calculators.h; arbitrary host code cannot run inside the GPU kernel");
     static_assert(Utility::CheckFunctor<CustomDistribution, ParamType, ParamType>::value,

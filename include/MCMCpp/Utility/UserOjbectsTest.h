@@ -54,6 +54,11 @@ template <class C>
 using DeviceIdentityExpr = decltype(static_cast<int>(C::hipCalcId) + std::declval<const C&>().hipParamCount() +
                                     (std::declval<const C&>().hipParams() ? 1 : 0));
 
+template <class C, class P>
+using BatchIdentityExpr = decltype(static_cast<int>(C::hipCalcId) +
+                                   std::declval<C&>().hipBatchLogPostProb(std::declval<const P*>(), 0LL, 0, std::declval<P*>(),
+                                                                          std::declval<void*>()));
+
 template <bool Found, class Got, class Want>
 struct ReturnsExactly : std::false_type
 {
@@ -97,6 +102,14 @@ struct CheckCalcUpdateWalker
 /// `const ParamType* hipParams() const`, `int hipParamCount() const` (see Device/Calculators.h).
 template <class TestClass>
 struct CheckDeviceCalculator : Detail::Detect<void, Detail::DeviceIdentityExpr, TestClass>
+{
+};
+
+/// True when the Calculator is a batch target (MCMCPP_HIP_CALC_BATCH, include/mcmcpp_hip.h): `static const int hipCalcId =
+/// MCMC::Device::BatchCalcId` and `int hipBatchLogPostProb(const ParamType* dProposals, long long count, int numParams,
+/// ParamType* dLogp, void* hipStream)`, which evaluates `count` proposals that live in device memory.
+template <class TestClass, class ParamType>
+struct CheckBatchCalculator : Detail::Detect<void, Detail::BatchIdentityExpr, TestClass, ParamType>
 {
 };
 

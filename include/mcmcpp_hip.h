@@ -40,7 +40,8 @@ enum {
     MCMCPP_HIP_E_UNSUPPORTED = 4, /* configuration outside what the kernels were built for */
     MCMCPP_HIP_E_STATE = 5,       /* run/get before set_state */
     MCMCPP_HIP_E_NOMEM = 6,
-    MCMCPP_HIP_E_COMM = 7         /* the collective library (RCCL) is missing or one of its calls failed */
+    MCMCPP_HIP_E_COMM = 7,        /* the collective library (RCCL) is missing or one of its calls failed */
+    MCMCPP_HIP_E_CALLBACK = 8     /* the batch log-posterior callback returned non-zero (mcmcpp_hip_set_batch_calculator) */
 };
 
 /* ParamType of the reference templates */
@@ -52,7 +53,9 @@ enum {
     MCMCPP_HIP_CALC_ISO_GAUSSIAN = 0,      /* params: none                    */
     MCMCPP_HIP_CALC_DENSE_GAUSSIAN = 1,    /* params: P[D*D] row-major        */
     MCMCPP_HIP_CALC_ROSENBROCK = 2,        /* params: a, b, c                 */
-    MCMCPP_HIP_CALC_SKEWED_GAUSSIAN_2D = 3 /* params: epsilon; requires D == 2 */
+    MCMCPP_HIP_CALC_SKEWED_GAUSSIAN_2D = 3, /* params: epsilon; requires D == 2 */
+    MCMCPP_HIP_CALC_BATCH = 4               /* params: none; a host callback evaluates each half-step's proposals in one
+                                               batch (mcmcpp_hip_set_batch_calculator) */
 };
 
 /* calculator ids from here on belong to user plug-ins (mcmcpp_hip_register_calculator) */
@@ -141,6 +144,36 @@ int mcmcpp_hip_comm_unique_id(void* id_out);
  * Registering an id again replaces it (handles created earlier keep what they were created with). */
 int mcmcpp_hip_register_calculator(int32_t calc_id, const void* table_f64, const void* table_f32, int32_t params_len);
 
+/* Batch targets (calc_id MCMCPP_HIP_CALC_BATCH): the log-posterior is whatever the caller computes for a whole half-step
+ * of proposals at once -- a GEMM over a dataset, a neural-network density, a torch function.  Every update of a half-step
+ * reads only the other colour (StretchMove.h:105-113), so the W/2 proposals of a half-step are formed first (one kernel),
+ * evaluated in one batch by the callback, and accepted (a second kernel): the reference's loop, operation for operation.
+ * A callback that computes the same bits as a built-in Calculator reproduces that Calculator's chains bit for bit.
+ *
+ *   proposals  device memory, [count][num_params] row-major elements of the handle's dtype
+ *   logp_out   device memory, [count] elements: the callback writes logp of every proposal here
+ *   hip_stream the handle's launch stream (hipStream_t); the accept kernel follows on it
+ *
+ * Contract:
+ *   - the callback runs on the thread that executes the run: for mcmcpp_hip_run_async that is the handle's worker thread;
+ *   - it is called once per half-step with count = W/2; mcmcpp_hip_calc_logp calls it in chunks of at most W/2;
+ *   - it either enqueues its work on hip_stream or finishes that work before it returns;
+ *   - it returns 0 on success.  Any other value ends the run with MCMCPP_HIP_E_CALLBACK (the message names the value), and
+ *     the walker state counts as undefined until the next set_state.
+ * Steps are plain launches on the handle's one stream (propose, callback, accept per half-step; the per-step accepted
+ * count behind each black half-step): no graph capture, no parallel branches.  Refused at create: the differential-
+ * evolution mover, num_chains > 1, shards and communicators; mcmcpp_hip_half_step_async returns MCMCPP_HIP_E_UNSUPPORTED.
+ * set_state, run and calc_logp return MCMCPP_HIP_E_STATE until a callback has been set.
+ */
+typedef int (*mcmcpp_hip_batch_logp_fn)(void* user, const void* proposals, void* logp_out, int64_t count, int32_t num_params,
+                                        void* hip_stream);
+
+/* Set (or replace) the batch callback of a handle created with MCMCPP_HIP_CALC_BATCH.  device_proposals (W/2 * D elements)
+ * and device_logp (W/2 elements) are optional caller-owned DEVICE buffers, 16-byte aligned, that the library forms the
+ * proposals in and the callback writes into (e.g. the storage of two torch tensors); NULL: the library allocates its own. */
+int mcmcpp_hip_set_batch_calculator(mcmcpp_hip_sampler* h, mcmcpp_hip_batch_logp_fn fn, void* user, void* device_proposals,
+                                    void* device_logp);
+
 /* EnsembleSampler::EnsembleSampler / ~EnsembleSampler */
 int mcmcpp_hip_create(const mcmcpp_hip_config* cfg, mcmcpp_hip_sampler** out);
 void mcmcpp_hip_destroy(mcmcpp_hip_sampler* h);
@@ -208,7 +241,8 @@ int mcmcpp_hip_calc_logp(mcmcpp_hip_sampler* h, const void* positions, int64_t c
 
 /* GPU time of the last mcmcpp_hip_run between HIP events recorded on the launch stream around the
  * step launches (excludes uploads / downloads), and the number of step-kernel launches it covers: one per
- * ensemble step for ensembles small enough to be stepped by the full-step kernel, two (red, black) otherwise. */
+ * ensemble step for ensembles small enough to be stepped by the full-step kernel, two (red, black) otherwise, four
+ * (propose and accept of each colour) for a batch target, whose time includes the callback's device work. */
 int mcmcpp_hip_last_run_timing(mcmcpp_hip_sampler* h, double* gpu_ms, int64_t* step_launches);
 
 /* Host-side cost of the last mcmcpp_hip_run: the time the calling thread spent enqueueing the step launches (and, for a

@@ -11,13 +11,18 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 F64, F32 = 0, 1
 CALC_ISO_GAUSSIAN, CALC_DENSE_GAUSSIAN, CALC_ROSENBROCK, CALC_SKEWED_GAUSSIAN_2D = 0, 1, 2, 3
+CALC_BATCH = 4  # a host callback evaluates each half-step's proposals in one batch (HipSampler(log_prob=...))
 MOVER_STRETCH, MOVER_DIFFERENTIAL_EVOLUTION = 0, 1
 OK = 0
+E_CALLBACK = 8
+
+# mcmcpp_hip_batch_logp_fn: (user, proposals, logp_out, count, num_params, hip_stream) -> int
+BATCH_LOGP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p)
 
 # every symbol include/mcmcpp_hip.h declares
 EXPORTS = [
     "mcmcpp_hip_abi_version", "mcmcpp_hip_register_calculator", "mcmcpp_hip_create", "mcmcpp_hip_destroy", "mcmcpp_hip_last_error",
-    "mcmcpp_hip_set_state", "mcmcpp_hip_seek", "mcmcpp_hip_run", "mcmcpp_hip_get_state", "mcmcpp_hip_reset_counters",
+    "mcmcpp_hip_set_batch_calculator", "mcmcpp_hip_set_state", "mcmcpp_hip_seek", "mcmcpp_hip_run", "mcmcpp_hip_get_state", "mcmcpp_hip_reset_counters",
     "mcmcpp_hip_get_counters", "mcmcpp_hip_calc_logp", "mcmcpp_hip_last_run_timing", "mcmcpp_hip_last_run_host_timing",
     "mcmcpp_hip_comm_unique_id", "mcmcpp_hip_last_run_exchange", "mcmcpp_hip_run_async", "mcmcpp_hip_wait_stored", "mcmcpp_hip_run_wait",
     "mcmcpp_hip_host_alloc", "mcmcpp_hip_host_free",
@@ -79,6 +84,8 @@ def lib():
         L.mcmcpp_hip_last_error.argtypes = [vp]
         L.mcmcpp_hip_last_error.restype = C.c_char_p
         L.mcmcpp_hip_set_state.argtypes = [vp, vp, vp]
+        if hasattr(L, "mcmcpp_hip_set_batch_calculator"):
+            L.mcmcpp_hip_set_batch_calculator.argtypes = [vp, vp, vp, vp, vp]
         L.mcmcpp_hip_seek.argtypes = [vp, C.c_uint64]
         L.mcmcpp_hip_run.argtypes = [vp, i64, i32, vp, vp]
         L.mcmcpp_hip_get_state.argtypes = [vp, vp, vp, vp]
@@ -172,9 +179,25 @@ class HipSampler:
 
     def __init__(self, W, D, calc_id, params=None, seed=0, stream=0, dtype=F64, device=-1, shard_begin=0,
                  shard_count=0, graph_steps=0, device_positions=None, hip_stream=None, alpha=(2, 1), mover=0,
-                 comm_world=0, comm_rank=0, comm_id=None, comm=None, num_chains=0):
+                 comm_world=0, comm_rank=0, comm_id=None, comm=None, num_chains=0, log_prob=None, batch_callback=None):
         """comm_world >= 1: this handle is rank comm_rank of a split ensemble (comm_id: the 128 bytes of comm_unique_id(),
-        the same on all ranks; or comm: an existing ncclComm_t as an integer); run() then steps the split ensemble."""
+        the same on all ranks; or comm: an existing ncclComm_t as an integer); run() then steps the split ensemble.
+
+        calc_id=CALC_BATCH takes the target from the caller, as exactly one of
+          log_prob        fn(x) -> logp: x a torch tensor (W/2, D) on the handle's device, logp (W/2,) of the same dtype
+                          (the handle then launches on a torch.cuda.Stream of its own, which fn's work is enqueued on)
+          batch_callback  (fn, user): a C function pointer of type mcmcpp_hip_batch_logp_fn (an integer address or a
+                          BATCH_LOGP_FN object) and its user pointer; the library's own device buffers are used."""
+        if (calc_id == CALC_BATCH) != (log_prob is not None or batch_callback is not None):
+            raise ValueError("log_prob / batch_callback go with calc_id=CALC_BATCH, and CALC_BATCH needs one of them")
+        if log_prob is not None and batch_callback is not None:
+            raise ValueError("give log_prob or batch_callback, not both")
+        self._torch_stream = None
+        if log_prob is not None:
+            import torch
+            dev = torch.device("cuda", device if device >= 0 else torch.cuda.current_device())
+            self._torch_stream = torch.cuda.Stream(device=dev)
+            hip_stream = self._torch_stream.cuda_stream
         self.W, self.D, self.dtype = W, D, dtype
         self.K = num_chains if num_chains > 1 else 1  # independent ensembles stepped together (leading array dimension)
         self.np_t = np_dtype(dtype)
@@ -190,6 +213,43 @@ class HipSampler:
         rc = lib().mcmcpp_hip_create(C.byref(self.cfg), C.byref(self.h))
         if rc != OK:
             raise HipError(rc, lib().mcmcpp_hip_last_error(None).decode())
+        self._cb_error = None
+        if log_prob is not None:
+            self._set_torch_target(log_prob, dev)
+        elif batch_callback is not None:
+            fn, user = batch_callback
+            self._cb = fn  # (kept alive as long as the handle)
+            fp = C.cast(fn, C.c_void_p) if isinstance(fn, C._CFuncPtr) else C.c_void_p(fn)
+            self._check(lib().mcmcpp_hip_set_batch_calculator(self.h, fp, user, None, None))
+
+    def _set_torch_target(self, log_prob, dev):
+        import torch
+        tt = torch.float64 if self.dtype == F64 else torch.float32
+        n = self.W // 2
+        # the proposals are formed in, and the log-posteriors read from, these tensors' storage
+        self._prop = torch.empty((n, self.D), dtype=tt, device=dev)
+        self._lp = torch.empty((n,), dtype=tt, device=dev)
+        prop_ptr = self._prop.data_ptr()
+        ts = self._torch_stream
+
+        def trampoline(user, proposals, logp_out, count, num_params, hip_stream):
+            try:
+                assert proposals == prop_ptr and num_params == self.D and 0 < count <= n
+                # (the current stream is thread-local: run_async calls from the handle's worker thread)
+                with torch.cuda.device(dev), torch.cuda.stream(ts):
+                    y = log_prob(self._prop[:count])
+                    if not isinstance(y, torch.Tensor) or tuple(y.shape) != (count,) or y.dtype != tt or y.device != dev:
+                        raise TypeError("log_prob must return a tensor of shape (%d,), dtype %s on %s; got %s" % (
+                            count, tt, dev, (tuple(y.shape), y.dtype, y.device) if isinstance(y, torch.Tensor) else type(y)))
+                    self._lp[:count].copy_(y)
+                return 0
+            except BaseException as e:  # (nothing may propagate through the C frames)
+                self._cb_error = e
+                return 1
+
+        self._cb = BATCH_LOGP_FN(trampoline)  # (kept alive as long as the handle)
+        self._check(lib().mcmcpp_hip_set_batch_calculator(self.h, C.cast(self._cb, C.c_void_p), None, C.c_void_p(prop_ptr),
+                                                          C.c_void_p(self._lp.data_ptr())))
 
     def close(self):
         if getattr(self, "h", None):
@@ -200,7 +260,11 @@ class HipSampler:
 
     def _check(self, rc):
         if rc != OK:
-            raise HipError(rc, lib().mcmcpp_hip_last_error(self.h).decode())
+            err = HipError(rc, lib().mcmcpp_hip_last_error(self.h).decode())
+            cause, self._cb_error = getattr(self, "_cb_error", None), None
+            if rc == E_CALLBACK and cause is not None:
+                raise err from cause
+            raise err
 
     def set_state(self, pos, logp):
         pos = np.ascontiguousarray(pos, dtype=self.np_t)

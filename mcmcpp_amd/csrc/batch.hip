@@ -1,0 +1,698 @@
+// batch.hip -- StretchMove with a batched log-posterior callback (calc_id MCMCPP_HIP_CALC_BATCH).
+//
+// The fused half-step kernel (stretch_kernel.hpp) evaluates a device Calculator between forming a proposal and
+// accepting it.  A batch target is evaluated by the caller instead -- a GEMM over a dataset, a neural-network density,
+// a torch function -- for all W/2 proposals of a half-step at once.  That is exact, not an approximation: every update
+// of a half-step reads only the other colour (StretchMove.h:105-113), so the half-step splits into
+//   stretch_propose_kernel   record + own row + partner row -> prop[W/2][D]; hand-over; the colour's next draws
+//   callback                 prop -> lp_new[W/2] (the caller's work, on the handle's stream)
+//   stretch_accept_kernel    the accept test of the fused kernel, row / logp / counter / chain slot / partial counts
+// with the same draws, the same operations in the same order, and therefore the same chain as a built-in Calculator that
+// computes the same bits.  Plain launches on one stream; the accepted counts of an ensemble step are summed by the
+// library's accepted_reduce_kernel behind the black accept.
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "../../include/mcmcpp_hip.h"
+#include "launch_table.hpp"
+#include "sampler_base.hpp"
+
+namespace mcmcpp
+{
+
+constexpr int kBatchThreads = 256;  // 4 wavefronts; a walker is LPW lanes x EPL elements, as in the fused kernels
+
+// One walker per group of LPW lanes.  Reads the walker's draw record (buffer draw_parity, this colour), its own row and
+// its partner's row and writes prop = par + z*(own - par) into row `li` of the dense [n][D] proposal buffer, every
+// operation rounded on its own (-ffp-contract=off; the loop above Calc::eval in stretch_half_step_kernel).  One lane of
+// the grid hands the stream and the counters to the next launch; the lanes of each walker make the three draws of the
+// colour's NEXT update into the other record buffer (the records this launch reads stay untouched: the accept kernel
+// reads them again).
+template <class T, int EPL, int LPW>
+__global__ void __launch_bounds__(kBatchThreads) stretch_propose_kernel(const HalfStepArgs<T> a, T* prop)
+{
+    const int sub = (int)threadIdx.x & (LPW - 1);
+    const int li = (int)blockIdx.x * (kBatchThreads / LPW) + (int)threadIdx.x / LPW;
+    const bool active = li < a.n;
+    const int lic = active ? li : 0;  // (a valid walker for every lane: nothing below reads out of bounds)
+    const int half_base = a.color ? a.n : 0, other_base = a.color ? 0 : a.n;
+    const bool vec_ok = a.vec_ok != 0;
+    const int i0 = sub * EPL;
+    const StepCtl ctl = *a.ctl_in;  // (wave-uniform)
+    if (blockIdx.x == 0 && threadIdx.x == 0) hand_over<T>(a, ctl, *a.run, a.color, a.ctl_out);
+
+    const DrawRec<T>* recs = a.draws + ((size_t)a.draw_parity * 2 + (size_t)a.color) * (size_t)a.n;
+    DrawRec<T>* next = a.draws + ((size_t)(1 - a.draw_parity) * 2 + (size_t)a.color) * (size_t)a.n;
+    const DrawUse<T> rec(recs[lic]);
+    T own[EPL], par[EPL];
+    load_slice<T, EPL>(a.pos + (size_t)(half_base + lic) * a.dims, i0, a.dims, vec_ok, active, own);
+    load_slice<T, EPL>(a.pos + (size_t)(other_base + (int)rec.partner) * a.dims, i0, a.dims, vec_ok, active, par);
+    // StretchMove.h:105-108  proposal = sel + z*(cur - sel)
+    T p[EPL];
+#pragma unroll
+    for (int e = 0; e < EPL; ++e)
+    {
+        const T d = own[e] - par[e];
+        const T zd = rec.z * d;
+        p[e] = par[e] + zd;
+    }
+    if (active) store_slice<T, EPL>(prop + (size_t)li * a.dims, i0, a.dims, vec_ok, p);
+
+    // the draws of this walker's next update (half-step + 2, base state ctl.state2): draw k by lane k of the group
+    if (active)
+    {
+        const bool direct = a.task_jump != nullptr;
+        for (int k = sub; k < 3; k += LPW)
+        {
+            Affine128 j_a, j_b;
+            if (direct)
+                j_a = a.task_jump[3 * li + k];
+            else
+            {
+                j_a = a.jump_hi[li >> 8];
+                j_b = a.jump_lo[li & 255];
+            }
+            compute_draw<T>(a, ctl.state2, j_a, j_b, direct, k, next + li);
+        }
+    }
+}
+
+// The accept half of stretch_half_step_kernel for the proposals in `prop` and their log-posteriors `lp_new` (the
+// callback's output).  It reads the same control record (ctl_in) and the same draw records as the propose launch of this
+// half-step: neither is written again before this colour's next update (the propose launch writes ctl_out and the other
+// record buffer; the other colour's launches read and write the other control record and the other colour's records).
+template <class T, int EPL, int LPW>
+__global__ void __launch_bounds__(kBatchThreads) stretch_accept_kernel(const HalfStepArgs<T> a, const T* prop, const T* lp_batch)
+{
+    const int lane = (int)threadIdx.x & 63;
+    const int sub = (int)threadIdx.x & (LPW - 1);
+    const int li = (int)blockIdx.x * (kBatchThreads / LPW) + (int)threadIdx.x / LPW;
+    const bool active = li < a.n;
+    const int lic = active ? li : 0;
+    const int w = (a.color ? a.n : 0) + lic;
+    const bool vec_ok = a.vec_ok != 0;
+    const int i0 = sub * EPL;
+    const StepCtl ctl = *a.ctl_in;
+    const RunInfo run = *a.run;
+
+    const DrawUse<T> rec(a.draws[((size_t)a.draw_parity * 2 + (size_t)a.color) * (size_t)a.n + lic]);
+    T own[EPL], p[EPL];
+    T* row = a.pos + (size_t)w * a.dims;
+    load_slice<T, EPL>(prop + (size_t)lic * a.dims, i0, a.dims, vec_ok, active, p);
+    const T lp_new = lp_batch[lic];
+    const T lp_old = a.logp[w];
+    const uint32_t nacc_old = a.n_accept[w];
+
+    // does this ensemble step go to the chain?  (EnsembleSampler.h:298-306: interval-1 unsaved, 1 saved)
+    long long save_slot = -1;
+    if (run.chain != nullptr && ctl.save_phase + 1u == (uint32_t)run.interval) save_slot = run.chain_slot_base + ctl.chain_slot;
+    if (save_slot >= 0) load_slice<T, EPL>(row, i0, a.dims, vec_ok, active, own);
+
+    // StretchMove.h:112-113  accept iff lnU < (probScaling + newProb) - oldProb
+    const T zs = rec.zs, ln_u = rec.ln_u;
+    const T delta = zs + lp_new - lp_old;
+    const bool accept = active && (ln_u < delta);
+    if (active && sub == 0)
+    {
+        const T margin = dev_abs(ln_u - delta);
+        const T scale = dev_abs(ln_u) + dev_abs(zs) + dev_abs(lp_new) + dev_abs(lp_old);
+        if (margin <= a.tie_eps * scale) count_near_tie(a.diag);
+    }
+    if (accept)
+    {
+        // Walker::jumpToNewPointSwap (Walker/Walker.h:172-179)
+        store_slice<T, EPL>(row, i0, a.dims, vec_ok, p);
+        if (sub == 0)
+        {
+            a.logp[w] = lp_new;
+            a.n_accept[w] = nacc_old + 1u;
+        }
+    }
+    if (save_slot >= 0 && active)
+    {
+        // Walker -> Chain::storeWalker (Chain/ChainBlock.h:125-131): cell = slot*W*D + walker*D + p
+        T* crow = reinterpret_cast<T*>(run.chain) + ((size_t)save_slot * (size_t)(2 * a.n) + (size_t)w) * a.dims;
+        if (accept)
+            store_slice<T, EPL>(crow, i0, a.dims, vec_ok, p);
+        else
+            store_slice<T, EPL>(crow, i0, a.dims, vec_ok, own);
+    }
+    // per-wavefront accepted count (every wavefront of the grid writes its entry, zero or not)
+    const unsigned accepted_here = (unsigned)__popcll(__ballot(accept && sub == 0));
+    if (a.partials != nullptr && run.accepted_per_step != nullptr && lane == 0)
+    {
+        const int wave = (int)blockIdx.x * (kBatchThreads / 64) + ((int)threadIdx.x >> 6);
+        a.partials[((size_t)ctl.partial_slot * 2 + (size_t)a.color) * (size_t)a.partial_waves + (size_t)wave] = accepted_here;
+    }
+}
+
+namespace
+{
+
+template <class T>
+struct BatchKernels
+{
+    typedef void (*Fn)(const HalfStepArgs<T>&, T* prop, const T* lp, unsigned grid, hipStream_t);
+    Fn propose, accept;
+};
+
+template <class T, int EPL, int LPW>
+void launch_propose(const HalfStepArgs<T>& a, T* prop, const T*, unsigned grid, hipStream_t st)
+{
+    hipLaunchKernelGGL((stretch_propose_kernel<T, EPL, LPW>), dim3(grid), dim3(kBatchThreads), 0, st, a, prop);
+}
+template <class T, int EPL, int LPW>
+void launch_accept(const HalfStepArgs<T>& a, T* prop, const T* lp, unsigned grid, hipStream_t st)
+{
+    hipLaunchKernelGGL((stretch_accept_kernel<T, EPL, LPW>), dim3(grid), dim3(kBatchThreads), 0, st, a, (const T*)prop, lp);
+}
+template <class T, int EPL, int LPW>
+BatchKernels<T> kernels_of()
+{
+    BatchKernels<T> k;
+    k.propose = &launch_propose<T, EPL, LPW>;
+    k.accept = &launch_accept<T, EPL, LPW>;
+    return k;
+}
+
+// the lane mapping of the fused kernels: LPW lanes x EPL elements cover D padded to a power of two (16 bytes per lane
+// until a walker fills a wavefront); one instantiation per (T, EPL, LPW) serves every D and every target
+template <class T>
+bool kernels_for(int lpw, int epl, BatchKernels<T>* out)
+{
+    constexpr int B = Vec16<T>::N;
+    switch (lpw)
+    {
+    case 1: *out = kernels_of<T, B, 1>(); return epl == B;
+    case 2: *out = kernels_of<T, B, 2>(); return epl == B;
+    case 4: *out = kernels_of<T, B, 4>(); return epl == B;
+    case 8: *out = kernels_of<T, B, 8>(); return epl == B;
+    case 16: *out = kernels_of<T, B, 16>(); return epl == B;
+    case 32: *out = kernels_of<T, B, 32>(); return epl == B;
+    case 64:
+        if (epl == B) *out = kernels_of<T, B, 64>();
+        else if (epl == 2 * B) *out = kernels_of<T, 2 * B, 64>();
+        else if (epl == 4 * B) *out = kernels_of<T, 4 * B, 64>();
+        else if (epl == 8 * B) *out = kernels_of<T, 8 * B, 64>();
+        else return false;
+        return true;
+    default: return false;
+    }
+}
+
+template <class T>
+class BatchSampler final : public mcmcpp_hip_sampler
+{
+public:
+    ~BatchSampler() override { release(); }
+
+    int init(const mcmcpp_hip_config& c)
+    {
+        cfg = c;
+        W = c.num_walkers;
+        D = c.num_params;
+        n = W / 2;
+        const int base = Vec16<T>::N;
+        const int n2 = pow2_at_least(D > base ? D : base);
+        lpw = n2 / base < 64 ? n2 / base : 64;
+        epl = n2 / lpw;
+        if (!kernels_for<T>(lpw, epl, &kern)) return fail(MCMCPP_HIP_E_UNSUPPORTED, "no batch kernels for D=%d (LPW=%d EPL=%d)", D, lpw, epl);
+        vec_ok = (D % base == 0) ? 1 : 0;
+        grid = (unsigned)(((long)n * lpw + kBatchThreads - 1) / kBatchThreads);
+        partial_waves = (int)grid * (kBatchThreads / 64);
+
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MCMCPP_HIP_E_NO_DEVICE, "no HIP device visible to this process");
+        if (c.device >= ndev) return fail(MCMCPP_HIP_E_NO_DEVICE, "device %d out of range (%d visible)", c.device, ndev);
+        if (c.device >= 0)
+            device = c.device;
+        else
+            HIP_TRY(hipGetDevice(&device));
+        HIP_TRY(hipSetDevice(device));
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, device));
+        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+            return fail(MCMCPP_HIP_E_NO_DEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
+        if (c.flags & MCMCPP_HIP_FLAG_CALLER_STREAM)
+            stream = (hipStream_t)c.hip_stream;
+        else
+        {
+            HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+            own_stream = true;
+        }
+        stream_valid = true;
+        HIP_TRY(hipEventCreate(&ev_t0));
+        HIP_TRY(hipEventCreate(&ev_t1));
+
+        if (c.device_positions)
+        {
+            if (((uintptr_t)c.device_positions & 15u) != 0) return fail(MCMCPP_HIP_E_ARG, "device_positions must be 16-byte aligned");
+            d_pos = (T*)c.device_positions;
+        }
+        else
+        {
+            HIP_TRY(hipMalloc(&d_own_pos, sizeof(T) * (size_t)W * D));
+            d_pos = d_own_pos;
+        }
+        HIP_TRY(hipMalloc(&d_logp, sizeof(T) * (size_t)W));
+        HIP_TRY(hipMalloc(&d_nacc, sizeof(uint32_t) * (size_t)W));
+        HIP_TRY(hipMalloc(&d_ctl, 2 * sizeof(StepCtl)));
+        HIP_TRY(hipMalloc(&d_run, sizeof(RunInfo)));
+        HIP_TRY(hipMalloc(&d_diag, sizeof(Diag)));
+        HIP_TRY(hipMalloc(&d_draws, sizeof(DrawRec<T>) * 4 * (size_t)n));
+        HIP_TRY(hipMalloc(&d_partials, sizeof(uint32_t) * 2 * (size_t)partial_waves));
+        HIP_TRY(hipMemset(d_logp, 0, sizeof(T) * (size_t)W));
+        HIP_TRY(hipMemset(d_nacc, 0, sizeof(uint32_t) * (size_t)W));
+        HIP_TRY(hipMemset(d_ctl, 0, 2 * sizeof(StepCtl)));
+        HIP_TRY(hipMemset(d_diag, 0, sizeof(Diag)));
+        HIP_TRY(hipMemset(d_draws, 0, sizeof(DrawRec<T>) * 4 * (size_t)n));
+        HIP_TRY(hipMemset(d_partials, 0, sizeof(uint32_t) * 2 * (size_t)partial_waves));
+        HIP_TRY(hipHostMalloc(&h_pinned, sizeof(Pinned), hipHostMallocDefault));
+        std::memset(h_pinned, 0, sizeof(Pinned));
+        h_pinned->run.interval = 1;
+        h_pinned->run.slot_mask = -1;
+        HIP_TRY(hipMemcpy(d_run, &h_pinned->run, sizeof(RunInfo), hipMemcpyHostToDevice));
+
+        // pcg64 stream (MultiSampler.h:54) and its jump tables, as the fused sampler builds them
+        pcg_seed(c.seed, c.stream, &state0, &inc);
+        {
+            std::vector<Affine128> lo(256), hi((size_t)(n + 255) / 256);
+            const Affine128 step3 = pcg_jump(inc, 3);
+            lo[0].mult = make_u128(0, 1);
+            lo[0].plus = make_u128(0, 0);
+            for (int k = 1; k < 256; ++k) lo[k] = compose(step3, lo[k - 1]);
+            const Affine128 step768 = pcg_jump(inc, 768);
+            hi[0] = lo[0];
+            for (size_t m = 1; m < hi.size(); ++m) hi[m] = compose(step768, hi[m - 1]);
+            HIP_TRY(hipMalloc(&d_jump_lo, sizeof(Affine128) * lo.size()));
+            HIP_TRY(hipMalloc(&d_jump_hi, sizeof(Affine128) * hi.size()));
+            HIP_TRY(hipMemcpy(d_jump_lo, lo.data(), sizeof(Affine128) * lo.size(), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d_jump_hi, hi.data(), sizeof(Affine128) * hi.size(), hipMemcpyHostToDevice));
+        }
+        half_jump = pcg_jump(inc, (unsigned __int128)3 * (unsigned)n);
+        const Knobs knobs = Knobs::from_environment();
+        if ((size_t)3 * n * sizeof(Affine128) <= ((size_t)knobs.task_table_mb << 20))
+        {
+            std::vector<Affine128> tj((size_t)3 * n);
+            const Affine128 step1 = pcg_jump(inc, 1);
+            tj[0] = step1;
+            for (size_t t = 1; t < tj.size(); ++t) tj[t] = compose(step1, tj[t - 1]);
+            HIP_TRY(hipMalloc(&d_task_jump, sizeof(Affine128) * tj.size()));
+            HIP_TRY(hipMemcpy(d_task_jump, tj.data(), sizeof(Affine128) * tj.size(), hipMemcpyHostToDevice));
+        }
+        chain_subchunk_bytes = (size_t)(knobs.chain_subchunk_mb > 0 ? knobs.chain_subchunk_mb : 32) << 20;
+        return MCMCPP_HIP_OK;
+    }
+
+    int set_batch_calculator(mcmcpp_hip_batch_logp_fn f, void* u, void* dprop, void* dlogp) override
+    {
+        if (!f) return fail(MCMCPP_HIP_E_ARG, "set_batch_calculator: fn is NULL");
+        if ((((uintptr_t)dprop) & 15u) != 0 || (((uintptr_t)dlogp) & 15u) != 0)
+            return fail(MCMCPP_HIP_E_ARG, "set_batch_calculator: device_proposals and device_logp must be 16-byte aligned");
+        HIP_TRY(hipSetDevice(device));
+        if ((!dprop && !d_own_prop) || (!dlogp && !d_own_lp)) HIP_TRY(hipStreamSynchronize(stream));
+        if (!dprop && !d_own_prop) HIP_TRY(hipMalloc(&d_own_prop, sizeof(T) * (size_t)n * D));
+        if (!dlogp && !d_own_lp) HIP_TRY(hipMalloc(&d_own_lp, sizeof(T) * (size_t)n));
+        fn = f;
+        user = u;
+        d_prop = dprop ? (T*)dprop : d_own_prop;
+        d_lp = dlogp ? (T*)dlogp : d_own_lp;
+        return MCMCPP_HIP_OK;
+    }
+
+    int set_state(const void* pos, const void* logp) override
+    {
+        if (!fn) return fail(MCMCPP_HIP_E_STATE, "set_state: no batch calculator (mcmcpp_hip_set_batch_calculator)");
+        if (!pos || !logp) return fail(MCMCPP_HIP_E_ARG, "set_state: null pointer");
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipMemcpyAsync(d_pos, pos, sizeof(T) * (size_t)W * D, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(d_logp, logp, sizeof(T) * (size_t)W, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemsetAsync(d_nacc, 0, sizeof(uint32_t) * (size_t)W, stream));
+        HIP_TRY(hipMemsetAsync(d_diag, 0, sizeof(Diag), stream));
+        half_steps = 0;
+        steps_since_reset = 0;
+        if (int rc = write_ctl()) return rc;
+        have_state = true;
+        return MCMCPP_HIP_OK;
+    }
+
+    int run(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step) override
+    {
+        if (!fn) return fail(MCMCPP_HIP_E_STATE, "run: no batch calculator (mcmcpp_hip_set_batch_calculator)");
+        if (!have_state) return fail(MCMCPP_HIP_E_STATE, "run: set_state has not been called (or a run failed half way)");
+        if (n_saved < 0 || interval < 1) return fail(MCMCPP_HIP_E_ARG, "run: n_saved >= 0 and interval >= 1 required");
+        HIP_TRY(hipSetDevice(device));
+        const int64_t total = n_saved * (int64_t)interval;
+        last_ms = 0.0;
+        last_launches = 0;
+        if (total == 0) return MCMCPP_HIP_OK;
+        const auto tp0 = std::chrono::steady_clock::now();
+        const size_t step_bytes = sizeof(T) * (size_t)W * D;
+        // stored steps go to a device buffer of sub_saved slots and from there to chain_out, a sub-chunk at a time
+        int64_t sub_saved = n_saved;
+        if (chain_out)
+        {
+            sub_saved = (int64_t)(chain_subchunk_bytes / step_bytes);
+            const int64_t eighth = (n_saved + 7) / 8;  // (wait_stored sees progress during a run)
+            if (sub_saved > eighth) sub_saved = eighth;
+            if (sub_saved < 1) sub_saved = 1;
+            if (int rc = ensure(&d_chain, &chain_capacity, step_bytes * (size_t)sub_saved)) return rc;
+        }
+        if (accepted_per_step)
+        {
+            if (int rc = ensure(&d_acc, &acc_capacity, sizeof(uint32_t) * (size_t)total)) return rc;
+        }
+        const int rc = run_steps(n_saved, interval, chain_out, accepted_per_step, sub_saved, step_bytes, total);
+        if (rc != MCMCPP_HIP_OK)
+        {
+            // the walkers, control and draw records are somewhere inside the run: nothing on the device can be trusted
+            const std::string keep = error;
+            (void)hipStreamSynchronize(stream);
+            (void)hipGetLastError();
+            have_state = false;
+            error = keep + " (the walker state on the device is no longer consistent: call set_state again)";
+            return rc;
+        }
+        host_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count();
+        return MCMCPP_HIP_OK;
+    }
+
+    int get_state(void* pos, void* logp, uint32_t* n_accept) override
+    {
+        if (!have_state) return fail(MCMCPP_HIP_E_STATE, "get_state: no walker state (set_state has not been called, or a run failed half way)");
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (pos) HIP_TRY(hipMemcpy(pos, d_pos, sizeof(T) * (size_t)W * D, hipMemcpyDeviceToHost));
+        if (logp) HIP_TRY(hipMemcpy(logp, d_logp, sizeof(T) * (size_t)W, hipMemcpyDeviceToHost));
+        if (n_accept) HIP_TRY(hipMemcpy(n_accept, d_nacc, sizeof(uint32_t) * (size_t)W, hipMemcpyDeviceToHost));
+        return MCMCPP_HIP_OK;
+    }
+
+    int seek(uint64_t steps_done) override
+    {
+        if (!have_state) return fail(MCMCPP_HIP_E_STATE, "seek: set_state has not been called");
+        if (steps_done > (~0ULL >> 2)) return fail(MCMCPP_HIP_E_ARG, "seek: step count out of range");
+        HIP_TRY(hipSetDevice(device));
+        half_steps = 2 * steps_done;
+        return write_ctl();
+    }
+
+    int reset_counters() override
+    {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipMemsetAsync(d_nacc, 0, sizeof(uint32_t) * (size_t)W, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        steps_since_reset = 0;
+        return MCMCPP_HIP_OK;
+    }
+
+    int get_counters(uint64_t* accepted, uint64_t* steps, uint64_t* ties, uint64_t* redraws) override
+    {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (accepted)
+        {
+            std::vector<uint32_t> a((size_t)W);
+            HIP_TRY(hipMemcpy(a.data(), d_nacc, sizeof(uint32_t) * (size_t)W, hipMemcpyDeviceToHost));
+            uint64_t s = 0;
+            for (uint32_t v : a) s += v;
+            *accepted = s;
+        }
+        if (steps) *steps = steps_since_reset;
+        if (ties || redraws)
+        {
+            Diag d;
+            HIP_TRY(hipMemcpy(&d, d_diag, sizeof(Diag), hipMemcpyDeviceToHost));
+            if (ties) *ties = d.near_ties;
+            if (redraws) *redraws = d.redraws;
+        }
+        return MCMCPP_HIP_OK;
+    }
+
+    // the callback on the caller's rows, in chunks of at most W/2 (the proposal buffer's size)
+    int calc_logp(const void* pos, int64_t count, void* out) override
+    {
+        if (!fn) return fail(MCMCPP_HIP_E_STATE, "calc_logp: no batch calculator (mcmcpp_hip_set_batch_calculator)");
+        if (count < 0 || (count > 0 && (!pos || !out))) return fail(MCMCPP_HIP_E_ARG, "calc_logp: bad arguments");
+        HIP_TRY(hipSetDevice(device));
+        // (the proposal buffer may still be read by the last run's work on the stream)
+        HIP_TRY(hipStreamSynchronize(stream));
+        for (int64_t first = 0; first < count; first += n)
+        {
+            const int64_t now = count - first < n ? count - first : n;
+            HIP_TRY(hipMemcpyAsync(d_prop, (const T*)pos + (size_t)first * D, sizeof(T) * (size_t)now * D, hipMemcpyHostToDevice, stream));
+            const int cb = fn(user, d_prop, d_lp, now, D, (void*)stream);
+            if (cb != 0)
+            {
+                (void)hipStreamSynchronize(stream);
+                return fail(MCMCPP_HIP_E_CALLBACK, "calc_logp: the batch log-posterior callback returned %d", cb);
+            }
+            HIP_TRY(hipMemcpyAsync((T*)out + first, d_lp, sizeof(T) * (size_t)now, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+        }
+        return MCMCPP_HIP_OK;
+    }
+
+    int last_run_timing(double* ms, int64_t* launches) override
+    {
+        if (ms) *ms = last_ms;
+        if (launches) *launches = last_launches;
+        return MCMCPP_HIP_OK;
+    }
+
+    int half_step_async(int32_t, int64_t) override
+    {
+        return fail(MCMCPP_HIP_E_UNSUPPORTED, "half_step_async: not with a batch target (its half-steps need the host callback; use run)");
+    }
+    int bind_device_chain(void*, int64_t) override
+    {
+        return fail(MCMCPP_HIP_E_UNSUPPORTED, "bind_device_chain: not with a batch target (it serves half_step_async)");
+    }
+    void* device_positions() override { return d_pos; }
+    int shard_span(int32_t color, int64_t* off, int64_t* cnt) override
+    {
+        if (color != 0 && color != 1) return fail(MCMCPP_HIP_E_ARG, "shard_span: colour must be 0 or 1");
+        if (off) *off = (int64_t)(color ? n : 0) * D;
+        if (cnt) *cnt = (int64_t)n * D;
+        return MCMCPP_HIP_OK;
+    }
+    int synchronize() override
+    {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return MCMCPP_HIP_OK;
+    }
+
+private:
+    struct Pinned  // host records on their way to the device (rewritten only after the stream has been synchronised)
+    {
+        StepCtl ctl;
+        RunInfo run;
+    };
+
+    template <class P>
+    int ensure(P** buf, size_t* capacity, size_t bytes)
+    {
+        if (bytes <= *capacity) return MCMCPP_HIP_OK;
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (*buf) (void)hipFree(*buf);
+        *buf = nullptr;
+        *capacity = 0;
+        if (hipMalloc(buf, bytes) != hipSuccess)
+        {
+            (void)hipGetLastError();
+            return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu bytes of device memory", bytes);
+        }
+        *capacity = bytes;
+        return MCMCPP_HIP_OK;
+    }
+
+    HalfStepArgs<T> make_args(int color, int parity) const
+    {
+        HalfStepArgs<T> a;
+        std::memset(&a, 0, sizeof a);
+        a.task_jump = d_task_jump;
+        a.jump_hi = d_jump_hi;
+        a.jump_lo = d_jump_lo;
+        a.diag = d_diag;
+        a.half_jump = half_jump;
+        a.redraw_threshold = (uint64_t)(0 - (uint64_t)n) % (uint64_t)n;
+        // GwDistribution<T,2,1> (MCMCpp/Utility/GwDistribution.h:45-55)
+        const T alpha = (T)(cfg.gw_alpha_num > 0 ? cfg.gw_alpha_num : 2) / (T)(cfg.gw_alpha_den > 0 ? cfg.gw_alpha_den : 1);
+        const T sqrt_a = std::sqrt(alpha);
+        const T inv_sqrt_a = (T)1 / sqrt_a;
+        a.gw_term1 = sqrt_a - inv_sqrt_a;
+        a.gw_inv_sqrt = inv_sqrt_a;
+        a.dims_minus_one = (T)(D - 1);
+        a.tie_eps = sizeof(T) == 8 ? (T)1e-12 : (T)6e-7;
+        a.n = n;
+        a.n_is_pow2 = (n & (n - 1)) == 0;
+        a.dims = D;
+        a.color = color;
+        a.shard_begin = 0;
+        a.shard_count = n;
+        for (int k = 0; k < 3; ++k) a.draw_jump[k] = pcg_jump(inc, (unsigned)k + 1);
+        a.inc = inc;
+        a.pos = d_pos;
+        a.logp = d_logp;
+        a.n_accept = d_nacc;
+        a.ctl_in = d_ctl + color;
+        a.ctl_out = d_ctl + (1 - color);
+        a.run = d_run;
+        a.draws = d_draws;
+        a.partials = d_partials;
+        a.partial_slots = 1;
+        a.partial_waves = partial_waves;
+        a.direct_save_slot = -1;
+        a.passes = 1;
+        a.vec_ok = vec_ok;
+        a.use_ctl_save = 1;
+        a.draw_parity = parity;
+        a.chains = 1;
+        return a;
+    }
+
+    // device StepCtl[0] <- {stream position of half-step `half_steps` (even), zeroed run counters}, and the draw records of
+    // the coming red and black updates (record buffer (half_steps / 2) & 1)
+    int write_ctl()
+    {
+        const Affine128 j = pcg_jump(inc, (unsigned __int128)3 * (unsigned)n * (unsigned __int128)half_steps);
+        StepCtl* c = &h_pinned->ctl;
+        HIP_TRY(hipStreamSynchronize(stream));  // (the pinned record may still be on its way from the previous call)
+        std::memset(c, 0, sizeof *c);
+        c->state = apply(j, state0);
+        const U128 state1 = apply(half_jump, c->state);
+        c->state2 = apply(half_jump, state1);
+        c->half_step = half_steps;
+        HIP_TRY(hipMemcpyAsync(d_ctl, c, sizeof(StepCtl), hipMemcpyHostToDevice, stream));
+        const int parity = (int)((half_steps >> 1) & 1);
+        launch_fill_draws(make_args(0, parity), c->state, nullptr, stream);
+        launch_fill_draws(make_args(1, parity), state1, nullptr, stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(stream));
+        return MCMCPP_HIP_OK;
+    }
+
+    int run_steps(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, int64_t sub_saved, size_t step_bytes,
+                  int64_t total)
+    {
+        if (int rc = write_ctl()) return rc;  // step_in_run = 0, stream position from the host-side half-step count
+        if (accepted_per_step) HIP_TRY(hipMemsetAsync(d_acc, 0, sizeof(uint32_t) * (size_t)total, stream));
+        HIP_TRY(hipEventRecord(ev_t0, stream));
+        const auto tp1 = std::chrono::steady_clock::now();
+        uint64_t step = half_steps >> 1;  // ensemble steps since set_state: its low bit selects the record buffer
+        int64_t done_steps = 0;
+        const int64_t n_sub = chain_out ? (n_saved + sub_saved - 1) / sub_saved : 1;
+        for (int64_t c = 0; c < n_sub; ++c)
+        {
+            const int64_t first = c * sub_saved;
+            const int64_t now = chain_out ? ((n_saved - first < sub_saved) ? n_saved - first : sub_saved) : n_saved;
+            RunInfo* ri = &h_pinned->run;  // (the stream was synchronised behind the previous sub-chunk)
+            std::memset(ri, 0, sizeof *ri);
+            ri->chain = chain_out ? (void*)d_chain : nullptr;
+            ri->accepted_per_step = accepted_per_step ? d_acc : nullptr;
+            ri->interval = interval;
+            ri->chain_slot_base = -first;
+            ri->slot_mask = -1;
+            ri->step_bytes = (int64_t)step_bytes;
+            HIP_TRY(hipMemcpyAsync(d_run, ri, sizeof(RunInfo), hipMemcpyHostToDevice, stream));
+            for (int64_t s = 0; s < now * (int64_t)interval; ++s, ++step)
+            {
+                const int parity = (int)(step & 1);
+                for (int color = 0; color < 2; ++color)
+                {
+                    const HalfStepArgs<T> a = make_args(color, parity);
+                    kern.propose(a, d_prop, d_lp, grid, stream);
+                    HIP_TRY(hipGetLastError());
+                    const int cb = fn(user, d_prop, d_lp, n, D, (void*)stream);
+                    if (cb != 0) return fail(MCMCPP_HIP_E_CALLBACK, "run: the batch log-posterior callback returned %d", cb);
+                    kern.accept(a, d_prop, d_lp, grid, stream);
+                    HIP_TRY(hipGetLastError());
+                }
+                // (the black propose launch left the control record of the next step in [0]: step_in_run = steps done)
+                if (accepted_per_step) launch_accepted_reduce(d_partials, 1, partial_waves, 1, d_ctl, d_run, stream, 1);
+                half_steps += 2;
+                steps_since_reset += 1;
+                ++done_steps;
+            }
+            if (chain_out)
+                HIP_TRY(hipMemcpyAsync((char*)chain_out + step_bytes * (size_t)first, d_chain, step_bytes * (size_t)now, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (chain_out) publish_stored(first + now);
+        }
+        HIP_TRY(hipEventRecord(ev_t1, stream));
+        if (accepted_per_step)
+            HIP_TRY(hipMemcpyAsync(accepted_per_step, d_acc, sizeof(uint32_t) * (size_t)total, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ev_t0, ev_t1));
+        last_ms = ms;
+        last_launches = 4 * done_steps;
+        host_enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp1).count();
+        return MCMCPP_HIP_OK;
+    }
+
+    void release()
+    {
+        if (device >= 0) (void)hipSetDevice(device);
+        if (stream_valid) (void)hipStreamSynchronize(stream);
+        void* bufs[] = {d_own_pos, d_logp, d_nacc, d_ctl, d_run, d_diag, d_draws, d_partials, d_jump_lo, d_jump_hi, d_task_jump,
+                        d_own_prop, d_own_lp, d_chain, d_acc};
+        for (void* p : bufs)
+            if (p) (void)hipFree(p);
+        if (h_pinned) (void)hipHostFree(h_pinned);
+        if (ev_t0) (void)hipEventDestroy(ev_t0);
+        if (ev_t1) (void)hipEventDestroy(ev_t1);
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
+
+    mcmcpp_hip_config cfg;
+    BatchKernels<T> kern;
+    mcmcpp_hip_batch_logp_fn fn = nullptr;
+    void* user = nullptr;
+    int W = 0, D = 0, n = 0, lpw = 1, epl = 1, vec_ok = 0, device = -1, partial_waves = 0;
+    unsigned grid = 1;
+    hipStream_t stream = nullptr;
+    bool own_stream = false, stream_valid = false, have_state = false;
+    hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
+    T *d_pos = nullptr, *d_own_pos = nullptr, *d_logp = nullptr;
+    T *d_prop = nullptr, *d_lp = nullptr, *d_own_prop = nullptr, *d_own_lp = nullptr;
+    uint32_t* d_nacc = nullptr;
+    StepCtl* d_ctl = nullptr;
+    RunInfo* d_run = nullptr;
+    Diag* d_diag = nullptr;
+    DrawRec<T>* d_draws = nullptr;  // [2 buffers][2 colours][n]: buffer (ensemble step & 1) holds the records of that step
+    uint32_t* d_partials = nullptr; // [2 colours][partial_waves]
+    Affine128 *d_jump_lo = nullptr, *d_jump_hi = nullptr, *d_task_jump = nullptr;
+    void* d_chain = nullptr;        // [sub_saved][W][D] stored steps of the sub-chunk in hand
+    uint32_t* d_acc = nullptr;
+    size_t chain_capacity = 0, acc_capacity = 0, chain_subchunk_bytes = 0;
+    Pinned* h_pinned = nullptr;
+    U128 state0, inc;
+    Affine128 half_jump;
+    uint64_t half_steps = 0, steps_since_reset = 0;
+    double last_ms = 0.0;
+    int64_t last_launches = 0;
+};
+
+}  // namespace
+
+mcmcpp_hip_sampler* make_batch_sampler(const mcmcpp_hip_config& cfg, int* rc)
+{
+    if (cfg.dtype == MCMCPP_HIP_F64)
+    {
+        BatchSampler<double>* s = new (std::nothrow) BatchSampler<double>();
+        if (s) *rc = s->init(cfg);
+        return s;
+    }
+    BatchSampler<float>* s = new (std::nothrow) BatchSampler<float>();
+    if (s) *rc = s->init(cfg);
+    return s;
+}
+
+}  // namespace mcmcpp

@@ -1914,6 +1914,13 @@ int check_config(const mcmcpp_hip_config* c, std::string& err)
     case MCMCPP_HIP_CALC_SKEWED_GAUSSIAN_2D:
         if (!c->calc_params || c->calc_params_len != 1 || c->num_params != 2) BAD("SkewedGaussian2D needs D == 2 and 1 parameter");
         break;
+    case MCMCPP_HIP_CALC_BATCH:
+        if (c->calc_params_len != 0) BAD("the batch target takes no parameters (the callback's user pointer carries them)");
+        if (c->mover != MCMCPP_HIP_MOVER_STRETCH) BAD("the batch target steps with StretchMove only (no differential evolution)");
+        if (c->num_chains > 1) BAD("the batch target runs one ensemble per handle (num_chains must be 0 or 1)");
+        if (c->shard_begin != 0 || c->shard_count != 0) BAD("the batch target runs the whole ensemble (no shards)");
+        if (c->comm_world >= 1 || c->comm || c->comm_id) BAD("the batch target runs on one device (no communicator)");
+        break;
     default:
     {
         RegisteredCalc r;
@@ -1982,6 +1989,11 @@ int mcmcpp_hip_create(const mcmcpp_hip_config* cfg, mcmcpp_hip_sampler** out)
         h = mcmcpp::make_de_sampler(*cfg, &irc);
         if (!h) return MCMCPP_HIP_E_NOMEM;
     }
+    else if (cfg->calc_id == MCMCPP_HIP_CALC_BATCH)
+    {
+        h = mcmcpp::make_batch_sampler(*cfg, &irc);
+        if (!h) return MCMCPP_HIP_E_NOMEM;
+    }
     else if (cfg->dtype == MCMCPP_HIP_F64)
     {
         Sampler<double>* s = new (std::nothrow) Sampler<double>();
@@ -2028,6 +2040,13 @@ const char* mcmcpp_hip_last_error(const mcmcpp_hip_sampler* h)
     if (h->async_active) return h->refuse("mcmcpp_hip_" name ": an asynchronous run is in progress (only wait_stored may be called before run_wait)"); \
     h->refused = nullptr
 
+int mcmcpp_hip_set_batch_calculator(mcmcpp_hip_sampler* h, mcmcpp_hip_batch_logp_fn fn, void* user, void* device_proposals,
+                                    void* device_logp)
+{
+    NEED_H;
+    NOT_WHILE_ASYNC("set_batch_calculator");
+    return h->set_batch_calculator(fn, user, device_proposals, device_logp);
+}
 int mcmcpp_hip_set_state(mcmcpp_hip_sampler* h, const void* positions, const void* logp)
 {
     NEED_H;

@@ -59,6 +59,11 @@ struct mcmcpp_hip_sampler
     virtual void* device_positions() = 0;
     virtual int shard_span(int32_t color, int64_t* off, int64_t* cnt) = 0;
     virtual int synchronize() = 0;
+    // calc_id MCMCPP_HIP_CALC_BATCH only (batch.hip)
+    virtual int set_batch_calculator(mcmcpp_hip_batch_logp_fn, void*, void*, void*)
+    {
+        return fail(MCMCPP_HIP_E_UNSUPPORTED, "set_batch_calculator: the handle was not created with calc_id MCMCPP_HIP_CALC_BATCH");
+    }
 
     // A call refused because the handle is busy with an asynchronous run: the message is a literal kept beside `error`,
     // which belongs to the worker thread while it runs (only the caller's thread touches `refused`).
@@ -181,4 +186,6 @@ struct Knobs
 const void* launch_table_lookup(int dtype, int calc_id);
 // Mover::DifferentialEvolution (diffevo.hip); *rc receives the init result, the handle carries the message
 mcmcpp_hip_sampler* make_de_sampler(const mcmcpp_hip_config& cfg, int* rc);
+// StretchMove with a batched log-posterior callback (batch.hip)
+mcmcpp_hip_sampler* make_batch_sampler(const mcmcpp_hip_config& cfg, int* rc);
 }  // namespace mcmcpp
