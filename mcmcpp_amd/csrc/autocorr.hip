@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/mcmcpp_hip.h"
+#include "sampler_base.hpp"
 
 namespace
 {
@@ -400,14 +401,9 @@ static int autocorr_entry(int32_t dtype, int32_t device, const void* const* step
         return ac_fail(MCMCPP_HIP_E_ARG, "autocorr_times: num_params * n_steps and num_walkers * num_params must be below 2^31");
     for (int64_t s = 0; steps && s < n_steps; ++s)
         if (!steps[s]) return ac_fail(MCMCPP_HIP_E_ARG, "autocorr_times: a step pointer is NULL");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return ac_fail(MCMCPP_HIP_E_NO_DEVICE, "no HIP device visible to this process");
-    if (device >= ndev) return ac_fail(MCMCPP_HIP_E_NO_DEVICE, "autocorr_times: device out of range");
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return ac_fail(MCMCPP_HIP_E_HIP, "hipGetDevice failed");
     hipDeviceProp_t prop;
-    if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess)
-        return ac_fail(MCMCPP_HIP_E_HIP, "autocorr_times: cannot select the device");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return ac_fail(MCMCPP_HIP_E_NO_DEVICE, "this library is built for gfx950 only");
+    std::string why;
+    if (int rc = mcmcpp::open_gfx950_device(device, &device, &prop, &why)) return ac_fail(rc, "autocorr_times: " + why);
     const int use = walkers_to_use == 0 ? num_walkers : walkers_to_use;
     if (dtype == MCMCPP_HIP_F64)
         return autocorr_times<double>(steps, static_cast<const double*>(device_steps), n_steps, num_walkers, num_params, use, window_scaling,

@@ -13,14 +13,12 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
-#include <cmath>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "../../include/mcmcpp_hip.h"
 #include "launch_table.hpp"
-#include "sampler_base.hpp"
+#include "sampler_host.hpp"
 
 namespace mcmcpp
 {
@@ -206,46 +204,24 @@ bool kernels_for(int lpw, int epl, BatchKernels<T>* out)
 }
 
 template <class T>
-class BatchSampler final : public mcmcpp_hip_sampler
+class BatchSampler final : public SamplerHost<T>
 {
+    MCMCPP_SAMPLER_HOST_NAMES;
+
 public:
     ~BatchSampler() override { release(); }
 
     int init(const mcmcpp_hip_config& c)
     {
         cfg = c;
-        W = c.num_walkers;
-        D = c.num_params;
-        n = W / 2;
-        const int base = Vec16<T>::N;
-        const int n2 = pow2_at_least(D > base ? D : base);
-        lpw = n2 / base < 64 ? n2 / base : 64;
-        epl = n2 / lpw;
+        set_shape(c);
         if (!kernels_for<T>(lpw, epl, &kern)) return fail(MCMCPP_HIP_E_UNSUPPORTED, "no batch kernels for D=%d (LPW=%d EPL=%d)", D, lpw, epl);
-        vec_ok = (D % base == 0) ? 1 : 0;
         grid = (unsigned)(((long)n * lpw + kBatchThreads - 1) / kBatchThreads);
         partial_waves = (int)grid * (kBatchThreads / 64);
 
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MCMCPP_HIP_E_NO_DEVICE, "no HIP device visible to this process");
-        if (c.device >= ndev) return fail(MCMCPP_HIP_E_NO_DEVICE, "device %d out of range (%d visible)", c.device, ndev);
-        if (c.device >= 0)
-            device = c.device;
-        else
-            HIP_TRY(hipGetDevice(&device));
-        HIP_TRY(hipSetDevice(device));
         hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, device));
-        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-            return fail(MCMCPP_HIP_E_NO_DEVICE, "device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
-        if (c.flags & MCMCPP_HIP_FLAG_CALLER_STREAM)
-            stream = (hipStream_t)c.hip_stream;
-        else
-        {
-            HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-            own_stream = true;
-        }
-        stream_valid = true;
+        if (int rc = open_device(c, &prop)) return rc;
+        if (int rc = open_stream(c)) return rc;
         HIP_TRY(hipEventCreate(&ev_t0));
         HIP_TRY(hipEventCreate(&ev_t1));
 
@@ -280,30 +256,19 @@ public:
 
         // pcg64 stream (MultiSampler.h:54) and its jump tables, as the fused sampler builds them
         pcg_seed(c.seed, c.stream, &state0, &inc);
-        {
-            std::vector<Affine128> lo(256), hi((size_t)(n + 255) / 256);
-            const Affine128 step3 = pcg_jump(inc, 3);
-            lo[0].mult = make_u128(0, 1);
-            lo[0].plus = make_u128(0, 0);
-            for (int k = 1; k < 256; ++k) lo[k] = compose(step3, lo[k - 1]);
-            const Affine128 step768 = pcg_jump(inc, 768);
-            hi[0] = lo[0];
-            for (size_t m = 1; m < hi.size(); ++m) hi[m] = compose(step768, hi[m - 1]);
-            HIP_TRY(hipMalloc(&d_jump_lo, sizeof(Affine128) * lo.size()));
-            HIP_TRY(hipMalloc(&d_jump_hi, sizeof(Affine128) * hi.size()));
-            HIP_TRY(hipMemcpy(d_jump_lo, lo.data(), sizeof(Affine128) * lo.size(), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(d_jump_hi, hi.data(), sizeof(Affine128) * hi.size(), hipMemcpyHostToDevice));
-        }
         half_jump = pcg_jump(inc, (unsigned __int128)3 * (unsigned)n);
         const Knobs knobs = Knobs::from_environment();
-        if ((size_t)3 * n * sizeof(Affine128) <= ((size_t)knobs.task_table_mb << 20))
         {
-            std::vector<Affine128> tj((size_t)3 * n);
-            const Affine128 step1 = pcg_jump(inc, 1);
-            tj[0] = step1;
-            for (size_t t = 1; t < tj.size(); ++t) tj[t] = compose(step1, tj[t - 1]);
-            HIP_TRY(hipMalloc(&d_task_jump, sizeof(Affine128) * tj.size()));
-            HIP_TRY(hipMemcpy(d_task_jump, tj.data(), sizeof(Affine128) * tj.size(), hipMemcpyHostToDevice));
+            const StretchJumpTables j = stretch_jump_tables(inc, n, (size_t)3 * n * sizeof(Affine128) <= ((size_t)knobs.task_table_mb << 20));
+            HIP_TRY(hipMalloc(&d_jump_lo, sizeof(Affine128) * j.lo.size()));
+            HIP_TRY(hipMalloc(&d_jump_hi, sizeof(Affine128) * j.hi.size()));
+            HIP_TRY(hipMemcpy(d_jump_lo, j.lo.data(), sizeof(Affine128) * j.lo.size(), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d_jump_hi, j.hi.data(), sizeof(Affine128) * j.hi.size(), hipMemcpyHostToDevice));
+            if (!j.task.empty())
+            {
+                HIP_TRY(hipMalloc(&d_task_jump, sizeof(Affine128) * j.task.size()));
+                HIP_TRY(hipMemcpy(d_task_jump, j.task.data(), sizeof(Affine128) * j.task.size(), hipMemcpyHostToDevice));
+            }
         }
         chain_subchunk_bytes = (size_t)(knobs.chain_subchunk_mb > 0 ? knobs.chain_subchunk_mb : 32) << 20;
         return MCMCPP_HIP_OK;
@@ -357,10 +322,7 @@ public:
         int64_t sub_saved = n_saved;
         if (chain_out)
         {
-            sub_saved = (int64_t)(chain_subchunk_bytes / step_bytes);
-            const int64_t eighth = (n_saved + 7) / 8;  // (wait_stored sees progress during a run)
-            if (sub_saved > eighth) sub_saved = eighth;
-            if (sub_saved < 1) sub_saved = 1;
+            sub_saved = stored_steps_per_subchunk(chain_subchunk_bytes, step_bytes, n_saved);
             if (int rc = ensure(&d_chain, &chain_capacity, step_bytes * (size_t)sub_saved)) return rc;
         }
         if (accepted_per_step)
@@ -370,12 +332,7 @@ public:
         const int rc = run_steps(n_saved, interval, chain_out, accepted_per_step, sub_saved, step_bytes, total);
         if (rc != MCMCPP_HIP_OK)
         {
-            // the walkers, control and draw records are somewhere inside the run: nothing on the device can be trusted
-            const std::string keep = error;
-            (void)hipStreamSynchronize(stream);
-            (void)hipGetLastError();
-            have_state = false;
-            error = keep + " (the walker state on the device is no longer consistent: call set_state again)";
+            abandon_state();
             return rc;
         }
         host_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count();
@@ -385,12 +342,7 @@ public:
     int get_state(void* pos, void* logp, uint32_t* n_accept) override
     {
         if (!have_state) return fail(MCMCPP_HIP_E_STATE, "get_state: no walker state (set_state has not been called, or a run failed half way)");
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (pos) HIP_TRY(hipMemcpy(pos, d_pos, sizeof(T) * (size_t)W * D, hipMemcpyDeviceToHost));
-        if (logp) HIP_TRY(hipMemcpy(logp, d_logp, sizeof(T) * (size_t)W, hipMemcpyDeviceToHost));
-        if (n_accept) HIP_TRY(hipMemcpy(n_accept, d_nacc, sizeof(uint32_t) * (size_t)W, hipMemcpyDeviceToHost));
-        return MCMCPP_HIP_OK;
+        return read_state(pos, logp, n_accept);
     }
 
     int seek(uint64_t steps_done) override
@@ -402,36 +354,11 @@ public:
         return write_ctl();
     }
 
-    int reset_counters() override
-    {
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipMemsetAsync(d_nacc, 0, sizeof(uint32_t) * (size_t)W, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        steps_since_reset = 0;
-        return MCMCPP_HIP_OK;
-    }
+    int reset_counters() override { return clear_accepted(); }
 
     int get_counters(uint64_t* accepted, uint64_t* steps, uint64_t* ties, uint64_t* redraws) override
     {
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (accepted)
-        {
-            std::vector<uint32_t> a((size_t)W);
-            HIP_TRY(hipMemcpy(a.data(), d_nacc, sizeof(uint32_t) * (size_t)W, hipMemcpyDeviceToHost));
-            uint64_t s = 0;
-            for (uint32_t v : a) s += v;
-            *accepted = s;
-        }
-        if (steps) *steps = steps_since_reset;
-        if (ties || redraws)
-        {
-            Diag d;
-            HIP_TRY(hipMemcpy(&d, d_diag, sizeof(Diag), hipMemcpyDeviceToHost));
-            if (ties) *ties = d.near_ties;
-            if (redraws) *redraws = d.redraws;
-        }
-        return MCMCPP_HIP_OK;
+        return read_counters(accepted, steps, ties, redraws);
     }
 
     // the callback on the caller's rows, in chunks of at most W/2 (the proposal buffer's size)
@@ -458,13 +385,6 @@ public:
         return MCMCPP_HIP_OK;
     }
 
-    int last_run_timing(double* ms, int64_t* launches) override
-    {
-        if (ms) *ms = last_ms;
-        if (launches) *launches = last_launches;
-        return MCMCPP_HIP_OK;
-    }
-
     int half_step_async(int32_t, int64_t) override
     {
         return fail(MCMCPP_HIP_E_UNSUPPORTED, "half_step_async: not with a batch target (its half-steps need the host callback; use run)");
@@ -472,20 +392,6 @@ public:
     int bind_device_chain(void*, int64_t) override
     {
         return fail(MCMCPP_HIP_E_UNSUPPORTED, "bind_device_chain: not with a batch target (it serves half_step_async)");
-    }
-    void* device_positions() override { return d_pos; }
-    int shard_span(int32_t color, int64_t* off, int64_t* cnt) override
-    {
-        if (color != 0 && color != 1) return fail(MCMCPP_HIP_E_ARG, "shard_span: colour must be 0 or 1");
-        if (off) *off = (int64_t)(color ? n : 0) * D;
-        if (cnt) *cnt = (int64_t)n * D;
-        return MCMCPP_HIP_OK;
-    }
-    int synchronize() override
-    {
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipStreamSynchronize(stream));
-        return MCMCPP_HIP_OK;
     }
 
 private:
@@ -514,30 +420,14 @@ private:
 
     HalfStepArgs<T> make_args(int color, int parity) const
     {
-        HalfStepArgs<T> a;
-        std::memset(&a, 0, sizeof a);
+        HalfStepArgs<T> a = stretch_args<T>(cfg, vec_ok, inc, half_jump);
         a.task_jump = d_task_jump;
         a.jump_hi = d_jump_hi;
         a.jump_lo = d_jump_lo;
         a.diag = d_diag;
-        a.half_jump = half_jump;
-        a.redraw_threshold = (uint64_t)(0 - (uint64_t)n) % (uint64_t)n;
-        // GwDistribution<T,2,1> (MCMCpp/Utility/GwDistribution.h:45-55)
-        const T alpha = (T)(cfg.gw_alpha_num > 0 ? cfg.gw_alpha_num : 2) / (T)(cfg.gw_alpha_den > 0 ? cfg.gw_alpha_den : 1);
-        const T sqrt_a = std::sqrt(alpha);
-        const T inv_sqrt_a = (T)1 / sqrt_a;
-        a.gw_term1 = sqrt_a - inv_sqrt_a;
-        a.gw_inv_sqrt = inv_sqrt_a;
-        a.dims_minus_one = (T)(D - 1);
-        a.tie_eps = sizeof(T) == 8 ? (T)1e-12 : (T)6e-7;
-        a.n = n;
-        a.n_is_pow2 = (n & (n - 1)) == 0;
-        a.dims = D;
         a.color = color;
         a.shard_begin = 0;
         a.shard_count = n;
-        for (int k = 0; k < 3; ++k) a.draw_jump[k] = pcg_jump(inc, (unsigned)k + 1);
-        a.inc = inc;
         a.pos = d_pos;
         a.logp = d_logp;
         a.n_accept = d_nacc;
@@ -548,10 +438,7 @@ private:
         a.partials = d_partials;
         a.partial_slots = 1;
         a.partial_waves = partial_waves;
-        a.direct_save_slot = -1;
         a.passes = 1;
-        a.vec_ok = vec_ok;
-        a.use_ctl_save = 1;
         a.draw_parity = parity;
         a.chains = 1;
         return a;
@@ -639,8 +526,7 @@ private:
 
     void release()
     {
-        if (device >= 0) (void)hipSetDevice(device);
-        if (stream_valid) (void)hipStreamSynchronize(stream);
+        quiesce();
         void* bufs[] = {d_own_pos, d_logp, d_nacc, d_ctl, d_run, d_diag, d_draws, d_partials, d_jump_lo, d_jump_hi, d_task_jump,
                         d_own_prop, d_own_lp, d_chain, d_acc};
         for (void* p : bufs)
@@ -648,24 +534,19 @@ private:
         if (h_pinned) (void)hipHostFree(h_pinned);
         if (ev_t0) (void)hipEventDestroy(ev_t0);
         if (ev_t1) (void)hipEventDestroy(ev_t1);
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
     }
 
     mcmcpp_hip_config cfg;
     BatchKernels<T> kern;
     mcmcpp_hip_batch_logp_fn fn = nullptr;
     void* user = nullptr;
-    int W = 0, D = 0, n = 0, lpw = 1, epl = 1, vec_ok = 0, device = -1, partial_waves = 0;
+    int partial_waves = 0;
     unsigned grid = 1;
-    hipStream_t stream = nullptr;
-    bool own_stream = false, stream_valid = false, have_state = false;
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
-    T *d_pos = nullptr, *d_own_pos = nullptr, *d_logp = nullptr;
+    T* d_own_pos = nullptr;
     T *d_prop = nullptr, *d_lp = nullptr, *d_own_prop = nullptr, *d_own_lp = nullptr;
-    uint32_t* d_nacc = nullptr;
     StepCtl* d_ctl = nullptr;
     RunInfo* d_run = nullptr;
-    Diag* d_diag = nullptr;
     DrawRec<T>* d_draws = nullptr;  // [2 buffers][2 colours][n]: buffer (ensemble step & 1) holds the records of that step
     uint32_t* d_partials = nullptr; // [2 colours][partial_waves]
     Affine128 *d_jump_lo = nullptr, *d_jump_hi = nullptr, *d_task_jump = nullptr;
@@ -675,24 +556,11 @@ private:
     Pinned* h_pinned = nullptr;
     U128 state0, inc;
     Affine128 half_jump;
-    uint64_t half_steps = 0, steps_since_reset = 0;
-    double last_ms = 0.0;
-    int64_t last_launches = 0;
+    uint64_t half_steps = 0;
 };
 
 }  // namespace
 
-mcmcpp_hip_sampler* make_batch_sampler(const mcmcpp_hip_config& cfg, int* rc)
-{
-    if (cfg.dtype == MCMCPP_HIP_F64)
-    {
-        BatchSampler<double>* s = new (std::nothrow) BatchSampler<double>();
-        if (s) *rc = s->init(cfg);
-        return s;
-    }
-    BatchSampler<float>* s = new (std::nothrow) BatchSampler<float>();
-    if (s) *rc = s->init(cfg);
-    return s;
-}
+mcmcpp_hip_sampler* make_batch_sampler(const mcmcpp_hip_config& cfg, int* rc) { return make_handle<BatchSampler>(cfg, rc); }
 
 }  // namespace mcmcpp

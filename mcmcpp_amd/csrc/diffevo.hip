@@ -11,39 +11,34 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <new>
 #include <unordered_map>
 #include <vector>
 
 #include "diffevo_plan.hpp"
 #include "launch_table.hpp"
-#include "sampler_base.hpp"
+#include "sampler_host.hpp"
 
 using namespace mcmcpp;
 
 namespace
 {
 template <class T>
-class DeSampler final : public mcmcpp_hip_sampler
+class DeSampler final : public SamplerHost<T>
 {
+    MCMCPP_SAMPLER_HOST_NAMES;
+
 public:
     ~DeSampler() override { release(); }
 
     int init(const mcmcpp_hip_config& c)
     {
         const Knobs knobs = Knobs::from_environment();
-        W = c.num_walkers;
-        D = c.num_params;
-        n = W / 2;
+        set_shape(c);
         table = static_cast<const LaunchTable<T>*>(launch_table_lookup(c.dtype, c.calc_id));
         if (!table) return fail(MCMCPP_HIP_E_ARG, "calc_id %d has no kernels for this element type", c.calc_id);
         if (table->abi != kLaunchTableAbi || table->elem_size != sizeof(T))
             return fail(MCMCPP_HIP_E_ARG, "calc_id %d: the plug-in was built against other headers (table abi %08x)", c.calc_id, table->abi);
-        const int base = Vec16<T>::N;
-        const int n2 = pow2_at_least(D > base ? D : base);
-        lpw = n2 / base < 64 ? n2 / base : 64;
-        epl = n2 / lpw;
-        const int lpw_log = ilog2(lpw), epl_shift = ilog2(epl / base);
+        const int lpw_log = ilog2(lpw), epl_shift = ilog2(epl / Vec16<T>::N);
         if (epl_shift >= kMaxEplShift || !table->de_update[lpw_log][epl_shift])
             return fail(MCMCPP_HIP_E_UNSUPPORTED, "no differential-evolution kernel for D=%d with this calculator (LPW=%d EPL=%d)", D, lpw, epl);
         update_fn = table->de_update[lpw_log][epl_shift];
@@ -62,27 +57,10 @@ public:
             }
         }
         calc_fn = table->calc[lpw_log][epl_shift];
-        vec_ok = (D % base == 0) ? 1 : 0;
 
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(MCMCPP_HIP_E_NO_DEVICE, "no HIP device visible to this process");
-        if (c.device >= ndev) return fail(MCMCPP_HIP_E_NO_DEVICE, "device %d out of range (%d visible)", c.device, ndev);
-        if (c.device >= 0)
-            device = c.device;
-        else
-            HIP_TRY(hipGetDevice(&device));
-        HIP_TRY(hipSetDevice(device));
         hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, device));
-        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-            return fail(MCMCPP_HIP_E_NO_DEVICE, "device %d is %s; this library is built for gfx950 (MI355X) only", device, prop.gcnArchName);
-        if (c.flags & MCMCPP_HIP_FLAG_CALLER_STREAM)
-            stream = static_cast<hipStream_t>(c.hip_stream);
-        else
-        {
-            HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-            own_stream = true;
-        }
+        if (int rc = open_device(c, &prop)) return rc;
+        if (int rc = open_stream(c)) return rc;
 
         scan_run = (int)knobs.de_scan_run.value_or(kDeScanRun);
         if (scan_run < 1) scan_run = 1;
@@ -151,24 +129,13 @@ public:
         HIP_TRY(hipMemset(d_diag, 0, sizeof(Diag)));
         if (c.calc_params_len > 0)
         {
-            // (the dense Gaussian's matrix goes over transposed, as for the stretch kernels: see DenseGaussianFn)
-            std::vector<T> prm((const T*)c.calc_params, (const T*)c.calc_params + c.calc_params_len);
-            if (c.calc_id == MCMCPP_HIP_CALC_DENSE_GAUSSIAN)
+            const CalcParams<T> p = calc_params_host<T>(c, matrix_core);
+            HIP_TRY(hipMalloc(&d_params, sizeof(T) * p.prm.size()));
+            HIP_TRY(hipMemcpy(d_params, p.prm.data(), sizeof(T) * p.prm.size(), hipMemcpyHostToDevice));
+            if (!p.pad.empty())
             {
-                const T* p = (const T*)c.calc_params;
-                for (int i = 0; i < D; ++i)
-                    for (int j = 0; j < D; ++j) prm[(size_t)j * D + i] = p[(size_t)i * D + j];
-            }
-            HIP_TRY(hipMalloc(&d_params, sizeof(T) * prm.size()));
-            HIP_TRY(hipMemcpy(d_params, prm.data(), sizeof(T) * prm.size(), hipMemcpyHostToDevice));
-            if (matrix_core)
-            {
-                // the matrix-core update kernels read P^T zero-padded to 32 x 32 straight into registers
-                std::vector<T> pad((size_t)32 * 32, (T)0);
-                for (int k = 0; k < D; ++k)
-                    for (int i = 0; i < D; ++i) pad[(size_t)k * 32 + i] = prm[(size_t)k * D + i];
-                HIP_TRY(hipMalloc(&d_params_padded, sizeof(T) * pad.size()));
-                HIP_TRY(hipMemcpy(d_params_padded, pad.data(), sizeof(T) * pad.size(), hipMemcpyHostToDevice));
+                HIP_TRY(hipMalloc(&d_params_padded, sizeof(T) * p.pad.size()));
+                HIP_TRY(hipMemcpy(d_params_padded, p.pad.data(), sizeof(T) * p.pad.size(), hipMemcpyHostToDevice));
             }
         }
 
@@ -176,20 +143,11 @@ public:
         pcg_seed(c.seed, c.stream, &state0, &inc);
         {
             const size_t scan_lanes = ((size_t)positions_max + scan_run - 1) / scan_run;
-            std::vector<Affine128> lo(256), hi((updates_max + 255) / 256), small((size_t)kDeShiftMax + (size_t)D + 2);
-            std::vector<Affine128> slo(256), shi((scan_lanes + 255) / 256);
-            Affine128 id;
-            id.mult = make_u128(0, 1);
-            id.plus = make_u128(0, 0);
-            const Affine128 step_u = pcg_jump(inc, per), step_b = pcg_jump(inc, (unsigned __int128)per * 256u), step_1 = pcg_jump(inc, 1);
-            lo[0] = hi[0] = small[0] = id;
-            for (size_t j = 1; j < lo.size(); ++j) lo[j] = compose(step_u, lo[j - 1]);
-            for (size_t m = 1; m < hi.size(); ++m) hi[m] = compose(step_b, hi[m - 1]);
-            for (size_t j = 1; j < small.size(); ++j) small[j] = compose(step_1, small[j - 1]);
-            const Affine128 step_r = pcg_jump(inc, (unsigned)scan_run), step_rb = pcg_jump(inc, (unsigned __int128)scan_run * 256u);
-            slo[0] = shi[0] = id;
-            for (size_t j = 1; j < slo.size(); ++j) slo[j] = compose(step_r, slo[j - 1]);
-            for (size_t m = 1; m < shi.size(); ++m) shi[m] = compose(step_rb, shi[m - 1]);
+            const std::vector<Affine128> small = jump_powers(pcg_jump(inc, 1), (size_t)kDeShiftMax + (size_t)D + 2);
+            const std::vector<Affine128> lo = jump_powers(pcg_jump(inc, per), 256);
+            const std::vector<Affine128> hi = jump_powers(pcg_jump(inc, (unsigned __int128)per * 256u), (updates_max + 255) / 256);
+            const std::vector<Affine128> slo = jump_powers(pcg_jump(inc, (unsigned)scan_run), 256);
+            const std::vector<Affine128> shi = jump_powers(pcg_jump(inc, (unsigned __int128)scan_run * 256u), (scan_lanes + 255) / 256);
             std::vector<Affine128> all;  // one allocation
             all.insert(all.end(), small.begin(), small.end());
             all.insert(all.end(), slo.begin(), slo.end());
@@ -247,21 +205,7 @@ public:
     {
         run_touched = false;
         const int rc = run_steps(n_saved, interval, chain_out, accepted_per_step);
-        if (rc != MCMCPP_HIP_OK && run_touched)
-        {
-            // launches went out and the call failed: the walkers are ahead of the host's counters (and the stream may
-            // be left capturing) -- nothing on the device can be trusted until the next set_state
-            hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
-            {
-                hipGraph_t g = nullptr;
-                (void)hipStreamEndCapture(stream, &g);
-                if (g) (void)hipGraphDestroy(g);
-            }
-            (void)hipStreamSynchronize(stream);
-            (void)hipGetLastError();
-            have_state = false;
-        }
+        if (rc != MCMCPP_HIP_OK && run_touched) abandon_state();
         return rc;
     }
 
@@ -344,14 +288,10 @@ public:
         last_launches = 2 * total;
         host_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         if (h.error)
-        {
-            have_state = false;
             return fail(MCMCPP_HIP_E_UNSUPPORTED,
                         "differential evolution: the random stream could not be followed (flags %u: 1 = more than %d draws thrown away in one "
-                        "batch of half-steps, 2 = more bad stream positions or events than the planner's lists hold, 4 = one update threw away more than %d draws); the state "
-                        "is undefined, call set_state",
+                        "batch of half-steps, 2 = more bad stream positions or events than the planner's lists hold, 4 = one update threw away more than %d draws)",
                         h.error, kDeShiftMax, kDeWindow - 2);
-        }
         return MCMCPP_HIP_OK;
     }
 
@@ -501,24 +441,10 @@ public:
         return MCMCPP_HIP_OK;
     }
 
-    int get_state(void* pos, void* logp, uint32_t* n_accept) override
-    {
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (pos) HIP_TRY(hipMemcpy(pos, d_pos, sizeof(T) * (size_t)W * D, hipMemcpyDeviceToHost));
-        if (logp) HIP_TRY(hipMemcpy(logp, d_logp, sizeof(T) * (size_t)W, hipMemcpyDeviceToHost));
-        if (n_accept) HIP_TRY(hipMemcpy(n_accept, d_nacc, sizeof(uint32_t) * (size_t)W, hipMemcpyDeviceToHost));
-        return MCMCPP_HIP_OK;
-    }
+    // (known inconsistency: unlike the stretch movers, no have_state check -- before set_state this returns OK)
+    int get_state(void* pos, void* logp, uint32_t* n_accept) override { return read_state(pos, logp, n_accept); }
 
-    int reset_counters() override
-    {
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipMemsetAsync(d_nacc, 0, sizeof(uint32_t) * (size_t)W, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        steps_since_reset = 0;
-        return MCMCPP_HIP_OK;
-    }
+    int reset_counters() override { return clear_accepted(); }
 
     int seek(uint64_t) override
     {
@@ -527,23 +453,7 @@ public:
 
     int get_counters(uint64_t* accepted, uint64_t* steps, uint64_t* ties, uint64_t* redraws) override
     {
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (accepted)
-        {
-            std::vector<uint32_t> acc((size_t)W);
-            HIP_TRY(hipMemcpy(acc.data(), d_nacc, sizeof(uint32_t) * (size_t)W, hipMemcpyDeviceToHost));
-            uint64_t s = 0;
-            for (uint32_t v : acc) s += v;
-            *accepted = s;
-        }
-        if (steps) *steps = steps_since_reset;
-        if (ties)
-        {
-            Diag d;
-            HIP_TRY(hipMemcpy(&d, d_diag, sizeof(Diag), hipMemcpyDeviceToHost));
-            *ties = d.near_ties;
-        }
+        if (int rc = read_counters(accepted, steps, ties, nullptr)) return rc;
         if (redraws)
         {
             // every draw thrown away so far (bounded_rand, ind2 == ind1): the stream is planned ahead of the updates, so
@@ -563,61 +473,16 @@ public:
         return MCMCPP_HIP_OK;
     }
 
-    int calc_logp(const void* pos, int64_t count, void* out) override
-    {
-        if (count < 0 || (count > 0 && (!pos || !out))) return fail(MCMCPP_HIP_E_ARG, "calc_logp: bad arguments");
-        if (count == 0) return MCMCPP_HIP_OK;
-        HIP_TRY(hipSetDevice(device));
-        struct Scratch  // freed on every way out
-        {
-            T *rows = nullptr, *out = nullptr;
-            ~Scratch()
-            {
-                if (rows) (void)hipFree(rows);
-                if (out) (void)hipFree(out);
-            }
-        } scratch;
-        HIP_TRY(hipMalloc(&scratch.rows, sizeof(T) * (size_t)count * D));
-        HIP_TRY(hipMalloc(&scratch.out, sizeof(T) * (size_t)count));
-        T *dp = scratch.rows, *dout = scratch.out;
-        HIP_TRY(hipMemcpyAsync(dp, pos, sizeof(T) * (size_t)count * D, hipMemcpyHostToDevice, stream));
-        const long long per_block = (long long)(64 / lpw) * kWavesPerBlock;
-        calc_fn(dp, dout, d_params, count, D, vec_ok, (unsigned)((count + per_block - 1) / per_block), stream);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(out, dout, sizeof(T) * (size_t)count, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        return MCMCPP_HIP_OK;
-    }
+    int calc_logp(const void* pos, int64_t count, void* out) override { return kernel_calc_logp(calc_fn, d_params, pos, count, out); }
 
-    int last_run_timing(double* ms, int64_t* launches) override
-    {
-        if (ms) *ms = last_ms;
-        if (launches) *launches = last_launches;
-        return MCMCPP_HIP_OK;
-    }
     int half_step_async(int32_t, int64_t) override { return unsupported("half_step_async"); }
     int bind_device_chain(void*, int64_t) override { return unsupported("bind_device_chain"); }
-    void* device_positions() override { return d_pos; }
-    int shard_span(int32_t color, int64_t* off, int64_t* cnt) override
-    {
-        if (color != 0 && color != 1) return fail(MCMCPP_HIP_E_ARG, "shard_span: colour must be 0 or 1");
-        if (off) *off = (int64_t)(color ? n : 0) * D;
-        if (cnt) *cnt = (int64_t)n * D;
-        return MCMCPP_HIP_OK;
-    }
-    int synchronize() override
-    {
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipStreamSynchronize(stream));
-        return MCMCPP_HIP_OK;
-    }
 
 private:
     int unsupported(const char* what) { return fail(MCMCPP_HIP_E_UNSUPPORTED, "%s: not available with the differential-evolution mover", what); }
     void release()
     {
-        if (device >= 0) (void)hipSetDevice(device);
-        if (stream && own_stream) (void)hipStreamSynchronize(stream);
+        quiesce();
         for (auto& kv : graph_cache)
             if (kv.second) (void)hipGraphExecDestroy(kv.second);
         void* bufs[] = {d_pos, d_logp, d_nacc, d_diag, d_head, d_batch, d_run, d_counts, d_params, d_params_padded, d_tables, d_chain, d_acc, d_recs, d_bad};
@@ -628,19 +493,15 @@ private:
             if (ev_t0[k]) (void)hipEventDestroy(ev_t0[k]);
             if (ev_t1[k]) (void)hipEventDestroy(ev_t1[k]);
         }
-        if (stream && own_stream) (void)hipStreamDestroy(stream);
     }
 
     const LaunchTable<T>* table = nullptr;
     typename LaunchTable<T>::DeFn update_fn = nullptr;
     typename LaunchTable<T>::CalcFn calc_fn = nullptr;
-    int W = 0, D = 0, n = 0, lpw = 1, epl = 1, vec_ok = 0, device = -1, walkers_per_block = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false, have_state = false;
-    T *d_pos = nullptr, *d_logp = nullptr, *d_params = nullptr, *d_params_padded = nullptr, *d_chain = nullptr;
+    int walkers_per_block = 0;
+    T *d_params = nullptr, *d_params_padded = nullptr, *d_chain = nullptr;
     bool matrix_core = false;
-    uint32_t *d_nacc = nullptr, *d_acc = nullptr;
-    Diag* d_diag = nullptr;
+    uint32_t* d_acc = nullptr;
     DeHead* d_head = nullptr;
     DeBatch* d_batch = nullptr;
     Affine128* d_tables = nullptr;  // jump_small, scan_lo, jump_lo, jump_hi, scan_hi
@@ -663,25 +524,12 @@ private:
     Affine128 *d_jump_lo = nullptr, *d_jump_hi = nullptr, *d_jump_small = nullptr;
     size_t chain_bytes = 0, acc_count = 0;
     U128 state0, inc;
-    uint64_t threshold = 0, steps_since_reset = 0, half_steps = 0;
+    uint64_t threshold = 0, half_steps = 0;
     T gamma = 0;
-    double last_ms = 0.0;
-    int64_t last_launches = 0;
 };
 }  // namespace
 
 namespace mcmcpp
 {
-mcmcpp_hip_sampler* make_de_sampler(const mcmcpp_hip_config& cfg, int* rc)
-{
-    if (cfg.dtype == MCMCPP_HIP_F64)
-    {
-        DeSampler<double>* s = new (std::nothrow) DeSampler<double>();
-        if (s) *rc = s->init(cfg);
-        return s;
-    }
-    DeSampler<float>* s = new (std::nothrow) DeSampler<float>();
-    if (s) *rc = s->init(cfg);
-    return s;
-}
+mcmcpp_hip_sampler* make_de_sampler(const mcmcpp_hip_config& cfg, int* rc) { return make_handle<DeSampler>(cfg, rc); }
 }  // namespace mcmcpp

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/mcmcpp_hip.h"
+#include "sampler_base.hpp"
 
 namespace
 {
@@ -523,14 +524,9 @@ int mcmcpp_hip_histograms_create(int32_t dtype, int32_t device, int32_t num_walk
     *out = nullptr;
     if ((dtype != MCMCPP_HIP_F64 && dtype != MCMCPP_HIP_F32) || num_walkers < 1 || num_params < 1 || num_params > 65535 || bins < 2)
         return fail(h, MCMCPP_HIP_E_ARG, "histograms_create: dtype must be F64/F32, num_walkers >= 1, 1 <= num_params <= 65535, bins >= 2");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(h, MCMCPP_HIP_E_NO_DEVICE, "no HIP device visible to this process");
-    if (device >= ndev) return fail(h, MCMCPP_HIP_E_NO_DEVICE, "histograms_create: device out of range");
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return fail(h, MCMCPP_HIP_E_HIP, "hipGetDevice failed");
     hipDeviceProp_t prop;
-    if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess)
-        return fail(h, MCMCPP_HIP_E_HIP, "histograms_create: cannot select the device");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(h, MCMCPP_HIP_E_NO_DEVICE, "this library is built for gfx950 only");
+    std::string why;
+    if (int rc = mcmcpp::open_gfx950_device(device, &device, &prop, &why)) return fail(h, rc, "histograms_create: " + why);
     const long long npairs = with_pairs ? (long long)num_params * (num_params - 1) / 2 : 0;
     // the 64-bit result arrays; refuse what cannot be addressed before asking the allocator
     const double pair_bytes = (double)npairs * (double)bins * (double)bins * 8.0;

@@ -28,7 +28,7 @@
 #include "launch_table.hpp"
 #include "exchange_kernels.hpp"
 #include "rccl_dyn.hpp"
-#include "sampler_base.hpp"
+#include "sampler_host.hpp"
 
 using namespace mcmcpp;
 
@@ -175,8 +175,11 @@ struct PinnedScratch
 static_assert(sizeof(StepCtl) <= 64 && sizeof(RunInfo) <= 64, "a control or run record is uploaded as one 64-byte line");
 
 template <class T>
-class Sampler final : public mcmcpp_hip_sampler
+class Sampler final : public SamplerHost<T>
 {
+    MCMCPP_SAMPLER_HOST_NAMES;
+    using Host::exchange_us_per_step, Host::xchg_bytes_per_step, Host::xchg_rollbacks, Host::xchg_cap_slots;
+
 public:
     Sampler() {}
     ~Sampler() override { release(); }
@@ -185,25 +188,17 @@ public:
     {
         cfg = c;
         knobs = Knobs::from_environment();
-        W = c.num_walkers;
-        D = c.num_params;
-        n = W / 2;
+        set_shape(c);
         table = table_for<T>(c.calc_id);
         if (!table) return fail(MCMCPP_HIP_E_ARG, "calc_id %d has no kernels for this element type", c.calc_id);
         if (table->abi != kLaunchTableAbi || table->elem_size != sizeof(T))
             return fail(MCMCPP_HIP_E_ARG, "calc_id %d: the plug-in was built against other headers (table abi %08x)", c.calc_id, table->abi);
 
-        // lane mapping: LPW lanes x EPL elements cover the walker's D-vector padded to a power of two
-        const int base = Vec16<T>::N;
-        const int n2 = pow2_at_least(D > base ? D : base);
-        lpw = n2 / base < 64 ? n2 / base : 64;
-        epl = n2 / lpw;
-        const int lpw_log = ilog2(lpw), epl_shift = ilog2(epl / base);
+        const int lpw_log = ilog2(lpw), epl_shift = ilog2(epl / Vec16<T>::N);
         if (epl_shift >= kMaxEplShift || !table->half_step[lpw_log][epl_shift])
             return fail(MCMCPP_HIP_E_UNSUPPORTED, "no kernel for D=%d with this calculator (LPW=%d EPL=%d)", D, lpw, epl);
         half_fn = table->half_step[lpw_log][epl_shift];
         calc_fn = table->calc[lpw_log][epl_shift];
-        vec_ok = (D % base == 0) ? 1 : 0;
 
         shard_begin = c.shard_begin;
         shard_count = c.shard_count > 0 ? c.shard_count : n;
@@ -224,20 +219,8 @@ public:
         }
         if (shard_begin < 0 || shard_begin + shard_count > n) return fail(MCMCPP_HIP_E_ARG, "shard out of range");
 
-        int ndev = 0;
-        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-            return fail(MCMCPP_HIP_E_NO_DEVICE, "no HIP device visible to this process");
-        if (c.device >= ndev) return fail(MCMCPP_HIP_E_NO_DEVICE, "device %d out of range (%d visible)", c.device, ndev);
-        if (c.device >= 0)
-            device = c.device;
-        else
-            HIP_TRY(hipGetDevice(&device));
-        HIP_TRY(hipSetDevice(device));
         hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, device));
-        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-            return fail(MCMCPP_HIP_E_NO_DEVICE, "device %d is %s; this library is built for gfx950 only", device,
-                        prop.gcnArchName);
+        if (int rc = open_device(c, &prop)) return rc;
         num_cus = prop.multiProcessorCount;
         if (c.comm_world >= 1)
         {
@@ -345,18 +328,7 @@ public:
         }
         if (K > 1 && (!whole || c.comm_world >= 1 || c.device_positions))
             return fail(MCMCPP_HIP_E_ARG, "num_chains > 1: whole ensembles on one device only (no shards, communicator or caller-owned positions)");
-        if (c.flags & MCMCPP_HIP_FLAG_CALLER_STREAM)
-        {
-            stream = (hipStream_t)c.hip_stream;  // may be the null (legacy default) stream
-            own_stream = false;
-            stream_valid = true;
-        }
-        else
-        {
-            HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-            own_stream = true;
-            stream_valid = true;
-        }
+        if (int rc = open_stream(c)) return rc;
         for (int k = 0; k < 4; ++k)
         {
             HIP_TRY(hipEventCreate(&ev_t0[k]));
@@ -423,26 +395,16 @@ public:
         HIP_TRY(hipMemset(d_ctl, 0, (size_t)kCtlChainStride * (size_t)K));
         HIP_TRY(hipHostMalloc(&h_pinned, sizeof(PinnedScratch), hipHostMallocDefault));
 
-        // calculator parameters (the dense Gaussian's matrix goes over transposed: see DenseGaussianFn)
+        // calculator parameters (and, for the matrix-core kernels, the padded matrix)
         if (c.calc_params_len > 0)
         {
-            std::vector<T> prm((const T*)c.calc_params, (const T*)c.calc_params + c.calc_params_len);
-            if (c.calc_id == MCMCPP_HIP_CALC_DENSE_GAUSSIAN)
+            const CalcParams<T> p = calc_params_host<T>(c, c.calc_id == MCMCPP_HIP_CALC_DENSE_GAUSSIAN && D <= 32);
+            if (int rc = carve(&d_params, sizeof(T) * p.prm.size())) return rc;
+            HIP_TRY(hipMemcpy(d_params, p.prm.data(), sizeof(T) * p.prm.size(), hipMemcpyHostToDevice));
+            if (!p.pad.empty())
             {
-                const T* p = (const T*)c.calc_params;
-                for (int i = 0; i < D; ++i)
-                    for (int j = 0; j < D; ++j) prm[(size_t)j * D + i] = p[(size_t)i * D + j];
-            }
-            if (int rc = carve(&d_params, sizeof(T) * prm.size())) return rc;
-            HIP_TRY(hipMemcpy(d_params, prm.data(), sizeof(T) * prm.size(), hipMemcpyHostToDevice));
-            if (c.calc_id == MCMCPP_HIP_CALC_DENSE_GAUSSIAN && D <= 32)
-            {
-                // the matrix-core kernels read P^T zero-padded to 32 x 32 straight into registers
-                std::vector<T> pad((size_t)32 * 32, (T)0);
-                for (int k = 0; k < D; ++k)
-                    for (int i = 0; i < D; ++i) pad[(size_t)k * 32 + i] = prm[(size_t)k * D + i];
-                if (int rc = carve(&d_params_padded, sizeof(T) * pad.size())) return rc;
-                HIP_TRY(hipMemcpy(d_params_padded, pad.data(), sizeof(T) * pad.size(), hipMemcpyHostToDevice));
+                if (int rc = carve(&d_params_padded, sizeof(T) * p.pad.size())) return rc;
+                HIP_TRY(hipMemcpy(d_params_padded, p.pad.data(), sizeof(T) * p.pad.size(), hipMemcpyHostToDevice));
             }
         }
 
@@ -454,26 +416,12 @@ public:
             pcg_seed(c.seed + (uint64_t)k, c.stream, &state0_of[k], &inc_k);  // (same stream: the same increment)
         }
         {
-            std::vector<Affine128> lo(256), hi((size_t)(n + 255) / 256);
-            const Affine128 step3 = pcg_jump(inc, 3);
-            lo[0].mult = make_u128(0, 1);
-            lo[0].plus = make_u128(0, 0);
-            for (int k = 1; k < 256; ++k) lo[k] = compose(step3, lo[k - 1]);
-            const Affine128 step768 = pcg_jump(inc, 768);
-            hi[0] = lo[0];
-            for (size_t m = 1; m < hi.size(); ++m) hi[m] = compose(step768, hi[m - 1]);
-            HIP_TRY(hipMemcpy(d_jump_lo, lo.data(), sizeof(Affine128) * lo.size(), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(d_jump_hi, hi.data(), sizeof(Affine128) * hi.size(), hipMemcpyHostToDevice));
+            const StretchJumpTables j = stretch_jump_tables(inc, n, have_task_table);
+            HIP_TRY(hipMemcpy(d_jump_lo, j.lo.data(), sizeof(Affine128) * j.lo.size(), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(d_jump_hi, j.hi.data(), sizeof(Affine128) * j.hi.size(), hipMemcpyHostToDevice));
+            if (have_task_table) HIP_TRY(hipMemcpy(d_task_jump, j.task.data(), sizeof(Affine128) * j.task.size(), hipMemcpyHostToDevice));
         }
         half_jump = pcg_jump(inc, (unsigned __int128)3 * (unsigned)n);
-        if (have_task_table)
-        {
-            std::vector<Affine128> tj((size_t)3 * n);
-            const Affine128 step1 = pcg_jump(inc, 1);
-            tj[0] = step1;
-            for (size_t t = 1; t < tj.size(); ++t) tj[t] = compose(step1, tj[t - 1]);
-            HIP_TRY(hipMemcpy(d_task_jump, tj.data(), sizeof(Affine128) * tj.size(), hipMemcpyHostToDevice));
-        }
 
         graph_steps = c.graph_steps == 0 ? (int)default_graph_steps() : c.graph_steps;
         // HIP cannot capture on the legacy default stream (hipErrorStreamCaptureUnsupported): a caller that hands over
@@ -556,7 +504,11 @@ public:
     {
         run_touched_device = false;
         const int rc = comm ? run_split(n_saved, interval, chain_out, accepted_per_step) : run_whole(n_saved, interval, chain_out, accepted_per_step);
-        if (rc != MCMCPP_HIP_OK && run_touched_device) abandon_state();
+        if (rc != MCMCPP_HIP_OK && run_touched_device)
+        {
+            abandon_state();
+            records_valid = false;
+        }
         return rc;
     }
 
@@ -567,26 +519,6 @@ public:
         for (int k = 0; k < K; ++k)
             std::memcpy(chain_out + step_bytes * ((size_t)n_saved * (size_t)k + (size_t)first), stage + step_bytes * (size_t)sub_saved * (size_t)k,
                         step_bytes * (size_t)count);
-    }
-
-    // A failure after the first launch of a run leaves walkers, control records and draw records ahead of the host's
-    // counters (and possibly the live ensemble in the second buffer, or the stream in capture mode): nothing on the
-    // device can be trusted any more.  The handle then insists on a new set_state, as the DE sampler does.
-    void abandon_state()
-    {
-        const std::string keep = error;
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
-        {
-            hipGraph_t g = nullptr;
-            (void)hipStreamEndCapture(stream, &g);
-            if (g) (void)hipGraphDestroy(g);
-        }
-        (void)hipStreamSynchronize(stream);
-        (void)hipGetLastError();
-        have_state = false;
-        records_valid = false;
-        error = keep + " (the walker state on the device is no longer consistent: call set_state again)";
     }
 
     int run_whole(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step)
@@ -604,13 +536,7 @@ public:
 
         const size_t step_bytes = sizeof(T) * (size_t)W * D;
         int64_t sub_saved = n_saved;  // stored steps per sub-chunk
-        if (chain_out)
-        {
-            sub_saved = (int64_t)(chain_subchunk_bytes / (step_bytes * (size_t)K));
-            const int64_t eighth = (n_saved + 7) / 8;  // keep the last (un-overlappable) host copy short
-            if (sub_saved > eighth) sub_saved = eighth;
-            if (sub_saved < 1) sub_saved = 1;
-        }
+        if (chain_out) sub_saved = stored_steps_per_subchunk(chain_subchunk_bytes, step_bytes * (size_t)K, n_saved);
         // Full-step kernels forward stored steps to pinned host memory themselves (trickle_stored_step): a ring of
         // `ring` slots on the device with a twin in pinned host memory, no copy engine, no gap in the launch sequence.
         const bool trickle = full_fn && chain_out && step_bytes % 16 == 0 && knobs.trickle != 0;
@@ -1337,8 +1263,7 @@ public:
 
     int get_counters(uint64_t* accepted, uint64_t* steps, uint64_t* ties, uint64_t* redraws) override
     {
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipStreamSynchronize(stream));
+        if (int rc = read_counters(nullptr, steps, ties, redraws)) return rc;
         if (accepted)
         {
             std::vector<uint32_t> a((size_t)W);
@@ -1351,50 +1276,10 @@ public:
             }
             *accepted = s;
         }
-        if (steps) *steps = steps_since_reset;
-        if (ties || redraws)
-        {
-            Diag d;
-            HIP_TRY(hipMemcpy(&d, d_diag, sizeof(Diag), hipMemcpyDeviceToHost));
-            if (ties) *ties = d.near_ties;
-            if (redraws) *redraws = d.redraws;
-        }
         return MCMCPP_HIP_OK;
     }
 
-    int calc_logp(const void* pos, int64_t count, void* out) override
-    {
-        if (count < 0 || (count > 0 && (!pos || !out))) return fail(MCMCPP_HIP_E_ARG, "calc_logp: bad arguments");
-        if (count == 0) return MCMCPP_HIP_OK;
-        HIP_TRY(hipSetDevice(device));
-        struct Scratch  // freed on every way out
-        {
-            T *rows = nullptr, *out = nullptr;
-            ~Scratch()
-            {
-                if (rows) (void)hipFree(rows);
-                if (out) (void)hipFree(out);
-            }
-        } scratch;
-        HIP_TRY(hipMalloc(&scratch.rows, sizeof(T) * (size_t)count * D));
-        HIP_TRY(hipMalloc(&scratch.out, sizeof(T) * (size_t)count));
-        T *dp = scratch.rows, *dout = scratch.out;
-        HIP_TRY(hipMemcpyAsync(dp, pos, sizeof(T) * (size_t)count * D, hipMemcpyHostToDevice, stream));
-        const long long per_block = (long long)(64 / lpw) * kWavesPerBlock;
-        const unsigned grid = (unsigned)((count + per_block - 1) / per_block);
-        calc_fn(dp, dout, d_params, count, D, vec_ok, grid, stream);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(out, dout, sizeof(T) * (size_t)count, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        return MCMCPP_HIP_OK;
-    }
-
-    int last_run_timing(double* ms, int64_t* launches) override
-    {
-        if (ms) *ms = last_ms;
-        if (launches) *launches = last_launches;
-        return MCMCPP_HIP_OK;
-    }
+    int calc_logp(const void* pos, int64_t count, void* out) override { return kernel_calc_logp(calc_fn, d_params, pos, count, out); }
 
     int half_step_async(int32_t color, int64_t save_slot) override
     {
@@ -1433,20 +1318,11 @@ public:
         return upload_idle_run_info();
     }
 
-    void* device_positions() override { return d_pos; }
-
     int shard_span(int32_t color, int64_t* off, int64_t* cnt) override
     {
         if (color != 0 && color != 1) return fail(MCMCPP_HIP_E_ARG, "shard_span: colour must be 0 or 1");
         if (off) *off = ((int64_t)(color ? n : 0) + shard_begin) * D;
         if (cnt) *cnt = (int64_t)shard_count * D;
-        return MCMCPP_HIP_OK;
-    }
-
-    int synchronize() override
-    {
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipStreamSynchronize(stream));
         return MCMCPP_HIP_OK;
     }
 
@@ -1501,8 +1377,7 @@ private:
 
     HalfStepArgs<T> make_args(int color) const
     {
-        HalfStepArgs<T> a;
-        std::memset(&a, 0, sizeof a);
+        HalfStepArgs<T> a = stretch_args<T>(cfg, vec_ok, inc, half_jump);
         a.pos = d_pos;
         a.logp = d_logp;
         a.n_accept = d_nacc;
@@ -1515,31 +1390,13 @@ private:
         a.task_jump = d_task_jump;
         a.calc_params = d_params;
         a.draws = d_draws;
-        a.half_jump = half_jump;
-        for (int k = 0; k < 3; ++k) a.draw_jump[k] = pcg_jump(inc, (unsigned)k + 1);
-        a.inc = inc;
-        a.redraw_threshold = (uint64_t)(0 - (uint64_t)n) % (uint64_t)n;
-        // GwDistribution<T,2,1> (MCMCpp/Utility/GwDistribution.h:45-55)
-        const T alpha = (T)(cfg.gw_alpha_num > 0 ? cfg.gw_alpha_num : 2) / (T)(cfg.gw_alpha_den > 0 ? cfg.gw_alpha_den : 1);
-        const T sqrt_a = std::sqrt(alpha);
-        const T inv_sqrt_a = (T)1 / sqrt_a;
-        a.gw_term1 = sqrt_a - inv_sqrt_a;
-        a.gw_inv_sqrt = inv_sqrt_a;
-        a.dims_minus_one = (T)(D - 1);
-        a.tie_eps = sizeof(T) == 8 ? (T)1e-12 : (T)6e-7;
-        a.n = n;
-        a.dims = D;
         a.color = color;
         a.shard_begin = shard_begin;
         a.shard_count = shard_count;
         a.passes = passes;
-        a.vec_ok = vec_ok;
-        a.n_is_pow2 = (n & (n - 1)) == 0;
         a.partials = d_partials;
         a.partial_slots = partial_slots;
         a.partial_waves = partial_waves;
-        a.direct_save_slot = -1;
-        a.use_ctl_save = 1;
         a.draw_parity = 0;
         a.pos_alt = d_pos_alt;
         a.logp_alt = d_logp + W;
@@ -1783,8 +1640,7 @@ private:
 
     void release()
     {
-        if (device >= 0) hipSetDevice(device);
-        if (stream_valid) hipStreamSynchronize(stream);  // half_step_async work may still be in flight
+        quiesce();  // (half_step_async work may still be in flight)
         for (hipGraphExec_t ex : graph_cache)
             if (ex) hipGraphExecDestroy(ex);
         if (arena) hipFree(arena);  // positions, log-posteriors, counters, records, tables, parameters, partial counts
@@ -1814,7 +1670,6 @@ private:
         if (h_split_stage) hipHostFree(h_split_stage);
         for (hipEvent_t e : ev_x)
             if (e) hipEventDestroy(e);
-        if (own_stream && stream) hipStreamDestroy(stream);
     }
 
     mcmcpp_hip_config cfg;
@@ -1838,8 +1693,8 @@ private:
     T* d_pos_alt = nullptr;
     uint64_t run_step = 0;                                  // ensemble steps enqueued in the current run()
     typename LaunchTable<T>::CalcFn calc_fn = nullptr;
-    int W = 0, D = 0, n = 0, lpw = 1, epl = 1, step_lpw = 1, passes = 1, vec_ok = 0, num_cus = 256;
-    int shard_begin = 0, shard_count = 0, device = -1, graph_steps = 32;
+    int step_lpw = 1, passes = 1, num_cus = 256;
+    int shard_begin = 0, shard_count = 0, graph_steps = 32;
     size_t chain_subchunk_bytes = 0, chain_half_capacity = 0, acc_capacity = 0;
     hipEvent_t ev_copied[2] = {nullptr, nullptr};
     void* arena = nullptr;  // one device allocation holding everything a step launch touches (see carve)
@@ -1849,14 +1704,11 @@ private:
     T* d_chain[2] = {nullptr, nullptr};
     void* h_stage[2] = {nullptr, nullptr};
     uint32_t* d_acc = nullptr;
-    hipStream_t stream = nullptr;
-    bool own_stream = false, own_pos = false, have_state = false, stream_valid = false, run_touched_device = false;
+    bool own_pos = false, run_touched_device = false;
     hipEvent_t ev_t0[4] = {nullptr, nullptr, nullptr, nullptr}, ev_t1[4] = {nullptr, nullptr, nullptr, nullptr};
-    T *d_pos = nullptr, *d_logp = nullptr, *d_params = nullptr, *d_params_padded = nullptr;
-    uint32_t* d_nacc = nullptr;
+    T *d_params = nullptr, *d_params_padded = nullptr;
     StepCtl* d_ctl = nullptr;
     RunInfo* d_run = nullptr;
-    Diag* d_diag = nullptr;
     uint64_t* d_status = nullptr;
     DrawRec<T>* d_draws = nullptr;
     DrawRec<T>* d_draws_batch = nullptr;  // [batch_draws][2][n]: records made ahead of the matrix-core full-step launches
@@ -1876,9 +1728,7 @@ private:
     Affine128 half_jump;
     HalfStepArgs<T> args_red, args_blk;
     std::vector<hipGraphExec_t> graph_cache;  // [steps] -> instantiated graph
-    uint64_t half_steps = 0, steps_since_reset = 0, enq_step = 0;
-    double last_ms = 0.0;
-    int64_t last_launches = 0;
+    uint64_t half_steps = 0, enq_step = 0;
     void* bound_chain = nullptr;
     int64_t bound_slots = 0;
 };
@@ -1982,32 +1832,11 @@ int mcmcpp_hip_create(const mcmcpp_hip_config* cfg, mcmcpp_hip_sampler** out)
     *out = nullptr;
     int rc = check_config(cfg, g_create_error);
     if (rc) return rc;
-    mcmcpp_hip_sampler* h = nullptr;
-    int irc;
-    if (cfg->mover == MCMCPP_HIP_MOVER_DIFFERENTIAL_EVOLUTION)
-    {
-        h = mcmcpp::make_de_sampler(*cfg, &irc);
-        if (!h) return MCMCPP_HIP_E_NOMEM;
-    }
-    else if (cfg->calc_id == MCMCPP_HIP_CALC_BATCH)
-    {
-        h = mcmcpp::make_batch_sampler(*cfg, &irc);
-        if (!h) return MCMCPP_HIP_E_NOMEM;
-    }
-    else if (cfg->dtype == MCMCPP_HIP_F64)
-    {
-        Sampler<double>* s = new (std::nothrow) Sampler<double>();
-        if (!s) return MCMCPP_HIP_E_NOMEM;
-        irc = s->init(*cfg);
-        h = s;
-    }
-    else
-    {
-        Sampler<float>* s = new (std::nothrow) Sampler<float>();
-        if (!s) return MCMCPP_HIP_E_NOMEM;
-        irc = s->init(*cfg);
-        h = s;
-    }
+    int irc = MCMCPP_HIP_OK;
+    mcmcpp_hip_sampler* h = cfg->mover == MCMCPP_HIP_MOVER_DIFFERENTIAL_EVOLUTION ? mcmcpp::make_de_sampler(*cfg, &irc)
+                            : cfg->calc_id == MCMCPP_HIP_CALC_BATCH               ? mcmcpp::make_batch_sampler(*cfg, &irc)
+                                                                                  : make_handle<Sampler>(*cfg, &irc);
+    if (!h) return MCMCPP_HIP_E_NOMEM;
     if (irc)
     {
         g_create_error = h->error;

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/mcmcpp_hip.h"
+#include "sampler_base.hpp"
 
 namespace
 {
@@ -219,14 +220,9 @@ int mcmcpp_hip_moments_create(int32_t dtype, int32_t device, int32_t num_walkers
     *out = nullptr;
     if ((dtype != MCMCPP_HIP_F64 && dtype != MCMCPP_HIP_F32) || num_walkers < 1 || num_params < 1 || num_params > 1024)
         return fail(m, MCMCPP_HIP_E_ARG, "moments_create: dtype must be F64/F32, num_walkers >= 1, 1 <= num_params <= 1024");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(m, MCMCPP_HIP_E_NO_DEVICE, "no HIP device visible to this process");
-    if (device >= ndev) return fail(m, MCMCPP_HIP_E_NO_DEVICE, "moments_create: device out of range");
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return fail(m, MCMCPP_HIP_E_HIP, "hipGetDevice failed");
     hipDeviceProp_t prop;
-    if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess)
-        return fail(m, MCMCPP_HIP_E_HIP, "moments_create: cannot select the device");
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return fail(m, MCMCPP_HIP_E_NO_DEVICE, "this library is built for gfx950 only");
+    std::string why;
+    if (int rc = mcmcpp::open_gfx950_device(device, &device, &prop, &why)) return fail(m, rc, ("moments_create: " + why).c_str());
     m = new (std::nothrow) mcmcpp_hip_moments();
     if (!m) return MCMCPP_HIP_E_NOMEM;
     m->dtype = dtype;

@@ -1,5 +1,6 @@
 // sampler_base.hpp -- what the C ABI handle is behind include/mcmcpp_hip.h: one abstract interface, implemented by the
-// stretch-move sampler (mcmcpp_hip.hip) and by the differential-evolution sampler (diffevo.hip).
+// fused stretch-move sampler (mcmcpp_hip.hip), the differential-evolution sampler (diffevo.hip) and the stretch move with a
+// batched log-posterior callback (batch.hip).  The host code the three share is in sampler_host.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +10,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <optional>
 #include <string>
@@ -118,6 +120,43 @@ inline Affine128 compose(const Affine128& g, const Affine128& f)  // g after f
     return r;
 }
 
+// Selects device `requested` (< 0: the calling thread's current one) and reads its properties.  Every handle and entry
+// point of the library opens its device here: anything but gfx950 is refused.  On failure *why holds the message.
+inline int open_gfx950_device(int requested, int* device, hipDeviceProp_t* prop, std::string* why)
+{
+    char buf[256];
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+    {
+        *why = "no HIP device visible to this process";
+        return MCMCPP_HIP_E_NO_DEVICE;
+    }
+    if (requested >= ndev)
+    {
+        snprintf(buf, sizeof buf, "device %d out of range (%d visible)", requested, ndev);
+        *why = buf;
+        return MCMCPP_HIP_E_NO_DEVICE;
+    }
+    int d = requested;
+    hipError_t e = d >= 0 ? hipSuccess : hipGetDevice(&d);
+    if (e == hipSuccess) e = hipSetDevice(d);
+    if (e == hipSuccess) e = hipGetDeviceProperties(prop, d);
+    if (e != hipSuccess)
+    {
+        snprintf(buf, sizeof buf, "cannot select device %d: %s", d, hipGetErrorString(e));
+        *why = buf;
+        return MCMCPP_HIP_E_HIP;
+    }
+    if (std::strncmp(prop->gcnArchName, "gfx950", 6) != 0)
+    {
+        snprintf(buf, sizeof buf, "device %d is %s; this library is built for gfx950 (MI355X) only", d, prop->gcnArchName);
+        *why = buf;
+        return MCMCPP_HIP_E_NO_DEVICE;
+    }
+    *device = d;
+    return MCMCPP_HIP_OK;
+}
+
 inline std::optional<long> env_long(const char* name)
 {
     const char* v = std::getenv(name);
@@ -184,8 +223,7 @@ struct Knobs
 
 // launch table (LaunchTable<double> / LaunchTable<float>) of a built-in or registered calculator, or nullptr
 const void* launch_table_lookup(int dtype, int calc_id);
-// Mover::DifferentialEvolution (diffevo.hip); *rc receives the init result, the handle carries the message
+// Mover::DifferentialEvolution (diffevo.hip) and StretchMove with a batched log-posterior callback (batch.hip): see make_handle
 mcmcpp_hip_sampler* make_de_sampler(const mcmcpp_hip_config& cfg, int* rc);
-// StretchMove with a batched log-posterior callback (batch.hip)
 mcmcpp_hip_sampler* make_batch_sampler(const mcmcpp_hip_config& cfg, int* rc);
 }  // namespace mcmcpp

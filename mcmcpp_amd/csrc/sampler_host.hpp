@@ -1,0 +1,325 @@
+// sampler_host.hpp -- the host code the three sampler handles share: the fused stretch move (Sampler, mcmcpp_hip.hip), the
+// differential-evolution mover (DeSampler, diffevo.hip) and the stretch move with a batched callback (BatchSampler,
+// batch.hip).  A thin base class (device, stream, lane mapping, the recovery rule, read-back) and the plain functions
+// behind their init.  Where the movers differ, the difference stays in the mover.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "launch_table.hpp"
+#include "sampler_base.hpp"
+
+namespace mcmcpp
+{
+
+// t[k] = the map of k steps: t[0] = identity, t[k] = step after t[k-1]
+inline std::vector<Affine128> jump_powers(const Affine128& step, size_t count)
+{
+    std::vector<Affine128> t(count);
+    if (count == 0) return t;
+    t[0].mult = make_u128(0, 1);
+    t[0].plus = make_u128(0, 0);
+    for (size_t k = 1; k < count; ++k) t[k] = compose(step, t[k - 1]);
+    return t;
+}
+
+// The stretch move's jump tables (see JumpTables): lo[k] maps 3k draws, hi[m] 768m draws, and (with_task) task[t] the t + 1
+// draws from a half-step's base state to the state behind its draw t
+struct StretchJumpTables
+{
+    std::vector<Affine128> lo, hi, task;
+};
+inline StretchJumpTables stretch_jump_tables(U128 inc, int n, bool with_task)
+{
+    StretchJumpTables j;
+    j.lo = jump_powers(pcg_jump(inc, 3), 256);
+    j.hi = jump_powers(pcg_jump(inc, 768), (size_t)(n + 255) / 256);
+    if (with_task)
+    {
+        j.task = jump_powers(pcg_jump(inc, 1), (size_t)3 * n + 1);
+        j.task.erase(j.task.begin());
+    }
+    return j;
+}
+
+// Calculator parameters as the kernels read them: the dense Gaussian's matrix transposed (see DenseGaussianFn) and, with
+// `padded`, P^T zero-padded to 32 x 32, which the matrix-core kernels read straight into registers
+template <class T>
+struct CalcParams
+{
+    std::vector<T> prm, pad;
+};
+template <class T>
+CalcParams<T> calc_params_host(const mcmcpp_hip_config& c, bool padded)
+{
+    const int D = c.num_params;
+    const T* p = (const T*)c.calc_params;
+    CalcParams<T> r;
+    r.prm.assign(p, p + c.calc_params_len);
+    if (c.calc_id == MCMCPP_HIP_CALC_DENSE_GAUSSIAN)
+        for (int i = 0; i < D; ++i)
+            for (int j = 0; j < D; ++j) r.prm[(size_t)j * D + i] = p[(size_t)i * D + j];
+    if (padded)
+    {
+        r.pad.assign((size_t)32 * 32, (T)0);
+        for (int k = 0; k < D; ++k)
+            for (int i = 0; i < D; ++i) r.pad[(size_t)k * 32 + i] = r.prm[(size_t)k * D + i];
+    }
+    return r;
+}
+
+// The fields of the stretch move's HalfStepArgs that follow from the configuration and the stream alone; the mover fills in
+// its buffers, the colour and its launch geometry.  One definition for the fused and the batch path: the same constants
+// are what makes their chains the same.
+template <class T>
+HalfStepArgs<T> stretch_args(const mcmcpp_hip_config& cfg, int vec_ok, U128 inc, const Affine128& half_jump)
+{
+    const int n = cfg.num_walkers / 2, D = cfg.num_params;
+    HalfStepArgs<T> a;
+    std::memset(&a, 0, sizeof a);
+    a.half_jump = half_jump;
+    for (int k = 0; k < 3; ++k) a.draw_jump[k] = pcg_jump(inc, (unsigned)k + 1);
+    a.inc = inc;
+    a.redraw_threshold = (uint64_t)(0 - (uint64_t)n) % (uint64_t)n;
+    // GwDistribution<T,2,1> (MCMCpp/Utility/GwDistribution.h:45-55)
+    const T alpha = (T)(cfg.gw_alpha_num > 0 ? cfg.gw_alpha_num : 2) / (T)(cfg.gw_alpha_den > 0 ? cfg.gw_alpha_den : 1);
+    const T sqrt_a = std::sqrt(alpha);
+    const T inv_sqrt_a = (T)1 / sqrt_a;
+    a.gw_term1 = sqrt_a - inv_sqrt_a;
+    a.gw_inv_sqrt = inv_sqrt_a;
+    a.dims_minus_one = (T)(D - 1);
+    a.tie_eps = sizeof(T) == 8 ? (T)1e-12 : (T)6e-7;
+    a.n = n;
+    a.n_is_pow2 = (n & (n - 1)) == 0;
+    a.dims = D;
+    a.vec_ok = vec_ok;
+    a.direct_save_slot = -1;
+    a.use_ctl_save = 1;
+    return a;
+}
+
+// Stored steps per sub-chunk of a run: what `budget` bytes of device chain hold, at most an eighth of the run (the last
+// host copy, which nothing overlaps, stays short, and a run_async caller sees progress), at least one
+inline int64_t stored_steps_per_subchunk(size_t budget, size_t stored_step_bytes, int64_t n_saved)
+{
+    int64_t s = (int64_t)(budget / stored_step_bytes);
+    const int64_t eighth = (n_saved + 7) / 8;
+    if (s > eighth) s = eighth;
+    if (s < 1) s = 1;
+    return s;
+}
+
+// S<double> or S<float> by cfg.dtype, then its init; nullptr: out of host memory.  *rc receives the init result, the
+// handle carries the message.
+template <template <class> class S>
+mcmcpp_hip_sampler* make_handle(const mcmcpp_hip_config& cfg, int* rc)
+{
+    if (cfg.dtype == MCMCPP_HIP_F64)
+    {
+        S<double>* s = new (std::nothrow) S<double>();
+        if (s) *rc = s->init(cfg);
+        return s;
+    }
+    S<float>* s = new (std::nothrow) S<float>();
+    if (s) *rc = s->init(cfg);
+    return s;
+}
+
+// The state and plumbing every sampler handle has.  Each mover keeps its precondition checks in its own overrides and
+// calls the helpers below from there.
+template <class T>
+class SamplerHost : public mcmcpp_hip_sampler
+{
+public:
+    ~SamplerHost() override
+    {
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
+
+    int last_run_timing(double* ms, int64_t* launches) override
+    {
+        if (ms) *ms = last_ms;
+        if (launches) *launches = last_launches;
+        return MCMCPP_HIP_OK;
+    }
+    void* device_positions() override { return d_pos; }
+    // (a handle of the whole ensemble; sharded handles override it)
+    int shard_span(int32_t color, int64_t* off, int64_t* cnt) override
+    {
+        if (color != 0 && color != 1) return fail(MCMCPP_HIP_E_ARG, "shard_span: colour must be 0 or 1");
+        if (off) *off = (int64_t)(color ? n : 0) * D;
+        if (cnt) *cnt = (int64_t)n * D;
+        return MCMCPP_HIP_OK;
+    }
+    int synchronize() override
+    {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return MCMCPP_HIP_OK;
+    }
+
+protected:
+    // W, D, n and the lane mapping of the kernels: LPW lanes x EPL elements cover the walker's D-vector padded to a power of
+    // two (16 bytes per lane until a walker fills a wavefront)
+    void set_shape(const mcmcpp_hip_config& c)
+    {
+        W = c.num_walkers;
+        D = c.num_params;
+        n = W / 2;
+        const int base = Vec16<T>::N;
+        const int n2 = pow2_at_least(D > base ? D : base);
+        lpw = n2 / base < 64 ? n2 / base : 64;
+        epl = n2 / lpw;
+        vec_ok = (D % base == 0) ? 1 : 0;
+    }
+
+    int open_device(const mcmcpp_hip_config& c, hipDeviceProp_t* prop)
+    {
+        std::string why;
+        if (int rc = open_gfx950_device(c.device, &device, prop, &why)) return fail(rc, "%s", why.c_str());
+        return MCMCPP_HIP_OK;
+    }
+
+    // the caller's stream (MCMCPP_HIP_FLAG_CALLER_STREAM; may be the null, legacy default stream) or one of the handle's own
+    int open_stream(const mcmcpp_hip_config& c)
+    {
+        if (c.flags & MCMCPP_HIP_FLAG_CALLER_STREAM)
+            stream = (hipStream_t)c.hip_stream;
+        else
+        {
+            HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+            own_stream = true;
+        }
+        stream_valid = true;
+        return MCMCPP_HIP_OK;
+    }
+
+    // first thing of a mover's release: nothing the handle enqueued is still in flight
+    void quiesce()
+    {
+        if (device >= 0) (void)hipSetDevice(device);
+        if (stream_valid) (void)hipStreamSynchronize(stream);
+    }
+
+    // A failure after the first launch of a run leaves walkers, control and draw records ahead of the host's counters (and
+    // possibly the stream in capture mode): nothing on the device can be trusted any more, the handle insists on a new
+    // set_state.
+    void abandon_state()
+    {
+        const std::string keep = error;
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
+        {
+            hipGraph_t g = nullptr;
+            (void)hipStreamEndCapture(stream, &g);
+            if (g) (void)hipGraphDestroy(g);
+        }
+        (void)hipStreamSynchronize(stream);
+        (void)hipGetLastError();
+        have_state = false;
+        error = keep + " (the walker state on the device is no longer consistent: call set_state again)";
+    }
+
+    // get_state of one ensemble
+    int read_state(void* pos, void* logp, uint32_t* n_accept)
+    {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (pos) HIP_TRY(hipMemcpy(pos, d_pos, sizeof(T) * (size_t)W * D, hipMemcpyDeviceToHost));
+        if (logp) HIP_TRY(hipMemcpy(logp, d_logp, sizeof(T) * (size_t)W, hipMemcpyDeviceToHost));
+        if (n_accept) HIP_TRY(hipMemcpy(n_accept, d_nacc, sizeof(uint32_t) * (size_t)W, hipMemcpyDeviceToHost));
+        return MCMCPP_HIP_OK;
+    }
+
+    // reset_counters of one ensemble
+    int clear_accepted()
+    {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipMemsetAsync(d_nacc, 0, sizeof(uint32_t) * (size_t)W, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        steps_since_reset = 0;
+        return MCMCPP_HIP_OK;
+    }
+
+    // get_counters behind a synchronisation: the accepted counters of one ensemble summed, the step count, the
+    // diagnostics record (any pointer may be null)
+    int read_counters(uint64_t* accepted, uint64_t* steps, uint64_t* ties, uint64_t* redraws)
+    {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (accepted)
+        {
+            std::vector<uint32_t> a((size_t)W);
+            HIP_TRY(hipMemcpy(a.data(), d_nacc, sizeof(uint32_t) * (size_t)W, hipMemcpyDeviceToHost));
+            uint64_t s = 0;
+            for (uint32_t v : a) s += v;
+            *accepted = s;
+        }
+        if (steps) *steps = steps_since_reset;
+        if (ties || redraws)
+        {
+            Diag d;
+            HIP_TRY(hipMemcpy(&d, d_diag, sizeof(Diag), hipMemcpyDeviceToHost));
+            if (ties) *ties = d.near_ties;
+            if (redraws) *redraws = d.redraws;
+        }
+        return MCMCPP_HIP_OK;
+    }
+
+    // calc_logp by the calculator's own kernel (`calc` of its launch table)
+    int kernel_calc_logp(typename LaunchTable<T>::CalcFn calc_fn, const T* params, const void* pos, int64_t count, void* out)
+    {
+        if (count < 0 || (count > 0 && (!pos || !out))) return fail(MCMCPP_HIP_E_ARG, "calc_logp: bad arguments");
+        if (count == 0) return MCMCPP_HIP_OK;
+        HIP_TRY(hipSetDevice(device));
+        struct Scratch  // freed on every way out
+        {
+            T *rows = nullptr, *out = nullptr;
+            ~Scratch()
+            {
+                if (rows) (void)hipFree(rows);
+                if (out) (void)hipFree(out);
+            }
+        } scratch;
+        HIP_TRY(hipMalloc(&scratch.rows, sizeof(T) * (size_t)count * D));
+        HIP_TRY(hipMalloc(&scratch.out, sizeof(T) * (size_t)count));
+        T *dp = scratch.rows, *dout = scratch.out;
+        HIP_TRY(hipMemcpyAsync(dp, pos, sizeof(T) * (size_t)count * D, hipMemcpyHostToDevice, stream));
+        const long long per_block = (long long)(64 / lpw) * kWavesPerBlock;
+        const unsigned grid = (unsigned)((count + per_block - 1) / per_block);
+        calc_fn(dp, dout, params, count, D, vec_ok, grid, stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(out, dout, sizeof(T) * (size_t)count, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return MCMCPP_HIP_OK;
+    }
+
+    int W = 0, D = 0, n = 0, lpw = 1, epl = 1, vec_ok = 0, device = -1;
+    hipStream_t stream = nullptr;
+    bool own_stream = false, stream_valid = false, have_state = false;
+    // the walkers: positions [W][D], log-posteriors [W], accepted counters [W] (the mover allocates them)
+    T *d_pos = nullptr, *d_logp = nullptr;
+    uint32_t* d_nacc = nullptr;
+    Diag* d_diag = nullptr;
+    uint64_t steps_since_reset = 0;
+    double last_ms = 0.0;
+    int64_t last_launches = 0;
+};
+
+// The names a mover uses from its dependent base (a class template does not see them without this)
+#define MCMCPP_SAMPLER_HOST_NAMES                                                                                               \
+    using Host = SamplerHost<T>;                                                                                                \
+    using Host::W, Host::D, Host::n, Host::lpw, Host::epl, Host::vec_ok, Host::device, Host::stream, Host::own_stream,        \
+        Host::stream_valid, Host::have_state, Host::d_pos, Host::d_logp, Host::d_nacc, Host::d_diag, Host::steps_since_reset, \
+        Host::last_ms, Host::last_launches;                                                                                     \
+    using Host::set_shape, Host::open_device, Host::open_stream, Host::quiesce, Host::abandon_state, Host::read_state,         \
+        Host::clear_accepted, Host::read_counters, Host::kernel_calc_logp;                                                      \
+    using Host::fail, Host::error, Host::publish_stored, Host::host_enqueue_ms, Host::host_wall_ms
+
+}  // namespace mcmcpp
