@@ -114,7 +114,8 @@ typedef struct mcmcpp_hip_config {
      * K = num_chains > 1 every array argument gains a leading chain dimension: set_state positions[K][W][D], logp[K][W];
      * run chain_out[K][n_saved][W][D] (chain k's stored steps are contiguous, like that sampler's own Chain),
      * accepted_per_step[K][steps]; get_state likewise.  Counters are summed over the chains.  Whole ensembles on one
-     * device (no shards, no communicator); at most 16 chains. */
+     * device (no shards, no communicator); at most 16 chains.  All chains share calc_params until
+     * mcmcpp_hip_set_chain_params gives a chain a block of its own (one model fitted to K data sets in the same launches). */
     int32_t num_chains;
     int32_t reserved0;
 } mcmcpp_hip_config;
@@ -234,8 +235,26 @@ int mcmcpp_hip_reset_counters(mcmcpp_hip_sampler* h);
 int mcmcpp_hip_get_counters(mcmcpp_hip_sampler* h, uint64_t* accepted, uint64_t* ensemble_steps,
                             uint64_t* near_ties, uint64_t* redraws);
 
-/* Calculator::calcLogPostProb evaluated by the device functor for `count` D-vectors (host in, host out). */
+/* Calculator::calcLogPostProb evaluated by the device functor for `count` D-vectors (host in, host out).  With per-chain
+ * parameters (mcmcpp_hip_set_chain_params) this is chain 0's calculator. */
 int mcmcpp_hip_calc_logp(mcmcpp_hip_sampler* h, const void* positions, int64_t count, void* logp_out);
+
+/* Per-chain calculator parameters.  Give chain `chain` (0 <= chain < K, K = max(num_chains, 1)) its own calculator
+ * parameters: `len` elements of the handle's dtype.  `len` must equal the handle's calc_params_len, and the block is checked
+ * as at create.  The parameters take effect at the next run / calc_logp.  Stored log-posteriors are NOT recomputed: call
+ * mcmcpp_hip_calc_logp_chain and then set_state (which rewinds the stream: mcmcpp_hip_seek puts it back).  Chains that never
+ * get their own block keep the parameters given at create.  With K = 1 this changes the handle's target without a new handle.
+ * Chain k then computes what a handle of its own with these parameters and seed + k would compute, bit for bit.
+ * Returns MCMCPP_HIP_E_ARG (with a message) for a chain out of range, a wrong len, a calculator that takes no parameters
+ * (IsoGaussian, the batch target), a block create would refuse, or a NULL pointer; MCMCPP_HIP_E_UNSUPPORTED for the
+ * differential-evolution mover, sharded handles, handles with a communicator and handles with caller-owned positions;
+ * MCMCPP_HIP_E_STATE while an asynchronous run is in progress.  The first block set allocates K rows of device memory
+ * outside the handle's step buffers. */
+int mcmcpp_hip_set_chain_params(mcmcpp_hip_sampler* h, int32_t chain, const void* params, int32_t len);
+
+/* mcmcpp_hip_calc_logp with chain `chain`'s parameters (same refusals as mcmcpp_hip_set_chain_params, except that a
+ * calculator without parameters is evaluated: all its chains are the same). */
+int mcmcpp_hip_calc_logp_chain(mcmcpp_hip_sampler* h, int32_t chain, const void* positions, int64_t count, void* logp_out);
 
 /* ---- measurement ---------------------------------------------------------------------------------- */
 

@@ -23,7 +23,7 @@ BATCH_LOGP_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int
 EXPORTS = [
     "mcmcpp_hip_abi_version", "mcmcpp_hip_register_calculator", "mcmcpp_hip_create", "mcmcpp_hip_destroy", "mcmcpp_hip_last_error",
     "mcmcpp_hip_set_batch_calculator", "mcmcpp_hip_set_state", "mcmcpp_hip_seek", "mcmcpp_hip_run", "mcmcpp_hip_get_state", "mcmcpp_hip_reset_counters",
-    "mcmcpp_hip_get_counters", "mcmcpp_hip_calc_logp", "mcmcpp_hip_last_run_timing", "mcmcpp_hip_last_run_host_timing",
+    "mcmcpp_hip_get_counters", "mcmcpp_hip_calc_logp", "mcmcpp_hip_set_chain_params", "mcmcpp_hip_calc_logp_chain", "mcmcpp_hip_last_run_timing", "mcmcpp_hip_last_run_host_timing",
     "mcmcpp_hip_comm_unique_id", "mcmcpp_hip_last_run_exchange", "mcmcpp_hip_run_async", "mcmcpp_hip_wait_stored", "mcmcpp_hip_run_wait",
     "mcmcpp_hip_host_alloc", "mcmcpp_hip_host_free",
     "mcmcpp_hip_half_step_async", "mcmcpp_hip_bind_device_chain", "mcmcpp_hip_device_positions",
@@ -92,6 +92,9 @@ def lib():
         L.mcmcpp_hip_reset_counters.argtypes = [vp]
         L.mcmcpp_hip_get_counters.argtypes = [vp, u64p, u64p, u64p, u64p]
         L.mcmcpp_hip_calc_logp.argtypes = [vp, vp, i64, vp]
+        if hasattr(L, "mcmcpp_hip_set_chain_params"):
+            L.mcmcpp_hip_set_chain_params.argtypes = [vp, i32, vp, i32]
+            L.mcmcpp_hip_calc_logp_chain.argtypes = [vp, i32, vp, i64, vp]
         L.mcmcpp_hip_last_run_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i64)]
         dp = C.POINTER(C.c_double)
         L.mcmcpp_hip_last_run_host_timing.argtypes = [vp, dp, dp, dp]
@@ -180,7 +183,10 @@ class HipSampler:
     def __init__(self, W, D, calc_id, params=None, seed=0, stream=0, dtype=F64, device=-1, shard_begin=0,
                  shard_count=0, graph_steps=0, device_positions=None, hip_stream=None, alpha=(2, 1), mover=0,
                  comm_world=0, comm_rank=0, comm_id=None, comm=None, num_chains=0, log_prob=None, batch_callback=None):
-        """comm_world >= 1: this handle is rank comm_rank of a split ensemble (comm_id: the 128 bytes of comm_unique_id(),
+        """params: the calculator's parameters, shared by all chains; or, with num_chains = K > 1, one row per chain
+        ((K, len) or (K, D, D)): row 0 goes to create, rows 1.. to set_chain_params.
+
+        comm_world >= 1: this handle is rank comm_rank of a split ensemble (comm_id: the 128 bytes of comm_unique_id(),
         the same on all ranks; or comm: an existing ncclComm_t as an integer); run() then steps the split ensemble.
 
         calc_id=CALC_BATCH takes the target from the caller, as exactly one of
@@ -201,7 +207,14 @@ class HipSampler:
         self.W, self.D, self.dtype = W, D, dtype
         self.K = num_chains if num_chains > 1 else 1  # independent ensembles stepped together (leading array dimension)
         self.np_t = np_dtype(dtype)
-        self.params = None if params is None else np.ascontiguousarray(params, dtype=self.np_t).ravel()
+        chain_params = None
+        if params is not None:
+            params = np.ascontiguousarray(params, dtype=self.np_t)
+            # (a (D, D) precision matrix is one shared block even when K == D)
+            if self.K > 1 and params.ndim >= 2 and params.shape[0] == self.K and not (calc_id == CALC_DENSE_GAUSSIAN and params.shape == (D, D)):
+                chain_params = params.reshape(self.K, -1)
+                params = chain_params[0]
+        self.params = None if params is None else params.ravel()
         self._comm_id = None if comm_id is None else C.create_string_buffer(bytes(comm_id), COMM_ID_BYTES)
         self.cfg = Config(C.sizeof(Config), dtype, W, D, calc_id, 0 if self.params is None else self.params.size,
                           _ptr(self.params), seed & (2**64 - 1), stream & (2**64 - 1), device, shard_begin,
@@ -221,6 +234,9 @@ class HipSampler:
             self._cb = fn  # (kept alive as long as the handle)
             fp = C.cast(fn, C.c_void_p) if isinstance(fn, C._CFuncPtr) else C.c_void_p(fn)
             self._check(lib().mcmcpp_hip_set_batch_calculator(self.h, fp, user, None, None))
+        if chain_params is not None:
+            for k in range(1, self.K):
+                self.set_chain_params(k, chain_params[k])
 
     def _set_torch_target(self, log_prob, dev):
         import torch
@@ -316,10 +332,20 @@ class HipSampler:
         self._check(lib().mcmcpp_hip_get_counters(self.h, *[C.byref(x) for x in v]))
         return dict(accepted=v[0].value, ensemble_steps=v[1].value, near_ties=v[2].value, redraws=v[3].value)
 
-    def calc_logp(self, pos):
+    def set_chain_params(self, chain, params):
+        """Chain `chain`'s own calculator parameters from the next run / calc_logp on (stored log-posteriors are not
+        recomputed: calc_logp(pos, chain) and set_state do that)."""
+        p = np.ascontiguousarray(params, dtype=self.np_t).ravel()
+        self._check(lib().mcmcpp_hip_set_chain_params(self.h, chain, _ptr(p), p.size))
+
+    def calc_logp(self, pos, chain=None):
+        """Log-posteriors of the rows of pos; chain=k: with chain k's parameters (None: the handle's own, i.e. chain 0's)."""
         pos = np.ascontiguousarray(pos, dtype=self.np_t).reshape(-1, self.D)
         out = np.empty(pos.shape[0], dtype=self.np_t)
-        self._check(lib().mcmcpp_hip_calc_logp(self.h, _ptr(pos), pos.shape[0], _ptr(out)))
+        if chain is None:
+            self._check(lib().mcmcpp_hip_calc_logp(self.h, _ptr(pos), pos.shape[0], _ptr(out)))
+        else:
+            self._check(lib().mcmcpp_hip_calc_logp_chain(self.h, chain, _ptr(pos), pos.shape[0], _ptr(out)))
         return out
 
     def last_run_timing(self):

@@ -385,6 +385,15 @@ public:
         return MCMCPP_HIP_OK;
     }
 
+    int set_chain_params(int32_t, const void*, int32_t) override
+    {
+        return fail(MCMCPP_HIP_E_ARG, "set_chain_params: the batch target takes no parameters (the callback's user pointer carries them)");
+    }
+    int calc_logp_chain(int32_t, const void*, int64_t, void*) override
+    {
+        return fail(MCMCPP_HIP_E_ARG, "calc_logp_chain: the batch target takes no parameters (the callback's user pointer carries them)");
+    }
+
     int half_step_async(int32_t, int64_t) override
     {
         return fail(MCMCPP_HIP_E_UNSUPPORTED, "half_step_async: not with a batch target (its half-steps need the host callback; use run)");

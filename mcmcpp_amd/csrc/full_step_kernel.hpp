@@ -176,7 +176,7 @@ stretch_full_step_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b, T* h
     uint32_t nacc_r = h_n_accept[ir];
     uint32_t nacc_b = h_n_accept[h_n + ir];
     typename Calc::Prefetch calc_pf;
-    Calc::block_prefetch(calc_pf, a.calc_params, h_dims, vec_ok, (int)threadIdx.x, 64 * kWavesPerBlock);
+    Calc::block_prefetch(calc_pf, chain_calc_params<MC>(a, chain), h_dims, vec_ok, (int)threadIdx.x, 64 * kWavesPerBlock);
 
     // ---- second round trip: everything the two records point to ----
     T par_r[EPL], own_x[EPL], par_x[EPL];
@@ -205,11 +205,11 @@ stretch_full_step_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b, T* h
 
     // ---- in its shadow: the calculator's tables, the hand-over to the next launch ----
     const bool has_block_scratch = Calc::block_scratch_elems(h_dims) != 0;
-    Calc::block_commit(calc_pf, sh_block, a.calc_params, h_dims, vec_ok, (int)threadIdx.x, 64 * kWavesPerBlock);
+    Calc::block_commit(calc_pf, sh_block, chain_calc_params<MC>(a, chain), h_dims, vec_ok, (int)threadIdx.x, 64 * kWavesPerBlock);
     if (has_block_scratch) __syncthreads();
     ctx.block_scratch = has_block_scratch ? sh_block : nullptr;
     typename Calc::template Regs<EPL, LPW> cregs;
-    Calc::template preload<EPL, LPW>(ctx, a.calc_params, cregs);
+    Calc::template preload<EPL, LPW>(ctx, chain_calc_params<MC>(a, chain), cregs);
     if (blockIdx.x == 0 && threadIdx.x == 0) hand_over_full<T>(a, ctl, run, const_cast<StepCtl*>(ctl_mine) + (h_flip ? -1 : 1));
     if (!wave_active) return;
 
@@ -254,7 +254,7 @@ stretch_full_step_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b, T* h
     };
     // `fin` receives the walker's row after the update; returns accept, lp_out = its log-posterior afterwards.
     auto finish = [&](const T (&own)[EPL], const T (&prop)[EPL], const DrawRec<T>& rec, T lp_old, bool count_ties, T (&fin)[EPL], T& lp_out) -> bool {
-        const T lp_new = Calc::template eval<EPL, LPW>(ctx, a.calc_params, cregs, prop);
+        const T lp_new = Calc::template eval<EPL, LPW>(ctx, chain_calc_params<MC>(a, chain), cregs, prop);
         const T delta = rec.zs + lp_new - lp_old;
         const bool accept = rec.ln_u < delta;
         if (count_ties && active && sub == 0)
@@ -381,6 +381,7 @@ stretch_full_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b,
         hot_pos_a += (size_t)chain * 2 * (size_t)h_n * (size_t)h_dims;
         hot_pos_b += (size_t)chain * 2 * (size_t)h_n * (size_t)h_dims;
         hot_logp_a = reinterpret_cast<T*>(reinterpret_cast<char*>(hot_logp_a) + (size_t)chain * logp_chain_stride_bytes<T>(h_n));
+        hot_matrix += (size_t)chain * (size_t)a.params_chain_stride;  // (the chain's own P^T; stride 0: shared)
     }
     const int h_use_ctl_save = (int)((hot_bits >> 23) & 1u);
     const int h_parity = (int)((hot_bits >> 24) & 1u);

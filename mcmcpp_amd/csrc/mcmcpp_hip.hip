@@ -174,6 +174,8 @@ struct PinnedScratch
 };
 static_assert(sizeof(StepCtl) <= 64 && sizeof(RunInfo) <= 64, "a control or run record is uploaded as one 64-byte line");
 
+int check_config(const mcmcpp_hip_config* c, std::string& err);
+
 template <class T>
 class Sampler final : public SamplerHost<T>
 {
@@ -1281,6 +1283,61 @@ public:
 
     int calc_logp(const void* pos, int64_t count, void* out) override { return kernel_calc_logp(calc_fn, d_params, pos, count, out); }
 
+    // Per-chain calculator parameters (ChainGeometry).  The first block set moves the parameters out of the arena (sized for
+    // one block) into [K][chain_params_stride], every row a copy of the create-time block; the step launches then carry the
+    // new pointers and the stride, so the cached graphs, which froze the old ones into their nodes, are dropped.  Later blocks
+    // are rewritten in place, ordered on the launch stream: the graphs read them from memory.
+    int set_chain_params(int32_t chain, const void* params, int32_t len) override
+    {
+        if (int rc = chain_params_supported("set_chain_params")) return rc;
+        if (chain < 0 || chain >= K) return fail(MCMCPP_HIP_E_ARG, "set_chain_params: chain %d outside 0..%d", chain, K - 1);
+        if (cfg.calc_params_len == 0) return fail(MCMCPP_HIP_E_ARG, "set_chain_params: calculator %d takes no parameters", cfg.calc_id);
+        if (len != cfg.calc_params_len)
+            return fail(MCMCPP_HIP_E_ARG, "set_chain_params: len %d, but the handle's calculator takes %d parameters", len, cfg.calc_params_len);
+        if (!params) return fail(MCMCPP_HIP_E_ARG, "set_chain_params: params is NULL");
+        mcmcpp_hip_config c = cfg;
+        c.calc_params = params;
+        std::string why;
+        if (int rc = check_config(&c, why)) return fail(rc, "set_chain_params: %s", why.c_str());
+        HIP_TRY(hipSetDevice(device));
+        const CalcParams<T> p = calc_params_host<T>(c, d_params_padded != nullptr);
+        const size_t prm_row = (p.prm.size() + 255 / sizeof(T)) & ~(size_t)(255 / sizeof(T));  // (the padded P^T 256-byte aligned)
+        if (!d_chain_params)
+        {
+            const size_t stride = prm_row + p.pad.size();
+            if (stride > (size_t)INT32_MAX) return fail(MCMCPP_HIP_E_ARG, "set_chain_params: %zu elements per chain are too many", stride);
+            void* dp = nullptr;
+            if (hipMalloc(&dp, sizeof(T) * stride * (size_t)K) != hipSuccess)
+                return fail(MCMCPP_HIP_E_NOMEM, "set_chain_params: cannot allocate %zu bytes of per-chain parameters", sizeof(T) * stride * (size_t)K);
+            T* const rows = static_cast<T*>(dp);
+            HIP_TRY(hipStreamSynchronize(stream));
+            drop_graphs();
+            for (int k = 0; k < K; ++k)
+            {
+                T* const row = rows + stride * (size_t)k;
+                HIP_TRY(hipMemcpyAsync(row, d_params, sizeof(T) * p.prm.size(), hipMemcpyDeviceToDevice, stream));
+                if (d_params_padded) HIP_TRY(hipMemcpyAsync(row + prm_row, d_params_padded, sizeof(T) * p.pad.size(), hipMemcpyDeviceToDevice, stream));
+            }
+            d_chain_params = rows;
+            d_params = rows;
+            if (d_params_padded) d_params_padded = rows + prm_row;
+            chain_params_stride = (int)stride;
+        }
+        T* const row = d_chain_params + (size_t)chain_params_stride * (size_t)chain;
+        HIP_TRY(hipMemcpyAsync(row, p.prm.data(), sizeof(T) * p.prm.size(), hipMemcpyHostToDevice, stream));
+        if (!p.pad.empty()) HIP_TRY(hipMemcpyAsync(row + prm_row, p.pad.data(), sizeof(T) * p.pad.size(), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return MCMCPP_HIP_OK;
+    }
+
+    int calc_logp_chain(int32_t chain, const void* pos, int64_t count, void* out) override
+    {
+        if (int rc = chain_params_supported("calc_logp_chain")) return rc;
+        if (chain < 0 || chain >= K) return fail(MCMCPP_HIP_E_ARG, "calc_logp_chain: chain %d outside 0..%d", chain, K - 1);
+        const T* prm = d_chain_params ? d_chain_params + (size_t)chain_params_stride * (size_t)chain : d_params;
+        return kernel_calc_logp(calc_fn, prm, pos, count, out);
+    }
+
     int half_step_async(int32_t color, int64_t save_slot) override
     {
         if (K > 1) return fail(MCMCPP_HIP_E_UNSUPPORTED, "half_step_async: not with several chains per handle");
@@ -1327,6 +1384,26 @@ public:
     }
 
 private:
+    // per-chain parameters: one whole ensemble per chain on this device, in buffers of the handle's own
+    int chain_params_supported(const char* what)
+    {
+        if (shard_count != n || shard_begin != 0) return fail(MCMCPP_HIP_E_UNSUPPORTED, "%s: not for a sharded handle", what);
+        if (cfg.comm_world >= 1) return fail(MCMCPP_HIP_E_UNSUPPORTED, "%s: not for a handle with a communicator", what);
+        if (!own_pos) return fail(MCMCPP_HIP_E_UNSUPPORTED, "%s: not for a handle with caller-owned positions", what);
+        return MCMCPP_HIP_OK;
+    }
+
+    // the instantiated graphs (their kernel nodes hold the launch arguments of the time of capture); the stream is idle
+    void drop_graphs()
+    {
+        for (hipGraphExec_t& ex : graph_cache)
+            if (ex)
+            {
+                (void)hipGraphExecDestroy(ex);
+                ex = nullptr;
+            }
+    }
+
     int hip_rc(hipError_t e, const char* what)
     {
         if (e == hipSuccess) return MCMCPP_HIP_OK;
@@ -1403,6 +1480,7 @@ private:
         a.pos_parity = 0;
         a.calc_params_padded = d_params_padded;
         a.chains = K;
+        a.params_chain_stride = chain_params_stride;
         // a fifth wavefront per workgroup computes the next draws when that is at most two rounds of 64 draws
         a.draw_wave = (3 * kWavesPerBlock * (64 / step_lpw) * passes <= 128 && knobs.no_draw_wave == 0) ? 1 : 0;
         return a;
@@ -1644,6 +1722,7 @@ private:
         for (hipGraphExec_t ex : graph_cache)
             if (ex) hipGraphExecDestroy(ex);
         if (arena) hipFree(arena);  // positions, log-posteriors, counters, records, tables, parameters, partial counts
+        if (d_chain_params) hipFree(d_chain_params);
         if (d_acc) hipFree(d_acc);
         if (d_draws_batch) hipFree(d_draws_batch);
         if (d_step_jump) hipFree(d_step_jump);
@@ -1706,7 +1785,9 @@ private:
     uint32_t* d_acc = nullptr;
     bool own_pos = false, run_touched_device = false;
     hipEvent_t ev_t0[4] = {nullptr, nullptr, nullptr, nullptr}, ev_t1[4] = {nullptr, nullptr, nullptr, nullptr};
-    T *d_params = nullptr, *d_params_padded = nullptr;
+    T *d_params = nullptr, *d_params_padded = nullptr;  // (row 0 of d_chain_params once a chain has parameters of its own)
+    T* d_chain_params = nullptr;  // [K][chain_params_stride] per-chain parameters (set_chain_params), or nullptr: shared
+    int chain_params_stride = 0;
     StepCtl* d_ctl = nullptr;
     RunInfo* d_run = nullptr;
     uint64_t* d_status = nullptr;
@@ -1881,6 +1962,18 @@ int mcmcpp_hip_set_state(mcmcpp_hip_sampler* h, const void* positions, const voi
     NEED_H;
     NOT_WHILE_ASYNC("set_state");
     return h->set_state(positions, logp);
+}
+int mcmcpp_hip_set_chain_params(mcmcpp_hip_sampler* h, int32_t chain, const void* params, int32_t len)
+{
+    NEED_H;
+    NOT_WHILE_ASYNC("set_chain_params");
+    return h->set_chain_params(chain, params, len);
+}
+int mcmcpp_hip_calc_logp_chain(mcmcpp_hip_sampler* h, int32_t chain, const void* pos, int64_t count, void* out)
+{
+    NEED_H;
+    NOT_WHILE_ASYNC("calc_logp_chain");
+    return h->calc_logp_chain(chain, pos, count, out);
 }
 int mcmcpp_hip_run(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step)
 {

@@ -61,6 +61,15 @@ struct mcmcpp_hip_sampler
     virtual void* device_positions() = 0;
     virtual int shard_span(int32_t color, int64_t* off, int64_t* cnt) = 0;
     virtual int synchronize() = 0;
+    // per-chain calculator parameters (mcmcpp_hip_set_chain_params): the fused stretch-move sampler only
+    virtual int set_chain_params(int32_t, const void*, int32_t)
+    {
+        return fail(MCMCPP_HIP_E_UNSUPPORTED, "set_chain_params: per-chain parameters are for stretch-move handles only (not differential evolution)");
+    }
+    virtual int calc_logp_chain(int32_t, const void*, int64_t, void*)
+    {
+        return fail(MCMCPP_HIP_E_UNSUPPORTED, "calc_logp_chain: per-chain parameters are for stretch-move handles only (not differential evolution)");
+    }
     // calc_id MCMCPP_HIP_CALC_BATCH only (batch.hip)
     virtual int set_batch_calculator(mcmcpp_hip_batch_logp_fn, void*, void*, void*)
     {

@@ -144,7 +144,11 @@ __device__ __forceinline__ JumpTables jump_tables_behind(const void* draws_base,
 //   control + run records      [chains]{StepCtl[2], pad to kRunBehindCtlBytes, RunInfo, pad to kCtlChainStride}
 //   draw records               [chains][2][2][n], then the shared jump tables
 //   partial accepted counts    [chains][partial_slots][2][partial_waves]
-// The chains differ in their seed (seed + chain: same stream increment, hence the same jump tables).
+// The chains differ in their seed (seed + chain: same stream increment, hence the same jump tables) and, once the host has
+// given any chain a parameter block of its own (mcmcpp_hip_set_chain_params), in their calculator parameters:
+//   calculator parameters      [chains][params_chain_stride]: the block (P^T for the dense target), zero padding to 256 bytes,
+//                              then -- dense target, D <= 32 -- the matrix-core kernels' zero-padded 32 x 32 P^T
+// calc_params and calc_params_padded point into row 0 and the MC kernels step both by chain * params_chain_stride (0: shared).
 constexpr int kCtlChainStride = 512;
 constexpr int kRunBehindCtlBytes = 256;
 constexpr int kMaxChains = 16;  // (four hot bits)
@@ -203,6 +207,8 @@ struct alignas(64) HalfStepArgs
     int draw_wave;              // 1: the workgroup carries extra wavefronts that compute the next draws
     int pos_parity;             // full-step kernels: 0: read pos/logp, write pos_alt/logp_alt; 1: the reverse
     int chains;                 // independent ensembles stepped by this launch (grid.y), 1..kMaxChains
+    int params_chain_stride;    // elements between two chains' rows of calc_params AND of calc_params_padded (one [chains][stride]
+                                // array, see ChainGeometry); 0: every chain reads the same parameters.  Read by MC kernels only
 };
 // the line layout above is what the kernels are tuned to: the updating wavefronts' fields start on line 4
 static_assert(offsetof(HalfStepArgs<double>, pos) == 256 && sizeof(HalfStepArgs<double>) == 448, "HalfStepArgs<double> layout moved");
@@ -498,6 +504,14 @@ __device__ __forceinline__ void compute_draw(const HalfStepArgs<T>& a, U128 base
 
 // The run record lies kRunBehindCtlBytes behind the first of the two control records (one allocation): a kernel short
 // of preloaded arguments reads it at an offset from the control record's address (load_records_and_warm_args).
+// The calculator parameters of chain `chain` (ChainGeometry; params_chain_stride 0: shared).  The single-ensemble
+// instantiations read a.calc_params where they always did.
+template <bool MC, class T>
+__device__ __forceinline__ const T* chain_calc_params(const HalfStepArgs<T>& a, int chain)
+{
+    return MC ? a.calc_params + (size_t)chain * (size_t)a.params_chain_stride : a.calc_params;
+}
+
 // Hot scalars of a launch, packed so that the arguments every wavefront needs before its first memory
 // access fit the 16 dwords the command processor preloads into SGPRs (-amdgpu-kernarg-preload-count=16);
 // everything else stays in the by-value HalfStepArgs and is fetched from the kernarg segment on demand.
@@ -737,7 +751,7 @@ stretch_half_step_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, uint32_
         nacc_old = h_n_accept[w0];  // every lane of the group reads the same word: no divergent branch, no wait
     }
     typename Calc::Prefetch calc_pf;
-    Calc::block_prefetch(calc_pf, a.calc_params, h_dims, vec_ok, (int)threadIdx.x, 64 * kWavesPerBlock);
+    Calc::block_prefetch(calc_pf, chain_calc_params<MC>(a, chain), h_dims, vec_ok, (int)threadIdx.x, 64 * kWavesPerBlock);
 
     const StepCtl* ctl_mine = hot_ctl_in;
     const RunInfo* run_mine = a.run;
@@ -772,11 +786,11 @@ stretch_half_step_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, uint32_
 
     // ---- in its shadow: the calculator's tables, the hand-over to the next launch, the next draws -----------
     const bool has_block_scratch = Calc::block_scratch_elems(h_dims) != 0;
-    Calc::block_commit(calc_pf, sh_block, a.calc_params, h_dims, vec_ok, (int)threadIdx.x, 64 * kWavesPerBlock);
+    Calc::block_commit(calc_pf, sh_block, chain_calc_params<MC>(a, chain), h_dims, vec_ok, (int)threadIdx.x, 64 * kWavesPerBlock);
     if (has_block_scratch) __syncthreads();
     ctx.block_scratch = has_block_scratch ? sh_block : nullptr;
     typename Calc::template Regs<EPL, LPW> cregs;
-    Calc::template preload<EPL, LPW>(ctx, a.calc_params, cregs);
+    Calc::template preload<EPL, LPW>(ctx, chain_calc_params<MC>(a, chain), cregs);
 
     // one lane of the grid hands the stream and the counters to the next launch (in the shadow of its gather wait;
     // in the extra wavefront it would lengthen the last wavefront to finish: measured)
@@ -854,7 +868,7 @@ stretch_half_step_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, uint32_
             const T zd = rec.z * d;
             prop[e] = par[e] + zd;
         }
-        const T lp_new = Calc::template eval<EPL, LPW>(ctx, a.calc_params, cregs, prop);
+        const T lp_new = Calc::template eval<EPL, LPW>(ctx, chain_calc_params<MC>(a, chain), cregs, prop);
 
         // StretchMove.h:112-113  accept iff lnU < (probScaling + newProb) - oldProb
         const T zs = rec.zs, ln_u = rec.ln_u;
@@ -1092,6 +1106,7 @@ stretch_half_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, ui
         hot_pos += (size_t)chain * 2 * (size_t)hot_n * (size_t)(hot_bits & 0xFFFu);
         hot_logp = reinterpret_cast<T*>(reinterpret_cast<char*>(hot_logp) + (size_t)chain * logp_chain_stride_bytes<T>(hot_n));
         hot_n_accept = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(hot_n_accept) + (size_t)chain * logp_chain_stride_bytes<T>(hot_n));
+        hot_matrix += (size_t)chain * (size_t)a.params_chain_stride;  // (the chain's own P^T; stride 0: shared)
     }
     const int h_color = (int)((hot_bits >> 20) & 1u);
     const int h_parity = (int)((hot_bits >> 24) & 1u);
