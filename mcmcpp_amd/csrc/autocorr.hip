@@ -25,7 +25,9 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mcmcpp_hip.h"
@@ -281,27 +283,6 @@ int ac_fail(int code, const std::string& msg)
     return code;
 }
 
-struct DeviceBuffers
-{
-    std::vector<void*> ptrs;
-    hipStream_t stream = nullptr;
-    ~DeviceBuffers()
-    {
-        if (stream) (void)hipStreamSynchronize(stream);
-        for (void* p : ptrs) (void)hipFree(p);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-    template <class U>
-    bool alloc(U** out, size_t count)
-    {
-        void* p = nullptr;
-        if (hipMalloc(&p, sizeof(U) * (count ? count : 1)) != hipSuccess) return false;
-        ptrs.push_back(p);
-        *out = static_cast<U*>(p);
-        return true;
-    }
-};
-
 #define AC_TRY(expr)                                                                                          \
     do                                                                                                        \
     {                                                                                                         \
@@ -330,57 +311,63 @@ int autocorr_times(const void* const* steps, const T* device_steps, int64_t n_st
     std::vector<int> walker_idx((size_t)use);
     for (int i = 0; i < use; ++i) walker_idx[(size_t)i] = (int)(((int64_t)i * W) / use);  // all of them, or evenly spaced
 
-    DeviceBuffers dev;
-    AC_TRY(hipStreamCreateWithFlags(&dev.stream, hipStreamNonBlocking));
+    mcmcpp::DeviceBuffer<T> d_upload, d_avg, d_tw, d_acov, d_sum, d_comp, d_times, d_scratch;
+    mcmcpp::DeviceBuffer<int> d_idx;
+    // (declared behind the buffers, so that on every way out the stream is idle and gone before they free themselves)
+    hipStream_t stream = nullptr;
+    AC_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    const auto sync_and_destroy = [](hipStream_t s) {
+        (void)hipStreamSynchronize(s);
+        (void)hipStreamDestroy(s);
+    };
+    const std::unique_ptr<std::remove_pointer_t<hipStream_t>, decltype(sync_and_destroy)> stream_owner(stream, sync_and_destroy);
     // walkers per pass over the transforms: bounded by 1 GiB of functions and 2 GiB of global scratch
     size_t per_walker = sizeof(T) * (size_t)D * n;
     size_t per_walker_scratch = lds ? 0 : sizeof(T) * (size_t)D * 2 * fft;
     int chunk = use;
     while (chunk > 1 && ((size_t)chunk * per_walker > ((size_t)1 << 30) || (size_t)chunk * per_walker_scratch > ((size_t)2 << 30))) chunk = (chunk + 1) / 2;
 
-    T *d_avg, *d_tw, *d_acov, *d_sum, *d_comp, *d_times, *d_scratch = nullptr;
-    T* d_upload = nullptr;
-    int* d_idx;
-    if ((steps && !dev.alloc(&d_upload, (size_t)n * step_elems)) || !dev.alloc(&d_avg, (size_t)use * D) || !dev.alloc(&d_tw, (size_t)fft) ||
-        !dev.alloc(&d_acov, (size_t)chunk * D * n) || !dev.alloc(&d_sum, (size_t)D * n) || !dev.alloc(&d_comp, (size_t)D * n) ||
-        !dev.alloc(&d_times, (size_t)D) || !dev.alloc(&d_idx, (size_t)use) || (!lds && !dev.alloc(&d_scratch, (size_t)chunk * D * 2 * fft)))
+    const auto alloc = [](auto& buf, size_t count) { return buf.alloc(sizeof(*buf.get()) * (count ? count : 1)) == hipSuccess; };
+    if ((steps && !alloc(d_upload, (size_t)n * step_elems)) || !alloc(d_avg, (size_t)use * D) || !alloc(d_tw, (size_t)fft) ||
+        !alloc(d_acov, (size_t)chunk * D * n) || !alloc(d_sum, (size_t)D * n) || !alloc(d_comp, (size_t)D * n) || !alloc(d_times, (size_t)D) ||
+        !alloc(d_idx, (size_t)use) || (!lds && !alloc(d_scratch, (size_t)chunk * D * 2 * fft)))
         return ac_fail(MCMCPP_HIP_E_NOMEM, "autocorr_times: cannot allocate device memory for the chain and the work arrays");
 
-    const T* d_steps = steps ? d_upload : device_steps;
+    const T* d_steps = steps ? d_upload.get() : device_steps;
     // upload: steps that follow each other in host memory go in one copy
     for (int64_t s = 0; steps && s < n_steps;)
     {
         int64_t e = s + 1;
         while (e < n_steps && static_cast<const T*>(steps[e]) == static_cast<const T*>(steps[e - 1]) + step_elems) ++e;
-        AC_TRY(hipMemcpyAsync(d_upload + (size_t)s * step_elems, steps[s], sizeof(T) * (size_t)(e - s) * step_elems, hipMemcpyHostToDevice, dev.stream));
+        AC_TRY(hipMemcpyAsync(d_upload + (size_t)s * step_elems, steps[s], sizeof(T) * (size_t)(e - s) * step_elems, hipMemcpyHostToDevice, stream));
         s = e;
     }
-    AC_TRY(hipMemcpyAsync(d_tw, tw.data(), sizeof(T) * tw.size(), hipMemcpyHostToDevice, dev.stream));
-    AC_TRY(hipMemcpyAsync(d_idx, walker_idx.data(), sizeof(int) * walker_idx.size(), hipMemcpyHostToDevice, dev.stream));
-    AC_TRY(hipMemsetAsync(d_sum, 0, sizeof(T) * (size_t)D * n, dev.stream));
-    AC_TRY(hipMemsetAsync(d_comp, 0, sizeof(T) * (size_t)D * n, dev.stream));
+    AC_TRY(hipMemcpyAsync(d_tw, tw.data(), sizeof(T) * tw.size(), hipMemcpyHostToDevice, stream));
+    AC_TRY(hipMemcpyAsync(d_idx, walker_idx.data(), sizeof(int) * walker_idx.size(), hipMemcpyHostToDevice, stream));
+    AC_TRY(hipMemsetAsync(d_sum, 0, sizeof(T) * (size_t)D * n, stream));
+    AC_TRY(hipMemsetAsync(d_comp, 0, sizeof(T) * (size_t)D * n, stream));
 
     const long long series_total = (long long)use * D;
-    hipLaunchKernelGGL(ac_chain_average_kernel<T>, dim3((unsigned)((series_total + kAcThreads - 1) / kAcThreads)), dim3(kAcThreads), 0, dev.stream, d_steps, n,
+    hipLaunchKernelGGL(ac_chain_average_kernel<T>, dim3((unsigned)((series_total + kAcThreads - 1) / kAcThreads)), dim3(kAcThreads), 0, stream, d_steps, n,
                        (long long)step_elems, d_idx, use, D, d_avg);
     for (int first = 0; first < use; first += chunk)
     {
         const int cw = use - first < chunk ? use - first : chunk;
         const unsigned ac_grid = (unsigned)(((cw * D + kXcds - 1) / kXcds) * kXcds);  // (whole rounds over the XCDs)
         if (lds)
-            hipLaunchKernelGGL((ac_autocov_kernel<T, true>), dim3(ac_grid), dim3(kAcThreads), sizeof(T) * 2 * (size_t)fft, dev.stream, d_steps, n,
+            hipLaunchKernelGGL((ac_autocov_kernel<T, true>), dim3(ac_grid), dim3(kAcThreads), sizeof(T) * 2 * (size_t)fft, stream, d_steps, n,
                                (long long)step_elems, d_idx, first, D, d_avg, d_tw, lg, d_scratch, d_acov, cw * D);
         else
-            hipLaunchKernelGGL((ac_autocov_kernel<T, false>), dim3(ac_grid), dim3(kAcThreads), 0, dev.stream, d_steps, n, (long long)step_elems, d_idx,
+            hipLaunchKernelGGL((ac_autocov_kernel<T, false>), dim3(ac_grid), dim3(kAcThreads), 0, stream, d_steps, n, (long long)step_elems, d_idx,
                                first, D, d_avg, d_tw, lg, d_scratch, d_acov, cw * D);
-        hipLaunchKernelGGL(ac_accumulate_kernel<T>, dim3((unsigned)(((long long)D * n + kAcThreads - 1) / kAcThreads)), dim3(kAcThreads), 0, dev.stream, d_acov, n,
+        hipLaunchKernelGGL(ac_accumulate_kernel<T>, dim3((unsigned)(((long long)D * n + kAcThreads - 1) / kAcThreads)), dim3(kAcThreads), 0, stream, d_acov, n,
                            D, cw, d_sum, d_comp);
     }
-    hipLaunchKernelGGL(ac_window_kernel<T>, dim3((unsigned)D), dim3(kAcThreads), 0, dev.stream, d_sum, n, use, window_scaling, d_times);
+    hipLaunchKernelGGL(ac_window_kernel<T>, dim3((unsigned)D), dim3(kAcThreads), 0, stream, d_sum, n, use, window_scaling, d_times);
     AC_TRY(hipGetLastError());
-    AC_TRY(hipMemcpyAsync(times, d_times, sizeof(T) * (size_t)D, hipMemcpyDeviceToHost, dev.stream));
-    if (functions) AC_TRY(hipMemcpyAsync(functions, d_sum, sizeof(T) * (size_t)D * n, hipMemcpyDeviceToHost, dev.stream));
-    AC_TRY(hipStreamSynchronize(dev.stream));
+    AC_TRY(hipMemcpyAsync(times, d_times, sizeof(T) * (size_t)D, hipMemcpyDeviceToHost, stream));
+    if (functions) AC_TRY(hipMemcpyAsync(functions, d_sum, sizeof(T) * (size_t)D * n, hipMemcpyDeviceToHost, stream));
+    AC_TRY(hipStreamSynchronize(stream));
     return MCMCPP_HIP_OK;
 }
 }  // namespace

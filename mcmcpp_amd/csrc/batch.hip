@@ -209,7 +209,7 @@ class BatchSampler final : public SamplerHost<T>
     MCMCPP_SAMPLER_HOST_NAMES;
 
 public:
-    ~BatchSampler() override { release(); }
+    ~BatchSampler() override { quiesce(); }
 
     int init(const mcmcpp_hip_config& c)
     {
@@ -222,8 +222,8 @@ public:
         hipDeviceProp_t prop;
         if (int rc = open_device(c, &prop)) return rc;
         if (int rc = open_stream(c)) return rc;
-        HIP_TRY(hipEventCreate(&ev_t0));
-        HIP_TRY(hipEventCreate(&ev_t1));
+        HIP_TRY(hipEventCreate(ev_t0.replace()));
+        HIP_TRY(hipEventCreate(ev_t1.replace()));
 
         if (c.device_positions)
         {
@@ -232,23 +232,26 @@ public:
         }
         else
         {
-            HIP_TRY(hipMalloc(&d_own_pos, sizeof(T) * (size_t)W * D));
+            HIP_TRY(d_own_pos.alloc(sizeof(T) * (size_t)W * D));
             d_pos = d_own_pos;
         }
-        HIP_TRY(hipMalloc(&d_logp, sizeof(T) * (size_t)W));
-        HIP_TRY(hipMalloc(&d_nacc, sizeof(uint32_t) * (size_t)W));
-        HIP_TRY(hipMalloc(&d_ctl, 2 * sizeof(StepCtl)));
-        HIP_TRY(hipMalloc(&d_run, sizeof(RunInfo)));
-        HIP_TRY(hipMalloc(&d_diag, sizeof(Diag)));
-        HIP_TRY(hipMalloc(&d_draws, sizeof(DrawRec<T>) * 4 * (size_t)n));
-        HIP_TRY(hipMalloc(&d_partials, sizeof(uint32_t) * 2 * (size_t)partial_waves));
+        HIP_TRY(d_own_logp.alloc(sizeof(T) * (size_t)W));
+        HIP_TRY(d_own_nacc.alloc(sizeof(uint32_t) * (size_t)W));
+        HIP_TRY(d_ctl.alloc(2 * sizeof(StepCtl)));
+        HIP_TRY(d_run.alloc(sizeof(RunInfo)));
+        HIP_TRY(d_own_diag.alloc(sizeof(Diag)));
+        HIP_TRY(d_draws.alloc(sizeof(DrawRec<T>) * 4 * (size_t)n));
+        HIP_TRY(d_partials.alloc(sizeof(uint32_t) * 2 * (size_t)partial_waves));
+        d_logp = d_own_logp;
+        d_nacc = d_own_nacc;
+        d_diag = d_own_diag;
         HIP_TRY(hipMemset(d_logp, 0, sizeof(T) * (size_t)W));
         HIP_TRY(hipMemset(d_nacc, 0, sizeof(uint32_t) * (size_t)W));
         HIP_TRY(hipMemset(d_ctl, 0, 2 * sizeof(StepCtl)));
         HIP_TRY(hipMemset(d_diag, 0, sizeof(Diag)));
         HIP_TRY(hipMemset(d_draws, 0, sizeof(DrawRec<T>) * 4 * (size_t)n));
         HIP_TRY(hipMemset(d_partials, 0, sizeof(uint32_t) * 2 * (size_t)partial_waves));
-        HIP_TRY(hipHostMalloc(&h_pinned, sizeof(Pinned), hipHostMallocDefault));
+        HIP_TRY(h_pinned.alloc(sizeof(Pinned)));
         std::memset(h_pinned, 0, sizeof(Pinned));
         h_pinned->run.interval = 1;
         h_pinned->run.slot_mask = -1;
@@ -260,13 +263,13 @@ public:
         const Knobs knobs = Knobs::from_environment();
         {
             const StretchJumpTables j = stretch_jump_tables(inc, n, (size_t)3 * n * sizeof(Affine128) <= ((size_t)knobs.task_table_mb << 20));
-            HIP_TRY(hipMalloc(&d_jump_lo, sizeof(Affine128) * j.lo.size()));
-            HIP_TRY(hipMalloc(&d_jump_hi, sizeof(Affine128) * j.hi.size()));
+            HIP_TRY(d_jump_lo.alloc(sizeof(Affine128) * j.lo.size()));
+            HIP_TRY(d_jump_hi.alloc(sizeof(Affine128) * j.hi.size()));
             HIP_TRY(hipMemcpy(d_jump_lo, j.lo.data(), sizeof(Affine128) * j.lo.size(), hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy(d_jump_hi, j.hi.data(), sizeof(Affine128) * j.hi.size(), hipMemcpyHostToDevice));
             if (!j.task.empty())
             {
-                HIP_TRY(hipMalloc(&d_task_jump, sizeof(Affine128) * j.task.size()));
+                HIP_TRY(d_task_jump.alloc(sizeof(Affine128) * j.task.size()));
                 HIP_TRY(hipMemcpy(d_task_jump, j.task.data(), sizeof(Affine128) * j.task.size(), hipMemcpyHostToDevice));
             }
         }
@@ -281,12 +284,12 @@ public:
             return fail(MCMCPP_HIP_E_ARG, "set_batch_calculator: device_proposals and device_logp must be 16-byte aligned");
         HIP_TRY(hipSetDevice(device));
         if ((!dprop && !d_own_prop) || (!dlogp && !d_own_lp)) HIP_TRY(hipStreamSynchronize(stream));
-        if (!dprop && !d_own_prop) HIP_TRY(hipMalloc(&d_own_prop, sizeof(T) * (size_t)n * D));
-        if (!dlogp && !d_own_lp) HIP_TRY(hipMalloc(&d_own_lp, sizeof(T) * (size_t)n));
+        if (!dprop && !d_own_prop) HIP_TRY(d_own_prop.alloc(sizeof(T) * (size_t)n * D));
+        if (!dlogp && !d_own_lp) HIP_TRY(d_own_lp.alloc(sizeof(T) * (size_t)n));
         fn = f;
         user = u;
-        d_prop = dprop ? (T*)dprop : d_own_prop;
-        d_lp = dlogp ? (T*)dlogp : d_own_lp;
+        d_prop = dprop ? (T*)dprop : d_own_prop.get();
+        d_lp = dlogp ? (T*)dlogp : d_own_lp.get();
         return MCMCPP_HIP_OK;
     }
 
@@ -323,11 +326,11 @@ public:
         if (chain_out)
         {
             sub_saved = stored_steps_per_subchunk(chain_subchunk_bytes, step_bytes, n_saved);
-            if (int rc = ensure(&d_chain, &chain_capacity, step_bytes * (size_t)sub_saved)) return rc;
+            if (int rc = ensure(d_chain, step_bytes * (size_t)sub_saved)) return rc;
         }
         if (accepted_per_step)
         {
-            if (int rc = ensure(&d_acc, &acc_capacity, sizeof(uint32_t) * (size_t)total)) return rc;
+            if (int rc = ensure(d_acc, sizeof(uint32_t) * (size_t)total)) return rc;
         }
         const int rc = run_steps(n_saved, interval, chain_out, accepted_per_step, sub_saved, step_bytes, total);
         if (rc != MCMCPP_HIP_OK)
@@ -411,19 +414,9 @@ private:
     };
 
     template <class P>
-    int ensure(P** buf, size_t* capacity, size_t bytes)
+    int ensure(DeviceBuffer<P>& buf, size_t bytes)
     {
-        if (bytes <= *capacity) return MCMCPP_HIP_OK;
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (*buf) (void)hipFree(*buf);
-        *buf = nullptr;
-        *capacity = 0;
-        if (hipMalloc(buf, bytes) != hipSuccess)
-        {
-            (void)hipGetLastError();
-            return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu bytes of device memory", bytes);
-        }
-        *capacity = bytes;
+        if (grow(buf, bytes, stream)) return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu bytes of device memory", bytes);
         return MCMCPP_HIP_OK;
     }
 
@@ -490,8 +483,8 @@ private:
             const int64_t now = chain_out ? ((n_saved - first < sub_saved) ? n_saved - first : sub_saved) : n_saved;
             RunInfo* ri = &h_pinned->run;  // (the stream was synchronised behind the previous sub-chunk)
             std::memset(ri, 0, sizeof *ri);
-            ri->chain = chain_out ? (void*)d_chain : nullptr;
-            ri->accepted_per_step = accepted_per_step ? d_acc : nullptr;
+            ri->chain = chain_out ? d_chain.get() : nullptr;
+            ri->accepted_per_step = accepted_per_step ? d_acc.get() : nullptr;
             ri->interval = interval;
             ri->chain_slot_base = -first;
             ri->slot_mask = -1;
@@ -533,36 +526,28 @@ private:
         return MCMCPP_HIP_OK;
     }
 
-    void release()
-    {
-        quiesce();
-        void* bufs[] = {d_own_pos, d_logp, d_nacc, d_ctl, d_run, d_diag, d_draws, d_partials, d_jump_lo, d_jump_hi, d_task_jump,
-                        d_own_prop, d_own_lp, d_chain, d_acc};
-        for (void* p : bufs)
-            if (p) (void)hipFree(p);
-        if (h_pinned) (void)hipHostFree(h_pinned);
-        if (ev_t0) (void)hipEventDestroy(ev_t0);
-        if (ev_t1) (void)hipEventDestroy(ev_t1);
-    }
-
     mcmcpp_hip_config cfg;
     BatchKernels<T> kern;
     mcmcpp_hip_batch_logp_fn fn = nullptr;
     void* user = nullptr;
     int partial_waves = 0;
     unsigned grid = 1;
-    hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
-    T* d_own_pos = nullptr;
-    T *d_prop = nullptr, *d_lp = nullptr, *d_own_prop = nullptr, *d_own_lp = nullptr;
-    StepCtl* d_ctl = nullptr;
-    RunInfo* d_run = nullptr;
-    DrawRec<T>* d_draws = nullptr;  // [2 buffers][2 colours][n]: buffer (ensemble step & 1) holds the records of that step
-    uint32_t* d_partials = nullptr; // [2 colours][partial_waves]
-    Affine128 *d_jump_lo = nullptr, *d_jump_hi = nullptr, *d_task_jump = nullptr;
-    void* d_chain = nullptr;        // [sub_saved][W][D] stored steps of the sub-chunk in hand
-    uint32_t* d_acc = nullptr;
-    size_t chain_capacity = 0, acc_capacity = 0, chain_subchunk_bytes = 0;
-    Pinned* h_pinned = nullptr;
+    Event ev_t0, ev_t1;
+    // the buffers behind the base's d_pos (unless the caller's), d_logp, d_nacc and d_diag
+    DeviceBuffer<T> d_own_pos, d_own_logp;
+    DeviceBuffer<uint32_t> d_own_nacc;
+    DeviceBuffer<Diag> d_own_diag;
+    T *d_prop = nullptr, *d_lp = nullptr;
+    DeviceBuffer<T> d_own_prop, d_own_lp;
+    DeviceBuffer<StepCtl> d_ctl;
+    DeviceBuffer<RunInfo> d_run;
+    DeviceBuffer<DrawRec<T>> d_draws;  // [2 buffers][2 colours][n]: buffer (ensemble step & 1) holds the records of that step
+    DeviceBuffer<uint32_t> d_partials; // [2 colours][partial_waves]
+    DeviceBuffer<Affine128> d_jump_lo, d_jump_hi, d_task_jump;
+    DeviceBuffer<> d_chain;            // [sub_saved][W][D] stored steps of the sub-chunk in hand
+    DeviceBuffer<uint32_t> d_acc;
+    size_t chain_subchunk_bytes = 0;
+    PinnedBuffer<Pinned> h_pinned;
     U128 state0, inc;
     Affine128 half_jump;
     uint64_t half_steps = 0;

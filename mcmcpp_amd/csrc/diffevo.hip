@@ -28,7 +28,7 @@ class DeSampler final : public SamplerHost<T>
     MCMCPP_SAMPLER_HOST_NAMES;
 
 public:
-    ~DeSampler() override { release(); }
+    ~DeSampler() override { quiesce(); }
 
     int init(const mcmcpp_hip_config& c)
     {
@@ -93,19 +93,23 @@ public:
         }
         scan_blocks = (int)(((positions_max + scan_run - 1) / scan_run + kDePlanThreads - 1) / kDePlanThreads);
 
-        HIP_TRY(hipMalloc(&d_pos, sizeof(T) * (size_t)W * D));
-        HIP_TRY(hipMalloc(&d_logp, sizeof(T) * (size_t)W));
-        HIP_TRY(hipMalloc(&d_nacc, sizeof(uint32_t) * (size_t)W));
-        HIP_TRY(hipMalloc(&d_diag, sizeof(Diag)));
-        HIP_TRY(hipMalloc(&d_counts, sizeof(uint32_t) * 2 * kDeSegments * kDeCountStride));  // two sets of lists (launch_boundary)
+        HIP_TRY(d_own_pos.alloc(sizeof(T) * (size_t)W * D));
+        HIP_TRY(d_own_logp.alloc(sizeof(T) * (size_t)W));
+        HIP_TRY(d_own_nacc.alloc(sizeof(uint32_t) * (size_t)W));
+        HIP_TRY(d_own_diag.alloc(sizeof(Diag)));
+        d_pos = d_own_pos;
+        d_logp = d_own_logp;
+        d_nacc = d_own_nacc;
+        d_diag = d_own_diag;
+        HIP_TRY(d_counts.alloc(sizeof(uint32_t) * 2 * kDeSegments * kDeCountStride));  // two sets of lists (launch_boundary)
         HIP_TRY(hipMemset(d_counts, 0, sizeof(uint32_t) * 2 * kDeSegments * kDeCountStride));
-        HIP_TRY(hipMalloc(&d_bad, sizeof(DeBad) * 2 * kDeSegments * (size_t)bad_capacity));
+        HIP_TRY(d_bad.alloc(sizeof(DeBad) * 2 * kDeSegments * (size_t)bad_capacity));
         HIP_TRY(hipMemset(d_bad, 0, sizeof(DeBad) * 2 * kDeSegments * (size_t)bad_capacity));
-        HIP_TRY(hipMalloc(&d_recs, sizeof(DeRec<T>) * updates_max));  // the records of the batch being stepped through
+        HIP_TRY(d_recs.alloc(sizeof(DeRec<T>) * updates_max));  // the records of the batch being stepped through
         for (int k = 0; k < 2; ++k)
         {
-            HIP_TRY(hipEventCreate(&ev_t0[k]));
-            HIP_TRY(hipEventCreate(&ev_t1[k]));
+            HIP_TRY(hipEventCreate(ev_t0[k].replace()));
+            HIP_TRY(hipEventCreate(ev_t1[k].replace()));
         }
         graph_steps = c.graph_steps == 0 ? 128 : (c.graph_steps > 32768 ? 32768 : c.graph_steps);  // (the step inside a replay travels in 16 bits)
         // HIP cannot capture on the legacy default stream: a caller that hands it over gets plain launches
@@ -114,15 +118,13 @@ public:
         const int per_block = walkers_per_block;
         update_blocks = (n + per_block - 1) / per_block;
         partial_waves = update_blocks * kWavesPerBlock;
-        HIP_TRY(hipMalloc(&d_head, sizeof(DeHead)));
-        HIP_TRY(hipMalloc(&d_batch, sizeof(DeBatch) * 2));  // batch b resolves into record b & 1
+        HIP_TRY(d_head.alloc(sizeof(DeHead)));
+        HIP_TRY(d_batch.alloc(sizeof(DeBatch) * 2));  // batch b resolves into record b & 1
         // the run record and, right behind it, the wavefronts' accepted counts of a replay: one allocation (the update kernel
         // reaches both through one preloaded pointer)
         {
             const size_t bytes = sizeof(DeRunInfo) + sizeof(uint32_t) * (size_t)replay_steps_max * 2 * (size_t)partial_waves;
-            void* p = nullptr;
-            HIP_TRY(hipMalloc(&p, bytes));
-            d_run = static_cast<DeRunInfo*>(p);
+            HIP_TRY(d_run.alloc(bytes));
             HIP_TRY(hipMemset(d_run, 0, bytes));
         }
         HIP_TRY(hipMemset(d_nacc, 0, sizeof(uint32_t) * (size_t)W));
@@ -130,11 +132,11 @@ public:
         if (c.calc_params_len > 0)
         {
             const CalcParams<T> p = calc_params_host<T>(c, matrix_core);
-            HIP_TRY(hipMalloc(&d_params, sizeof(T) * p.prm.size()));
+            HIP_TRY(d_params.alloc(sizeof(T) * p.prm.size()));
             HIP_TRY(hipMemcpy(d_params, p.prm.data(), sizeof(T) * p.prm.size(), hipMemcpyHostToDevice));
             if (!p.pad.empty())
             {
-                HIP_TRY(hipMalloc(&d_params_padded, sizeof(T) * p.pad.size()));
+                HIP_TRY(d_params_padded.alloc(sizeof(T) * p.pad.size()));
                 HIP_TRY(hipMemcpy(d_params_padded, p.pad.data(), sizeof(T) * p.pad.size(), hipMemcpyHostToDevice));
             }
         }
@@ -154,7 +156,7 @@ public:
             all.insert(all.end(), lo.begin(), lo.end());
             all.insert(all.end(), hi.begin(), hi.end());
             all.insert(all.end(), shi.begin(), shi.end());
-            HIP_TRY(hipMalloc(&d_tables, sizeof(Affine128) * all.size()));
+            HIP_TRY(d_tables.alloc(sizeof(Affine128) * all.size()));
             HIP_TRY(hipMemcpy(d_tables, all.data(), sizeof(Affine128) * all.size(), hipMemcpyHostToDevice));
             d_jump_small = d_tables;
             d_scan_lo = d_jump_small + small.size();
@@ -232,24 +234,12 @@ public:
         {
             const int64_t fit = (int64_t)(((size_t)256 << 20) / step_bytes);
             if (piece > fit) piece = fit < 1 ? 1 : fit;
-            if ((size_t)piece * step_bytes > chain_bytes)
-            {
-                if (d_chain) HIP_TRY(hipFree(d_chain));
-                d_chain = nullptr;
-                chain_bytes = 0;
-                HIP_TRY(hipMalloc(&d_chain, (size_t)piece * step_bytes));
-                chain_bytes = (size_t)piece * step_bytes;
-            }
+            if (const hipError_t e = grow(d_chain, (size_t)piece * step_bytes, stream))
+                return fail(MCMCPP_HIP_E_HIP, "hipMalloc(&d_chain, (size_t)piece * step_bytes) failed: %s", hipGetErrorString(e));
         }
         const int64_t acc_piece = accepted_per_step ? piece * (int64_t)interval : 0;
-        if (accepted_per_step && (size_t)acc_piece > acc_count)
-        {
-            if (d_acc) HIP_TRY(hipFree(d_acc));
-            d_acc = nullptr;
-            acc_count = 0;
-            HIP_TRY(hipMalloc(&d_acc, sizeof(uint32_t) * (size_t)acc_piece));
-            acc_count = (size_t)acc_piece;
-        }
+        if (const hipError_t e = grow(d_acc, sizeof(uint32_t) * (size_t)acc_piece, stream))
+            return fail(MCMCPP_HIP_E_HIP, "hipMalloc(&d_acc, sizeof(uint32_t) * (size_t)acc_piece) failed: %s", hipGetErrorString(e));
 
         run_touched = true;
         double gpu_ms = 0.0;
@@ -259,8 +249,8 @@ public:
             {
                 DeRunInfo ri;
                 std::memset(&ri, 0, sizeof ri);
-                ri.chain = chain_out ? d_chain : nullptr;
-                ri.accepted = accepted_per_step ? d_acc : nullptr;
+                ri.chain = chain_out ? d_chain.get() : nullptr;
+                ri.accepted = accepted_per_step ? d_acc.get() : nullptr;
                 ri.interval = (uint32_t)interval;
                 HIP_TRY(hipMemcpyAsync(d_run, &ri, sizeof ri, hipMemcpyHostToDevice, stream));
                 HIP_TRY(hipStreamSynchronize(stream));  // (the source is on this stack frame)
@@ -393,8 +383,6 @@ public:
             {
                 // (runs of ever-changing lengths: the graphs still queued have been launched, not destroyed under them)
                 HIP_TRY(hipStreamSynchronize(stream));
-                for (auto& kv : graph_cache)
-                    if (kv.second) (void)hipGraphExecDestroy(kv.second);
                 graph_cache.clear();
             }
             hipGraph_t g = nullptr;
@@ -402,10 +390,10 @@ public:
             int rc = enqueue_replay(steps, phase);
             if (rc) return rc;
             HIP_TRY(hipStreamEndCapture(stream, &g));
-            hipGraphExec_t ex = nullptr;
-            HIP_TRY(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
+            GraphExec ex;
+            HIP_TRY(hipGraphInstantiate(ex.replace(), g, nullptr, nullptr, 0));
             HIP_TRY(hipGraphDestroy(g));
-            it = graph_cache.emplace(key, ex).first;
+            it = graph_cache.emplace(key, std::move(ex)).first;
         }
         *out = it->second;
         return MCMCPP_HIP_OK;
@@ -480,49 +468,37 @@ public:
 
 private:
     int unsupported(const char* what) { return fail(MCMCPP_HIP_E_UNSUPPORTED, "%s: not available with the differential-evolution mover", what); }
-    void release()
-    {
-        quiesce();
-        for (auto& kv : graph_cache)
-            if (kv.second) (void)hipGraphExecDestroy(kv.second);
-        void* bufs[] = {d_pos, d_logp, d_nacc, d_diag, d_head, d_batch, d_run, d_counts, d_params, d_params_padded, d_tables, d_chain, d_acc, d_recs, d_bad};
-        for (void* b : bufs)
-            if (b) (void)hipFree(b);
-        for (int k = 0; k < 2; ++k)
-        {
-            if (ev_t0[k]) (void)hipEventDestroy(ev_t0[k]);
-            if (ev_t1[k]) (void)hipEventDestroy(ev_t1[k]);
-        }
-    }
-
     const LaunchTable<T>* table = nullptr;
     typename LaunchTable<T>::DeFn update_fn = nullptr;
     typename LaunchTable<T>::CalcFn calc_fn = nullptr;
     int walkers_per_block = 0;
-    T *d_params = nullptr, *d_params_padded = nullptr, *d_chain = nullptr;
+    // the buffers behind the base's d_pos, d_logp, d_nacc and d_diag
+    DeviceBuffer<T> d_own_pos, d_own_logp;
+    DeviceBuffer<uint32_t> d_own_nacc;
+    DeviceBuffer<Diag> d_own_diag;
+    DeviceBuffer<T> d_params, d_params_padded, d_chain;
     bool matrix_core = false;
-    uint32_t* d_acc = nullptr;
-    DeHead* d_head = nullptr;
-    DeBatch* d_batch = nullptr;
-    Affine128* d_tables = nullptr;  // jump_small, scan_lo, jump_lo, jump_hi, scan_hi
-    uint32_t* d_counts = nullptr;
-    DeBad* d_bad = nullptr;
+    DeviceBuffer<uint32_t> d_acc;
+    DeviceBuffer<DeHead> d_head;
+    DeviceBuffer<DeBatch> d_batch;
+    DeviceBuffer<Affine128> d_tables;  // jump_small, scan_lo, jump_lo, jump_hi, scan_hi
+    DeviceBuffer<uint32_t> d_counts;
+    DeviceBuffer<DeBad> d_bad;
     Affine128 *d_scan_lo = nullptr, *d_scan_hi = nullptr;
     int bad_capacity = 0, scan_run = kDeScanRun, batch_max = kDeBatchMax;
     long long positions_max = 0;
-    DeRec<T>* d_recs = nullptr;
-    DeRunInfo* d_run = nullptr;
+    DeviceBuffer<DeRec<T>> d_recs;
+    DeviceBuffer<DeRunInfo> d_run;
     DeArgs<T> args;
     int update_blocks = 0, partial_waves = 0, graph_steps = 128, replay_steps_max = 128;
     int resolve_capacity = 0, scan_blocks = 0;
     bool primed = false;    // batches 0 and 1 planned behind the last set_state
     Affine128 batch_jump;   // (D+3) * n * batch_max draws
     bool run_touched = false;
-    hipEvent_t ev_t0[2] = {nullptr, nullptr}, ev_t1[2] = {nullptr, nullptr};
-    std::unordered_map<uint64_t, hipGraphExec_t> graph_cache;
+    Event ev_t0[2], ev_t1[2];
+    std::unordered_map<uint64_t, GraphExec> graph_cache;
 
     Affine128 *d_jump_lo = nullptr, *d_jump_hi = nullptr, *d_jump_small = nullptr;
-    size_t chain_bytes = 0, acc_count = 0;
     U128 state0, inc;
     uint64_t threshold = 0, half_steps = 0;
     T gamma = 0;

@@ -192,17 +192,14 @@ struct mcmcpp_hip_histograms
     size_t chunk_bytes = 0;        // MCMCPP_HIP_HIST_CHUNK_MB
     size_t lds_limit = 0;          // dynamic LDS per block for the counters
     int idx_bytes = 1;             // 1 / 2 / 4 (bins <= 256 / <= 65536 / more)
-    unsigned long long *d_single = nullptr, *d_pairs = nullptr, *d_clamped = nullptr;
-    int* d_ij = nullptr;           // [npairs][2]
-    int* d_nan = nullptr;
-    void* d_edges = nullptr;       // [P][2] (low edge, width) in T
-    void* d_part = nullptr;        // bounds partials
-    size_t part_cap = 0;
-    void* d_chunk = nullptr;       // host path upload buffer
-    size_t chunk_cap = 0;
-    void* d_idx = nullptr;         // bin indices [P][col]
-    size_t idx_cap = 0;
-    hipStream_t stream = nullptr;
+    mcmcpp::DeviceBuffer<unsigned long long> d_single, d_pairs, d_clamped;
+    mcmcpp::DeviceBuffer<int> d_ij;      // [npairs][2]
+    mcmcpp::DeviceBuffer<int> d_nan;
+    mcmcpp::DeviceBuffer<> d_edges;      // [P][2] (low edge, width) in T
+    mcmcpp::DeviceBuffer<> d_part;       // bounds partials
+    mcmcpp::DeviceBuffer<> d_chunk;      // host path upload buffer
+    mcmcpp::DeviceBuffer<> d_idx;        // bin indices [P][col]
+    hipStream_t stream = nullptr;        // (destroyed after the buffers: mcmcpp_hip_histograms_destroy)
     bool have_result = false;
     long long points = 0;
     std::vector<unsigned char> bounds;  // [P][2] in T
@@ -230,19 +227,10 @@ int fail(mcmcpp_hip_histograms* h, int code, const std::string& msg, hipError_t 
         if (e_ != hipSuccess) return fail(h, MCMCPP_HIP_E_HIP, #expr, e_); \
     } while (0)
 
-int ensure(mcmcpp_hip_histograms* h, void** buf, size_t* cap, size_t bytes, const char* what)
+int ensure(mcmcpp_hip_histograms* h, mcmcpp::DeviceBuffer<>& buf, size_t bytes, const char* what)
 {
-    if (*cap >= bytes) return MCMCPP_HIP_OK;
-    HIST_TRY(hipStreamSynchronize(h->stream));
-    if (*buf) hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    if (hipMalloc(buf, bytes) != hipSuccess)
-    {
-        *buf = nullptr;
+    if (mcmcpp::grow(buf, bytes, h->stream))
         return fail(h, MCMCPP_HIP_E_NOMEM, std::string("histograms: cannot allocate ") + what + " (" + std::to_string(bytes) + " bytes)");
-    }
-    *cap = bytes;
     return MCMCPP_HIP_OK;
 }
 
@@ -265,10 +253,10 @@ int bounds_pass(mcmcpp_hip_histograms* h, const Span<T>& sp, std::vector<T>& lo,
     const unsigned per = (n + blocks - 1) / blocks;
     blocks = (n + per - 1) / per;
     const size_t pbytes = sizeof(T) * 2 * (size_t)blocks * h->P;
-    int rc = ensure(h, &h->d_part, &h->part_cap, pbytes, "the bounds partials");
+    int rc = ensure(h, h->d_part, pbytes, "the bounds partials");
     if (rc) return rc;
     hipLaunchKernelGGL((hist_bounds_kernel<T>), dim3(blocks), dim3(kHistThreads), 0, h->stream, sp.base, sp.step_stride, (unsigned)h->W, h->P,
-                       n, per, (T*)h->d_part, h->d_nan);
+                       n, per, (T*)h->d_part.get(), h->d_nan);
     HIST_TRY(hipGetLastError());
     std::vector<T> part(2 * (size_t)blocks * h->P);
     HIST_TRY(hipMemcpyAsync(part.data(), h->d_part, pbytes, hipMemcpyDeviceToHost, h->stream));
@@ -289,15 +277,15 @@ int count_pass_t(mcmcpp_hip_histograms* h, const Span<T>& sp)
     const unsigned n = (unsigned)(sp.n_steps * h->W);
     if (n == 0) return MCMCPP_HIP_OK;
     const size_t col = ((size_t)n + 15) & ~(size_t)15;
-    int rc = ensure(h, &h->d_idx, &h->idx_cap, sizeof(I) * col * h->P, "the bin index buffer");
+    int rc = ensure(h, h->d_idx, sizeof(I) * col * h->P, "the bin index buffer");
     if (rc) return rc;
-    I* idx = (I*)h->d_idx;
+    I* idx = (I*)h->d_idx.get();
     const int bins = h->bins;
     {
         unsigned blocks = (n + kHistThreads - 1) / kHistThreads;
         if (blocks > (unsigned)h->cus * 8) blocks = (unsigned)h->cus * 8;
         hipLaunchKernelGGL((hist_bin_kernel<T, I>), dim3(blocks), dim3(kHistThreads), 0, h->stream, sp.base, sp.step_stride, (unsigned)h->W,
-                           h->P, n, (const T*)h->d_edges, bins, idx, col, h->d_clamped);
+                           h->P, n, (const T*)h->d_edges.get(), bins, idx, col, h->d_clamped);
         HIST_TRY(hipGetLastError());
     }
     // slices of samples: enough blocks to fill the device, each slice long enough to amortise its flush
@@ -447,7 +435,7 @@ int compute_host(mcmcpp_hip_histograms* h, const void* const* steps, int64_t n_s
     const size_t step_elems = (size_t)h->W * h->P, step_bytes = sizeof(T) * step_elems;
     const long long per = steps_per_chunk(h, step_bytes);
     const long long first_chunk = n_steps < per ? n_steps : per;
-    int rc = ensure(h, &h->d_chunk, &h->chunk_cap, step_bytes * (size_t)(first_chunk > 0 ? first_chunk : 1), "the upload buffer");
+    int rc = ensure(h, h->d_chunk, step_bytes * (size_t)(first_chunk > 0 ? first_chunk : 1), "the upload buffer");
     if (rc) return rc;
     auto upload = [&](long long k0, long long now) -> int {
         HIST_TRY(hipStreamSynchronize(h->stream));  // the previous chunk's kernels have read the buffer
@@ -457,13 +445,13 @@ int compute_host(mcmcpp_hip_histograms* h, const void* const* steps, int64_t n_s
             const char* src = (const char*)steps[k0 + k];
             long long run = 1;
             while (k + run < now && (const char*)steps[k0 + k + run] == src + step_bytes * (size_t)run) ++run;
-            HIST_TRY(hipMemcpyAsync((char*)h->d_chunk + step_bytes * (size_t)k, src, step_bytes * (size_t)run, hipMemcpyHostToDevice, h->stream));
+            HIST_TRY(hipMemcpyAsync((char*)h->d_chunk.get() + step_bytes * (size_t)k, src, step_bytes * (size_t)run, hipMemcpyHostToDevice, h->stream));
             k += run;
         }
         return MCMCPP_HIP_OK;
     };
     std::vector<T> lo(h->P, std::numeric_limits<T>::max()), hi(h->P, std::numeric_limits<T>::min());
-    const Span<T> whole{(const T*)h->d_chunk, (long long)step_elems, 0};
+    const Span<T> whole{(const T*)h->d_chunk.get(), (long long)step_elems, 0};
     for (long long k0 = 0; k0 < n_steps; k0 += per)
     {
         const long long now = (n_steps - k0 < per) ? n_steps - k0 : per;
@@ -563,19 +551,15 @@ int mcmcpp_hip_histograms_create(int32_t dtype, int32_t device, int32_t num_walk
         return code;
     };
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bad(MCMCPP_HIP_E_HIP, "histograms_create: cannot create a stream");
-    if (hipMalloc(&h->d_single, (size_t)single_bytes) != hipSuccess || hipMalloc(&h->d_clamped, 8 * (size_t)num_params) != hipSuccess ||
-        hipMalloc(&h->d_nan, sizeof(int)) != hipSuccess || hipMalloc(&h->d_edges, 2 * esize * (size_t)num_params) != hipSuccess)
+    if (h->d_single.alloc((size_t)single_bytes) != hipSuccess || h->d_clamped.alloc(8 * (size_t)num_params) != hipSuccess ||
+        h->d_nan.alloc(sizeof(int)) != hipSuccess || h->d_edges.alloc(2 * esize * (size_t)num_params) != hipSuccess)
         return bad(MCMCPP_HIP_E_NOMEM, "histograms_create: cannot allocate device memory");
     if (npairs > 0)
     {
-        if (hipMalloc(&h->d_pairs, (size_t)pair_bytes) != hipSuccess)
-        {
-            h->d_pairs = nullptr;
-            (void)hipGetLastError();
+        if (h->d_pairs.alloc((size_t)pair_bytes) != hipSuccess)
             return bad(MCMCPP_HIP_E_NOMEM, "histograms_create: cannot allocate the " + std::to_string((size_t)pair_bytes) +
                                                "-byte 64-bit pair histograms (" + std::to_string(npairs) + " pairs of " + std::to_string(bins) +
                                                " x " + std::to_string(bins) + " bins)");
-        }
         std::vector<int> ij(2 * (size_t)npairs);
         size_t q = 0;
         for (int i = 1; i < num_params; ++i)
@@ -584,7 +568,7 @@ int mcmcpp_hip_histograms_create(int32_t dtype, int32_t device, int32_t num_walk
                 ij[2 * q] = i;
                 ij[2 * q + 1] = j;
             }
-        if (hipMalloc(&h->d_ij, sizeof(int) * ij.size()) != hipSuccess) return bad(MCMCPP_HIP_E_NOMEM, "histograms_create: cannot allocate the pair table");
+        if (h->d_ij.alloc(sizeof(int) * ij.size()) != hipSuccess) return bad(MCMCPP_HIP_E_NOMEM, "histograms_create: cannot allocate the pair table");
         if (hipMemcpy(h->d_ij, ij.data(), sizeof(int) * ij.size(), hipMemcpyHostToDevice) != hipSuccess)
             return bad(MCMCPP_HIP_E_HIP, "histograms_create: cannot upload the pair table");
     }
@@ -596,12 +580,10 @@ void mcmcpp_hip_histograms_destroy(mcmcpp_hip_histograms* h)
 {
     if (!h) return;
     hipSetDevice(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    for (void* p : {(void*)h->d_single, (void*)h->d_pairs, (void*)h->d_clamped, (void*)h->d_ij, (void*)h->d_nan, h->d_edges, h->d_part, h->d_chunk,
-                    h->d_idx})
-        if (p) hipFree(p);
-    if (h->stream) hipStreamDestroy(h->stream);
-    delete h;
+    const hipStream_t stream = h->stream;
+    if (stream) hipStreamSynchronize(stream);
+    delete h;  // (the buffers free themselves)
+    if (stream) hipStreamDestroy(stream);
 }
 
 int mcmcpp_hip_histograms_compute(mcmcpp_hip_histograms* h, const void* const* steps, int64_t n_steps)

@@ -184,7 +184,11 @@ class Sampler final : public SamplerHost<T>
 
 public:
     Sampler() {}
-    ~Sampler() override { release(); }
+    ~Sampler() override
+    {
+        quiesce();  // (half_step_async work may still be in flight; the members free themselves behind this)
+        if (own_comm && comm && rccl) (void)rccl->CommDestroy(comm);
+    }
 
     int init(const mcmcpp_hip_config& c)
     {
@@ -318,25 +322,19 @@ public:
         if (c.comm_world > 1 && knobs.comm_compact != 0)
         {
             const uint32_t cap_full = (uint32_t)((full_fn ? 2 : 1) * shard_count);
-            void* p = nullptr;
-            HIP_TRY(hipMalloc(&p, xblock_bytes<T>(cap_full, D) * (size_t)c.comm_world));
-            d_xblocks = (char*)p;
-            HIP_TRY(hipMalloc(&p, sizeof(uint32_t) * (size_t)W));
-            d_seen = (uint32_t*)p;
-            HIP_TRY(hipMalloc(&p, sizeof(XStats)));
-            d_xstats = (XStats*)p;
-            HIP_TRY(hipMalloc(&p, sizeof(T) * (size_t)W * D + (sizeof(T) + sizeof(uint32_t)) * (size_t)W + sizeof(Diag)));
-            d_snap = (char*)p;
+            HIP_TRY(d_xblocks.alloc(xblock_bytes<T>(cap_full, D) * (size_t)c.comm_world));
+            HIP_TRY(d_seen.alloc(sizeof(uint32_t) * (size_t)W));
+            HIP_TRY(d_xstats.alloc(sizeof(XStats)));
+            HIP_TRY(d_snap.alloc(sizeof(T) * (size_t)W * D + (sizeof(T) + sizeof(uint32_t)) * (size_t)W + sizeof(Diag)));
         }
         if (K > 1 && (!whole || c.comm_world >= 1 || c.device_positions))
             return fail(MCMCPP_HIP_E_ARG, "num_chains > 1: whole ensembles on one device only (no shards, communicator or caller-owned positions)");
         if (int rc = open_stream(c)) return rc;
         for (int k = 0; k < 4; ++k)
         {
-            HIP_TRY(hipEventCreate(&ev_t0[k]));
-            HIP_TRY(hipEventCreate(&ev_t1[k]));
+            HIP_TRY(hipEventCreate(ev_t0[k].replace()));
+            HIP_TRY(hipEventCreate(ev_t1[k].replace()));
         }
-
 
         {
             // upper bound of everything carved below (each piece rounded up to 256 bytes)
@@ -346,8 +344,7 @@ public:
                           + (size_t)K * logp_chain_stride_bytes<T>(n) + (size_t)K * kCtlChainStride + tables_total_bytes(n, true, K)
                           + sizeof(T) * ((size_t)(c.calc_params_len > 0 ? c.calc_params_len : 0) + 32 * 32)
                           + (size_t)K * sizeof(uint32_t) * graph_len * 2 * waves_bound + 64 * 1024;
-            HIP_TRY(hipMalloc(&arena, need));
-            arena_bytes = need;
+            HIP_TRY(arena.alloc(need));
             arena_used = 0;
         }
         if (c.device_positions)
@@ -395,7 +392,7 @@ public:
         HIP_TRY(hipMemset(d_logp, 0, logp_chain_stride_bytes<T>(n) * (size_t)K));
         HIP_TRY(hipMemset(d_diag, 0, sizeof(Diag)));
         HIP_TRY(hipMemset(d_ctl, 0, (size_t)kCtlChainStride * (size_t)K));
-        HIP_TRY(hipHostMalloc(&h_pinned, sizeof(PinnedScratch), hipHostMallocDefault));
+        HIP_TRY(h_pinned.alloc(sizeof(PinnedScratch)));
 
         // calculator parameters (and, for the matrix-core kernels, the padded matrix)
         if (c.calc_params_len > 0)
@@ -440,11 +437,11 @@ public:
             // (by default as many steps as a graph replays: one fill launch per replay)
             const long want = knobs.batch_draws > 0 ? knobs.batch_draws : (long)graph_steps;
             batch_draws = (int)(want > 512 ? 512 : want);
-            HIP_TRY(hipMalloc(&d_draws_batch, sizeof(DrawRec<T>) * (size_t)batch_draws * 2 * (size_t)n));
+            HIP_TRY(d_draws_batch.alloc(sizeof(DrawRec<T>) * (size_t)batch_draws * 2 * (size_t)n));
             HIP_TRY(hipMemset(d_draws_batch, 0, sizeof(DrawRec<T>) * (size_t)batch_draws * 2 * (size_t)n));  // (partner indices a kernel may follow)
             std::vector<Affine128> sj((size_t)batch_draws);
             for (size_t j = 0; j < sj.size(); ++j) sj[j] = pcg_jump(inc, (unsigned __int128)6 * (unsigned)n * (unsigned __int128)j);
-            HIP_TRY(hipMalloc(&d_step_jump, sizeof(Affine128) * sj.size()));
+            HIP_TRY(d_step_jump.alloc(sizeof(Affine128) * sj.size()));
             HIP_TRY(hipMemcpy(d_step_jump, sj.data(), sizeof(Affine128) * sj.size(), hipMemcpyHostToDevice));
         }
         partial_slots = graph_steps >= 1 ? graph_steps : 1;
@@ -469,8 +466,8 @@ public:
     int carve(P** out, size_t bytes)
     {
         const size_t off = (arena_used + 255) & ~(size_t)255;
-        if (off + bytes > arena_bytes) return fail(MCMCPP_HIP_E_NOMEM, "internal: device arena too small (%zu + %zu > %zu)", off, bytes, arena_bytes);
-        *out = reinterpret_cast<P*>(static_cast<char*>(arena) + off);
+        if (off + bytes > arena.bytes()) return fail(MCMCPP_HIP_E_NOMEM, "internal: device arena too small (%zu + %zu > %zu)", off, bytes, arena.bytes());
+        *out = reinterpret_cast<P*>(arena + off);
         arena_used = off + bytes;
         return MCMCPP_HIP_OK;
     }
@@ -598,7 +595,7 @@ public:
                 // (several chains: one record each; the upload slots rotate per sub-chunk as for one chain)
                 RunInfo* ri = K > 1 ? &h_pinned->chain_run[c % 4][k] : &h_pinned->run[c % 4];
                 // chain k's stored steps of this sub-chunk: the k-th run of sub_saved steps of the device half
-                ri->chain = chain_out ? (void*)((char*)d_chain[buf] + step_bytes * (size_t)sub_saved * (size_t)k) : nullptr;
+                ri->chain = chain_out ? (void*)((char*)d_chain[buf].get() + step_bytes * (size_t)sub_saved * (size_t)k) : nullptr;
                 ri->accepted_per_step = accepted_per_step ? d_acc + (size_t)k * (size_t)total : nullptr;
                 ri->interval = interval;
                 ri->chain_slot_base = -first;
@@ -731,22 +728,8 @@ public:
         int64_t stage_slots = (int64_t)(((size_t)256 << 20) / step_bytes);
         if (stage_slots < 1) stage_slots = 1;
         if (stage_slots > n_saved) stage_slots = n_saved;
-        if (chain_out && total > 0)
-        {
-            if (step_bytes * (size_t)stage_slots > split_stage_capacity)
-            {
-                HIP_TRY(hipStreamSynchronize(stream));
-                if (h_split_stage) hipHostFree(h_split_stage);
-                h_split_stage = nullptr;
-                split_stage_capacity = 0;
-                if (hipHostMalloc(&h_split_stage, step_bytes * (size_t)stage_slots, hipHostMallocDefault) != hipSuccess)
-                {
-                    (void)hipGetLastError();
-                    return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu bytes of pinned staging", step_bytes * (size_t)stage_slots);
-                }
-                split_stage_capacity = step_bytes * (size_t)stage_slots;
-            }
-        }
+        if (chain_out && total > 0 && grow(h_split_stage, step_bytes * (size_t)stage_slots, stream))
+            return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu bytes of pinned staging", step_bytes * (size_t)stage_slots);
         *stage_slots_out = stage_slots;
         // (the per-step accepted counts are always kept on the device and all-reduced at the end of a split run, whether this
         //  rank's caller wants them or not: a collective must not depend on one rank's arguments)
@@ -755,8 +738,8 @@ public:
         if (rc) return rc;
         if (ev_x.empty())
         {
-            ev_x.assign(2 * kMaxExchangeSamples, nullptr);
-            for (hipEvent_t& e : ev_x) HIP_TRY(hipEventCreate(&e));
+            ev_x.resize(2 * kMaxExchangeSamples);
+            for (Event& e : ev_x) HIP_TRY(hipEventCreate(e.replace()));
         }
         return MCMCPP_HIP_OK;
     }
@@ -1306,10 +1289,9 @@ public:
         {
             const size_t stride = prm_row + p.pad.size();
             if (stride > (size_t)INT32_MAX) return fail(MCMCPP_HIP_E_ARG, "set_chain_params: %zu elements per chain are too many", stride);
-            void* dp = nullptr;
-            if (hipMalloc(&dp, sizeof(T) * stride * (size_t)K) != hipSuccess)
+            DeviceBuffer<T> rows;
+            if (rows.alloc(sizeof(T) * stride * (size_t)K) != hipSuccess)
                 return fail(MCMCPP_HIP_E_NOMEM, "set_chain_params: cannot allocate %zu bytes of per-chain parameters", sizeof(T) * stride * (size_t)K);
-            T* const rows = static_cast<T*>(dp);
             HIP_TRY(hipStreamSynchronize(stream));
             drop_graphs();
             for (int k = 0; k < K; ++k)
@@ -1318,9 +1300,9 @@ public:
                 HIP_TRY(hipMemcpyAsync(row, d_params, sizeof(T) * p.prm.size(), hipMemcpyDeviceToDevice, stream));
                 if (d_params_padded) HIP_TRY(hipMemcpyAsync(row + prm_row, d_params_padded, sizeof(T) * p.pad.size(), hipMemcpyDeviceToDevice, stream));
             }
-            d_chain_params = rows;
             d_params = rows;
             if (d_params_padded) d_params_padded = rows + prm_row;
+            d_chain_params = std::move(rows);
             chain_params_stride = (int)stride;
         }
         T* const row = d_chain_params + (size_t)chain_params_stride * (size_t)chain;
@@ -1394,15 +1376,7 @@ private:
     }
 
     // the instantiated graphs (their kernel nodes hold the launch arguments of the time of capture); the stream is idle
-    void drop_graphs()
-    {
-        for (hipGraphExec_t& ex : graph_cache)
-            if (ex)
-            {
-                (void)hipGraphExecDestroy(ex);
-                ex = nullptr;
-            }
-    }
+    void drop_graphs() { graph_cache.clear(); }
 
     int hip_rc(hipError_t e, const char* what)
     {
@@ -1586,7 +1560,7 @@ private:
     int graph_for(int steps, int start_parity, int pos_parity, hipGraphExec_t* out)
     {
         const size_t key = (size_t)steps * 4 + (size_t)start_parity * 2 + (size_t)pos_parity;
-        if (graph_cache.size() <= key) graph_cache.resize(key + 1, nullptr);
+        if (graph_cache.size() <= key) graph_cache.resize(key + 1);
         if (!graph_cache[key])
         {
             hipGraph_t g = nullptr;
@@ -1594,10 +1568,8 @@ private:
             enqueue_step_sequence(steps, start_parity, pos_parity);
             launch_accepted_reduce(d_partials, partial_slots, partial_waves, steps, ctl_after(pos_parity + steps), d_run, stream, K);
             HIP_TRY(hipStreamEndCapture(stream, &g));
-            hipGraphExec_t ex = nullptr;
-            HIP_TRY(hipGraphInstantiate(&ex, g, nullptr, nullptr, 0));
+            HIP_TRY(hipGraphInstantiate(graph_cache[key].replace(), g, nullptr, nullptr, 0));
             HIP_TRY(hipGraphDestroy(g));
-            graph_cache[key] = ex;
         }
         *out = graph_cache[key];
         return MCMCPP_HIP_OK;
@@ -1659,96 +1631,20 @@ private:
     // chain and their pinned staging twins
     int ensure_run_buffers(size_t acc_entries, size_t half_bytes, size_t ring_bytes, bool need_host_ring = true)
     {
-        if (ring_bytes > ring_capacity)
-        {
-            HIP_TRY(hipStreamSynchronize(stream));
-            if (d_ring) hipFree(d_ring);
-            d_ring = nullptr;
-            ring_capacity = 0;
-            if (hipMalloc(&d_ring, ring_bytes) != hipSuccess) return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu bytes of device chain", ring_bytes);
-            ring_capacity = ring_bytes;
-        }
-        if (need_host_ring && ring_bytes > host_ring_capacity)
-        {
-            HIP_TRY(hipStreamSynchronize(stream));
-            if (h_ring) hipHostFree(h_ring);
-            h_ring = nullptr;
-            host_ring_capacity = 0;
-            if (hipHostMalloc(&h_ring, ring_bytes, hipHostMallocDefault) != hipSuccess)
-                return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu bytes of pinned staging", ring_bytes);
-            host_ring_capacity = ring_bytes;
-        }
-        if (acc_entries > acc_capacity)
-        {
-            if (d_acc) hipFree(d_acc);
-            d_acc = nullptr;
-            acc_capacity = 0;
-            if (hipMalloc(&d_acc, sizeof(uint32_t) * acc_entries) != hipSuccess)
-                return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu accepted counters", acc_entries);
-            acc_capacity = acc_entries;
-        }
+        if (grow(d_ring, ring_bytes, stream)) return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu bytes of device chain", ring_bytes);
+        if (need_host_ring && grow(h_ring, ring_bytes, stream))
+            return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu bytes of pinned staging", ring_bytes);
+        if (grow(d_acc, sizeof(uint32_t) * acc_entries, stream)) return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu accepted counters", acc_entries);
         if (half_bytes > 0 && ev_copied[0] == nullptr)
         {
-            for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreateWithFlags(&ev_copied[k], hipEventDisableTiming));
+            for (int k = 0; k < 2; ++k) HIP_TRY(hipEventCreateWithFlags(ev_copied[k].replace(), hipEventDisableTiming));
         }
-        if (half_bytes > chain_half_capacity)
-        {
-            HIP_TRY(hipStreamSynchronize(stream));
-            for (int k = 0; k < 2; ++k)
-            {
-                if (d_chain[k]) hipFree(d_chain[k]);
-                if (h_stage[k]) hipHostFree(h_stage[k]);
-                d_chain[k] = nullptr;
-                h_stage[k] = nullptr;
-            }
-            chain_half_capacity = 0;
-            for (int k = 0; k < 2; ++k)
-            {
-                void* dp = nullptr;
-                if (hipMalloc(&dp, half_bytes) != hipSuccess)
-                    return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu bytes of device chain", half_bytes);
-                d_chain[k] = (T*)dp;
-                if (hipHostMalloc(&h_stage[k], half_bytes, hipHostMallocDefault) != hipSuccess)
-                    return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu bytes of pinned staging", half_bytes);
-            }
-            chain_half_capacity = half_bytes;
-        }
-        return MCMCPP_HIP_OK;
-    }
-
-    void release()
-    {
-        quiesce();  // (half_step_async work may still be in flight)
-        for (hipGraphExec_t ex : graph_cache)
-            if (ex) hipGraphExecDestroy(ex);
-        if (arena) hipFree(arena);  // positions, log-posteriors, counters, records, tables, parameters, partial counts
-        if (d_chain_params) hipFree(d_chain_params);
-        if (d_acc) hipFree(d_acc);
-        if (d_draws_batch) hipFree(d_draws_batch);
-        if (d_step_jump) hipFree(d_step_jump);
         for (int k = 0; k < 2; ++k)
         {
-            if (d_chain[k]) hipFree(d_chain[k]);
-            if (h_stage[k]) hipHostFree(h_stage[k]);
-            if (ev_copied[k]) hipEventDestroy(ev_copied[k]);
+            if (grow(d_chain[k], half_bytes, stream)) return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu bytes of device chain", half_bytes);
+            if (grow(h_stage[k], half_bytes, stream)) return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu bytes of pinned staging", half_bytes);
         }
-        if (d_ring) hipFree(d_ring);
-        if (h_ring) hipHostFree(h_ring);
-
-        if (h_pinned) hipHostFree(h_pinned);
-        for (int k = 0; k < 4; ++k)
-        {
-            if (ev_t0[k]) hipEventDestroy(ev_t0[k]);
-            if (ev_t1[k]) hipEventDestroy(ev_t1[k]);
-        }
-        if (d_xblocks) hipFree(d_xblocks);
-        if (d_seen) hipFree(d_seen);
-        if (d_xstats) hipFree(d_xstats);
-        if (d_snap) hipFree(d_snap);
-        if (own_comm && comm && rccl) (void)rccl->CommDestroy(comm);
-        if (h_split_stage) hipHostFree(h_split_stage);
-        for (hipEvent_t e : ev_x)
-            if (e) hipEventDestroy(e);
+        return MCMCPP_HIP_OK;
     }
 
     mcmcpp_hip_config cfg;
@@ -1757,14 +1653,13 @@ private:
     ncclComm_t comm = nullptr;
     bool own_comm = false;
     // split ensembles of more than one rank, exchanging moved rows only (exchange_kernels.hpp)
-    char* d_xblocks = nullptr;      // [comm_world][block]: this rank's block and, behind the all-gather, everybody's
-    uint32_t* d_seen = nullptr;     // [W]: a walker's accepted counter as of the last exchange (own slice)
-    XStats* d_xstats = nullptr;
-    char* d_snap = nullptr;         // positions, log-posteriors, counters, diagnostics in front of the chunk in hand
-    uint32_t xcap_learned = 0;      // the slot bound the last run ended with
-    void* h_split_stage = nullptr;  // split ensembles: pinned staging of stored steps
-    size_t split_stage_capacity = 0;
-    std::vector<hipEvent_t> ev_x;   // split ensembles: events around a sample of exchanges
+    DeviceBuffer<char> d_xblocks;     // [comm_world][block]: this rank's block and, behind the all-gather, everybody's
+    DeviceBuffer<uint32_t> d_seen;    // [W]: a walker's accepted counter as of the last exchange (own slice)
+    DeviceBuffer<XStats> d_xstats;
+    DeviceBuffer<char> d_snap;        // positions, log-posteriors, counters, diagnostics in front of the chunk in hand
+    uint32_t xcap_learned = 0;        // the slot bound the last run ended with
+    PinnedBuffer<char> h_split_stage; // split ensembles: pinned staging of stored steps
+    std::vector<Event> ev_x;          // split ensembles: events around a sample of exchanges
     const LaunchTable<T>* table = nullptr;
     typename LaunchTable<T>::HalfStepFn half_fn = nullptr;
     typename LaunchTable<T>::HalfStepFn full_fn = nullptr;  // non-null: run() steps with one launch per ensemble step
@@ -1774,26 +1669,26 @@ private:
     typename LaunchTable<T>::CalcFn calc_fn = nullptr;
     int step_lpw = 1, passes = 1, num_cus = 256;
     int shard_begin = 0, shard_count = 0, graph_steps = 32;
-    size_t chain_subchunk_bytes = 0, chain_half_capacity = 0, acc_capacity = 0;
-    hipEvent_t ev_copied[2] = {nullptr, nullptr};
-    void* arena = nullptr;  // one device allocation holding everything a step launch touches (see carve)
-    size_t arena_bytes = 0, arena_used = 0;
-    void *d_ring = nullptr, *h_ring = nullptr;  // full-step chain path: device ring of stored steps and its pinned host twin
-    size_t ring_capacity = 0, host_ring_capacity = 0;
-    T* d_chain[2] = {nullptr, nullptr};
-    void* h_stage[2] = {nullptr, nullptr};
-    uint32_t* d_acc = nullptr;
+    size_t chain_subchunk_bytes = 0;
+    Event ev_copied[2];
+    DeviceBuffer<char> arena;  // one device allocation holding everything a step launch touches (see carve)
+    size_t arena_used = 0;
+    DeviceBuffer<char> d_ring;  // full-step chain path: device ring of stored steps
+    PinnedBuffer<char> h_ring;  // and its pinned host twin
+    DeviceBuffer<T> d_chain[2];
+    PinnedBuffer<char> h_stage[2];
+    DeviceBuffer<uint32_t> d_acc;
     bool own_pos = false, run_touched_device = false;
-    hipEvent_t ev_t0[4] = {nullptr, nullptr, nullptr, nullptr}, ev_t1[4] = {nullptr, nullptr, nullptr, nullptr};
+    Event ev_t0[4], ev_t1[4];
     T *d_params = nullptr, *d_params_padded = nullptr;  // (row 0 of d_chain_params once a chain has parameters of its own)
-    T* d_chain_params = nullptr;  // [K][chain_params_stride] per-chain parameters (set_chain_params), or nullptr: shared
+    DeviceBuffer<T> d_chain_params;  // [K][chain_params_stride] per-chain parameters (set_chain_params), or empty: shared
     int chain_params_stride = 0;
     StepCtl* d_ctl = nullptr;
     RunInfo* d_run = nullptr;
     uint64_t* d_status = nullptr;
     DrawRec<T>* d_draws = nullptr;
-    DrawRec<T>* d_draws_batch = nullptr;  // [batch_draws][2][n]: records made ahead of the matrix-core full-step launches
-    Affine128* d_step_jump = nullptr;     // [batch_draws]
+    DeviceBuffer<DrawRec<T>> d_draws_batch;  // [batch_draws][2][n]: records made ahead of the matrix-core full-step launches
+    DeviceBuffer<Affine128> d_step_jump;     // [batch_draws]
     int batch_draws = 0;                  // 0: the step launches make their own next records
     uint32_t* d_partials = nullptr;
     int partial_slots = 1, partial_waves = 0;
@@ -1802,13 +1697,13 @@ private:
     // which ensemble step the draw records on the device belong to, if known, and whether the black ones carry partner2
     bool records_valid = false, records_partner2 = false, run_info_idle = false;
     uint64_t records_step = 0;
-    PinnedScratch* h_pinned = nullptr;
+    PinnedBuffer<PinnedScratch> h_pinned;
     U128 state0, inc;
     U128 state0_of[kMaxChains];  // per chain (seed + k)
     int K = 1;                   // independent ensembles stepped by one launch
     Affine128 half_jump;
     HalfStepArgs<T> args_red, args_blk;
-    std::vector<hipGraphExec_t> graph_cache;  // [steps] -> instantiated graph
+    std::vector<GraphExec> graph_cache;  // [steps] -> instantiated graph
     uint64_t half_steps = 0, enq_step = 0;
     void* bound_chain = nullptr;
     int64_t bound_slots = 0;
@@ -2044,10 +1939,7 @@ void* mcmcpp_hip_host_alloc(uint64_t bytes)
     }
     return p;
 }
-void mcmcpp_hip_host_free(void* p)
-{
-    if (p) (void)hipHostFree(p);
-}
+void mcmcpp_hip_host_free(void* p) { mcmcpp::free_pinned(p); }
 int mcmcpp_hip_get_state(mcmcpp_hip_sampler* h, void* positions, void* logp, uint32_t* n_accept)
 {
     NEED_H;

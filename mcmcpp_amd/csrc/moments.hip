@@ -159,10 +159,9 @@ struct mcmcpp_hip_moments
     bool matrix_core = false;
     long long points = 0;       // samples accumulated so far
     size_t slot_elems = 0;
-    double *d_partial = nullptr, *d_total = nullptr;
-    void* d_chunk = nullptr;
-    size_t chunk_bytes = 0;
-    hipStream_t stream = nullptr;
+    mcmcpp::DeviceBuffer<double> d_partial, d_total;
+    mcmcpp::DeviceBuffer<char> d_chunk;
+    hipStream_t stream = nullptr;  // (destroyed after the buffers: mcmcpp_hip_moments_destroy)
 };
 
 namespace
@@ -237,8 +236,8 @@ int mcmcpp_hip_moments_create(int32_t dtype, int32_t device, int32_t num_walkers
     while (m->slots > kMomentWavesPerBlock && (size_t)m->slots * m->slot_elems * sizeof(double) > ((size_t)256 << 20)) m->slots /= 2;
     m->slots -= m->slots % kMomentWavesPerBlock;
     if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&m->d_partial, sizeof(double) * (size_t)m->slots * m->slot_elems) != hipSuccess ||
-        hipMalloc(&m->d_total, sizeof(double) * m->slot_elems) != hipSuccess ||
+        m->d_partial.alloc(sizeof(double) * (size_t)m->slots * m->slot_elems) != hipSuccess ||
+        m->d_total.alloc(sizeof(double) * m->slot_elems) != hipSuccess ||
         hipMemset(m->d_partial, 0, sizeof(double) * (size_t)m->slots * m->slot_elems) != hipSuccess)
     {
         g_moments_error = "moments_create: cannot allocate device memory";
@@ -253,12 +252,10 @@ void mcmcpp_hip_moments_destroy(mcmcpp_hip_moments* m)
 {
     if (!m) return;
     hipSetDevice(m->device);
-    if (m->stream) hipStreamSynchronize(m->stream);
-    if (m->d_partial) hipFree(m->d_partial);
-    if (m->d_total) hipFree(m->d_total);
-    if (m->d_chunk) hipFree(m->d_chunk);
-    if (m->stream) hipStreamDestroy(m->stream);
-    delete m;
+    const hipStream_t stream = m->stream;
+    if (stream) hipStreamSynchronize(stream);
+    delete m;  // (the buffers free themselves)
+    if (stream) hipStreamDestroy(stream);
 }
 
 int mcmcpp_hip_moments_reset(mcmcpp_hip_moments* m)
@@ -283,15 +280,7 @@ int mcmcpp_hip_moments_add_steps(mcmcpp_hip_moments* m, const void* steps, int64
     int64_t per_chunk = (int64_t)(((size_t)64 << 20) / step_bytes);
     if (per_chunk < 1) per_chunk = 1;
     if (per_chunk > n_steps) per_chunk = n_steps;
-    if (m->chunk_bytes < step_bytes * (size_t)per_chunk)
-    {
-        MOM_TRY(hipStreamSynchronize(m->stream));
-        if (m->d_chunk) hipFree(m->d_chunk);
-        m->d_chunk = nullptr;
-        m->chunk_bytes = 0;
-        if (hipMalloc(&m->d_chunk, step_bytes * (size_t)per_chunk) != hipSuccess) return fail(m, MCMCPP_HIP_E_NOMEM, "moments_add_steps: cannot allocate the upload buffer");
-        m->chunk_bytes = step_bytes * (size_t)per_chunk;
-    }
+    if (mcmcpp::grow(m->d_chunk, step_bytes * (size_t)per_chunk, m->stream)) return fail(m, MCMCPP_HIP_E_NOMEM, "moments_add_steps: cannot allocate the upload buffer");
     for (int64_t first = 0; first < n_steps; first += per_chunk)
     {
         const int64_t now = (n_steps - first < per_chunk) ? n_steps - first : per_chunk;
@@ -304,8 +293,8 @@ int mcmcpp_hip_moments_add_steps(mcmcpp_hip_moments* m, const void* steps, int64
                 MOM_TRY(hipMemcpyAsync((char*)m->d_chunk + step_bytes * (size_t)k, src + step_bytes * (size_t)(k * step_stride), step_bytes,
                                        hipMemcpyHostToDevice, m->stream));
         const long long n_samples = (long long)now * m->W;
-        const int rc = m->dtype == MCMCPP_HIP_F64 ? accumulate<double>(m, (const double*)m->d_chunk, n_samples)
-                                                  : accumulate<float>(m, (const float*)m->d_chunk, n_samples);
+        const int rc = m->dtype == MCMCPP_HIP_F64 ? accumulate<double>(m, (const double*)m->d_chunk.get(), n_samples)
+                                                  : accumulate<float>(m, (const float*)m->d_chunk.get(), n_samples);
         if (rc) return rc;
         m->points += n_samples;
     }

@@ -1,6 +1,7 @@
 // sampler_base.hpp -- what the C ABI handle is behind include/mcmcpp_hip.h: one abstract interface, implemented by the
 // fused stretch-move sampler (mcmcpp_hip.hip), the differential-evolution sampler (diffevo.hip) and the stretch move with a
-// batched log-posterior callback (batch.hip).  The host code the three share is in sampler_host.hpp.
+// batched log-posterior callback (batch.hip).  The host code the three share is in sampler_host.hpp.  Also the owners of
+// the library's HIP resources, which every handle (the analysis handles included) uses.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -15,6 +16,7 @@
 #include <optional>
 #include <string>
 #include <thread>
+#include <utility>
 
 #include "../../include/mcmcpp_hip.h"
 
@@ -109,6 +111,120 @@ struct mcmcpp_hip_sampler
 
 namespace mcmcpp
 {
+// ---- Owners of the HIP resources the handles hold ("Who frees what") ----------------------------
+// Every device buffer, pinned host buffer, event and instantiated graph of the library belongs to one of these, and they
+// are the only code that gives one back to the runtime.  Move-only.  A handle quiesces its stream in its destructor's
+// body; its members then free themselves, before the stream goes with the base class.
+
+inline void free_device(void* p)
+{
+    if (p) (void)hipFree(p);
+}
+inline void free_pinned(void* p)
+{
+    if (p) (void)hipHostFree(p);
+}
+
+// A block of device memory (Pinned: of pinned host memory) seen as T[], and its capacity in bytes
+template <class T, bool Pinned>
+class HipBuffer
+{
+public:
+    HipBuffer() = default;
+    HipBuffer(const HipBuffer&) = delete;
+    HipBuffer& operator=(const HipBuffer&) = delete;
+    HipBuffer(HipBuffer&& o) noexcept : p_(std::exchange(o.p_, nullptr)), bytes_(std::exchange(o.bytes_, 0)) {}
+    HipBuffer& operator=(HipBuffer&& o) noexcept
+    {
+        std::swap(p_, o.p_);  // (o frees what this held)
+        std::swap(bytes_, o.bytes_);
+        return *this;
+    }
+    ~HipBuffer() { reset(); }
+
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+    T* operator->() const { return p_; }
+    size_t bytes() const { return bytes_; }
+
+    void reset()
+    {
+        (Pinned ? free_pinned : free_device)(p_);
+        p_ = nullptr;
+        bytes_ = 0;
+    }
+    // a new block of `bytes` in place of the old one; on failure the buffer is empty and the runtime's last error cleared
+    hipError_t alloc(size_t bytes)
+    {
+        reset();
+        void* p = nullptr;
+        const hipError_t e = Pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
+        if (e != hipSuccess)
+        {
+            (void)hipGetLastError();
+            return e;
+        }
+        p_ = static_cast<T*>(p);
+        bytes_ = bytes;
+        return hipSuccess;
+    }
+
+private:
+    T* p_ = nullptr;
+    size_t bytes_ = 0;
+};
+template <class T = void>
+using DeviceBuffer = HipBuffer<T, false>;
+template <class T = void>
+using PinnedBuffer = HipBuffer<T, true>;
+
+// The one grow rule for buffers kept from call to call: nothing if `buf` holds `bytes` already; else, once `stream` is
+// idle (work on it may still use the old block), the old block goes and one of `bytes` takes its place.  Returns the
+// synchronisation's error or the allocation's (the buffer is then empty and the runtime's last error cleared).
+template <class T, bool Pinned>
+hipError_t grow(HipBuffer<T, Pinned>& buf, size_t bytes, hipStream_t stream)
+{
+    if (bytes <= buf.bytes()) return hipSuccess;
+    if (const hipError_t e = hipStreamSynchronize(stream)) return e;
+    buf.reset();
+    return buf.alloc(bytes);
+}
+
+// A hipEvent_t or hipGraphExec_t, destroyed with its owner
+template <class H, hipError_t (*Destroy)(H)>
+class HipHandle
+{
+public:
+    HipHandle() = default;
+    HipHandle(const HipHandle&) = delete;
+    HipHandle& operator=(const HipHandle&) = delete;
+    HipHandle(HipHandle&& o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
+    HipHandle& operator=(HipHandle&& o) noexcept
+    {
+        std::swap(h_, o.h_);
+        return *this;
+    }
+    ~HipHandle() { reset(); }
+
+    operator H() const { return h_; }
+    void reset()
+    {
+        if (h_) (void)Destroy(h_);
+        h_ = nullptr;
+    }
+    // where a create call writes the new handle (the old one destroyed first)
+    H* replace()
+    {
+        reset();
+        return &h_;
+    }
+
+private:
+    H h_ = nullptr;
+};
+using Event = HipHandle<hipEvent_t, hipEventDestroy>;
+using GraphExec = HipHandle<hipGraphExec_t, hipGraphExecDestroy>;
+
 inline int pow2_at_least(int v)
 {
     int p = 1;

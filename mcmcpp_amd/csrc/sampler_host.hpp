@@ -200,7 +200,7 @@ protected:
         return MCMCPP_HIP_OK;
     }
 
-    // first thing of a mover's release: nothing the handle enqueued is still in flight
+    // first thing of a mover's destructor: nothing the handle enqueued is still in flight when its members free themselves
     void quiesce()
     {
         if (device >= 0) (void)hipSetDevice(device);
@@ -278,18 +278,9 @@ protected:
         if (count < 0 || (count > 0 && (!pos || !out))) return fail(MCMCPP_HIP_E_ARG, "calc_logp: bad arguments");
         if (count == 0) return MCMCPP_HIP_OK;
         HIP_TRY(hipSetDevice(device));
-        struct Scratch  // freed on every way out
-        {
-            T *rows = nullptr, *out = nullptr;
-            ~Scratch()
-            {
-                if (rows) (void)hipFree(rows);
-                if (out) (void)hipFree(out);
-            }
-        } scratch;
-        HIP_TRY(hipMalloc(&scratch.rows, sizeof(T) * (size_t)count * D));
-        HIP_TRY(hipMalloc(&scratch.out, sizeof(T) * (size_t)count));
-        T *dp = scratch.rows, *dout = scratch.out;
+        DeviceBuffer<T> dp, dout;  // (freed on every way out)
+        HIP_TRY(dp.alloc(sizeof(T) * (size_t)count * D));
+        HIP_TRY(dout.alloc(sizeof(T) * (size_t)count));
         HIP_TRY(hipMemcpyAsync(dp, pos, sizeof(T) * (size_t)count * D, hipMemcpyHostToDevice, stream));
         const long long per_block = (long long)(64 / lpw) * kWavesPerBlock;
         const unsigned grid = (unsigned)((count + per_block - 1) / per_block);
