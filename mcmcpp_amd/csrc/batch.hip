@@ -253,8 +253,7 @@ public:
         HIP_TRY(hipMemset(d_partials, 0, sizeof(uint32_t) * 2 * (size_t)partial_waves));
         HIP_TRY(h_pinned.alloc(sizeof(Pinned)));
         std::memset(h_pinned, 0, sizeof(Pinned));
-        h_pinned->run.interval = 1;
-        h_pinned->run.slot_mask = -1;
+        h_pinned->run = idle_run_info();
         HIP_TRY(hipMemcpy(d_run, &h_pinned->run, sizeof(RunInfo), hipMemcpyHostToDevice));
 
         // pcg64 stream (MultiSampler.h:54) and its jump tables, as the fused sampler builds them
@@ -482,12 +481,11 @@ private:
             const int64_t first = c * sub_saved;
             const int64_t now = chain_out ? ((n_saved - first < sub_saved) ? n_saved - first : sub_saved) : n_saved;
             RunInfo* ri = &h_pinned->run;  // (the stream was synchronised behind the previous sub-chunk)
-            std::memset(ri, 0, sizeof *ri);
+            *ri = idle_run_info();
             ri->chain = chain_out ? d_chain.get() : nullptr;
             ri->accepted_per_step = accepted_per_step ? d_acc.get() : nullptr;
             ri->interval = interval;
             ri->chain_slot_base = -first;
-            ri->slot_mask = -1;
             ri->step_bytes = (int64_t)step_bytes;
             HIP_TRY(hipMemcpyAsync(d_run, ri, sizeof(RunInfo), hipMemcpyHostToDevice, stream));
             for (int64_t s = 0; s < now * (int64_t)interval; ++s, ++step)

@@ -151,7 +151,8 @@ struct DenseGaussianFn
     static constexpr bool kNeedsStage = true;
     static constexpr int kMaxPadded = 64;
     // walkers of 17..32 dimensions take the matrix-core kernels (stretch_half_step_mfma_kernel): the slot of that range
-    // is 16 lanes x 2 elements for fp64, 8 lanes x 4 elements for fp32
+    // is 16 lanes x 2 elements for fp64, 8 lanes x 4 elements for fp32 (tests/cpp/step_plan_cases.cpp repeats this rule to say
+    // which launch-table slots exist: keep the two together)
     template <int EPL, int LPW>
     struct MatrixCore
     {

@@ -44,15 +44,14 @@ public:
         update_fn = table->de_update[lpw_log][epl_shift];
         walkers_per_block = (64 / lpw) * kWavesPerBlock;
         {
-            // the dense Gaussian's product on the matrix cores (de_update_mfma_kernel): fp64, even D, 8 walkers per wavefront
-            const long mc_min = knobs.matrix_core_min_walkers;
-            if (table->de_update_mc[0][lpw_log][epl_shift] && c.calc_id == MCMCPP_HIP_CALC_DENSE_GAUSSIAN && D % 2 == 0 && D <= 32 && mc_min >= 0 && n >= mc_min)
+            // the dense Gaussian's product on the matrix cores (de_update_mfma_kernel), where plan_de_update says so
+            StepShape s = {};
+            s.W = W, s.D = D, s.n = n, s.lpw = lpw, s.elem_size = (int)sizeof(T), s.calc_id = c.calc_id;
+            s.de_update_mc = table->de_update_mc[0][lpw_log][epl_shift] != nullptr;
+            if (const int per_wave = plan_de_update(s, knobs))
             {
-                // 16 walkers per wavefront once the chip is full (as the stretch kernels: MCMCPP_HIP_MATRIX_CORE_4PASS_WALKERS)
-                const long four_pass = knobs.matrix_core_4pass.value_or(32768);
-                const int big = n >= four_pass ? 1 : 0;
-                update_fn = table->de_update_mc[big][lpw_log][epl_shift];
-                walkers_per_block = (big ? 16 : 8) * kWavesPerBlock;
+                update_fn = table->de_update_mc[per_wave == 16 ? 1 : 0][lpw_log][epl_shift];
+                walkers_per_block = per_wave * kWavesPerBlock;
                 matrix_core = true;
             }
         }

@@ -43,8 +43,6 @@ namespace
 {
 thread_local std::string g_create_error;
 
-
-
 // memcpy of a large block split over a few threads (the un-overlapped tail of a run's chain download: a single core
 // moves ~12 GB/s into pageable memory)
 void parallel_memcpy(char* dst, const char* src, size_t bytes)
@@ -203,9 +201,42 @@ public:
         const int lpw_log = ilog2(lpw), epl_shift = ilog2(epl / Vec16<T>::N);
         if (epl_shift >= kMaxEplShift || !table->half_step[lpw_log][epl_shift])
             return fail(MCMCPP_HIP_E_UNSUPPORTED, "no kernel for D=%d with this calculator (LPW=%d EPL=%d)", D, lpw, epl);
-        half_fn = table->half_step[lpw_log][epl_shift];
         calc_fn = table->calc[lpw_log][epl_shift];
 
+        if (int rc = resolve_shard(c)) return rc;
+        hipDeviceProp_t prop;
+        if (int rc = open_device(c, &prop)) return rc;
+        if (int rc = open_communicator(c)) return rc;
+        K = c.num_chains > 1 ? c.num_chains : 1;
+        if (K > kMaxChains) return fail(MCMCPP_HIP_E_ARG, "num_chains %d exceeds %d", K, kMaxChains);
+        if (K > 1 && (shard_count != n || shard_begin != 0 || c.comm_world >= 1 || c.device_positions))
+            return fail(MCMCPP_HIP_E_ARG, "num_chains > 1: whole ensembles on one device only (no shards, communicator or caller-owned positions)");
+        if (int rc = open_stream(c)) return rc;
+
+        // which kernels step this handle, and their launch geometry (step_plan.hpp)
+        StepShape s = {};
+        s.W = W, s.D = D, s.n = n, s.lpw = lpw, s.elem_size = (int)sizeof(T), s.calc_id = c.calc_id;
+        s.shard_begin = shard_begin, s.shard_count = shard_count, s.chains = K, s.comm_world = c.comm_world;
+        s.num_cus = prop.multiProcessorCount;
+        s.graph_steps = c.graph_steps;
+        s.can_capture = own_stream || !(stream == nullptr || stream == hipStreamLegacy);
+        for (int v = 0; v < 3; ++v) s.half_step_mc[v] = table->half_step_mc[v][lpw_log][epl_shift] != nullptr;
+        s.full_step = table->full_step[lpw_log][epl_shift] != nullptr;
+        s.full_step_mc = table->full_step_mc[lpw_log][epl_shift] != nullptr;
+        plan = plan_stretch_step(s, knobs);
+        static_assert((int)HalfStepKernel::MatrixCore8 == 1 && (int)HalfStepKernel::MatrixCore16 == 2 && (int)HalfStepKernel::MatrixCore16Late == 3, "half_step_mc[] is indexed by the enum");
+        half_fn = plan.matrix_core_half() ? table->half_step_mc[(int)plan.half - 1][lpw_log][epl_shift] : table->half_step[lpw_log][epl_shift];
+        full_fn = plan.full == FullStepKernel::MatrixCore ? table->full_step_mc[lpw_log][epl_shift]
+                  : plan.full == FullStepKernel::Plain    ? table->full_step[lpw_log][epl_shift]
+                                                          : nullptr;
+
+        if (int rc = allocate(c)) return rc;
+        return upload_constants(c);
+    }
+
+    // the walkers of each colour this handle updates: the whole half, the configured shard, or the rank's slice
+    int resolve_shard(const mcmcpp_hip_config& c)
+    {
         shard_begin = c.shard_begin;
         shard_count = c.shard_count > 0 ? c.shard_count : n;
         if (c.comm_world >= 1)
@@ -224,126 +255,63 @@ public:
             if (!c.comm && !c.comm_id) return fail(MCMCPP_HIP_E_ARG, "comm_world >= 1 needs comm_id or comm");
         }
         if (shard_begin < 0 || shard_begin + shard_count > n) return fail(MCMCPP_HIP_E_ARG, "shard out of range");
+        return MCMCPP_HIP_OK;
+    }
 
-        hipDeviceProp_t prop;
-        if (int rc = open_device(c, &prop)) return rc;
-        num_cus = prop.multiProcessorCount;
-        if (c.comm_world >= 1)
+    // split ensembles: the caller's communicator, or one of the handle's own from the caller's id
+    int open_communicator(const mcmcpp_hip_config& c)
+    {
+        if (c.comm_world < 1) return MCMCPP_HIP_OK;
+        std::string why;
+        rccl = Rccl::get(&why);
+        if (!rccl) return fail(MCMCPP_HIP_E_COMM, "%s", why.c_str());
+        if (c.comm)
         {
-            std::string why;
-            rccl = Rccl::get(&why);
-            if (!rccl) return fail(MCMCPP_HIP_E_COMM, "%s", why.c_str());
-            if (c.comm)
-            {
-                comm = static_cast<ncclComm_t>(c.comm);
-                int cnt = -1, rk = -1;
-                NCCL_TRY(rccl->CommCount(comm, &cnt));
-                NCCL_TRY(rccl->CommUserRank(comm, &rk));
-                if (cnt != c.comm_world || rk != c.comm_rank)
-                    return fail(MCMCPP_HIP_E_ARG, "the communicator is rank %d of %d, the config says %d of %d", rk, cnt, c.comm_rank, c.comm_world);
-            }
-            else
-            {
-                ncclUniqueId id;
-                static_assert(sizeof(id) == MCMCPP_HIP_COMM_ID_BYTES, "mcmcpp_hip.h states the size of an RCCL id");
-                std::memcpy(&id, c.comm_id, sizeof id);
-                NCCL_TRY(rccl->CommInitRank(&comm, c.comm_world, id, c.comm_rank));
-                own_comm = true;
-            }
+            comm = static_cast<ncclComm_t>(c.comm);
+            int cnt = -1, rk = -1;
+            NCCL_TRY(rccl->CommCount(comm, &cnt));
+            NCCL_TRY(rccl->CommUserRank(comm, &rk));
+            if (cnt != c.comm_world || rk != c.comm_rank)
+                return fail(MCMCPP_HIP_E_ARG, "the communicator is rank %d of %d, the config says %d of %d", rk, cnt, c.comm_rank, c.comm_world);
         }
-
-        // Walkers per wavefront: fill the chip first (about two wavefronts per SIMD), then up to 8 per wavefront (still
-        // served by the draw wavefront) and 16 for the largest ensembles.  Measured, 32 dims fp64 (tools/sweep_passes.txt):
-        // 65 536 walkers 5.2 / 5.8 / 4.4e9 walker-steps/s with 4 / 8 / 16 walkers per wavefront, 262 144: 7.4e9 with 8,
-        // 1 M: 6.7 / 8.0 / 7.8 / 7.4e9 with 8 / 16 / 32 / 64.
-        // Independent ensembles stepped by the same launches (BASELINE config 4 on one GPU): chain k is seeded with
-        // seed + k on the same stream, so all chains share the jump tables; see ChainGeometry for the layout.  What a
-        // launch has to fill the chip with is the walkers of all chains together.
-        K = c.num_chains > 1 ? c.num_chains : 1;
-        if (K > kMaxChains) return fail(MCMCPP_HIP_E_ARG, "num_chains %d exceeds %d", K, kMaxChains);
-        const long launch_walkers = (long)shard_count * K;  // walkers of one colour a launch updates
-        const int wpp = 64 / lpw;
-        long forced = knobs.passes;
-        if (forced > 0)
-            passes = (int)forced;
         else
         {
-            const long target_waves = (long)num_cus * 4 * knobs.waves_per_simd;
-            const int per_wave_cap = launch_walkers > 196608 ? 16 : 8;
-            passes = 1;
-            while (passes * 2 <= lpw && wpp * passes * 2 <= per_wave_cap && launch_walkers / ((long)wpp * passes * 2) >= target_waves) passes *= 2;
+            ncclUniqueId id;
+            static_assert(sizeof(id) == MCMCPP_HIP_COMM_ID_BYTES, "mcmcpp_hip.h states the size of an RCCL id");
+            std::memcpy(&id, c.comm_id, sizeof id);
+            NCCL_TRY(rccl->CommInitRank(&comm, c.comm_world, id, c.comm_rank));
+            own_comm = true;
         }
-        if (passes < 1) passes = 1;
-        if (passes > lpw) passes = lpw;
-        step_lpw = lpw;  // lanes per walker of the step kernels in use
-        // Matrix-core variants of the half-step kernel (dense calculators, fp64, even D in 18..32): the wavefront's
-        // walkers are rows of one MFMA tile -- 8 walkers (2 passes) until the chip is full, 16 (4 passes) beyond.
-        const long mc_min = knobs.matrix_core_min_walkers;
-        int mc_level = -1;  // matrix-core half-step kernel in use: 0 = 8 walkers per wavefront, 1 = 16, 2 = 16 with late draws
-        if (table->half_step_mc[0][lpw_log][epl_shift] && (D % 2 == 0) && mc_min >= 0 && shard_count >= mc_min &&
-            c.calc_id == MCMCPP_HIP_CALC_DENSE_GAUSSIAN &&     // (they read the padded matrix this file prepares)
-            (size_t)W * (size_t)D * sizeof(T) < (1ull << 32))  // (and address a chain's arrays with 32-bit byte offsets)
-        {
-            // (measured after the round-3 rework, us per launch with 8 / 16 walkers per wavefront: 16 384 updates 5.04 / 5.23,
-            //  20 480: 7.37 / 6.57, 24 576: 7.54 / 6.63, 28 672: 9.97 / 6.72, 32 768: 10.02 / 6.78 -- profiles/r03_mc_p2_p4.txt)
-            mc_level = launch_walkers >= knobs.matrix_core_4pass.value_or(18432) ? 1 : 0;
-            // (about as many updates as one round of wavefront slots holds at three wavefronts per SIMD, or more: four per SIMD,
-            //  draws behind the accept -- profiles/r03_mc_threshold.txt)
-            if (mc_level == 1 && knobs.matrix_core_late >= 0 && launch_walkers >= knobs.matrix_core_late && table->half_step_mc[2][lpw_log][epl_shift]) mc_level = 2;
-            half_fn = table->half_step_mc[mc_level][lpw_log][epl_shift];
-            passes = mc_level == 0 ? 2 : 4;
-            step_lpw = 16;  // (the matrix-core kernels map a walker to 16 lanes x 2 elements in either element type)
-        }
+        return MCMCPP_HIP_OK;
+    }
 
-        // One launch per ensemble step (full_step_kernel.hpp) while the ensemble is small enough that a half-step
-        // launch is bounded by its launch boundary and latencies rather than by HBM; needs the whole ensemble here.
-        // A rank of a split ensemble takes the same kernels for its slice (they repeat red updates owned by other ranks,
-        // so the ranks exchange rows once per ensemble step), by the size of what it updates.
-        full_fn = nullptr;
-        const bool whole = shard_count == n && shard_begin == 0;
-        // (measured, 32 dims fp64, us per ensemble step full / half: isotropic 32 768 walkers 7 % in favour of full steps;
-        //  dense with the matrix-core half-step kernel 10.75 / 10.06 at 32 768, 5.47 / 7.28 at 16 384: profiles/r03_mc_probe_e.txt)
-        const bool mc_half = mc_level >= 0;
-        const long full_step_max = knobs.full_step_max_walkers >= 0 ? knobs.full_step_max_walkers : (mc_half ? 32767 : 32768);
-        if ((c.comm_world >= 1 ? (knobs.comm_full_step != 0 && knobs.full_step != 0) : (whole && knobs.full_step != 0)) &&
-            2 * launch_walkers <= full_step_max)
+    // every buffer of the handle, sized by the plan
+    int allocate(const mcmcpp_hip_config& c)
+    {
+        const size_t step_bytes = sizeof(T) * (size_t)W * D;
+        if (plan.compact_exchange)
         {
-            full_fn = table->full_step[lpw_log][epl_shift];
-            full_wpb = kWavesPerBlock * (64 / lpw);
-            if (table->full_step_mc[lpw_log][epl_shift] && (D % 2 == 0) && mc_min >= 0 && shard_count >= mc_min &&
-                c.calc_id == MCMCPP_HIP_CALC_DENSE_GAUSSIAN &&  // (it reads the padded matrix this file prepares)
-                W < (1 << 24) && (size_t)W * (size_t)D * sizeof(T) < (1ull << 32))  // (and addresses rows by 24-bit products, 32-bit offsets)
-            {
-                full_fn = table->full_step_mc[lpw_log][epl_shift];
-                full_wpb = kWavesPerBlock * 8;
-            }
-        }
-
-        if (c.comm_world > 1 && knobs.comm_compact != 0)
-        {
-            const uint32_t cap_full = (uint32_t)((full_fn ? 2 : 1) * shard_count);
-            HIP_TRY(d_xblocks.alloc(xblock_bytes<T>(cap_full, D) * (size_t)c.comm_world));
+            snap.logp = step_bytes;
+            snap.nacc = snap.logp + sizeof(T) * (size_t)W;
+            snap.diag = snap.nacc + sizeof(uint32_t) * (size_t)W;
+            HIP_TRY(d_xblocks.alloc(xblock_bytes<T>(exchange_cap_full(), D) * (size_t)c.comm_world));
             HIP_TRY(d_seen.alloc(sizeof(uint32_t) * (size_t)W));
             HIP_TRY(d_xstats.alloc(sizeof(XStats)));
-            HIP_TRY(d_snap.alloc(sizeof(T) * (size_t)W * D + (sizeof(T) + sizeof(uint32_t)) * (size_t)W + sizeof(Diag)));
+            HIP_TRY(d_snap.alloc(snap.diag + sizeof(Diag)));
         }
-        if (K > 1 && (!whole || c.comm_world >= 1 || c.device_positions))
-            return fail(MCMCPP_HIP_E_ARG, "num_chains > 1: whole ensembles on one device only (no shards, communicator or caller-owned positions)");
-        if (int rc = open_stream(c)) return rc;
         for (int k = 0; k < 4; ++k)
         {
             HIP_TRY(hipEventCreate(ev_t0[k].replace()));
             HIP_TRY(hipEventCreate(ev_t1[k].replace()));
         }
 
+        const size_t partials_bytes = sizeof(uint32_t) * (size_t)plan.partial_slots * 2 * (size_t)plan.partial_waves * K;
         {
-            // upper bound of everything carved below (each piece rounded up to 256 bytes)
-            const size_t graph_len = (size_t)(c.graph_steps == 0 ? default_graph_steps() : (c.graph_steps > 0 ? c.graph_steps : 1));
-            const size_t waves_bound = (size_t)n + 64;  // no kernel uses more wavefronts per colour than walkers
-            size_t need = (size_t)K * 2 * sizeof(T) * (size_t)W * D    // pos, pos_alt
-                          + (size_t)K * logp_chain_stride_bytes<T>(n) + (size_t)K * kCtlChainStride + tables_total_bytes(n, true, K)
-                          + sizeof(T) * ((size_t)(c.calc_params_len > 0 ? c.calc_params_len : 0) + 32 * 32)
-                          + (size_t)K * sizeof(uint32_t) * graph_len * 2 * waves_bound + 64 * 1024;
+            // everything carved below (each piece rounded up to 256 bytes)
+            static_assert(sizeof(Affine128) == kJumpEntryBytes, "the plan sizes the task table by this");
+            size_t need = (size_t)K * (full_fn ? 2 : 1) * step_bytes  // pos, pos_alt
+                          + (size_t)K * logp_chain_stride_bytes<T>(n) + (size_t)K * kCtlChainStride + tables_total_bytes(n, plan.have_task_table, K)
+                          + sizeof(T) * ((size_t)(c.calc_params_len > 0 ? c.calc_params_len : 0) + 32 * 32) + partials_bytes + 64 * 1024;
             HIP_TRY(arena.alloc(need));
             arena_used = 0;
         }
@@ -355,7 +323,7 @@ public:
         }
         else
         {
-            if (int rc = carve(&d_pos, sizeof(T) * (size_t)W * D * K)) return rc;
+            if (int rc = carve(&d_pos, step_bytes * K)) return rc;
             own_pos = true;
         }
         // log-posteriors [2][W] (the second half is the full-step kernels' other buffer) and, right behind them, the
@@ -364,7 +332,7 @@ public:
         if (int rc = carve(&d_logp, logp_chain_stride_bytes<T>(n) * (size_t)K)) return rc;
         d_nacc = reinterpret_cast<uint32_t*>(d_logp + 2 * (size_t)W);
         if (full_fn)
-            if (int rc = carve(&d_pos_alt, sizeof(T) * (size_t)W * D * K)) return rc;
+            if (int rc = carve(&d_pos_alt, step_bytes * K)) return rc;
         {
             // the two control records and, kRunBehindCtlBytes behind the first, the run record: one piece (a kernel short
             // of preloaded arguments derives the run record's address)
@@ -379,21 +347,35 @@ public:
         // the draw records (two buffers: see HalfStepArgs::draws) and, right behind them, the jump tables: one piece
         // whose layout follows from n alone (JumpTables), so that kernels reach the tables from the record pointer
         static_assert(sizeof(DrawRec<T>) == 32, "the table offsets assume 32-byte records");
-        have_task_table = (size_t)3 * n * sizeof(Affine128) <= ((size_t)knobs.task_table_mb << 20);
         {
+            const bool task = plan.have_task_table;
             char* piece = nullptr;
-            if (int rc = carve(&piece, tables_total_bytes(n, have_task_table, K))) return rc;
+            if (int rc = carve(&piece, tables_total_bytes(n, task, K))) return rc;
             d_draws = reinterpret_cast<DrawRec<T>*>(piece);
-            d_task_jump = have_task_table ? reinterpret_cast<Affine128*>(piece + tables_offset_task(n, K)) : nullptr;
-            d_jump_hi = reinterpret_cast<Affine128*>(piece + tables_offset_hi(n, have_task_table, K));
-            d_jump_lo = reinterpret_cast<Affine128*>(piece + tables_offset_lo(n, have_task_table, K));
+            d_task_jump = task ? reinterpret_cast<Affine128*>(piece + tables_offset_task(n, K)) : nullptr;
+            d_jump_hi = reinterpret_cast<Affine128*>(piece + tables_offset_hi(n, task, K));
+            d_jump_lo = reinterpret_cast<Affine128*>(piece + tables_offset_lo(n, task, K));
         }
         HIP_TRY(hipMemset(d_draws, 0, sizeof(DrawRec<T>) * (size_t)W * 2 * K));
         HIP_TRY(hipMemset(d_logp, 0, logp_chain_stride_bytes<T>(n) * (size_t)K));
         HIP_TRY(hipMemset(d_diag, 0, sizeof(Diag)));
         HIP_TRY(hipMemset(d_ctl, 0, (size_t)kCtlChainStride * (size_t)K));
         HIP_TRY(h_pinned.alloc(sizeof(PinnedScratch)));
+        if (plan.batch_draws > 0)
+        {
+            HIP_TRY(d_draws_batch.alloc(sizeof(DrawRec<T>) * (size_t)plan.batch_draws * 2 * (size_t)n));
+            HIP_TRY(hipMemset(d_draws_batch, 0, sizeof(DrawRec<T>) * (size_t)plan.batch_draws * 2 * (size_t)n));  // (partner indices a kernel may follow)
+            HIP_TRY(d_step_jump.alloc(sizeof(Affine128) * (size_t)plan.batch_draws));
+        }
+        if (int rc = carve(&d_partials, partials_bytes)) return rc;
+        HIP_TRY(hipMemset(d_partials, 0, partials_bytes));
+        chain_subchunk_bytes = (size_t)knobs.chain_subchunk_mb << 20;
+        return MCMCPP_HIP_OK;
+    }
 
+    // what the kernels read and no run changes: calculator parameters, the random stream's seeds and jump tables
+    int upload_constants(const mcmcpp_hip_config& c)
+    {
         // calculator parameters (and, for the matrix-core kernels, the padded matrix)
         if (c.calc_params_len > 0)
         {
@@ -415,49 +397,24 @@ public:
             pcg_seed(c.seed + (uint64_t)k, c.stream, &state0_of[k], &inc_k);  // (same stream: the same increment)
         }
         {
-            const StretchJumpTables j = stretch_jump_tables(inc, n, have_task_table);
+            const StretchJumpTables j = stretch_jump_tables(inc, n, plan.have_task_table);
             HIP_TRY(hipMemcpy(d_jump_lo, j.lo.data(), sizeof(Affine128) * j.lo.size(), hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy(d_jump_hi, j.hi.data(), sizeof(Affine128) * j.hi.size(), hipMemcpyHostToDevice));
-            if (have_task_table) HIP_TRY(hipMemcpy(d_task_jump, j.task.data(), sizeof(Affine128) * j.task.size(), hipMemcpyHostToDevice));
+            if (plan.have_task_table) HIP_TRY(hipMemcpy(d_task_jump, j.task.data(), sizeof(Affine128) * j.task.size(), hipMemcpyHostToDevice));
         }
         half_jump = pcg_jump(inc, (unsigned __int128)3 * (unsigned)n);
-
-        graph_steps = c.graph_steps == 0 ? (int)default_graph_steps() : c.graph_steps;
-        // HIP cannot capture on the legacy default stream (hipErrorStreamCaptureUnsupported): a caller that hands over
-        // NULL / hipStreamLegacy gets plain launches instead of graph replays
-        if (!own_stream && (stream == nullptr || stream == hipStreamLegacy)) graph_steps = -1;
-        // Draw records made ahead of the step launches, a batch of steps per launch (fill_draws_batch_kernel): for the
-        // matrix-core full-step kernel of one whole ensemble on one device.  step_jump[j]: the draws of j ensemble steps.
-        batch_draws = 0;
-        // (only for handles that step by graph replays: with plain launches -- the caller's legacy default stream -- every
-        //  step would drag a fill launch of its own along, and a replay's worth of record memory would sit unused)
-        if (full_fn && full_fn == table->full_step_mc[lpw_log][epl_shift] && K == 1 && c.comm_world < 1 && whole && knobs.batch_draws != 0 && knobs.no_draw_wave == 0 &&
-            graph_steps >= 1)
+        if (plan.batch_draws > 0)
         {
-            // (by default as many steps as a graph replays: one fill launch per replay)
-            const long want = knobs.batch_draws > 0 ? knobs.batch_draws : (long)graph_steps;
-            batch_draws = (int)(want > 512 ? 512 : want);
-            HIP_TRY(d_draws_batch.alloc(sizeof(DrawRec<T>) * (size_t)batch_draws * 2 * (size_t)n));
-            HIP_TRY(hipMemset(d_draws_batch, 0, sizeof(DrawRec<T>) * (size_t)batch_draws * 2 * (size_t)n));  // (partner indices a kernel may follow)
-            std::vector<Affine128> sj((size_t)batch_draws);
+            // step_jump[j]: the draws of j ensemble steps
+            std::vector<Affine128> sj((size_t)plan.batch_draws);
             for (size_t j = 0; j < sj.size(); ++j) sj[j] = pcg_jump(inc, (unsigned __int128)6 * (unsigned)n * (unsigned __int128)j);
-            HIP_TRY(d_step_jump.alloc(sizeof(Affine128) * sj.size()));
             HIP_TRY(hipMemcpy(d_step_jump, sj.data(), sizeof(Affine128) * sj.size(), hipMemcpyHostToDevice));
         }
-        partial_slots = graph_steps >= 1 ? graph_steps : 1;
-        partial_waves = (int)(full_fn ? full_grid_blocks() : grid_blocks()) * kWavesPerBlock;
-        if ((int)grid_blocks() * kWavesPerBlock > partial_waves) partial_waves = (int)grid_blocks() * kWavesPerBlock;
-        if (int rc = carve(&d_partials, sizeof(uint32_t) * (size_t)partial_slots * 2 * (size_t)partial_waves * K)) return rc;
-        HIP_TRY(hipMemset(d_partials, 0, sizeof(uint32_t) * (size_t)partial_slots * 2 * (size_t)partial_waves * K));
-        chain_subchunk_bytes = (size_t)knobs.chain_subchunk_mb << 20;
         return MCMCPP_HIP_OK;
     }
 
-    // Ensemble steps per hipGraph replay.  A boundary between two replays costs a few microseconds of the launch
-    // sequence: ensembles small enough for one launch per step (5.6 us each) take 300 per replay -- with the bench's
-    // slicing interval of 100 that is three stored steps per replay, as many as the forwarding ring allows; measured 1.5 %
-    // over 128 -- larger ones, whose launches are long and whose per-step counters grow with the walker count, 128.
-    long default_graph_steps() const { return (knobs.graph_steps >= 0 ? knobs.graph_steps : (W <= 32768 ? 300 : 128)); }
+    // a block of the compact exchange that holds every walker of an exchange
+    uint32_t exchange_cap_full() const { return (uint32_t)((full_fn ? 2 : 1) * shard_count); }
 
     // Everything a step launch touches lives in ONE device allocation, carved here (one allocation, one free; tried as
     // a way to make the cold first accesses of a launch cheaper through fewer address translations: no measurable
@@ -548,7 +505,7 @@ public:
             ring = 4;
             while (ring < 64 && (size_t)(2 * ring) * step_bytes <= 2 * chain_subchunk_bytes) ring *= 2;
             // the host enqueues one chunk ahead of the one it waits for: stored steps of two chunks are in flight
-            int64_t per_chunk = (graph_steps > 0 ? graph_steps : 64) / (int64_t)interval;
+            int64_t per_chunk = (plan.graph_steps > 0 ? plan.graph_steps : 64) / (int64_t)interval;
             if (!direct_stage && per_chunk > (ring - 2) / 2) per_chunk = (ring - 2) / 2;
             if (per_chunk < 1) per_chunk = 1;
             chunk_steps = per_chunk * interval;
@@ -595,13 +552,11 @@ public:
                 // (several chains: one record each; the upload slots rotate per sub-chunk as for one chain)
                 RunInfo* ri = K > 1 ? &h_pinned->chain_run[c % 4][k] : &h_pinned->run[c % 4];
                 // chain k's stored steps of this sub-chunk: the k-th run of sub_saved steps of the device half
+                *ri = idle_run_info();
                 ri->chain = chain_out ? (void*)((char*)d_chain[buf].get() + step_bytes * (size_t)sub_saved * (size_t)k) : nullptr;
                 ri->accepted_per_step = accepted_per_step ? d_acc + (size_t)k * (size_t)total : nullptr;
                 ri->interval = interval;
                 ri->chain_slot_base = -first;
-                ri->stage = nullptr;
-                ri->slot_mask = -1;
-                ri->slice_bytes = 0;
                 ri->step_bytes = (int64_t)step_bytes;
                 HIP_TRY(hipMemcpyAsync(run_of(k), ri, sizeof(RunInfo), hipMemcpyHostToDevice, stream));
             }
@@ -644,17 +599,7 @@ public:
                 hand_out_subchunk((char*)chain_out, (const char*)h_stage[pending_buf], step_bytes, sub_saved, n_saved, pending_first, pending_count);
                 publish_stored(pending_first + pending_count);
             }
-            if (full_fn && (run_step & 1))
-            {
-                // an odd number of full steps leaves the ensemble in the second buffer: bring it (and the control
-                // record) home, so that everything outside run() only ever knows the first
-                HIP_TRY(hipMemcpyAsync(d_pos, d_pos_alt, sizeof(T) * (size_t)W * D * K, hipMemcpyDeviceToDevice, stream));
-                for (int k = 0; k < K; ++k)
-                {
-                    HIP_TRY(hipMemcpyAsync(logp_of(k), logp_of(k) + W, sizeof(T) * (size_t)W, hipMemcpyDeviceToDevice, stream));
-                    HIP_TRY(hipMemcpyAsync(ctl_of(k), ctl_of(k) + 1, sizeof(StepCtl), hipMemcpyDeviceToDevice, stream));
-                }
-            }
+            if ((rc = bring_ensemble_home())) return rc;
             HIP_TRY(hipStreamSynchronize(stream));
             for (int64_t c = (n_sub > 3 ? n_sub - 3 : 0); c < n_sub; ++c)
             {
@@ -668,7 +613,7 @@ public:
             steps_since_reset += (uint64_t)total;
             // the last launch left the records of the next ensemble step behind (full-step launches: with partner2) --
             // unless the records were made ahead in batches, which leaves the two-buffer records alone
-            records_valid = batch_draws == 0;
+            records_valid = plan.batch_draws == 0;
             records_step = half_steps >> 1;
             records_partner2 = full_fn != nullptr;
             if (accepted_per_step)
@@ -841,13 +786,9 @@ public:
         run_info_idle = false;
         {
             RunInfo* ri = &h_pinned->run[0];
-            ri->chain = nullptr;  // (stored steps are copied from the replica after the exchange)
+            *ri = idle_run_info();  // (no chain: stored steps are copied from the replica after the exchange)
             ri->accepted_per_step = d_acc;
             ri->interval = interval;
-            ri->chain_slot_base = 0;
-            ri->stage = nullptr;
-            ri->slot_mask = -1;
-            ri->slice_bytes = 0;
             ri->step_bytes = (int64_t)step_bytes;
             HIP_TRY(hipMemcpyAsync(d_run, ri, sizeof(RunInfo), hipMemcpyHostToDevice, stream));
         }
@@ -867,13 +808,15 @@ public:
         fill_red.shard_begin = 0;
         fill_red.shard_count = n;
 
-        const bool compact = d_xblocks != nullptr;
-        const uint32_t cap_full = (uint32_t)((full_fn ? 2 : 1) * shard_count);  // a block that holds every walker of an exchange
+        const bool compact = plan.compact_exchange;
+        const uint32_t cap_full = exchange_cap_full();
+        // the slot bound MCMCPP_HIP_COMM_COMPACT_CAP sets, or 0: learned from the run
+        const uint32_t cap_set = knobs.comm_compact_cap > 0 ? (uint32_t)(knobs.comm_compact_cap < (long)cap_full ? knobs.comm_compact_cap : (long)cap_full) : 0;
         uint32_t cap = cap_full;
         if (compact)
         {
-            if (knobs.comm_compact_cap > 0)
-                cap = (uint32_t)(knobs.comm_compact_cap < (long)cap_full ? knobs.comm_compact_cap : (long)cap_full);
+            if (cap_set)
+                cap = cap_set;
             else if (xcap_learned > 0)
                 cap = xcap_learned < cap_full ? xcap_learned : cap_full;
             if (full_fn)
@@ -888,7 +831,7 @@ public:
         int samples = 0;
         int64_t handed = 0;  // stored steps handed to the caller
         double xbytes = 0.0;  // bytes this rank received in the exchanges of the steps that count
-        bool learning = compact && knobs.comm_compact_cap <= 0 && xcap_learned == 0;  // first chunk: short, whole-slice blocks
+        bool learning = compact && !cap_set && xcap_learned == 0;  // first chunk: short, whole-slice blocks
         HIP_TRY(hipEventRecord(ev_t0[0], stream));
         const auto tp1 = std::chrono::steady_clock::now();
         int64_t s0 = 0;  // first step of the chunk in hand
@@ -908,16 +851,19 @@ public:
             }
             if (compact)
             {
-                // snapshot: everything a repeated chunk must find as this one found it
-                T* cur = (full_fn && (run_step & 1)) ? d_pos_alt : d_pos;
-                T* curl = (full_fn && (run_step & 1)) ? d_logp + W : d_logp;
-                HIP_TRY(hipMemcpyAsync(d_snap, cur, step_bytes, hipMemcpyDeviceToDevice, stream));
-                HIP_TRY(hipMemcpyAsync(d_snap + step_bytes, curl, sizeof(T) * (size_t)W, hipMemcpyDeviceToDevice, stream));
-                HIP_TRY(hipMemcpyAsync(d_snap + step_bytes + sizeof(T) * (size_t)W, d_nacc, sizeof(uint32_t) * (size_t)W, hipMemcpyDeviceToDevice, stream));
-                HIP_TRY(hipMemcpyAsync(d_snap + step_bytes + (sizeof(T) + sizeof(uint32_t)) * (size_t)W, d_diag, sizeof(Diag), hipMemcpyDeviceToDevice, stream));
+                const bool in_alt = full_fn && (run_step & 1);
+                if ((rc = snapshot(in_alt ? d_pos_alt : d_pos, in_alt ? d_logp + W : d_logp))) return rc;
                 if ((rc = exchange_reset(cap))) return rc;
             }
             int unreduced = 0;
+            // (the per-wavefront accepted counts are summed once per partial_slots steps, and at the end of a chunk)
+            auto reduce_accepted_if_due = [&](bool last_of_chunk) {
+                if (++unreduced == plan.partial_slots || last_of_chunk)
+                {
+                    launch_accepted_reduce(d_partials, plan.partial_slots, plan.partial_waves, unreduced, ctl_after((int64_t)run_step + 1), d_run, stream, K);
+                    unreduced = 0;
+                }
+            };
             int64_t staged = handed;
             const int samples_before = samples;
             for (int64_t s = s0; s < s0 + len; ++s)
@@ -931,12 +877,7 @@ public:
                     fill_red.draw_parity = parity;
                     launch_fill_draws(fill_red, red_base, nullptr, stream);
                     enqueue_step(parity, pos_parity);
-                    // (the per-wavefront accepted counts are summed once per partial_slots steps, and at the end of a chunk)
-                    if (++unreduced == partial_slots || last_of_chunk)
-                    {
-                        launch_accepted_reduce(d_partials, partial_slots, partial_waves, unreduced, ctl_after((int64_t)run_step + 1), d_run, stream, K);
-                        unreduced = 0;
-                    }
+                    reduce_accepted_if_due(last_of_chunk);
                     HIP_TRY(hipGetLastError());
                     cur_pos = pos_parity ? d_pos : d_pos_alt;
                     T* other_pos = pos_parity ? d_pos_alt : d_pos;
@@ -952,18 +893,14 @@ public:
                 {
                     args_red.draw_parity = parity;
                     args_blk.draw_parity = parity;
-                    half_fn(args_red, grid_blocks_for(args_red.shard_count), stream);
+                    half_fn(args_red, plan.grid_blocks_for(args_red.shard_count), stream);
                     HIP_TRY(hipGetLastError());
                     if (sample) HIP_TRY(hipEventRecord(ev_x[2 * samples], stream));
                     rc = compact ? exchange_compact(d_pos, nullptr, d_logp, nullptr, 0, 1, cap) : exchange_rows(d_pos, nullptr, 0, 1);
                     if (rc) return rc;
                     if (sample) HIP_TRY(hipEventRecord(ev_x[2 * samples + 1], stream));
-                    half_fn(args_blk, grid_blocks_for(args_blk.shard_count), stream);
-                    if (++unreduced == partial_slots || last_of_chunk)
-                    {
-                        launch_accepted_reduce(d_partials, partial_slots, partial_waves, unreduced, ctl_after((int64_t)run_step + 1), d_run, stream, K);
-                        unreduced = 0;
-                    }
+                    half_fn(args_blk, plan.grid_blocks_for(args_blk.shard_count), stream);
+                    reduce_accepted_if_due(last_of_chunk);
                     HIP_TRY(hipGetLastError());
                     rc = compact ? exchange_compact(d_pos, nullptr, d_logp, nullptr, 1, 1, cap) : exchange_rows(d_pos, nullptr, 1, 1);
                     if (rc) return rc;
@@ -987,19 +924,10 @@ public:
                 if (hx->overflow)
                 {
                     // Some block of some exchange of this chunk was too small: whatever the chunk computed rests on a
-                    // replica that missed rows.  Back to the snapshot -- into both buffers, so that the repeated chunk may
-                    // start at buffer 0 like a run does -- and once more with blocks nothing can overflow.  Every rank
-                    // reads the same gathered headers, so every rank takes this branch together.
+                    // replica that missed rows.  Back to the snapshot (rollback) and once more with blocks nothing can
+                    // overflow.  Every rank reads the same gathered headers, so every rank takes this branch together.
                     ++xchg_rollbacks;
-                    HIP_TRY(hipMemcpyAsync(d_pos, d_snap, step_bytes, hipMemcpyDeviceToDevice, stream));
-                    HIP_TRY(hipMemcpyAsync(d_logp, d_snap + step_bytes, sizeof(T) * (size_t)W, hipMemcpyDeviceToDevice, stream));
-                    if (full_fn)
-                    {
-                        HIP_TRY(hipMemcpyAsync(d_pos_alt, d_snap, step_bytes, hipMemcpyDeviceToDevice, stream));
-                        HIP_TRY(hipMemcpyAsync(d_logp + W, d_snap + step_bytes, sizeof(T) * (size_t)W, hipMemcpyDeviceToDevice, stream));
-                    }
-                    HIP_TRY(hipMemcpyAsync(d_nacc, d_snap + step_bytes + sizeof(T) * (size_t)W, sizeof(uint32_t) * (size_t)W, hipMemcpyDeviceToDevice, stream));
-                    HIP_TRY(hipMemcpyAsync(d_diag, d_snap + step_bytes + (sizeof(T) + sizeof(uint32_t)) * (size_t)W, sizeof(Diag), hipMemcpyDeviceToDevice, stream));
+                    if ((rc = rollback())) return rc;
                     half_steps = half_steps0 + 2 * (uint64_t)s0;
                     records_valid = false;
                     rc = write_ctl((uint64_t)s0, interval);
@@ -1013,7 +941,7 @@ public:
                     continue;  // (the same chunk again)
                 }
                 xbytes += (double)len * (double)(full_fn ? 1 : 2) * (double)(cfg.comm_world - 1) * (double)xblock_bytes<T>(cap, D);
-                if (knobs.comm_compact_cap <= 0)
+                if (!cap_set)
                 {
                     // the next chunk's bound: what this one needed, plus an eighth and a little
                     uint64_t want = (uint64_t)hx->max_count + hx->max_count / 8 + 64;
@@ -1022,7 +950,7 @@ public:
                     xcap_learned = cap;
                 }
                 else
-                    cap = (uint32_t)(knobs.comm_compact_cap < (long)cap_full ? knobs.comm_compact_cap : (long)cap_full);
+                    cap = cap_set;
                 learning = false;
             }
             else
@@ -1037,12 +965,7 @@ public:
             s0 += len;
         }
         const auto tp2 = std::chrono::steady_clock::now();
-        if (full_fn && (run_step & 1))
-        {
-            HIP_TRY(hipMemcpyAsync(d_pos, d_pos_alt, sizeof(T) * (size_t)W * D, hipMemcpyDeviceToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(d_logp, d_logp + W, sizeof(T) * (size_t)W, hipMemcpyDeviceToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(d_ctl, d_ctl + 1, sizeof(StepCtl), hipMemcpyDeviceToDevice, stream));
-        }
+        if ((rc = bring_ensemble_home())) return rc;
         HIP_TRY(hipEventRecord(ev_t1[0], stream));
         // every rank ends the run with the whole ensemble's log-posteriors and accepted counters (get_state is then the
         // same on all ranks), and with the ensemble-wide accepted counts per step
@@ -1101,10 +1024,10 @@ public:
         for (int k = 0; k < K; ++k)
         {
             RunInfo* ri = &h_pinned->chain_run[0][k];
+            *ri = idle_run_info();
             ri->chain = (char*)d_ring + ring_bytes * (size_t)k;
             ri->accepted_per_step = want_accepted ? d_acc + (size_t)k * (size_t)total : nullptr;
             ri->interval = interval;
-            ri->chain_slot_base = 0;
             ri->stage = direct ? (void*)(direct_stage + out_bytes * (size_t)k) : (void*)((char*)h_ring + ring_bytes * (size_t)k);
             ri->slot_mask = ring - 1;
             ri->slice_bytes = (int64_t)(((step_bytes + (size_t)interval - 1) / (size_t)interval + 15) / 16 * 16) | (direct ? 1 : 0);
@@ -1337,7 +1260,7 @@ public:
         a.use_ctl_save = 0;
         a.partials = nullptr;
         a.direct_save_slot = save_slot;
-        half_fn(a, grid_blocks(), stream);
+        half_fn(a, plan.grid_blocks_for(shard_count), stream);
         HIP_TRY(hipGetLastError());
         half_steps += 1;
         if (color == 1) steps_since_reset += 1;
@@ -1384,18 +1307,51 @@ private:
         return fail(MCMCPP_HIP_E_HIP, "%s failed: %s", what, hipGetErrorString(e));
     }
 
+    // An odd number of full steps leaves the ensemble in the second buffer: bring it (and the control record) home, so
+    // that everything outside run() only ever knows the first
+    int bring_ensemble_home()
+    {
+        if (!full_fn || !(run_step & 1)) return MCMCPP_HIP_OK;
+        HIP_TRY(hipMemcpyAsync(d_pos, d_pos_alt, sizeof(T) * (size_t)W * D * K, hipMemcpyDeviceToDevice, stream));
+        for (int k = 0; k < K; ++k)
+        {
+            HIP_TRY(hipMemcpyAsync(logp_of(k), logp_of(k) + W, sizeof(T) * (size_t)W, hipMemcpyDeviceToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(ctl_of(k), ctl_of(k) + 1, sizeof(StepCtl), hipMemcpyDeviceToDevice, stream));
+        }
+        return MCMCPP_HIP_OK;
+    }
+
+    // d_snap <- everything a repeated chunk of a split run must find as this one found it (cur_pos, cur_logp: the buffers
+    // that hold the ensemble now)
+    int snapshot(const T* cur_pos, const T* cur_logp)
+    {
+        HIP_TRY(hipMemcpyAsync(d_snap, cur_pos, snap.logp, hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(d_snap + snap.logp, cur_logp, sizeof(T) * (size_t)W, hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(d_snap + snap.nacc, d_nacc, sizeof(uint32_t) * (size_t)W, hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(d_snap + snap.diag, d_diag, sizeof(Diag), hipMemcpyDeviceToDevice, stream));
+        return MCMCPP_HIP_OK;
+    }
+
+    // ... and back -- into both buffers, so that the repeated chunk may start at buffer 0 like a run does
+    int rollback()
+    {
+        HIP_TRY(hipMemcpyAsync(d_pos, d_snap, snap.logp, hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(d_logp, d_snap + snap.logp, sizeof(T) * (size_t)W, hipMemcpyDeviceToDevice, stream));
+        if (full_fn)
+        {
+            HIP_TRY(hipMemcpyAsync(d_pos_alt, d_snap, snap.logp, hipMemcpyDeviceToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(d_logp + W, d_snap + snap.logp, sizeof(T) * (size_t)W, hipMemcpyDeviceToDevice, stream));
+        }
+        HIP_TRY(hipMemcpyAsync(d_nacc, d_snap + snap.nacc, sizeof(uint32_t) * (size_t)W, hipMemcpyDeviceToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(d_diag, d_snap + snap.diag, sizeof(Diag), hipMemcpyDeviceToDevice, stream));
+        return MCMCPP_HIP_OK;
+    }
+
     // RunInfo used outside run(): the chain bound for half_step_async (if any), no per-step counters
     int upload_idle_run_info()
     {
-        RunInfo ri;
+        RunInfo ri = idle_run_info();
         ri.chain = bound_chain;
-        ri.accepted_per_step = nullptr;
-        ri.interval = 1;
-        ri.chain_slot_base = 0;
-        ri.stage = nullptr;
-        ri.slot_mask = -1;
-        ri.slice_bytes = 0;
-        ri.step_bytes = 0;
         HIP_TRY(hipStreamSynchronize(stream));
         HIP_TRY(hipMemcpy(d_run, &ri, sizeof ri, hipMemcpyHostToDevice));
         run_info_idle = true;
@@ -1407,17 +1363,6 @@ private:
     uint32_t* nacc_of(int k) const { return reinterpret_cast<uint32_t*>(logp_of(k) + 2 * (size_t)W); }
     StepCtl* ctl_of(int k) const { return reinterpret_cast<StepCtl*>(reinterpret_cast<char*>(d_ctl) + (size_t)kCtlChainStride * (size_t)k); }
     RunInfo* run_of(int k) const { return reinterpret_cast<RunInfo*>(reinterpret_cast<char*>(d_run) + (size_t)kCtlChainStride * (size_t)k); }
-
-    unsigned grid_blocks() const { return grid_blocks_for(shard_count); }
-    unsigned grid_blocks_for(int count) const
-    {
-        const long per_wave = (long)(64 / step_lpw) * passes;
-        const long waves = (count + per_wave - 1) / per_wave;
-        return (unsigned)((waves + kWavesPerBlock - 1) / kWavesPerBlock);
-    }
-
-    unsigned full_grid_blocks() const { return full_grid_blocks_for(shard_count); }
-    unsigned full_grid_blocks_for(int count) const { return (unsigned)((count + full_wpb - 1) / full_wpb); }
 
     HalfStepArgs<T> make_args(int color, int parity) const
     {
@@ -1444,10 +1389,10 @@ private:
         a.color = color;
         a.shard_begin = shard_begin;
         a.shard_count = shard_count;
-        a.passes = passes;
+        a.passes = plan.passes;
         a.partials = d_partials;
-        a.partial_slots = partial_slots;
-        a.partial_waves = partial_waves;
+        a.partial_slots = plan.partial_slots;
+        a.partial_waves = plan.partial_waves;
         a.draw_parity = 0;
         a.pos_alt = d_pos_alt;
         a.logp_alt = d_logp + W;
@@ -1455,8 +1400,7 @@ private:
         a.calc_params_padded = d_params_padded;
         a.chains = K;
         a.params_chain_stride = chain_params_stride;
-        // a fifth wavefront per workgroup computes the next draws when that is at most two rounds of 64 draws
-        a.draw_wave = (3 * kWavesPerBlock * (64 / step_lpw) * passes <= 128 && knobs.no_draw_wave == 0) ? 1 : 0;
+        a.draw_wave = plan.half_draw_wave;
         return a;
     }
 
@@ -1478,7 +1422,7 @@ private:
             c->step_in_run = step_in_run;
             c->chain_slot = (long long)(step_in_run / (uint64_t)interval);
             c->save_phase = (uint32_t)(step_in_run % (uint64_t)interval);
-            c->partial_slot = (uint32_t)(step_in_run % (uint64_t)partial_slots);
+            c->partial_slot = (uint32_t)(step_in_run % (uint64_t)plan.partial_slots);
             HIP_TRY(hipMemcpyAsync(ctl_of(k) + (half_steps & 1), c, sizeof(StepCtl), hipMemcpyHostToDevice, stream));
             if (refill)
             {
@@ -1511,23 +1455,21 @@ private:
             a.pos_parity = pos_parity;
             a.ctl_in = d_ctl + pos_parity;
             a.ctl_out = d_ctl + (1 - pos_parity);
-            a.partial_waves = partial_waves;
-            // the next draws by four extra wavefronts (two per colour) when that is one round of 64 draws each
-            a.draw_wave = (3 * ((full_wpb + 1) / 2) <= 64 && knobs.no_draw_wave == 0) ? 1 : 0;
+            a.draw_wave = plan.full_draw_wave;
             if (batch_slot >= 0)
             {
                 a.draw_wave = 2;
                 a.draw_parity = 0;
                 a.draws = d_draws_batch + (size_t)batch_slot * 2 * (size_t)n;
             }
-            full_fn(a, full_grid_blocks_for(a.shard_count), stream);
+            full_fn(a, plan.full_grid_blocks_for(a.shard_count), stream);
             a.draws = d_draws;
             return;
         }
         args_red.draw_parity = parity;
         args_blk.draw_parity = parity;
-        half_fn(args_red, grid_blocks_for(args_red.shard_count), stream);
-        half_fn(args_blk, grid_blocks_for(args_blk.shard_count), stream);
+        half_fn(args_red, plan.grid_blocks_for(args_red.shard_count), stream);
+        half_fn(args_blk, plan.grid_blocks_for(args_blk.shard_count), stream);
     }
 
     // the draw records of `count` ensemble steps from the one that reads position buffer pos_parity on (its control
@@ -1544,10 +1486,10 @@ private:
     {
         for (int s = 0; s < steps; ++s)
         {
-            if (batch_draws > 0)
+            if (plan.batch_draws > 0)
             {
-                if (s % batch_draws == 0) fill_batch((pos_parity + s) & 1, steps - s < batch_draws ? steps - s : batch_draws);
-                enqueue_step(0, (pos_parity + s) & 1, s % batch_draws);
+                if (s % plan.batch_draws == 0) fill_batch((pos_parity + s) & 1, steps - s < plan.batch_draws ? steps - s : plan.batch_draws);
+                enqueue_step(0, (pos_parity + s) & 1, s % plan.batch_draws);
             }
             else
                 enqueue_step((start_parity + s) & 1, (pos_parity + s) & 1);
@@ -1566,7 +1508,7 @@ private:
             hipGraph_t g = nullptr;
             HIP_TRY(hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed));
             enqueue_step_sequence(steps, start_parity, pos_parity);
-            launch_accepted_reduce(d_partials, partial_slots, partial_waves, steps, ctl_after(pos_parity + steps), d_run, stream, K);
+            launch_accepted_reduce(d_partials, plan.partial_slots, plan.partial_waves, steps, ctl_after(pos_parity + steps), d_run, stream, K);
             HIP_TRY(hipStreamEndCapture(stream, &g));
             HIP_TRY(hipGraphInstantiate(graph_cache[key].replace(), g, nullptr, nullptr, 0));
             HIP_TRY(hipGraphDestroy(g));
@@ -1577,9 +1519,9 @@ private:
 
     int ensure_graphs()
     {
-        if (graph_steps < 1) return MCMCPP_HIP_OK;
+        if (plan.graph_steps < 1) return MCMCPP_HIP_OK;
         hipGraphExec_t ex;
-        return graph_for(graph_steps, (int)(enq_step & 1), 0, &ex);
+        return graph_for(plan.graph_steps, (int)(enq_step & 1), 0, &ex);
     }
 
     // the control record the last launch of a step sequence leaves behind: the half-step pair always ends in [0],
@@ -1591,17 +1533,17 @@ private:
     {
         // enq_step: ensemble steps enqueued since set_state/seek (its low bit selects the record buffer)
         int64_t left = steps;
-        if (graph_steps >= 1)
+        if (plan.graph_steps >= 1)
         {
             hipGraphExec_t ex = nullptr;
-            while (left >= graph_steps)
+            while (left >= plan.graph_steps)
             {
-                int rc = graph_for(graph_steps, (int)(enq_step & 1), (int)(run_step & 1), &ex);
+                int rc = graph_for(plan.graph_steps, (int)(enq_step & 1), (int)(run_step & 1), &ex);
                 if (rc) return rc;
                 HIP_TRY(hipGraphLaunch(ex, stream));
-                left -= graph_steps;
-                enq_step += (uint64_t)graph_steps;
-                run_step += (uint64_t)graph_steps;
+                left -= plan.graph_steps;
+                enq_step += (uint64_t)plan.graph_steps;
+                run_step += (uint64_t)plan.graph_steps;
             }
             if (left > 0)
             {
@@ -1618,7 +1560,7 @@ private:
             for (; left > 0; --left)
             {
                 enqueue_step_sequence(1, (int)(enq_step & 1), (int)(run_step & 1));
-                launch_accepted_reduce(d_partials, partial_slots, partial_waves, 1, ctl_after((int64_t)run_step + 1), d_run, stream, K);
+                launch_accepted_reduce(d_partials, plan.partial_slots, plan.partial_waves, 1, ctl_after((int64_t)run_step + 1), d_run, stream, K);
                 enq_step += 1;
                 run_step += 1;
             }
@@ -1656,19 +1598,19 @@ private:
     DeviceBuffer<char> d_xblocks;     // [comm_world][block]: this rank's block and, behind the all-gather, everybody's
     DeviceBuffer<uint32_t> d_seen;    // [W]: a walker's accepted counter as of the last exchange (own slice)
     DeviceBuffer<XStats> d_xstats;
-    DeviceBuffer<char> d_snap;        // positions, log-posteriors, counters, diagnostics in front of the chunk in hand
+    DeviceBuffer<char> d_snap;        // positions | log-posteriors | counters | diagnostics in front of the chunk in hand
+    struct { size_t logp, nacc, diag; } snap = {};  // byte offsets into d_snap (the positions are at 0)
     uint32_t xcap_learned = 0;        // the slot bound the last run ended with
     PinnedBuffer<char> h_split_stage; // split ensembles: pinned staging of stored steps
     std::vector<Event> ev_x;          // split ensembles: events around a sample of exchanges
     const LaunchTable<T>* table = nullptr;
+    StepPlan plan;  // which kernels step this handle, their launch geometry and what follows from it (step_plan.hpp)
     typename LaunchTable<T>::HalfStepFn half_fn = nullptr;
     typename LaunchTable<T>::HalfStepFn full_fn = nullptr;  // non-null: run() steps with one launch per ensemble step
-    int full_wpb = 1;                                       // walkers of each colour per full-step workgroup
     T* d_pos_alt = nullptr;
     uint64_t run_step = 0;                                  // ensemble steps enqueued in the current run()
     typename LaunchTable<T>::CalcFn calc_fn = nullptr;
-    int step_lpw = 1, passes = 1, num_cus = 256;
-    int shard_begin = 0, shard_count = 0, graph_steps = 32;
+    int shard_begin = 0, shard_count = 0;
     size_t chain_subchunk_bytes = 0;
     Event ev_copied[2];
     DeviceBuffer<char> arena;  // one device allocation holding everything a step launch touches (see carve)
@@ -1689,11 +1631,8 @@ private:
     DrawRec<T>* d_draws = nullptr;
     DeviceBuffer<DrawRec<T>> d_draws_batch;  // [batch_draws][2][n]: records made ahead of the matrix-core full-step launches
     DeviceBuffer<Affine128> d_step_jump;     // [batch_draws]
-    int batch_draws = 0;                  // 0: the step launches make their own next records
     uint32_t* d_partials = nullptr;
-    int partial_slots = 1, partial_waves = 0;
     Affine128 *d_jump_lo = nullptr, *d_jump_hi = nullptr, *d_task_jump = nullptr;  // behind d_draws: see JumpTables
-    bool have_task_table = false;
     // which ensemble step the draw records on the device belong to, if known, and whether the black ones carry partner2
     bool records_valid = false, records_partner2 = false, run_info_idle = false;
     uint64_t records_step = 0;

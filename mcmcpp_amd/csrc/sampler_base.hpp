@@ -10,15 +10,14 @@
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <mutex>
-#include <optional>
 #include <string>
 #include <thread>
 #include <utility>
 
 #include "../../include/mcmcpp_hip.h"
+#include "step_plan.hpp"
 
 struct mcmcpp_hip_sampler
 {
@@ -225,18 +224,6 @@ private:
 using Event = HipHandle<hipEvent_t, hipEventDestroy>;
 using GraphExec = HipHandle<hipGraphExec_t, hipGraphExecDestroy>;
 
-inline int pow2_at_least(int v)
-{
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-inline int ilog2(int v)
-{
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
 inline Affine128 compose(const Affine128& g, const Affine128& f)  // g after f
 {
     Affine128 r;
@@ -281,70 +268,6 @@ inline int open_gfx950_device(int requested, int* device, hipDeviceProp_t* prop,
     *device = d;
     return MCMCPP_HIP_OK;
 }
-
-inline std::optional<long> env_long(const char* name)
-{
-    const char* v = std::getenv(name);
-    if (v && *v) return std::strtol(v, nullptr, 10);
-    return std::nullopt;
-}
-inline long env_long(const char* name, long fallback) { return env_long(name).value_or(fallback); }
-
-// The library's tuning knobs (environment variables, DESIGN.md section 9 lists them).  Read ONCE, when a handle is
-// created; nothing on the launch path touches the environment.  Negative "unset" values mean "library default"; a knob
-// whose default differs between the movers is left empty when unset (-1 is one of its values).
-struct Knobs
-{
-    long passes;                  // MCMCPP_HIP_PASSES                   walkers-per-wavefront rounds of the half-step kernels (0: chosen from the size)
-    long waves_per_simd;          // MCMCPP_HIP_WAVES_PER_SIMD           wavefronts per SIMD to reach before a wavefront takes more walkers (2)
-    long matrix_core_min_walkers; // MCMCPP_HIP_MATRIX_CORE_MIN_WALKERS  smallest shard stepped by the matrix-core kernels (0; -1: never)
-    std::optional<long> matrix_core_4pass;  // MCMCPP_HIP_MATRIX_CORE_4PASS_WALKERS from this many updates per launch on: 16 walkers per wavefront
-                                            //                                      (stretch 18432, differential evolution 32768)
-    long matrix_core_late;        // MCMCPP_HIP_MATRIX_CORE_LATE_DRAWS    from this many updates per launch on: the 16-walker wavefronts make their next draws behind the accept, four to a SIMD (49152; -1: never)
-    long full_step;               // MCMCPP_HIP_FULL_STEP                1: one launch per ensemble step for small ensembles (1)
-    long full_step_max_walkers;   // MCMCPP_HIP_FULL_STEP_MAX_WALKERS    largest ensemble stepped that way (-1: 32768; 32767 where the matrix-core
-                                  //                                     half-step kernel is the alternative)
-    long task_table_mb;           // MCMCPP_HIP_TASK_TABLE_MB            size limit of the one-entry-per-draw jump table (16)
-    long chain_subchunk_mb;       // MCMCPP_HIP_CHAIN_SUBCHUNK_MB        device chain staging per sub-chunk / ring budget (32)
-    long graph_steps;             // MCMCPP_HIP_GRAPH_STEPS              ensemble steps per hipGraph replay (-1 here: 300 up to 32768 walkers, else 128)
-    long trickle;                 // MCMCPP_HIP_TRICKLE                  1: stored steps forwarded to pinned memory by the launches (1)
-    long no_draw_wave;            // MCMCPP_HIP_NO_DRAW_WAVE             1: no extra draw wavefronts (0)
-    long batch_draws;             // MCMCPP_HIP_BATCH_DRAWS              ensemble steps whose draw records one launch makes ahead of the matrix-core full-step launches; 0: the launches make them themselves; -1: as many as a graph replays (-1)
-    long pinned_direct;           // MCMCPP_HIP_PINNED_DIRECT            1: stored steps forwarded straight into a pinned chain_out (1)
-    long comm_full_step;          // MCMCPP_HIP_COMM_FULL_STEP           split ensembles: 1 = one exchange per ensemble step (1), 0 = one per half-step
-    long comm_compact;            // MCMCPP_HIP_COMM_COMPACT             split ensembles of more than one rank: 1 = exchange only the rows that moved (1), 0 = all-gather the slices
-    long comm_compact_cap;        // MCMCPP_HIP_COMM_COMPACT_CAP         slots of an exchange block (0: learned from the run; a bound that is too small costs
-                                  //                                     a repeated chunk, never a wrong chain)
-    long comm_compact_chunk;      // MCMCPP_HIP_COMM_COMPACT_CHUNK       ensemble steps between two looks at the overflow flag (256)
-    std::optional<long> de_scan_run;  // MCMCPP_HIP_DE_SCAN_RUN          differential evolution: stream positions one scanning lane steps through (kDeScanRun)
-    std::optional<long> de_batch;     // MCMCPP_HIP_DE_BATCH             differential evolution: half-steps planned together (kDeBatchMax)
-    static Knobs from_environment()
-    {
-        Knobs k;
-        k.passes = env_long("MCMCPP_HIP_PASSES", 0);
-        k.waves_per_simd = env_long("MCMCPP_HIP_WAVES_PER_SIMD", 2);
-        k.matrix_core_min_walkers = env_long("MCMCPP_HIP_MATRIX_CORE_MIN_WALKERS", 0);
-        k.matrix_core_4pass = env_long("MCMCPP_HIP_MATRIX_CORE_4PASS_WALKERS");
-        k.matrix_core_late = env_long("MCMCPP_HIP_MATRIX_CORE_LATE_DRAWS", 49152);
-        k.full_step = env_long("MCMCPP_HIP_FULL_STEP", 1);
-        k.full_step_max_walkers = env_long("MCMCPP_HIP_FULL_STEP_MAX_WALKERS", -1);
-        k.task_table_mb = env_long("MCMCPP_HIP_TASK_TABLE_MB", 16);
-        k.chain_subchunk_mb = env_long("MCMCPP_HIP_CHAIN_SUBCHUNK_MB", 32);
-        k.graph_steps = env_long("MCMCPP_HIP_GRAPH_STEPS", -1);
-        k.trickle = env_long("MCMCPP_HIP_TRICKLE", 1);
-        k.no_draw_wave = env_long("MCMCPP_HIP_NO_DRAW_WAVE", 0);
-        k.batch_draws = env_long("MCMCPP_HIP_BATCH_DRAWS", -1);
-        k.pinned_direct = env_long("MCMCPP_HIP_PINNED_DIRECT", 1);
-        k.comm_full_step = env_long("MCMCPP_HIP_COMM_FULL_STEP", 1);
-        k.comm_compact = env_long("MCMCPP_HIP_COMM_COMPACT", 1);
-        k.comm_compact_cap = env_long("MCMCPP_HIP_COMM_COMPACT_CAP", 0);
-        k.comm_compact_chunk = env_long("MCMCPP_HIP_COMM_COMPACT_CHUNK", 256);
-        if (k.comm_compact_chunk < 1) k.comm_compact_chunk = 1;
-        k.de_scan_run = env_long("MCMCPP_HIP_DE_SCAN_RUN");
-        k.de_batch = env_long("MCMCPP_HIP_DE_BATCH");
-        return k;
-    }
-};
 
 // launch table (LaunchTable<double> / LaunchTable<float>) of a built-in or registered calculator, or nullptr
 const void* launch_table_lookup(int dtype, int calc_id);

@@ -104,6 +104,16 @@ HalfStepArgs<T> stretch_args(const mcmcpp_hip_config& cfg, int vec_ok, U128 inc,
     return a;
 }
 
+// The run record of a handle that is not inside run(): no chain, no per-step counters, nothing forwarded.  A run starts
+// from it and sets what differs.
+inline RunInfo idle_run_info()
+{
+    RunInfo ri = {};
+    ri.interval = 1;
+    ri.slot_mask = -1;  // (slots are not reused; stage nullptr and slice_bytes 0: no forwarding)
+    return ri;
+}
+
 // Stored steps per sub-chunk of a run: what `budget` bytes of device chain hold, at most an eighth of the run (the last
 // host copy, which nothing overlaps, stays short, and a run_async caller sees progress), at least one
 inline int64_t stored_steps_per_subchunk(size_t budget, size_t stored_step_bytes, int64_t n_saved)
@@ -172,11 +182,10 @@ protected:
         W = c.num_walkers;
         D = c.num_params;
         n = W / 2;
-        const int base = Vec16<T>::N;
-        const int n2 = pow2_at_least(D > base ? D : base);
-        lpw = n2 / base < 64 ? n2 / base : 64;
-        epl = n2 / lpw;
-        vec_ok = (D % base == 0) ? 1 : 0;
+        const LaneMap m = lane_map(D, (int)sizeof(T));
+        lpw = m.lpw;
+        epl = m.epl;
+        vec_ok = m.vec_ok;
     }
 
     int open_device(const mcmcpp_hip_config& c, hipDeviceProp_t* prop)

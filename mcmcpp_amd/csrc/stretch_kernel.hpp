@@ -32,6 +32,7 @@
 #include "calculators.hpp"
 #include "fast_log.hpp"
 #include "pcg128.hpp"
+#include "step_plan.hpp"  // kWavesPerBlock: updating wavefronts per workgroup
 
 namespace mcmcpp
 {
@@ -350,8 +351,6 @@ __device__ __forceinline__ double dev_log(double x) { return fast_log(x); }
 __device__ __forceinline__ float dev_log(float x) { return logf(x); }
 __device__ __forceinline__ double dev_abs(double x) { return fabs(x); }
 __device__ __forceinline__ float dev_abs(float x) { return fabsf(x); }
-
-constexpr int kWavesPerBlock = 4;  // updating wavefronts per workgroup
 
 // dynamic LDS of one workgroup: [proposal stage (if the calculator wants it)][calculator tables]
 template <class T, class Calc, int EPL>
