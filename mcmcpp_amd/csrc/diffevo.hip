@@ -173,7 +173,7 @@ public:
         args.gamma = gamma;
         args.jitter_width = (T)2.0e-4;  // DifferentialEvolution.h:120-121
         args.jitter_low = (T)-1.0e-4;
-        args.tie_eps = sizeof(T) == 8 ? (T)1e-12 : (T)6e-7;
+        args.tie_eps = accept_tie_eps<T>();
         args.partial_waves = partial_waves;
         return MCMCPP_HIP_OK;
     }

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "canonical.hpp"  // raw 64-bit output -> uniform variate in [0, 1)
+
 namespace mcmcpp
 {
 
@@ -99,26 +101,6 @@ inline Affine128 pcg_jump(U128 inc, unsigned __int128 delta)
         delta >>= 1;
     }
     return acc;
-}
-
-// libstdc++ generate_canonical<T>(pcg64): T(r) rounded to nearest, divided by 2^64, clamped below 1
-// (bits/random.tcc:3345-3380; MultiSampler.h:60,86 through uniform_real / exponential distributions)
-__device__ __forceinline__ double canonical(uint64_t r, double)
-{
-    // u64 -> f64 round-to-nearest-even: hi*2^32 is exact, lo is exact, one rounded add
-    const double hi = (double)(uint32_t)(r >> 32);
-    const double lo = (double)(uint32_t)r;
-    double u = __builtin_fma(hi, 4294967296.0, lo) * 5.42101086242752217003726400434970855712890625e-20;
-    // fma(hi, 2^32, lo) rounds once (the product is exact), as the conversion instruction would
-    if (u >= 1.0) u = 0.99999999999999988897769753748434595763683319091796875;
-    return u;
-}
-
-__device__ __forceinline__ float canonical(uint64_t r, float)
-{
-    float u = (float)r * 5.42101086242752217003726400434970855712890625e-20f;
-    if (u >= 1.0f) u = 0.999999940395355224609375f;
-    return u;
 }
 
 }  // namespace mcmcpp

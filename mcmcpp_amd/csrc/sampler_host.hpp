@@ -14,6 +14,7 @@
 
 #include "launch_table.hpp"
 #include "sampler_base.hpp"
+#include "tie_eps.h"
 
 namespace mcmcpp
 {
@@ -74,6 +75,13 @@ CalcParams<T> calc_params_host(const mcmcpp_hip_config& c, bool padded)
     return r;
 }
 
+// The near-tie band of the accept test in the element type (tie_eps.h: the oracle reads the same two numbers)
+template <class T>
+inline T accept_tie_eps()
+{
+    return sizeof(T) == 8 ? (T)MCMCPP_TIE_EPS_F64 : (T)MCMCPP_TIE_EPS_F32;
+}
+
 // The fields of the stretch move's HalfStepArgs that follow from the configuration and the stream alone; the mover fills in
 // its buffers, the colour and its launch geometry.  One definition for the fused and the batch path: the same constants
 // are what makes their chains the same.
@@ -94,7 +102,7 @@ HalfStepArgs<T> stretch_args(const mcmcpp_hip_config& cfg, int vec_ok, U128 inc,
     a.gw_term1 = sqrt_a - inv_sqrt_a;
     a.gw_inv_sqrt = inv_sqrt_a;
     a.dims_minus_one = (T)(D - 1);
-    a.tie_eps = sizeof(T) == 8 ? (T)1e-12 : (T)6e-7;
+    a.tie_eps = accept_tie_eps<T>();
     a.n = n;
     a.n_is_pow2 = (n & (n - 1)) == 0;
     a.dims = D;

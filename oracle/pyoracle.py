@@ -42,7 +42,7 @@ def build(force=False):
     so = os.path.join(_HERE, "liboracle.so")
     if force or not os.path.exists(so) or any(
             os.path.getmtime(os.path.join(_HERE, f)) > os.path.getmtime(so)
-            for f in ("stretch_oracle.c", "stretch_oracle_typed.inc", "stretch_oracle.h")):
+            for f in ("stretch_oracle.c", "stretch_oracle_typed.inc", "stretch_oracle.h", "../mcmcpp_amd/csrc/tie_eps.h")):
         subprocess.check_call(["make", "-C", _HERE, "liboracle.so"], stdout=subprocess.DEVNULL)
     if os.path.exists("/root/reference/MCMCpp/EnsembleSampler.h"):
         for name in ("libmcmcpp_ref.so", "libmcmcpp_ref_o3.so"):
@@ -70,6 +70,8 @@ def lib():
         for f in ("so_half_steps_done", "so_near_ties", "so_redraws"):
             getattr(L, f).argtypes = [C.c_void_p]
             getattr(L, f).restype = C.c_uint64
+        L.so_tie_eps.argtypes = [C.c_int32]
+        L.so_tie_eps.restype = C.c_double
         L.so_seek.argtypes = [C.c_void_p, C.c_uint64]
         L.so_last_near_tie.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                        C.POINTER(C.c_double)]
@@ -135,6 +137,11 @@ def jump_coeffs(inc, delta):
     M = 2**64 - 1
     lib().so_pcg64_jump_coeffs((inc >> 64) & M, inc & M, (delta >> 64) & M, delta & M, C.byref(m), C.byref(p))
     return (m[0] << 64) | m[1], (p[0] << 64) | p[1]
+
+
+def tie_eps(dtype):
+    """The oracle's near-tie band in element type dtype."""
+    return lib().so_tie_eps(dtype)
 
 
 def init_positions(dtype, W, D, salt=0):

@@ -7,6 +7,8 @@
 #define _GNU_SOURCE /* sincos, sincosf */
 #include "stretch_oracle.h"
 
+#include "../mcmcpp_amd/csrc/tie_eps.h" /* the near-tie band: one definition with the device library */
+
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -155,7 +157,7 @@ struct so_sampler {
 #define FMA(a, b, c) fma(a, b, c)
 #define FABS(x) fabs(x)
 #define CANON(r) so_canonical_f64(r)
-#define TIE_EPS 1e-12
+#define TIE_EPS MCMCPP_TIE_EPS_F64
 #include "stretch_oracle_typed.inc"
 #undef REAL
 #undef SFX
@@ -175,7 +177,7 @@ struct so_sampler {
 #define FMA(a, b, c) fmaf(a, b, c)
 #define FABS(x) fabsf(x)
 #define CANON(r) so_canonical_f32(r)
-#define TIE_EPS 6e-7f
+#define TIE_EPS MCMCPP_TIE_EPS_F32
 #include "stretch_oracle_typed.inc"
 #undef REAL
 #undef SFX
@@ -332,6 +334,8 @@ int so_last_near_tie(const so_sampler* s, uint64_t* half_step, uint32_t* walker,
     return 0;
 }
 uint64_t so_redraws(const so_sampler* s) { return s ? s->redraws : 0; }
+
+double so_tie_eps(int32_t dtype) { return dtype == SO_F64 ? (double)MCMCPP_TIE_EPS_F64 : (double)(float)MCMCPP_TIE_EPS_F32; }
 
 int so_chain_covariance(int32_t dtype, const void* steps, int64_t n_steps, int32_t walkers, int32_t dims, int32_t slice,
                         void* mean, void* cov, void* corr)

@@ -106,6 +106,8 @@ int so_last_near_tie(const so_sampler* s, uint64_t* half_step, uint32_t* walker,
 int so_seek(so_sampler* s, uint64_t ensemble_steps_done);
 /* bounded_rand rejections (only possible when W/2 is not a power of two) */
 uint64_t so_redraws(const so_sampler* s);
+/* the near-tie band of the accept test in element type `dtype` (mcmcpp_amd/csrc/tie_eps.h) */
+double so_tie_eps(int32_t dtype);
 
 /* evaluate a calculator on one D-vector (used to build initial logp arrays in tests and bench) */
 int so_calc_logp(const so_config* cfg, const void* x, void* out);
