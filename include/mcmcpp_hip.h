@@ -228,7 +228,13 @@ int mcmcpp_hip_reset_counters(mcmcpp_hip_sampler* h);
 /* getAcceptedSteps / getTotalSteps material (EnsembleSampler.h:260-282), plus two parity diagnostics:
  *   accepted        sum of n_accept over the walkers this handle updates
  *   ensemble_steps  ensemble steps executed since set_state / reset_counters
- *   near_ties       accept decisions whose margin was within a few ulp (could flip under another libm log)
+ *   near_ties       accept decisions whose margin was within a few ulp (could flip under another libm log).
+ *                   The rule: |ln U - delta| <= tie_eps * (|ln U| + |(D-1) ln z| + |logp_new| + |logp_old|) AND the
+ *                   margin |ln U - delta| is finite, that is, every operand of the accept test is finite.  A
+ *                   proposal outside the support (logp_new = -inf), a walker that still sits outside it
+ *                   (logp_old = -inf) and +inf on either side are decided by the comparison alone, which no
+ *                   rounding of a logarithm can flip: they are not counted.  Neither is a decision with a NaN
+ *                   operand (the first comparison is false).
  *   redraws         pcg bounded_rand rejections met (only possible when W/2 is not a power of two; the
  *                   reference would have consumed one more draw there, so trajectories part)
  * Any pointer may be NULL. */

@@ -119,7 +119,7 @@ __global__ void __launch_bounds__(kBatchThreads) stretch_accept_kernel(const Hal
     {
         const T margin = dev_abs(ln_u - delta);
         const T scale = dev_abs(ln_u) + dev_abs(zs) + dev_abs(lp_new) + dev_abs(lp_old);
-        if (margin <= a.tie_eps * scale) count_near_tie(a.diag);
+        if (near_tie(margin, a.tie_eps * scale)) count_near_tie(a.diag);
     }
     if (accept)
     {

@@ -261,7 +261,7 @@ stretch_full_step_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b, T* h
         {
             const T margin = dev_abs(rec.ln_u - delta);
             const T scale = dev_abs(rec.ln_u) + dev_abs(rec.zs) + dev_abs(lp_new) + dev_abs(lp_old);
-            if (margin <= a.tie_eps * scale) count_near_tie(a.diag);
+            if (near_tie(margin, a.tie_eps * scale)) count_near_tie(a.diag);
         }
 #pragma unroll
         for (int e = 0; e < EPL; ++e) fin[e] = accept ? prop[e] : own[e];
@@ -506,7 +506,7 @@ stretch_full_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b,
         {
             const T margin = dev_abs(rec.ln_u - delta);
             const T scale = dev_abs(rec.ln_u) + dev_abs(rec.zs) + dev_abs(lp_new) + dev_abs(lp_old);
-            if (margin <= a.tie_eps * scale) count_near_tie(a.diag);
+            if (near_tie(margin, a.tie_eps * scale)) count_near_tie(a.diag);
         }
         fin[0] = accept ? prop[0] : own[0];
         fin[1] = accept ? prop[1] : own[1];

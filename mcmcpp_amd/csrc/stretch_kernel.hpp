@@ -352,6 +352,15 @@ __device__ __forceinline__ float dev_log(float x) { return logf(x); }
 __device__ __forceinline__ double dev_abs(double x) { return fabs(x); }
 __device__ __forceinline__ float dev_abs(float x) { return fabsf(x); }
 
+// Is this accept decision a near tie (include/mcmcpp_hip.h: near_ties)?  Inside the band, and the margin finite: with an
+// infinite log-posterior on either side margin and band are both +inf, which no rounding of a logarithm can flip; a NaN
+// on either side fails the first comparison already.
+template <class T>
+__device__ __forceinline__ bool near_tie(T margin, T band)
+{
+    return margin <= band && margin < (T)__builtin_huge_val();
+}
+
 // dynamic LDS of one workgroup: [proposal stage (if the calculator wants it)][calculator tables]
 template <class T, class Calc, int EPL>
 struct LdsLayout
@@ -877,7 +886,7 @@ stretch_half_step_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, uint32_
         {
             const T margin = dev_abs(ln_u - delta);
             const T scale = dev_abs(ln_u) + dev_abs(zs) + dev_abs(lp_new) + dev_abs(lp_old);
-            if (margin <= a.tie_eps * scale) count_near_tie(a.diag);
+            if (near_tie(margin, a.tie_eps * scale)) count_near_tie(a.diag);
         }
         if (accept)
         {
@@ -1302,7 +1311,7 @@ stretch_half_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, ui
         {
             const T margin = dev_abs(ln_u - delta);
             const T scale = dev_abs(ln_u) + dev_abs(zs) + dev_abs(lp_new[q]) + dev_abs(lp_old[q]);
-            if (margin <= a.tie_eps * scale) count_near_tie(a.diag);
+            if (near_tie(margin, a.tie_eps * scale)) count_near_tie(a.diag);
         }
         if (accept)
         {

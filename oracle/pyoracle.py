@@ -17,6 +17,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 F64, F32 = 0, 1
 CALC_ISO_GAUSSIAN, CALC_DENSE_GAUSSIAN, CALC_ROSENBROCK, CALC_SKEWED_GAUSSIAN_2D = 0, 1, 2, 3
+# test target only (stretch_oracle.h): the isotropic Gaussian inside |x_j| <= half_width, `outside` elsewhere; params = [half_width, outside]
+CALC_BOXED_ISO_GAUSSIAN = 100
 MOVER_STRETCH, MOVER_DIFFERENTIAL_EVOLUTION = 0, 1
 MODE_SEQUENTIAL, MODE_COUNTER = 0, 1
 
@@ -70,6 +72,8 @@ def lib():
         for f in ("so_half_steps_done", "so_near_ties", "so_redraws"):
             getattr(L, f).argtypes = [C.c_void_p]
             getattr(L, f).restype = C.c_uint64
+        L.so_boxed_outside_evals.argtypes = []
+        L.so_boxed_outside_evals.restype = C.c_uint64
         L.so_tie_eps.argtypes = [C.c_int32]
         L.so_tie_eps.restype = C.c_double
         L.so_seek.argtypes = [C.c_void_p, C.c_uint64]
@@ -142,6 +146,11 @@ def jump_coeffs(inc, delta):
 def tie_eps(dtype):
     """The oracle's near-tie band in element type dtype."""
     return lib().so_tie_eps(dtype)
+
+
+def boxed_outside_evals():
+    """Evaluations of CALC_BOXED_ISO_GAUSSIAN that fell outside the box so far in this process (take differences)."""
+    return lib().so_boxed_outside_evals()
 
 
 def init_positions(dtype, W, D, salt=0):

@@ -11,6 +11,7 @@
  * calcLogPostProb(T*) is a legal reference Calculator) and with the reference's SkewedGaussianTwoDim.
  */
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <random>
@@ -35,6 +36,27 @@ using arrow_vendored::pcg64;
 
 namespace
 {
+/* Test target with a bounded support (oracle/stretch_oracle.h: SO_CALC_BOXED_ISO_GAUSSIAN = 100), as a reference
+ * Calculator: IsoGaussian's value -- its own calcLogPostProb, hence its bits -- where every |x_j| <= halfWidth, and
+ * `outside` verbatim elsewhere (a NaN coordinate fails the comparison, so it is outside). */
+template <class T>
+class BoxedIsoGaussian
+{
+public:
+    BoxedIsoGaussian(int numParams, T halfWidthIn, T outsideIn) : dims(numParams), halfWidth(halfWidthIn), outside(outsideIn), inner(numParams) {}
+    T calcLogPostProb(T* paramSet)
+    {
+        for (int j = 0; j < dims; ++j)
+            if (!(std::fabs(paramSet[j]) <= halfWidth)) return outside;
+        return inner.calcLogPostProb(paramSet);
+    }
+
+private:
+    int dims;
+    T halfWidth, outside;
+    MCMC::Device::IsoGaussian<T> inner;
+};
+
 template <class T, class MoverType>
 int runMover(MoverType& mover, int W, int D, int seed, const T* initPos, const T* initLogp, int nCalls,
              int stepsPerCall, int slicing, T* chainOut, long long chainCapacitySteps,
@@ -161,6 +183,11 @@ int dispatch(int calcId, int threads, int alphaCode, int W, int D, const T* para
     case MCMC::Device::SkewedGaussian2DId:
     {
         SkewedGaussianTwoDim<T> c(params[0]);  // the reference's own test Calculator
+        MCMCPP_REF_GO(c);
+    }
+    case 100:
+    {
+        BoxedIsoGaussian<T> c(D, params[0], params[1]);
         MCMCPP_REF_GO(c);
     }
     case 103:

@@ -149,6 +149,9 @@ struct so_sampler {
     double tie_ln_u, tie_delta;
 };
 
+/* evaluations of SO_CALC_BOXED_ISO_GAUSSIAN that fell outside the box, in this process (so_boxed_outside_evals) */
+static uint64_t boxed_outside_evals;
+
 #define REAL double
 #define SFX(n) n##_f64
 #define LOG(x) log(x)
@@ -208,6 +211,9 @@ static int check_cfg(const so_config* c)
         break;
     case SO_CALC_SKEWED_GAUSSIAN_2D:
         if (!c->calc_params || c->calc_params_len != 1 || c->num_params != 2) return -5;
+        break;
+    case SO_CALC_BOXED_ISO_GAUSSIAN:
+        if (!c->calc_params || c->calc_params_len != 2) return -5;
         break;
     default: return -6;
     }
@@ -334,6 +340,7 @@ int so_last_near_tie(const so_sampler* s, uint64_t* half_step, uint32_t* walker,
     return 0;
 }
 uint64_t so_redraws(const so_sampler* s) { return s ? s->redraws : 0; }
+uint64_t so_boxed_outside_evals(void) { return boxed_outside_evals; }
 
 double so_tie_eps(int32_t dtype) { return dtype == SO_F64 ? (double)MCMCPP_TIE_EPS_F64 : (double)(float)MCMCPP_TIE_EPS_F32; }
 

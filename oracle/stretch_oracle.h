@@ -40,7 +40,11 @@ enum {
     SO_CALC_ISO_GAUSSIAN = 0,   /* -1/2 sum x^2                       params: none                  */
     SO_CALC_DENSE_GAUSSIAN = 1, /* -1/2 x^T P x                       params: P[D*D] row-major      */
     SO_CALC_ROSENBROCK = 2,     /* -c sum b(x_{i+1}-x_i^2)^2+(a-x_i)^2 params: a, b, c               */
-    SO_CALC_SKEWED_GAUSSIAN_2D = 3 /* reference test target, D == 2   params: epsilon               */
+    SO_CALC_SKEWED_GAUSSIAN_2D = 3, /* reference test target, D == 2  params: epsilon               */
+    /* Test target only, not a MCMCPP_HIP_CALC_* id: the isotropic Gaussian's value (same operation order, same bits)
+     * where every |x_j| <= half_width, and `outside` verbatim elsewhere (-inf for a bounded prior; NaN and +inf to
+     * test how the accept comparison treats them).                   params: half_width, outside */
+    SO_CALC_BOXED_ISO_GAUSSIAN = 100
 };
 
 /* how the random stream is walked */
@@ -96,7 +100,12 @@ void* so_logp_ptr(so_sampler* s);
 int so_get_state(so_sampler* s, void* positions, void* logp, uint32_t* n_accept);
 
 uint64_t so_half_steps_done(const so_sampler* s);
-/* decisions whose margin |lnU - delta| was within a few ulp: a different libm `log` could flip them */
+/* decisions whose margin |lnU - delta| was within a few ulp: a different libm `log` could flip them.
+ * The rule: a decision is counted when margin <= tie_eps * (|lnU| + |(D-1) ln z| + |logp_new| + |logp_old|) AND the
+ * margin is finite, that is, when every operand of the accept test is finite.  A proposal outside the support
+ * (logp_new = -inf), a walker that starts there (logp_old = -inf) or +inf on either side make margin and band both
+ * +inf: no rounding of a logarithm can flip such a decision, so it is not counted.  A NaN on either side fails the
+ * first comparison and is not counted either.  The device library states the same rule (include/mcmcpp_hip.h). */
 uint64_t so_near_ties(const so_sampler* s);
 /* the most recent of them: the half-step (counted from set_state / so_seek's origin), the walker (0 .. W-1), the decision
  * taken and the two sides of the comparison; -1 when there has been none */
@@ -108,6 +117,10 @@ int so_seek(so_sampler* s, uint64_t ensemble_steps_done);
 uint64_t so_redraws(const so_sampler* s);
 /* the near-tie band of the accept test in element type `dtype` (mcmcpp_amd/csrc/tie_eps.h) */
 double so_tie_eps(int32_t dtype);
+
+/* SO_CALC_BOXED_ISO_GAUSSIAN: how many evaluations in this process (proposals and so_calc_logp calls alike) fell outside the
+ * box.  Tests take the difference around a run to know how many proposals left the support. */
+uint64_t so_boxed_outside_evals(void);
 
 /* evaluate a calculator on one D-vector (used to build initial logp arrays in tests and bench) */
 int so_calc_logp(const so_config* cfg, const void* x, void* out);

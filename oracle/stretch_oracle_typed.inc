@@ -57,8 +57,26 @@ static REAL SFX(calc_logp)(int calc_id, int D, const REAL* prm, const REAL* x)
         REAL t2 = x[0] / (REAL)2 + x[1];
         return (((t1 * t1) / eps) + (t2 * t2)) / (REAL)-2;
     }
+    case SO_CALC_BOXED_ISO_GAUSSIAN: {
+        /* test target with a bounded support: the isotropic Gaussian's bits inside the box, prm[1] verbatim outside.
+         * A NaN coordinate fails the comparison, so it is outside. */
+        for (int j = 0; j < D; ++j)
+            if (!(FABS(x[j]) <= prm[0])) {
+#pragma omp atomic
+                ++boxed_outside_evals;
+                return prm[1];
+            }
+        for (int j = 0; j < D; ++j) t[j] = x[j] * x[j];
+        return (REAL)-0.5 * SFX(tree_sum)(t, 0, n2, D);
+    }
     default: return (REAL)0;
     }
+}
+
+/* The near-tie rule (stretch_oracle.h: so_near_ties): inside the band, and the margin finite. */
+static int SFX(near_tie)(REAL margin, REAL band)
+{
+    return margin <= band && margin < (REAL)INFINITY;
 }
 
 /* One StretchMove::updateWalker (MCMCpp/Movers/StretchMove.h:100-123) given the three raw draws.
@@ -93,7 +111,7 @@ static int SFX(update_walker)(so_sampler* s, REAL* cur, REAL* cur_lp, const REAL
     {
         REAL margin = FABS(ln_u - delta);
         REAL scale = FABS(ln_u) + FABS(zs) + FABS(new_lp) + FABS(*cur_lp);
-        if (margin <= (REAL)TIE_EPS * scale) {
+        if (SFX(near_tie)(margin, (REAL)TIE_EPS * scale)) {
             ++*ties;
 #pragma omp critical(so_tie_record)
             {
@@ -225,7 +243,7 @@ static int SFX(de_update_walker)(so_sampler* s, REAL* cur, REAL* cur_lp, const R
     {
         REAL margin = FABS(neg_exp - delta);
         REAL scale = FABS(neg_exp) + FABS(new_lp) + FABS(*cur_lp);
-        if (margin <= (REAL)TIE_EPS * scale) ++*ties;
+        if (SFX(near_tie)(margin, (REAL)TIE_EPS * scale)) ++*ties;
     }
     if (accept) {
         memcpy(cur, prop, sizeof(REAL) * (size_t)D);

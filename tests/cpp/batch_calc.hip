@@ -1,5 +1,8 @@
 // batch_calc.hip -- batch log-posterior callbacks for tests/test_batch_calc.py (mcmcpp_hip_set_batch_calculator).
 //
+// Kind 4 is a target with a bounded support (params = {half_width, outside}): IsoGaussian's value where every
+// |x_j| <= half_width, `outside` verbatim elsewhere; it counts the rows it found outside (batch_calc_outside).
+//
 // The four built-in Calculators restated one thread per walker, in the operation order of their host twins
 // (include/MCMCpp/Device/Calculators.h): element terms combined by the canonical pairwise tree sum over +0 padding to a
 // power of two, every product and sum rounded on its own (built with -ffp-contract=off), fma exactly where the twin
@@ -15,7 +18,7 @@
 
 namespace
 {
-enum Kind { kIso = 0, kDense = 1, kRosenbrock = 2, kSkewed = 3 };
+enum Kind { kIso = 0, kDense = 1, kRosenbrock = 2, kSkewed = 3, kBoxedIso = 4 };
 
 struct Ctx
 {
@@ -24,6 +27,7 @@ struct Ctx
     int64_t calls;          // callbacks so far
     int64_t fail_at;        // >= 0: the call with this index returns fail_code
     int fail_code;
+    unsigned long long* d_outside;  // device counter: rows the boxed target found outside its box
 };
 
 // Pairwise tree sum of term(0) .. term(P2-1) (term(j) = +0 for j >= dims) without an array: a binary counter of partial
@@ -51,7 +55,8 @@ __device__ T tree_sum(int dims, Term term)
 }
 
 template <class T>
-__global__ void batch_logp_kernel(int kind, const T* __restrict__ x, T* __restrict__ out, long long count, int dims, const T* __restrict__ prm)
+__global__ void batch_logp_kernel(int kind, const T* __restrict__ x, T* __restrict__ out, long long count, int dims, const T* __restrict__ prm,
+                                  unsigned long long* outside)
 {
     const long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= count) return;
@@ -87,6 +92,22 @@ __global__ void batch_logp_kernel(int kind, const T* __restrict__ x, T* __restri
         const T scaled = s * prm[2];
         lp = -scaled;
     }
+    else if (kind == kBoxedIso)
+    {
+        bool inside = true;
+        for (int j = 0; j < dims; ++j)
+            if (!(r[j] <= prm[0] && r[j] >= -prm[0])) inside = false;  // (a NaN coordinate is outside)
+        if (inside)
+        {
+            const T s = tree_sum<T>(dims, [&](int j) { return r[j] * r[j]; });
+            lp = (T)(-0.5) * s;
+        }
+        else
+        {
+            lp = prm[1];
+            atomicAdd(outside, 1ULL);
+        }
+    }
     else
     {
         const T half = r[0] / (T)2;
@@ -102,7 +123,8 @@ __global__ void batch_logp_kernel(int kind, const T* __restrict__ x, T* __restri
 
 extern "C"
 {
-// kind: 0 IsoGaussian, 1 DenseGaussian (P[D*D] row-major), 2 Rosenbrock (a, b, c), 3 SkewedGaussian2D (eps)
+// kind: 0 IsoGaussian, 1 DenseGaussian (P[D*D] row-major), 2 Rosenbrock (a, b, c), 3 SkewedGaussian2D (eps),
+//       4 boxed IsoGaussian (half_width, outside)
 void* batch_calc_create(int kind, int dtype, int dims, const void* params, int n_params)
 {
     Ctx* c = new (std::nothrow) Ctx();
@@ -126,6 +148,14 @@ void* batch_calc_create(int kind, int dtype, int dims, const void* params, int n
         delete c;
         return nullptr;
     }
+    c->d_outside = nullptr;
+    if (hipMalloc(&c->d_outside, sizeof(unsigned long long)) != hipSuccess || hipMemset(c->d_outside, 0, sizeof(unsigned long long)) != hipSuccess)
+    {
+        (void)hipFree(c->d_outside);
+        (void)hipFree(c->d_params);
+        delete c;
+        return nullptr;
+    }
     return c;
 }
 
@@ -134,7 +164,17 @@ void batch_calc_destroy(void* user)
     Ctx* c = static_cast<Ctx*>(user);
     if (!c) return;
     (void)hipFree(c->d_params);
+    (void)hipFree(c->d_outside);
     delete c;
+}
+
+// rows the boxed target found outside its box so far (synchronises the device); -1 on error
+int64_t batch_calc_outside(void* user)
+{
+    Ctx* c = static_cast<Ctx*>(user);
+    unsigned long long v = 0;
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&v, c->d_outside, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return (int64_t)v;
 }
 
 // the call with index `call` (counted from now) returns `code` instead of evaluating anything
@@ -158,10 +198,10 @@ int batch_calc_logp(void* user, const void* proposals, void* logp_out, int64_t c
     const unsigned block = 256, grid = (unsigned)((count + block - 1) / block);
     if (c->dtype == 0)
         hipLaunchKernelGGL(batch_logp_kernel<double>, dim3(grid), dim3(block), 0, (hipStream_t)hip_stream, c->kind, (const double*)proposals,
-                           (double*)logp_out, (long long)count, (int)num_params, (const double*)c->d_params);
+                           (double*)logp_out, (long long)count, (int)num_params, (const double*)c->d_params, c->d_outside);
     else
         hipLaunchKernelGGL(batch_logp_kernel<float>, dim3(grid), dim3(block), 0, (hipStream_t)hip_stream, c->kind, (const float*)proposals,
-                           (float*)logp_out, (long long)count, (int)num_params, (const float*)c->d_params);
+                           (float*)logp_out, (long long)count, (int)num_params, (const float*)c->d_params, c->d_outside);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 }

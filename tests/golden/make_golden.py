@@ -77,6 +77,17 @@ CASES = {
                              alpha_code=2),
     "de_c2_16384x32": dict(W=16384, D=32, calc=po.CALC_DENSE_GAUSSIAN, dtype=po.F64, steps=10, keep=[], rho=0.5, mover=1, alpha_code=2,
                            digest=[1, 2, 10], sample_rows=[0, 1, 8191, 8192, 16383]),
+    # The bounded test target (oracle/stretch_oracle.h: SO_CALC_BOXED_ISO_GAUSSIAN, stated as a reference Calculator in
+    # oracle/ref_driver.cpp): params = [half_width, outside].  Start: tests/goldens.boxed_start (every fourth walker outside).
+    # With outside = +inf every walker leaves the box within a few steps and freezes there, hence the short run.
+    "boxed64x4": dict(W=64, D=4, calc=po.CALC_BOXED_ISO_GAUSSIAN, dtype=po.F64, steps=200, keep=[1, 2, 10, 200], boxed=(1.25, -np.inf)),
+    "boxed64x4_f32": dict(W=64, D=4, calc=po.CALC_BOXED_ISO_GAUSSIAN, dtype=po.F32, steps=200, keep=[1, 2, 10, 200], boxed=(1.25, -np.inf)),
+    "boxed64x4_nan": dict(W=64, D=4, calc=po.CALC_BOXED_ISO_GAUSSIAN, dtype=po.F64, steps=200, keep=[1, 2, 10, 200], boxed=(1.25, np.nan)),
+    "boxed64x4_pinf": dict(W=64, D=4, calc=po.CALC_BOXED_ISO_GAUSSIAN, dtype=po.F64, steps=10, keep=[1, 2, 5, 10], boxed=(1.25, np.inf)),
+    "de_boxed64x4": dict(W=64, D=4, calc=po.CALC_BOXED_ISO_GAUSSIAN, dtype=po.F64, steps=200, keep=[1, 2, 10, 200], boxed=(1.25, -np.inf),
+                         mover=1, alpha_code=2),
+    "de_boxed64x4_f32": dict(W=64, D=4, calc=po.CALC_BOXED_ISO_GAUSSIAN, dtype=po.F32, steps=200, keep=[1, 2, 10, 200], boxed=(1.25, -np.inf),
+                             mover=1, alpha_code=2),
     "c3_4096x32": dict(W=4096, D=32, calc=po.CALC_ROSENBROCK, dtype=po.F64, steps=20, keep=[],
                        params=[1.0, 100.0, 0.05], digest=[1, 2, 20], sample_rows=[0, 2047, 2048, 4095]),
 }
@@ -85,7 +96,9 @@ CASES = {
 def make(name, c):
     W, D, dtype = c["W"], c["D"], c["dtype"]
     t = po.np_dtype(dtype)
-    if "rho" in c:
+    if "boxed" in c:
+        params = np.asarray(c["boxed"], dtype=t)
+    elif "rho" in c:
         params = ar1_precision(D, c["rho"], t).ravel()
     elif "params" in c:
         params = np.asarray(c["params"], dtype=t)
@@ -95,6 +108,10 @@ def make(name, c):
     orc = po.Oracle(W, D, c["calc"], params, seed=0, dtype=dtype, alpha=alpha, mover=c.get("mover", 0))
     if c.get("skewed_init"):
         pos, logp = po.reference_skewed_initial_values(W, 0.13, 53)
+    elif "boxed" in c:
+        from tests.goldens import boxed_start
+        pos, _ = boxed_start(dtype, W, D, c["boxed"][0])
+        logp = orc.logp(pos)
     else:
         pos = po.init_positions(dtype, W, D, salt=0)
         logp = orc.logp(pos)
@@ -120,6 +137,7 @@ def make(name, c):
         out["init_logp_sha256"] = np.array(sha(logp))
     chain = ref["chain"]
     assert np.array_equal(chain[0], pos)
+    assert np.all(np.isfinite(chain)), "a position of the reference's chain is not finite"
     for k in c["keep"]:
         out["chain_step_%d" % k] = chain[k]
     for k in c.get("digest", []):
@@ -254,8 +272,14 @@ def main():
         print(make_covariance(), flush=True)
     if not want or "autocorr" in want:
         print(make_autocorr(), flush=True)
-    if not want:
-        with open(os.path.join(HERE, "MANIFEST.json"), "w") as f:
+    path = os.path.join(HERE, "MANIFEST.json")
+    if want and summary and os.path.exists(path):  # some fixtures only: their entries replace or follow the others
+        made = {e["name"]: e for e in summary}
+        with open(path) as f:
+            kept = [made.pop(e["name"], e) for e in json.load(f)]
+        summary = kept + list(made.values())
+    if summary:
+        with open(path, "w") as f:
             json.dump(summary, f, indent=1)
 
 

@@ -15,6 +15,10 @@ DIGEST = ["iso600x130", "c2_16384x32", "c3_4096x32"]
 # next row f3: Mover::DifferentialEvolution
 DE_SMALL = ["de_iso64x4", "de_iso100x7", "de_iso14x3", "de_rosen80x8", "de_dense96x16", "de_dense80x5_f32"]
 DE_DIGEST = ["de_c2_16384x32"]
+# the bounded test target (po.CALC_BOXED_ISO_GAUSSIAN, params = [half_width, outside]) run by the reference: outside = -inf
+# in both element types and under both movers, NaN and +inf under the stretch move in fp64
+BOXED = ["boxed64x4", "boxed64x4_f32", "boxed64x4_nan", "boxed64x4_pinf"]
+DE_BOXED = ["de_boxed64x4", "de_boxed64x4_f32"]
 
 
 def sha(a):
@@ -62,6 +66,25 @@ class Golden:
     @property
     def checked_steps(self):
         return self.full_steps + self.digest_steps
+
+
+def boxed_start(dtype, W, D, half_width, salt=0, spread=0.9, push=1.5):
+    """Initial positions for the boxed target and the indices of the walkers that start outside the box.  Every walker sits
+    inside (the splitmix64 recipe, scaled from [-2, 2) to `spread` half widths) except every fourth, which has ONE coordinate
+    pushed out to `push` half widths; which coordinate, and then its sign, rotates with the walker index, so that the offending
+    element meets every lane position of a walker's lane group."""
+    t = po.np_dtype(dtype)
+    pos = (po.init_positions(dtype, W, D, salt=salt) * t(0.5 * spread * half_width)).astype(t)
+    outside = np.arange(3, W, 4)
+    for k, w in enumerate(outside):
+        pos[w, k % D] = t(push * half_width) * t(-1 if (k // D) & 1 else 1)
+    return pos, outside
+
+
+def in_box(x, half_width):
+    """Per row of x[..., D]: every |x_j| <= half_width (a NaN coordinate is outside)."""
+    with np.errstate(invalid="ignore"):
+        return np.all(np.abs(x) <= x.dtype.type(half_width), axis=-1)
 
 
 def ar_chain(n, W, D, seed, phi, dtype=np.float64):

@@ -31,11 +31,30 @@ def _params(calc, D, rng):
     return None
 
 
+def _same(a, b):
+    """Bit-for-bit equality in which a NaN equals a NaN (its sign and payload differ between host and device)."""
+    return np.array_equal(a, b, equal_nan=np.asarray(a).dtype.kind == "f")
+
+
+def overflow_walkers(pos, logp, orc):
+    """Every eighth walker at 1e200 * x, where its log-posterior is not finite: it never moves.  Two more in sixteen keep
+    their position and are given a log-posterior of NaN (never moves) or -inf (takes the first finite proposal)."""
+    W = pos.shape[0]
+    far = np.arange(5, W, 8)
+    pos[far] *= 1e200
+    logp[:] = orc.logp(pos)
+    assert not np.isfinite(logp[far]).any()
+    logp[2::16] = np.nan
+    logp[10::16] = -np.inf
+    return np.concatenate([far, np.arange(2, W, 16)])
+
+
 def run_ranks(G, W, D, calc, dtype=capi.F64, scheme="step", runs=((3, 2), (1, 1), (2, 3)), chain_on="all", seed=9, env=None,
-              oracle_threads=4, bad_rank=None, expect=None):
+              oracle_threads=4, bad_rank=None, expect=None, init=None):
     """One ensemble over G ranks; returns a list of problems (empty: everything equal to the oracle).
     expect: optional check of the exchange statistics, called with [(bytes per step, repeated chunks, block slots)] of
-    rank 0's runs; returns a list of problems."""
+    rank 0's runs; returns a list of problems.
+    init: optional change of the initial state, called with (pos, logp, oracle); returns the walkers that must never move."""
     env = dict(env or {})
     env["MCMCPP_HIP_COMM_FULL_STEP"] = "1" if scheme == "step" else "0"
     saved_env = {k: os.environ.get(k) for k in env}
@@ -48,11 +67,17 @@ def run_ranks(G, W, D, calc, dtype=capi.F64, scheme="step", runs=((3, 2), (1, 1)
         orc = po.Oracle(W, D, calc, params, seed=seed, dtype=po_t)
         pos = po.init_positions(po_t, W, D, salt=1)
         logp = orc.logp(pos)
+        frozen = init(pos, logp, orc) if init is not None else None
         orc.set_state(pos, logp)
         want = []
         for n_saved, interval in runs:
             chain, acc = orc.run(n_saved, interval=interval, mode=po.MODE_COUNTER, threads=oracle_threads)
             want.append((chain, acc, orc.get_state()))
+        if frozen is not None:
+            # (on the oracle's side: the run does what the case is there for)
+            if not (np.all(want[-1][2][2][frozen] == 0) and np.array_equal(want[-1][2][0][frozen], pos[frozen]) and orc.near_ties == 0
+                    and all(np.all(np.isfinite(w[0])) and int(w[1].sum()) > 0 for w in want)):
+                problems.append("the oracle's run does not meet the case's input conditions")
         cid = capi.comm_unique_id()
         got = [None] * G
         errors = [None] * G
@@ -103,11 +128,11 @@ def run_ranks(G, W, D, calc, dtype=capi.F64, scheme="step", runs=((3, 2), (1, 1)
                 wchain, wacc, wstate = want[k]
                 if acc is not None and not np.array_equal(acc, wacc):
                     problems.append("rank %d run %d: accepted counts differ" % (r, k))
-                if chain is not None and not np.array_equal(chain, wchain):
+                if chain is not None and not _same(chain, wchain):
                     problems.append("rank %d run %d: chains differ" % (r, k))
                 for name, a, b in zip(("positions", "logp", "n_accept"), state, wstate):
-                    if not np.array_equal(a, b):
-                        problems.append("rank %d run %d: %s differ (%d cells)" % (r, k, name, int(np.sum(np.asarray(a) != np.asarray(b)))))
+                    if not _same(a, b):
+                        problems.append("rank %d run %d: %s differ" % (r, k, name))
             c = out[len(runs)]
             if c["near_ties"] != 0 or c["redraws"] != 0:
                 problems.append("rank %d: near ties %d, redraws %d" % (r, c["near_ties"], c["redraws"]))
@@ -200,6 +225,11 @@ case("iso32768x64_G2_rank0_stores_half_scheme")(lambda: run_ranks(
 for _scheme in ("step", "half"):
     case("rosen296x3_G2_%s" % _scheme)(lambda scheme=_scheme: run_ranks(2, 296, 3, po.CALC_ROSENBROCK, scheme=scheme, runs=((25, 2), (7, 1))))
     case("iso340x5_f32_G5_%s" % _scheme)(lambda scheme=_scheme: run_ranks(5, 340, 5, po.CALC_ISO_GAUSSIAN, dtype=capi.F32, scheme=scheme, runs=((30, 1),)))
+# walkers whose log-posterior is not finite (tests/test_nonfinite.py): they never move, so the compact exchange never sends their
+# rows -- every replica must still hold them, and the stated NaN / -inf log-posteriors, exactly as the oracle does
+for _scheme in ("step", "half"):
+    case("dense4096x32_G4_%s_walkers_that_overflow" % _scheme)(lambda scheme=_scheme: run_ranks(
+        4, 4096, 32, po.CALC_DENSE_GAUSSIAN, scheme=scheme, runs=((6, 2), (3, 1)), init=overflow_walkers))
 case("one_rank_fails_before_the_first_launch")(lambda: run_ranks(4, 4096, 32, po.CALC_ISO_GAUSSIAN, runs=((2, 2),), bad_rank=2))
 # BASELINE config 5 at full size, eight ranks (8 192 walkers of each colour per rank): one exchange per ensemble step, then
 # the reference's scheme (one per half-step)

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle as po
-from tests.goldens import DE_DIGEST, DE_SMALL, Golden
+from tests.goldens import DE_BOXED, DE_DIGEST, DE_SMALL, Golden
 
 
 def run_oracle(g, split=None):
@@ -29,11 +29,13 @@ def run_oracle(g, split=None):
     return orc
 
 
-@pytest.mark.parametrize("name", DE_SMALL + DE_DIGEST)
+@pytest.mark.parametrize("name", DE_SMALL + DE_DIGEST + DE_BOXED)
 def test_oracle_differential_evolution_matches_reference_golden(name):
     g = Golden(name)
     assert g.mover == po.MOVER_DIFFERENTIAL_EVOLUTION
     orc = run_oracle(g)
+    if name in DE_BOXED:
+        assert orc.near_ties == 0  # (proposals outside the support are decided by the comparison alone)
     n = g.W // 2
     if n & (n - 1) and n < 64:
         assert orc.redraws > 0  # the fixture does exercise the data-dependent draw count

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import pyoracle as po
-from tests.goldens import DIGEST, GOLDEN_DIR, SMALL, Golden
+from tests.goldens import BOXED, DIGEST, GOLDEN_DIR, SMALL, Golden, boxed_start
 
 
 def test_pcg32_known_answer_published_demo():
@@ -97,12 +97,12 @@ def _run_oracle(g, mode, threads=1):
     return pos, logp, nacc
 
 
-@pytest.mark.parametrize("name", SMALL + DIGEST)
+@pytest.mark.parametrize("name", SMALL + DIGEST + BOXED)
 def test_oracle_sequential_matches_reference_golden(name):
     _run_oracle(Golden(name), po.MODE_SEQUENTIAL)
 
 
-@pytest.mark.parametrize("name", SMALL + DIGEST)
+@pytest.mark.parametrize("name", SMALL + DIGEST + BOXED)
 def test_oracle_counter_addressed_matches_reference_golden(name):
     g = Golden(name)
     a = _run_oracle(g, po.MODE_COUNTER, threads=1)
@@ -168,3 +168,23 @@ def test_oracle_against_live_reference(calc, W, D, dtype):
     chain, acc = orc.run(120)
     np.testing.assert_array_equal(ref["chain"][1:], chain)
     assert int(acc.sum()) + W == int(ref["accepted"][-1])
+
+
+@pytest.mark.parametrize("mover,W,D,dtype,outside", [(0, 50, 6, po.F32, -np.inf), (0, 22, 3, po.F64, np.nan), (0, 38, 5, po.F32, np.inf),
+                                                     (1, 50, 6, po.F64, -np.inf), (1, 22, 3, po.F32, np.nan)])
+def test_oracle_against_live_reference_on_a_bounded_target(mover, W, D, dtype, outside):
+    """The boxed target at shapes no fixture has, walkers that start outside the support included: every comparison with a
+    -inf, NaN or +inf log-posterior must fall as the compiled reference's falls."""
+    if not po.reference_available():
+        pytest.skip("oracle/_ref not prebuilt here")
+    params = np.array([1.25, outside], dtype=po.np_dtype(dtype))
+    orc = po.Oracle(W, D, po.CALC_BOXED_ISO_GAUSSIAN, params, seed=13, dtype=dtype, mover=mover)
+    pos, started_outside = boxed_start(dtype, W, D, 1.25, salt=2)
+    logp = orc.logp(pos)
+    assert not np.any(np.isfinite(logp[started_outside])) and np.all(np.isfinite(np.delete(logp, started_outside)))
+    ref = po.reference_run(W, D, po.CALC_BOXED_ISO_GAUSSIAN, params, 13, pos, logp, 1, 90, dtype=dtype, alpha_code=2 if mover else 0)
+    orc.set_state(pos, logp)
+    chain, acc = orc.run(90)
+    np.testing.assert_array_equal(ref["chain"][1:], chain)
+    assert int(acc.sum()) + W == int(ref["accepted"][-1])
+    assert orc.near_ties == 0
