@@ -468,57 +468,28 @@ public:
         return rc;
     }
 
-    // staging -> the caller's memory: stored steps [first, first + count) of every chain (chain k's steps are n_saved steps
-    // apart in the caller's array, sub_saved steps apart in the staging buffer)
-    void hand_out_subchunk(char* chain_out, const char* stage, size_t step_bytes, int64_t sub_saved, int64_t n_saved, int64_t first, int64_t count) const
-    {
-        for (int k = 0; k < K; ++k)
-            std::memcpy(chain_out + step_bytes * ((size_t)n_saved * (size_t)k + (size_t)first), stage + step_bytes * (size_t)sub_saved * (size_t)k,
-                        step_bytes * (size_t)count);
-    }
-
-    int run_whole(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step)
+    // the checks every run() makes before it touches the device
+    int check_run(int64_t n_saved, int32_t interval, bool whole_only)
     {
         if (!have_state) return fail(MCMCPP_HIP_E_STATE, "run: set_state has not been called");
         if (n_saved < 0 || interval < 1) return fail(MCMCPP_HIP_E_ARG, "run: n_saved >= 0 and interval >= 1 required");
-        if (shard_count != n) return fail(MCMCPP_HIP_E_UNSUPPORTED, "run: a sharded handle is driven with half_step_async");
+        if (whole_only && shard_count != n) return fail(MCMCPP_HIP_E_UNSUPPORTED, "run: a sharded handle is driven with half_step_async");
         if (half_steps & 1) return fail(MCMCPP_HIP_E_STATE, "run: an ensemble step is half done (half_step_async)");
         HIP_TRY(hipSetDevice(device));
-        const int64_t total = n_saved * (int64_t)interval;
-        last_ms = 0.0;
-        last_launches = 0;
-        if (total == 0) return MCMCPP_HIP_OK;
-        const auto tp0 = std::chrono::steady_clock::now();
+        return MCMCPP_HIP_OK;
+    }
 
-        const size_t step_bytes = sizeof(T) * (size_t)W * D;
-        int64_t sub_saved = n_saved;  // stored steps per sub-chunk
-        if (chain_out) sub_saved = stored_steps_per_subchunk(chain_subchunk_bytes, step_bytes * (size_t)K, n_saved);
-        // Full-step kernels forward stored steps to pinned host memory themselves (trickle_stored_step): a ring of
-        // `ring` slots on the device with a twin in pinned host memory, no copy engine, no gap in the launch sequence.
-        const bool trickle = full_fn && chain_out && step_bytes % 16 == 0 && knobs.trickle != 0;
-        // chain_out in pinned host memory (mcmcpp_hip_host_alloc: the facade's Chain blocks): the launches forward stored
-        // steps straight into their final place -- no pinned twin of the device ring, no host copy
-        void* direct_stage = (trickle && knobs.pinned_direct != 0) ? device_view_of_pinned(chain_out, step_bytes * (size_t)n_saved * K) : nullptr;
-        int64_t ring = 0, chunk_steps = 0;
-        if (trickle)
-        {
-            ring = 4;
-            while (ring < 64 && (size_t)(2 * ring) * step_bytes <= 2 * chain_subchunk_bytes) ring *= 2;
-            // the host enqueues one chunk ahead of the one it waits for: stored steps of two chunks are in flight
-            int64_t per_chunk = (plan.graph_steps > 0 ? plan.graph_steps : 64) / (int64_t)interval;
-            if (!direct_stage && per_chunk > (ring - 2) / 2) per_chunk = (ring - 2) / 2;
-            if (per_chunk < 1) per_chunk = 1;
-            chunk_steps = per_chunk * interval;
-        }
-        int rc = ensure_run_buffers(accepted_per_step ? (size_t)total * K : 0, (chain_out && !trickle) ? step_bytes * (size_t)sub_saved * K : 0,
-                                    trickle ? step_bytes * (size_t)ring * K : 0, direct_stage == nullptr);
-        if (rc) return rc;
-        if (accepted_per_step) HIP_TRY(hipMemsetAsync(d_acc, 0, sizeof(uint32_t) * (size_t)total * K, stream));
+    // The start of a run on the device: the per-step counters cleared, the control records at step 0 of the run, the rows
+    // marked as moved for the full-step kernels, the launch arguments.  split_record: the one run record of a split run
+    // (a whole-ensemble run uploads a record per sub-chunk).
+    int begin_run(size_t acc_entries, const RunInfo* split_record)
+    {
+        if (acc_entries) HIP_TRY(hipMemsetAsync(d_acc, 0, sizeof(uint32_t) * acc_entries, stream));
         run_touched_device = true;  // from here on an error leaves the device ahead of the host's bookkeeping
-        rc = write_ctl(0);  // step_in_run = 0, stream position from the host-side half-step count
-        if (rc) return rc;
+        if (int rc = write_ctl(0)) return rc;  // step_in_run = 0, stream position from the host-side half-step count
         records_valid = false;  // (until this call has finished: an error on the way leaves them unknown)
         run_info_idle = false;
+        if (split_record) HIP_TRY(hipMemcpyAsync(d_run, split_record, sizeof(RunInfo), hipMemcpyHostToDevice, stream));
         if (full_fn)
         {
             for (int k = 0; k < K; ++k)
@@ -529,40 +500,90 @@ public:
         run_step = 0;
         args_red = make_args(0);
         args_blk = make_args(1);
-        rc = ensure_graphs();
-        if (rc) return rc;
+        return MCMCPP_HIP_OK;
+    }
 
-        const auto tp1 = std::chrono::steady_clock::now();
-        double launch_ms = 0.0;  // GPU time of the step launches alone (downloads excluded)
-        if (trickle)
+    // The end of a run that succeeded: the host's bookkeeping moves on, the per-step accepted counts go to the caller, the
+    // two host timings.  records_left: did the last launch leave the draw records of the next ensemble step behind (full-step
+    // launches: with partner2)?
+    using TimePoint = std::chrono::steady_clock::time_point;
+    int finish_run(int64_t total, double gpu_ms, bool records_left, uint32_t* accepted_per_step, TimePoint tp0, TimePoint tp1, TimePoint tp2)
+    {
+        last_ms = gpu_ms;
+        last_launches = full_fn ? total : 2 * total;  // (a launch steps all chains)
+        half_steps += 2 * (uint64_t)total;
+        steps_since_reset += (uint64_t)total;
+        records_valid = records_left;
+        records_step = half_steps >> 1;
+        records_partner2 = full_fn != nullptr;  // (read only while records_valid)
+        if (accepted_per_step) HIP_TRY(hipMemcpy(accepted_per_step, d_acc, sizeof(uint32_t) * (size_t)total * K, hipMemcpyDeviceToHost));
+        const TimePoint tp3 = std::chrono::steady_clock::now();
+        host_enqueue_ms = std::chrono::duration<double, std::milli>(tp2 - tp1).count();
+        host_wall_ms = std::chrono::duration<double, std::milli>(tp3 - tp0).count();
+        return MCMCPP_HIP_OK;
+    }
+
+    // a sub-chunk whose staging half still has to reach chain_out: wait for its copy, hand it out (every chain), announce it
+    int hand_out_staged(char* chain_out, const ChainPlan& cp, size_t step_bytes, StoredRange staged, int buf)
+    {
+        if (staged.to == staged.from) return MCMCPP_HIP_OK;
+        HIP_TRY(hipEventSynchronize(ev_copied[buf]));
+        for (int k = 0; k < K; ++k)
         {
-            rc = run_trickle(n_saved, interval, (char*)chain_out, accepted_per_step != nullptr, step_bytes, ring, chunk_steps, &launch_ms, (char*)direct_stage);
-            sub_saved = n_saved + 1;  // (the sub-chunk loop below has nothing to do)
+            const SubchunkCopy c = subchunk_copy(step_bytes, cp.sub_saved, cp.n_saved, staged.from, staged.to - staged.from, k);
+            std::memcpy(chain_out + c.dst, (const char*)h_stage[buf] + c.src, c.bytes);
         }
-        const int64_t n_sub = trickle ? 0 : (n_saved + sub_saved - 1) / sub_saved;
-        int64_t pending_first = -1, pending_count = 0;  // sub-chunk whose staging still has to reach chain_out
+        publish_stored(staged.to);
+        return MCMCPP_HIP_OK;
+    }
+
+    int run_whole(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step)
+    {
+        if (int rc = check_run(n_saved, interval, true)) return rc;
+        const int64_t total = n_saved * (int64_t)interval;
+        last_ms = 0.0;
+        last_launches = 0;
+        if (total == 0) return MCMCPP_HIP_OK;
+        const TimePoint tp0 = std::chrono::steady_clock::now();
+
+        // how the stored steps reach the caller (run_plan.hpp): sub-chunks through staging, or -- full-step kernels -- the
+        // launches forward them to pinned host memory themselves (trickle_stored_step): a ring on the device with a twin in
+        // pinned host memory, no copy engine, no gap in the launch sequence
+        const size_t step_bytes = sizeof(T) * (size_t)W * D;
+        const ChainRequest want = {step_bytes, K, n_saved, interval, chain_out != nullptr, accepted_per_step != nullptr, full_fn != nullptr,
+                                   chain_subchunk_bytes, plan.graph_steps, knobs.trickle, knobs.pinned_direct};
+        // chain_out in pinned host memory (mcmcpp_hip_host_alloc: the facade's Chain blocks): the launches forward stored
+        // steps straight into their final place -- no pinned twin of the device ring, no host copy
+        void* direct_stage = pinned_question_matters(want) ? device_view_of_pinned(chain_out, step_bytes * (size_t)n_saved * K) : nullptr;
+        const ChainPlan cp = plan_chain(want, direct_stage != nullptr);
+        int rc = ensure_run_buffers(cp.acc_entries, cp.half_bytes, cp.ring_bytes, cp.need_host_ring);
+        if (rc) return rc;
+        if ((rc = begin_run(cp.acc_entries, nullptr))) return rc;
+        if ((rc = ensure_graphs())) return rc;
+
+        const TimePoint tp1 = std::chrono::steady_clock::now();
+        double launch_ms = 0.0;  // GPU time of the step launches alone (downloads excluded)
+        if (cp.mode == ChainMode::Trickle)
+            rc = run_trickle(n_saved, interval, (char*)chain_out, accepted_per_step != nullptr, step_bytes, cp, &launch_ms, (char*)direct_stage);
+        StoredRange pending = {0, 0};  // sub-chunk whose staging still has to reach chain_out
         int pending_buf = 0;
-        for (int64_t c = 0; c < n_sub && rc == MCMCPP_HIP_OK; ++c)
+        for (int64_t c = 0; c < cp.n_sub && rc == MCMCPP_HIP_OK; ++c)
         {
             const int buf = (int)(c & 1);
-            const int64_t first = c * sub_saved;
-            const int64_t now = (n_saved - first < sub_saved) ? n_saved - first : sub_saved;
+            const StoredRange sub = cp.subchunk(c);
             for (int k = 0; k < K; ++k)
             {
                 // (several chains: one record each; the upload slots rotate per sub-chunk as for one chain)
                 RunInfo* ri = K > 1 ? &h_pinned->chain_run[c % 4][k] : &h_pinned->run[c % 4];
                 // chain k's stored steps of this sub-chunk: the k-th run of sub_saved steps of the device half
-                *ri = idle_run_info();
-                ri->chain = chain_out ? (void*)((char*)d_chain[buf].get() + step_bytes * (size_t)sub_saved * (size_t)k) : nullptr;
-                ri->accepted_per_step = accepted_per_step ? d_acc + (size_t)k * (size_t)total : nullptr;
-                ri->interval = interval;
-                ri->chain_slot_base = -first;
-                ri->step_bytes = (int64_t)step_bytes;
+                *ri = run_info_of_run(chain_out ? (char*)d_chain[buf].get() + subchunk_chain_offset(step_bytes, cp.sub_saved, k) : nullptr,
+                                      accepted_per_step ? d_acc + (size_t)k * (size_t)total : nullptr, interval, step_bytes);
+                ri->chain_slot_base = -sub.from;
                 HIP_TRY(hipMemcpyAsync(run_of(k), ri, sizeof(RunInfo), hipMemcpyHostToDevice, stream));
             }
             // the events of slot c%4 were last used by sub-chunk c-4, which has long been waited for
             HIP_TRY(hipEventRecord(ev_t0[c & 3], stream));
-            rc = enqueue_steps(now * interval);
+            rc = enqueue_steps((sub.to - sub.from) * interval);
             if (rc) break;
             HIP_TRY(hipEventRecord(ev_t1[c & 3], stream));
             if (c >= 3)
@@ -576,55 +597,29 @@ public:
             {
                 // the staging buffer is free: its previous content (sub-chunk c-2) was copied out below
                 // (the whole device half in one copy: with several chains, chain k's steps sit sub_saved steps apart)
-                const size_t half_used = K > 1 ? step_bytes * (size_t)sub_saved * (size_t)(K - 1) + step_bytes * (size_t)now : step_bytes * (size_t)now;
-                HIP_TRY(hipMemcpyAsync(h_stage[buf], d_chain[buf], half_used, hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipMemcpyAsync(h_stage[buf], d_chain[buf], subchunk_half_used(step_bytes, cp.sub_saved, sub.to - sub.from, K), hipMemcpyDeviceToHost, stream));
                 HIP_TRY(hipEventRecord(ev_copied[buf], stream));
-                if (pending_first >= 0)
-                {
-                    HIP_TRY(hipEventSynchronize(ev_copied[pending_buf]));
-                    hand_out_subchunk((char*)chain_out, (const char*)h_stage[pending_buf], step_bytes, sub_saved, n_saved, pending_first, pending_count);
-                    publish_stored(pending_first + pending_count);
-                }
-                pending_first = first;
-                pending_count = now;
+                if ((rc = hand_out_staged((char*)chain_out, cp, step_bytes, pending, pending_buf))) return rc;
+                pending = sub;
                 pending_buf = buf;
             }
         }
-        const auto tp2 = std::chrono::steady_clock::now();
-        if (rc == MCMCPP_HIP_OK)
+        const TimePoint tp2 = std::chrono::steady_clock::now();
+        if (rc) return rc;
+        if ((rc = hand_out_staged((char*)chain_out, cp, step_bytes, pending, pending_buf))) return rc;
+        if ((rc = bring_ensemble_home())) return rc;
+        HIP_TRY(hipStreamSynchronize(stream));
+        for (int64_t c = (cp.n_sub > 3 ? cp.n_sub - 3 : 0); c < cp.n_sub; ++c)
         {
-            if (pending_first >= 0)
-            {
-                HIP_TRY(hipEventSynchronize(ev_copied[pending_buf]));
-                hand_out_subchunk((char*)chain_out, (const char*)h_stage[pending_buf], step_bytes, sub_saved, n_saved, pending_first, pending_count);
-                publish_stored(pending_first + pending_count);
-            }
-            if ((rc = bring_ensemble_home())) return rc;
-            HIP_TRY(hipStreamSynchronize(stream));
-            for (int64_t c = (n_sub > 3 ? n_sub - 3 : 0); c < n_sub; ++c)
-            {
-                float ms = 0.f;
-                HIP_TRY(hipEventElapsedTime(&ms, ev_t0[c & 3], ev_t1[c & 3]));
-                launch_ms += ms;
-            }
-            last_ms = launch_ms;
-            last_launches = full_fn ? total : 2 * total;  // (a launch steps all chains)
-            half_steps += 2 * (uint64_t)total;
-            steps_since_reset += (uint64_t)total;
-            // the last launch left the records of the next ensemble step behind (full-step launches: with partner2) --
-            // unless the records were made ahead in batches, which leaves the two-buffer records alone
-            records_valid = plan.batch_draws == 0;
-            records_step = half_steps >> 1;
-            records_partner2 = full_fn != nullptr;
-            if (accepted_per_step)
-                HIP_TRY(hipMemcpy(accepted_per_step, d_acc, sizeof(uint32_t) * (size_t)total * K, hipMemcpyDeviceToHost));
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, ev_t0[c & 3], ev_t1[c & 3]));
+            launch_ms += ms;
         }
-        const auto tp3 = std::chrono::steady_clock::now();
-        host_enqueue_ms = std::chrono::duration<double, std::milli>(tp2 - tp1).count();
-        host_wall_ms = std::chrono::duration<double, std::milli>(tp3 - tp0).count();
         exchange_us_per_step = 0.0;
+        // the last launch left the records of the next ensemble step behind -- unless the records were made ahead in
+        // batches, which leaves the two-buffer records alone
         // (the device-side RunInfo still points to run-scoped buffers; half_step_async replaces it before it launches)
-        return rc;
+        return finish_run(total, launch_ms, plan.batch_draws == 0, accepted_per_step, tp0, tp1, tp2);
     }
 
     // ---- one ensemble split over the ranks of an RCCL communicator (BASELINE config 5) -----------------
@@ -661,18 +656,12 @@ public:
     // fails on this rank only -- the caller agrees on it with the other ranks (agree_on_status) before the first launch.
     int prepare_split(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, int64_t* stage_slots_out)
     {
-        if (!have_state) return fail(MCMCPP_HIP_E_STATE, "run: set_state has not been called");
-        if (n_saved < 0 || interval < 1) return fail(MCMCPP_HIP_E_ARG, "run: n_saved >= 0 and interval >= 1 required");
-        if (half_steps & 1) return fail(MCMCPP_HIP_E_STATE, "run: an ensemble step is half done (half_step_async)");
-        HIP_TRY(hipSetDevice(device));
+        if (int rc = check_run(n_saved, interval, false)) return rc;
         const int64_t total = n_saved * (int64_t)interval;
         const size_t step_bytes = sizeof(T) * (size_t)W * D;
         // stored steps: device -> pinned staging on the launch stream, handed to the caller a staging buffer at a time
-        // (the same number on every rank, whether it stores or not: the chunks of a run end where the staging buffer of
-        //  the ranks that do store is full, and every rank must cut its run into the same chunks)
-        int64_t stage_slots = (int64_t)(((size_t)256 << 20) / step_bytes);
-        if (stage_slots < 1) stage_slots = 1;
-        if (stage_slots > n_saved) stage_slots = n_saved;
+        // (the same number of slots on every rank, whether it stores or not: every rank must cut its run into the same chunks)
+        const int64_t stage_slots = split_stage_slots(step_bytes, n_saved);
         if (chain_out && total > 0 && grow(h_split_stage, step_bytes * (size_t)stage_slots, stream))
             return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu bytes of pinned staging", step_bytes * (size_t)stage_slots);
         *stage_slots_out = stage_slots;
@@ -778,30 +767,9 @@ public:
         if (total == 0) return MCMCPP_HIP_OK;
         const size_t step_bytes = sizeof(T) * (size_t)W * D;
         constexpr int kMaxSamples = kMaxExchangeSamples;
-        HIP_TRY(hipMemsetAsync(d_acc, 0, sizeof(uint32_t) * (size_t)total, stream));
-        run_touched_device = true;
-        rc = write_ctl(0);
-        if (rc) return rc;
-        records_valid = false;
-        run_info_idle = false;
-        {
-            RunInfo* ri = &h_pinned->run[0];
-            *ri = idle_run_info();  // (no chain: stored steps are copied from the replica after the exchange)
-            ri->accepted_per_step = d_acc;
-            ri->interval = interval;
-            ri->step_bytes = (int64_t)step_bytes;
-            HIP_TRY(hipMemcpyAsync(d_run, ri, sizeof(RunInfo), hipMemcpyHostToDevice, stream));
-        }
-        if (full_fn)
-        {
-            hipLaunchKernelGGL(mark_rows_moved_kernel, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, stream, d_nacc, W, kRowMovedBit);
-            HIP_TRY(hipGetLastError());
-        }
+        h_pinned->run[0] = run_info_of_run(nullptr, d_acc, interval, step_bytes);  // (no chain: stored steps are copied from the replica after the exchange)
+        if ((rc = begin_run((size_t)total, &h_pinned->run[0]))) return rc;
         const uint64_t half_steps0 = half_steps;  // (the member moves on when the run has succeeded)
-        enq_step = half_steps0 >> 1;
-        run_step = 0;
-        args_red = make_args(0);
-        args_blk = make_args(1);
         // engine state in front of the red half-step of the coming ensemble step (what write_ctl put into the control record)
         U128 red_base = apply(pcg_jump(inc, (unsigned __int128)3 * (unsigned)n * (unsigned __int128)half_steps0), state0);
         HalfStepArgs<T> fill_red = make_args(0);
@@ -810,21 +778,14 @@ public:
 
         const bool compact = plan.compact_exchange;
         const uint32_t cap_full = exchange_cap_full();
-        // the slot bound MCMCPP_HIP_COMM_COMPACT_CAP sets, or 0: learned from the run
-        const uint32_t cap_set = knobs.comm_compact_cap > 0 ? (uint32_t)(knobs.comm_compact_cap < (long)cap_full ? knobs.comm_compact_cap : (long)cap_full) : 0;
-        uint32_t cap = cap_full;
-        if (compact)
+        // the slot bound of the exchange blocks (run_plan.hpp): what MCMCPP_HIP_COMM_COMPACT_CAP sets, or learned from the run
+        const uint32_t cap_set = split_cap_set(knobs.comm_compact_cap, cap_full);
+        uint32_t cap = split_first_cap(compact, cap_set, xcap_learned, cap_full);
+        if (compact && full_fn)
         {
-            if (cap_set)
-                cap = cap_set;
-            else if (xcap_learned > 0)
-                cap = xcap_learned < cap_full ? xcap_learned : cap_full;
-            if (full_fn)
-            {
-                // a remote walker's row must be current in BOTH buffers (the scatter keeps it so from here on)
-                HIP_TRY(hipMemcpyAsync(d_pos_alt, d_pos, step_bytes, hipMemcpyDeviceToDevice, stream));
-                HIP_TRY(hipMemcpyAsync(d_logp + W, d_logp, sizeof(T) * (size_t)W, hipMemcpyDeviceToDevice, stream));
-            }
+            // a remote walker's row must be current in BOTH buffers (the scatter keeps it so from here on)
+            HIP_TRY(hipMemcpyAsync(d_pos_alt, d_pos, step_bytes, hipMemcpyDeviceToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(d_logp + W, d_logp, sizeof(T) * (size_t)W, hipMemcpyDeviceToDevice, stream));
         }
 
         const int64_t sample_stride = total > kMaxSamples ? total / kMaxSamples : 1;
@@ -837,18 +798,8 @@ public:
         int64_t s0 = 0;  // first step of the chunk in hand
         while (s0 < total)
         {
-            // ---- how far this chunk goes
-            int64_t len = total - s0;
-            if (compact)
-            {
-                const int64_t want = learning ? 16 : knobs.comm_compact_chunk;
-                if (len > want) len = want;
-            }
-            if (any_rank_stores)
-            {
-                const int64_t fits = (s0 / interval + stage_slots) * (int64_t)interval - s0;  // steps until the staging buffer is full
-                if (len > fits) len = fits;
-            }
+            // ---- how far this chunk goes (every rank cuts alike)
+            const int64_t len = split_chunk_length(total, s0, compact, learning, knobs.comm_compact_chunk, any_rank_stores, interval, stage_slots);
             if (compact)
             {
                 const bool in_alt = full_fn && (run_step & 1);
@@ -940,21 +891,14 @@ public:
                     cap = cap_full;
                     continue;  // (the same chunk again)
                 }
-                xbytes += (double)len * (double)(full_fn ? 1 : 2) * (double)(cfg.comm_world - 1) * (double)xblock_bytes<T>(cap, D);
-                if (!cap_set)
-                {
-                    // the next chunk's bound: what this one needed, plus an eighth and a little
-                    uint64_t want = (uint64_t)hx->max_count + hx->max_count / 8 + 64;
-                    want = (want + 63) & ~(uint64_t)63;
-                    cap = want < cap_full ? (uint32_t)want : cap_full;
-                    xcap_learned = cap;
-                }
-                else
-                    cap = cap_set;
+                xbytes += split_bytes_compact(len, full_fn != nullptr, cfg.comm_world, xblock_bytes<T>(cap, D));
+                // the next chunk's bound: what this one needed, plus an eighth and a little
+                if (!cap_set) xcap_learned = split_next_cap(hx->max_count, cap_full);
+                cap = cap_set ? cap_set : xcap_learned;
                 learning = false;
             }
             else
-                xbytes += (double)len * (double)(cfg.comm_world - 1) * (double)shard_count * 2.0 * (double)((size_t)D + (full_fn ? 1 : 0)) * sizeof(T);
+                xbytes += split_bytes_whole(len, full_fn != nullptr, cfg.comm_world, shard_count, D, sizeof(T));
             if (chain_out && staged > handed && (staged - handed == stage_slots || !more || compact))
             {
                 HIP_TRY(hipStreamSynchronize(stream));
@@ -979,10 +923,10 @@ public:
         NCCL_TRY(rccl->AllReduce(d_acc, d_acc, (size_t)total, ncclUint32, ncclSum, comm, stream));
         NCCL_TRY(rccl->GroupEnd());
         HIP_TRY(hipStreamSynchronize(stream));
+        float run_ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&run_ms, ev_t0[0], ev_t1[0]));
         {
             float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, ev_t0[0], ev_t1[0]));
-            last_ms = ms;
             double sum = 0.0;
             for (int k = 0; k < samples; ++k)
             {
@@ -994,124 +938,86 @@ public:
         }
         xchg_bytes_per_step = xbytes / (double)total;
         xchg_cap_slots = compact ? (int64_t)cap : 0;
-        last_launches = full_fn ? total : 2 * total;
-        half_steps += 2 * (uint64_t)total;
-        steps_since_reset += (uint64_t)total;
-        records_valid = full_fn == nullptr;  // (full-step scheme: the next run re-primes, the red records of other ranks' walkers are per step anyway)
-        records_step = half_steps >> 1;
-        records_partner2 = false;
-        if (accepted_per_step) HIP_TRY(hipMemcpy(accepted_per_step, d_acc, sizeof(uint32_t) * (size_t)total, hipMemcpyDeviceToHost));
-        const auto tp3 = std::chrono::steady_clock::now();
-        host_enqueue_ms = std::chrono::duration<double, std::milli>(tp2 - tp1).count();
-        host_wall_ms = std::chrono::duration<double, std::milli>(tp3 - tp0).count();
-        return MCMCPP_HIP_OK;
+        // (full-step scheme: the next run re-primes, the red records of other ranks' walkers are per step anyway)
+        return finish_run(total, run_ms, full_fn == nullptr, accepted_per_step, tp0, tp1, tp2);
     }
 
-    // The chain path of the full-step kernels.  Stored step k is complete in the pinned ring when ensemble step
-    // (k + 2) * interval - 1 has finished (every launch forwards 1/interval of the previous stored step), and its
-    // ring slot is overwritten from step (k + ring + 1) * interval on: the host enqueues chunks of steps, stays one
-    // chunk ahead of the one it waits for, copies out whatever has become complete and never lets the launches
-    // run into a slot it has not copied yet.  The run's last stored step has no launches behind it: it is copied
-    // from the device ring at the end.
-    int run_trickle(int64_t n_saved, int32_t interval, char* chain_out, bool want_accepted, size_t step_bytes, int64_t ring,
-                    int64_t chunk_steps, double* launch_ms, char* direct_stage)
+    // The chain path of the full-step kernels: the launches forward stored steps into the pinned ring (or into chain_out
+    // itself, `direct_stage`), the host enqueues chunks of steps, stays one chunk ahead of the one it waits for and copies
+    // out whatever has become complete.  TrickleWindow (run_plan.hpp) keeps the schedule; the HIP calls and copies are here.
+    int run_trickle(int64_t n_saved, int32_t interval, char* chain_out, bool want_accepted, size_t step_bytes, const ChainPlan& cp, double* launch_ms,
+                    char* direct_stage)
     {
         const int64_t total = n_saved * (int64_t)interval;
-        const bool direct = direct_stage != nullptr;  // the launches forward into chain_out itself (pinned memory)
         // chain k: its own ring of stored steps on the device (and, unless the launches forward into chain_out itself,
         // its own twin in pinned memory); in the caller's memory chain k is the k-th run of n_saved steps
-        const size_t ring_bytes = step_bytes * (size_t)ring, out_bytes = step_bytes * (size_t)n_saved;
+        const size_t ring_bytes = step_bytes * (size_t)cp.ring, out_bytes = step_bytes * (size_t)n_saved;
         for (int k = 0; k < K; ++k)
         {
             RunInfo* ri = &h_pinned->chain_run[0][k];
-            *ri = idle_run_info();
-            ri->chain = (char*)d_ring + ring_bytes * (size_t)k;
-            ri->accepted_per_step = want_accepted ? d_acc + (size_t)k * (size_t)total : nullptr;
-            ri->interval = interval;
-            ri->stage = direct ? (void*)(direct_stage + out_bytes * (size_t)k) : (void*)((char*)h_ring + ring_bytes * (size_t)k);
-            ri->slot_mask = ring - 1;
-            ri->slice_bytes = (int64_t)(((step_bytes + (size_t)interval - 1) / (size_t)interval + 15) / 16 * 16) | (direct ? 1 : 0);
-            ri->step_bytes = (int64_t)step_bytes;
+            *ri = run_info_of_run((char*)d_ring + ring_bytes * (size_t)k, want_accepted ? d_acc + (size_t)k * (size_t)total : nullptr, interval, step_bytes);
+            ri->stage = cp.direct ? (void*)(direct_stage + out_bytes * (size_t)k) : (void*)((char*)h_ring + ring_bytes * (size_t)k);
+            ri->slot_mask = cp.ring - 1;
+            ri->slice_bytes = cp.slice_bytes;
             HIP_TRY(hipMemcpyAsync(run_of(k), ri, sizeof(RunInfo), hipMemcpyHostToDevice, stream));
         }
 
-        int64_t enq = 0, copied = 0;       // ensemble steps enqueued; stored steps handed to the caller
-        int64_t chunk_end[4] = {0, 0, 0, 0};
-        int64_t next_chunk = 0, oldest = 0;  // chunks enqueued / chunks whose completion has been processed
+        TrickleWindow win(n_saved, interval, cp);
+        // pinned ring -> the caller's memory (forwarded into chain_out itself, they are where they belong already)
+        auto copy_out = [&](StoredRange r, bool quick) {
+            if (cp.direct) return;
+            for (int64_t s = r.from; s < r.to; ++s)
+                for (int k = 0; k < K; ++k)
+                {
+                    char* dst = chain_out + out_bytes * (size_t)k + step_bytes * (size_t)s;
+                    const char* src = (char*)h_ring + ring_bytes * (size_t)k + step_bytes * (size_t)win.ring_slot(s);
+                    if (quick)
+                        parallel_memcpy(dst, src, step_bytes);  // nothing left to overlap with: be quick
+                    else
+                        std::memcpy(dst, src, step_bytes);
+                }
+        };
         auto process_oldest = [&]() -> int {
-            const int e = (int)(oldest & 3);
+            const int e = win.event_slot(win.oldest);
             float ms = 0.f;
             HIP_TRY(hipEventSynchronize(ev_t1[e]));
             HIP_TRY(hipEventElapsedTime(&ms, ev_t0[e], ev_t1[e]));
             *launch_ms += ms;
-            const int64_t complete = chunk_end[e] / interval - 1;  // stored steps fully forwarded by now
-            if (direct)
-            {
-                if (complete > copied) copied = complete;  // (they are where they belong already)
-            }
-            else
-                for (; copied < complete; ++copied)
-                    for (int k = 0; k < K; ++k)
-                    {
-                        char* dst = chain_out + out_bytes * (size_t)k + step_bytes * (size_t)copied;
-                        const char* src = (char*)h_ring + ring_bytes * (size_t)k + step_bytes * (size_t)(copied & (ring - 1));
-                        if (enq == total)
-                            parallel_memcpy(dst, src, step_bytes);  // nothing left to overlap with: be quick
-                        else
-                            std::memcpy(dst, src, step_bytes);
-                    }
-            publish_stored(copied);
-            ++oldest;
+            copy_out(win.process_oldest(), win.all_enqueued());
+            publish_stored(win.copied);
             return MCMCPP_HIP_OK;
         };
-        while (enq < total)
+        while (!win.all_enqueued())
         {
-            int64_t now = (total - enq < chunk_steps) ? total - enq : chunk_steps;
-            // The stored steps that become complete with the LAST chunk are copied out with nothing left to overlap: the
-            // run ends with a chunk of one interval, so that this tail is one stored step instead of a chunk's worth
-            // (11.80 -> 11.55 ms per 2 000 steps at C2)
-            if (!direct && now == total - enq && now > (int64_t)interval) now -= interval;
-            // at most two chunks in flight, and no launch may forward into a ring slot that is still to be copied out
-            // (forwarding into the final place needs no such care: a device slot is reused ring + 1 stored steps after it
-            //  was written, its forwarding is over one stored step after)
-            while (next_chunk > oldest && (next_chunk - oldest >= 2 || (!direct && enq + now > (copied + ring + 1) * (int64_t)interval)))
+            const int64_t now = win.next_length();
+            while (win.must_process_oldest_before(now))
             {
                 const int rc = process_oldest();
                 if (rc) return rc;
             }
-            const int e = (int)(next_chunk & 3);
+            const int e = win.event_slot(win.next_chunk);
             HIP_TRY(hipEventRecord(ev_t0[e], stream));
             const int rc = enqueue_steps(now);
             if (rc) return rc;
             HIP_TRY(hipEventRecord(ev_t1[e], stream));
-            enq += now;
-            chunk_end[e] = enq;
-            ++next_chunk;
+            win.enqueued(now);
         }
         // What the launches do not forward: the run's last stored step.  Its download is queued now, behind the last
         // launch, so that it runs while the host still copies out the steps before it.
         for (int k = 0; k < K; ++k)
         {
-            const size_t off = ring_bytes * (size_t)k + step_bytes * (size_t)((n_saved - 1) & (ring - 1));
-            char* dst = direct ? chain_out + out_bytes * (size_t)k + step_bytes * (size_t)(n_saved - 1) : (char*)h_ring + off;
+            const size_t off = ring_bytes * (size_t)k + step_bytes * (size_t)win.ring_slot(n_saved - 1);
+            char* dst = cp.direct ? chain_out + out_bytes * (size_t)k + step_bytes * (size_t)(n_saved - 1) : (char*)h_ring + off;
             HIP_TRY(hipMemcpyAsync(dst, (char*)d_ring + off, step_bytes, hipMemcpyDeviceToHost, stream));
         }
-        while (next_chunk > oldest)
+        while (win.in_flight())
         {
             const int rc = process_oldest();
             if (rc) return rc;
         }
         HIP_TRY(hipStreamSynchronize(stream));
-        if (direct)
-            copied = n_saved;
-        else
-            for (; copied < n_saved; ++copied)  // (exactly one: every earlier one has been forwarded and copied above)
-                for (int k = 0; k < K; ++k)
-                {
-                    const size_t off = ring_bytes * (size_t)k + step_bytes * (size_t)(copied & (ring - 1));
-                    parallel_memcpy(chain_out + out_bytes * (size_t)k + step_bytes * (size_t)copied, (char*)h_ring + off, step_bytes);
-                }
-        publish_stored(copied);
+        copy_out(win.tail(), true);  // (exactly one: every earlier one has been forwarded and copied above)
+        publish_stored(win.copied);
         return MCMCPP_HIP_OK;
     }
 

@@ -1,0 +1,233 @@
+// run_plan.hpp -- how a run() delivers its stored steps and cuts itself into chunks: ring size, chunk lengths, when the host
+// must wait, where a sub-chunk lands in the caller's array, where a split run cuts so that every rank cuts alike, and the
+// slot bound of its exchange blocks.  Pure functions and one small value type over plain numbers.  No HIP header: this file
+// compiles with the host compiler alone, and tests/test_run_plan.py checks the schedules there, case by case.  The samplers
+// keep every HIP and RCCL call and ask here for the numbers.
+#pragma once
+
+#include <cstddef>
+#include <cstdint>
+
+namespace mcmcpp
+{
+// Stored steps per sub-chunk of a run: what `budget` bytes of device chain hold, at most an eighth of the run (the last
+// host copy, which nothing overlaps, stays short, and a run_async caller sees progress), at least one
+inline int64_t stored_steps_per_subchunk(size_t budget, size_t stored_step_bytes, int64_t n_saved)
+{
+    int64_t s = (int64_t)(budget / stored_step_bytes);
+    const int64_t eighth = (n_saved + 7) / 8;
+    if (s > eighth) s = eighth;
+    if (s < 1) s = 1;
+    return s;
+}
+
+// ---- chain delivery of a whole-ensemble run (Sampler::run_whole) -------------------------------------------------------
+// Nothing: no chain_out, the steps run as one sub-chunk.  Subchunks: device chain halves -> pinned staging -> chain_out.
+// Trickle: the full-step launches forward stored steps themselves (trickle_stored_step) through a ring of `ring` slots on
+// the device -- into its pinned twin, or, when chain_out is pinned memory, straight into their final place (`direct`).
+enum class ChainMode { Nothing, Subchunks, Trickle };
+
+struct ChainRequest
+{
+    size_t step_bytes;       // one stored step of one chain
+    int chains;              // K
+    int64_t n_saved;
+    int32_t interval;
+    bool chain_out, want_accepted;
+    bool full_step;          // a full-step kernel steps the handle
+    size_t subchunk_bytes;   // MCMCPP_HIP_CHAIN_SUBCHUNK_MB in bytes
+    int graph_steps;         // StepPlan::graph_steps
+    long trickle, pinned_direct;  // the knobs
+};
+
+inline ChainMode chain_mode(const ChainRequest& r)
+{
+    if (!r.chain_out) return ChainMode::Nothing;
+    return r.full_step && r.step_bytes % 16 == 0 && r.trickle != 0 ? ChainMode::Trickle : ChainMode::Subchunks;
+}
+// Is it worth asking the runtime whether chain_out is pinned memory?  (The answer goes into plan_chain.)
+inline bool pinned_question_matters(const ChainRequest& r) { return chain_mode(r) == ChainMode::Trickle && r.pinned_direct != 0; }
+
+struct StoredRange { int64_t from, to; };  // stored steps [from, to)
+
+struct ChainPlan
+{
+    int64_t n_saved;
+    ChainMode mode;
+    bool direct;                      // Trickle, straight into a pinned chain_out
+    int64_t sub_saved, n_sub;         // stored steps per sub-chunk, sub-chunks (Trickle: none)
+    int64_t ring, chunk_steps;        // Trickle: ring slots (a power of two), ensemble steps per chunk
+    size_t acc_entries, half_bytes, ring_bytes;  // ensure_run_buffers
+    bool need_host_ring;
+    int64_t slice_bytes;              // RunInfo::slice_bytes: what one launch forwards of a stored step, low bit = direct
+
+    // the stored steps of sub-chunk c
+    StoredRange subchunk(int64_t c) const
+    {
+        const int64_t first = c * sub_saved;
+        return {first, n_saved - first < sub_saved ? n_saved : first + sub_saved};
+    }
+};
+
+inline ChainPlan plan_chain(const ChainRequest& r, bool chain_out_pinned)
+{
+    ChainPlan p = {};
+    p.n_saved = r.n_saved;
+    p.mode = chain_mode(r);
+    p.direct = pinned_question_matters(r) && chain_out_pinned;
+    p.sub_saved = r.chain_out ? stored_steps_per_subchunk(r.subchunk_bytes, r.step_bytes * (size_t)r.chains, r.n_saved) : r.n_saved;
+    if (p.mode == ChainMode::Trickle)
+    {
+        p.ring = 4;
+        while (p.ring < 64 && (size_t)(2 * p.ring) * r.step_bytes <= 2 * r.subchunk_bytes) p.ring *= 2;
+        // the host enqueues one chunk ahead of the one it waits for: stored steps of two chunks are in flight
+        int64_t per_chunk = (r.graph_steps > 0 ? r.graph_steps : 64) / (int64_t)r.interval;
+        if (!p.direct && per_chunk > (p.ring - 2) / 2) per_chunk = (p.ring - 2) / 2;
+        if (per_chunk < 1) per_chunk = 1;
+        p.chunk_steps = per_chunk * r.interval;
+        p.ring_bytes = r.step_bytes * (size_t)p.ring * (size_t)r.chains;
+        p.slice_bytes = (int64_t)(((r.step_bytes + (size_t)r.interval - 1) / (size_t)r.interval + 15) / 16 * 16) | (p.direct ? 1 : 0);
+    }
+    else
+    {
+        p.n_sub = (r.n_saved + p.sub_saved - 1) / p.sub_saved;
+        if (r.chain_out) p.half_bytes = r.step_bytes * (size_t)p.sub_saved * (size_t)r.chains;
+    }
+    p.acc_entries = r.want_accepted ? (size_t)(r.n_saved * (int64_t)r.interval) * (size_t)r.chains : 0;
+    p.need_host_ring = !p.direct;
+    return p;
+}
+
+// ---- the trickle window (Sampler::run_trickle) -------------------------------------------------------------------------
+// Stored step k is complete in the pinned ring when ensemble step (k + 2) * interval - 1 has finished (every launch forwards
+// 1/interval of the previous stored step), and its ring slot is overwritten from step (k + ring + 1) * interval on.  The
+// host enqueues chunks of steps, stays one chunk ahead of the one it waits for, hands out whatever has become complete and
+// never lets the launches run into a slot it has not copied yet.  The run's last stored step has no launches behind it:
+// it is fetched at the end (tail).
+struct TrickleWindow
+{
+    int64_t n_saved, interval, ring, chunk_steps;
+    bool direct;
+    int64_t enq = 0, copied = 0;         // ensemble steps enqueued; stored steps handed to the caller
+    int64_t chunk_end[4] = {0, 0, 0, 0};
+    int64_t next_chunk = 0, oldest = 0;  // chunks enqueued / chunks whose completion has been processed
+
+    TrickleWindow(int64_t n_saved_, int64_t interval_, const ChainPlan& p) : n_saved(n_saved_), interval(interval_), ring(p.ring), chunk_steps(p.chunk_steps), direct(p.direct) {}
+
+    int64_t total() const { return n_saved * interval; }
+    bool all_enqueued() const { return enq == total(); }
+    bool in_flight() const { return next_chunk > oldest; }
+    static int event_slot(int64_t chunk) { return (int)(chunk & 3); }
+    int64_t ring_slot(int64_t stored_step) const { return stored_step & (ring - 1); }
+
+    int64_t next_length() const
+    {
+        int64_t now = (total() - enq < chunk_steps) ? total() - enq : chunk_steps;
+        // The stored steps that become complete with the LAST chunk are copied out with nothing left to overlap: the
+        // run ends with a chunk of one interval, so that this tail is one stored step instead of a chunk's worth
+        // (11.80 -> 11.55 ms per 2 000 steps at C2)
+        if (!direct && now == total() - enq && now > interval) now -= interval;
+        return now;
+    }
+    // at most two chunks in flight, and no launch may forward into a ring slot that is still to be copied out
+    // (forwarding into the final place needs no such care: a device slot is reused ring + 1 stored steps after it
+    //  was written, its forwarding is over one stored step after)
+    bool must_process_oldest_before(int64_t now) const
+    {
+        return in_flight() && (next_chunk - oldest >= 2 || (!direct && enq + now > (copied + ring + 1) * interval));
+    }
+    void enqueued(int64_t now)
+    {
+        enq += now;
+        chunk_end[event_slot(next_chunk)] = enq;
+        ++next_chunk;
+    }
+    // the oldest chunk has finished: the stored steps that are fully forwarded now and were not handed out before
+    StoredRange process_oldest()
+    {
+        const int64_t complete = chunk_end[event_slot(oldest)] / interval - 1;
+        const StoredRange r = {copied, complete > copied ? complete : copied};
+        copied = r.to;
+        ++oldest;
+        return r;
+    }
+    // behind the final synchronisation: what the launches did not forward (exactly one stored step, the last)
+    StoredRange tail()
+    {
+        const StoredRange r = {copied, n_saved};
+        copied = n_saved;
+        return r;
+    }
+};
+
+// ---- the sub-chunk path ------------------------------------------------------------------------------------------------
+// staging -> the caller's memory, stored steps [first, first + count) of chain k: chain k's steps are n_saved steps apart
+// in the caller's array, sub_saved steps apart in the staging buffer
+inline size_t subchunk_chain_offset(size_t step_bytes, int64_t sub_saved, int k) { return step_bytes * (size_t)sub_saved * (size_t)k; }
+struct SubchunkCopy { size_t dst, src, bytes; };
+inline SubchunkCopy subchunk_copy(size_t step_bytes, int64_t sub_saved, int64_t n_saved, int64_t first, int64_t count, int k)
+{
+    return {step_bytes * ((size_t)n_saved * (size_t)k + (size_t)first), subchunk_chain_offset(step_bytes, sub_saved, k), step_bytes * (size_t)count};
+}
+// bytes of a device chain half in use by a sub-chunk of `now` stored steps (the whole half goes to staging in one copy)
+inline size_t subchunk_half_used(size_t step_bytes, int64_t sub_saved, int64_t now, int chains)
+{
+    return step_bytes * (size_t)sub_saved * (size_t)(chains - 1) + step_bytes * (size_t)now;
+}
+
+// ---- split runs (Sampler::run_split) -----------------------------------------------------------------------------------
+// Slots of the pinned staging of stored steps: 256 MiB worth, at least one, at most the run's.  The same number on every
+// rank, whether it stores or not: the chunks of a run end where the staging buffer of the ranks that do store is full.
+inline int64_t split_stage_slots(size_t step_bytes, int64_t n_saved)
+{
+    int64_t slots = (int64_t)(((size_t)256 << 20) / step_bytes);
+    if (slots < 1) slots = 1;
+    if (slots > n_saved) slots = n_saved;
+    return slots;
+}
+// How far the chunk that starts at step s0 goes.  Exchanging moved rows only: 16 steps while the slot bound is being
+// learned, compact_chunk otherwise (the host looks at the overflow flag at the end of a chunk).
+inline int64_t split_chunk_length(int64_t total, int64_t s0, bool compact, bool learning, long compact_chunk, bool any_rank_stores, int32_t interval,
+                                  int64_t stage_slots)
+{
+    int64_t len = total - s0;
+    if (compact)
+    {
+        const int64_t want = learning ? 16 : compact_chunk;
+        if (len > want) len = want;
+    }
+    if (any_rank_stores)
+    {
+        const int64_t fits = (s0 / interval + stage_slots) * (int64_t)interval - s0;  // steps until the staging buffer is full
+        if (len > fits) len = fits;
+    }
+    return len;
+}
+// the slot bound MCMCPP_HIP_COMM_COMPACT_CAP sets, or 0: learned from the run
+inline uint32_t split_cap_set(long knob_cap, uint32_t cap_full) { return knob_cap > 0 ? (uint32_t)(knob_cap < (long)cap_full ? knob_cap : (long)cap_full) : 0; }
+// the slot bound of a run's first chunk (cap_full: a block that holds every walker of an exchange)
+inline uint32_t split_first_cap(bool compact, uint32_t cap_set, uint32_t cap_learned, uint32_t cap_full)
+{
+    if (!compact) return cap_full;
+    if (cap_set) return cap_set;
+    return cap_learned > 0 && cap_learned < cap_full ? cap_learned : cap_full;
+}
+// the next chunk's bound: what the last one needed, plus an eighth and a little
+inline uint32_t split_next_cap(uint32_t max_count, uint32_t cap_full)
+{
+    uint64_t want = (uint64_t)max_count + max_count / 8 + 64;
+    want = (want + 63) & ~(uint64_t)63;
+    return want < cap_full ? (uint32_t)want : cap_full;
+}
+// bytes this rank received in the exchanges of `len` steps: blocks of moved rows (one exchange per ensemble step with the
+// full-step kernels, two otherwise) ...
+inline double split_bytes_compact(int64_t len, bool full_step, int comm_world, size_t block_bytes)
+{
+    return (double)len * (double)(full_step ? 1 : 2) * (double)(comm_world - 1) * (double)block_bytes;
+}
+// ... or the other ranks' whole slices of both colours (the full-step scheme carries the log-posteriors along)
+inline double split_bytes_whole(int64_t len, bool full_step, int comm_world, int shard_count, int dims, size_t elem_size)
+{
+    return (double)len * (double)(comm_world - 1) * (double)shard_count * 2.0 * (double)((size_t)dims + (full_step ? 1 : 0)) * elem_size;
+}
+}  // namespace mcmcpp

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "launch_table.hpp"
+#include "run_plan.hpp"
 #include "sampler_base.hpp"
 #include "tie_eps.h"
 
@@ -122,15 +123,16 @@ inline RunInfo idle_run_info()
     return ri;
 }
 
-// Stored steps per sub-chunk of a run: what `budget` bytes of device chain hold, at most an eighth of the run (the last
-// host copy, which nothing overlaps, stays short, and a run_async caller sees progress), at least one
-inline int64_t stored_steps_per_subchunk(size_t budget, size_t stored_step_bytes, int64_t n_saved)
+// The run record of a run(): the idle one with the device chain (or ring), the per-step counters, the slicing interval and
+// the size of a stored step; the caller sets what its path adds (chain_slot_base; stage, slot_mask, slice_bytes).
+inline RunInfo run_info_of_run(void* chain, uint32_t* accepted_per_step, int32_t interval, size_t step_bytes)
 {
-    int64_t s = (int64_t)(budget / stored_step_bytes);
-    const int64_t eighth = (n_saved + 7) / 8;
-    if (s > eighth) s = eighth;
-    if (s < 1) s = 1;
-    return s;
+    RunInfo ri = idle_run_info();
+    ri.chain = chain;
+    ri.accepted_per_step = accepted_per_step;
+    ri.interval = interval;
+    ri.step_bytes = (int64_t)step_bytes;
+    return ri;
 }
 
 // S<double> or S<float> by cfg.dtype, then its init; nullptr: out of host memory.  *rc receives the init result, the

@@ -396,6 +396,24 @@ def test_stored_steps_forwarded_by_the_launches(W, D, dtype, interval, n_saved):
     _assert_same_state(orc, hip)
 
 
+@pytest.mark.parametrize("pinned", [False, True], ids=["pageable", "pinned"])
+def test_smallest_ring_of_stored_steps_at_interval_3(monkeypatch, pinned):
+    """A ring of 4 slots (a 1 MiB budget against 524 800-byte steps) at a slicing interval above 1: into pageable memory the host
+    may run one stored step ahead of what it has copied out (chunks of one interval, tests/test_run_plan.py); into pinned
+    memory the launches write the steps in place.  Chain, accepted counts and final state equal the oracle's, bit for bit."""
+    monkeypatch.setenv("MCMCPP_HIP_CHAIN_SUBCHUNK_MB", "1")
+    W, D, interval = 2048 + 2, 32, 3
+    orc, hip = _oracle_and_hip(W, D, po.CALC_DENSE_GAUSSIAN, po.F64, seed=8, steps=0)
+    block = capi.pinned_empty((12, W, D)) if pinned else np.empty((12, W, D))
+    block[:] = np.nan
+    for first, part in ((0, 10), (10, 2)):      # a second, short run on the same handle
+        oc, oa = orc.run(part, interval=interval, mode=po.MODE_COUNTER, threads=4)
+        hc, ha = hip.run(part, interval=interval, out=block[first:first + part])
+        np.testing.assert_array_equal(hc, oc)
+        np.testing.assert_array_equal(ha, oa)
+    _assert_same_state(orc, hip)
+
+
 def test_hip_reproduces_reference_own_test_run():
     """The reference's SkewedGaussian/StretchMove test end to end: 320 x 2, slicing 30, 40 019 stored steps
     (1.2 M ensemble steps); accepted/total exactly as the reference prints them."""
