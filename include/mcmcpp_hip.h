@@ -310,7 +310,9 @@ int mcmcpp_hip_synchronize(mcmcpp_hip_sampler* h);
  * correlation matrix of stored chain steps.  The sums  s_i = sum x_i,  S_ij = sum x_i x_j  over all samples are a
  * rank-N update X^T X and run on the matrix cores (fp64 accumulation for both element types); the slicing the
  * reference's calculateCovar(start, end, sliceInterval) does while iterating is expressed by step_stride.
- *   create      dtype MCMCPP_HIP_F64 / _F32 = the chain's ParamType; device -1 = current
+ *   create      dtype MCMCPP_HIP_F64 / _F32 = the chain's ParamType; device -1 = current; 1 <= num_params <= 1024.
+ *               MCMCPP_HIP_MOMENTS_CHUNK_MB (read here, default 64) sizes the chunks add_steps uploads host steps in
+ *               (a chunk holds at least one step)
  *   add_steps   n_steps stored steps of num_walkers*num_params elements each (host memory), consecutive ones
  *               step_stride steps apart; may be called repeatedly (chain blocks, several chains)
  *   finish      CovarianceMatrix::finalizeMatrix: mean[D], cov[D*D], corr[D*D] in the chain's element type (any may

@@ -3,7 +3,8 @@
 //
 // The reference walks the chain sample by sample and Kahan-sums x_i and x_i*x_j (D*(D+1)/2 products per sample).
 // That is a rank-N update S = X^T X of a D x D matrix -- GEMM-shaped work, so it runs on the matrix cores:
-//   * stored steps ([n][W][D], host memory) are uploaded in chunks; a wavefront takes samples four at a time, every
+//   * stored steps ([n][W][D], host memory) are uploaded in chunks of MCMCPP_HIP_MOMENTS_CHUNK_MB (read at create,
+//     default 64; at least one step); a wavefront takes samples four at a time, every
 //     lane holding element (sample l/16, parameter 16 t + l%16) of the 4 x D slab -- which is at once the A operand
 //     (16 parameters x 4 samples) and the B operand (4 samples x 16 parameters) of v_mfma_f64_16x16x4_f64
 //     (layouts measured in tools/mfma_probe.hip), so one 16-byte-coalesced load feeds both sides;
@@ -13,11 +14,13 @@
 //     fixed order at the end: results do not depend on scheduling.
 // Parity bar (tests/test_moments.py): the reference's order of operations cannot be kept by a parallel sum, so
 // covariance and correlation agree with the oracle's restatement of the reference within a stated tolerance
-// (fp64: 1e-10 of sqrt(var_i var_j); the device sum is the more accurate of the two for fp32 chains).
+// (fp64: 1e-10 of sqrt(var_i var_j); the device sum is the more accurate of the two for fp32 chains), and with an
+// extended-precision reference within a bar that scales with the means (tests/moments_reference.py).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
@@ -159,6 +162,7 @@ struct mcmcpp_hip_moments
     bool matrix_core = false;
     long long points = 0;       // samples accumulated so far
     size_t slot_elems = 0;
+    size_t chunk_bytes = 0;     // MCMCPP_HIP_MOMENTS_CHUNK_MB
     mcmcpp::DeviceBuffer<double> d_partial, d_total;
     mcmcpp::DeviceBuffer<char> d_chunk;
     hipStream_t stream = nullptr;  // (destroyed after the buffers: mcmcpp_hip_moments_destroy)
@@ -235,6 +239,13 @@ int mcmcpp_hip_moments_create(int32_t dtype, int32_t device, int32_t num_walkers
     m->slots = m->matrix_core ? prop.multiProcessorCount * kMomentWavesPerBlock * 2 : prop.multiProcessorCount;  // two workgroups per CU
     while (m->slots > kMomentWavesPerBlock && (size_t)m->slots * m->slot_elems * sizeof(double) > ((size_t)256 << 20)) m->slots /= 2;
     m->slots -= m->slots % kMomentWavesPerBlock;
+    size_t mb = 64;
+    if (const char* env = std::getenv("MCMCPP_HIP_MOMENTS_CHUNK_MB"))
+    {
+        const long long v = std::atoll(env);
+        if (v >= 1) mb = (size_t)v;
+    }
+    m->chunk_bytes = mb << 20;
     if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess ||
         m->d_partial.alloc(sizeof(double) * (size_t)m->slots * m->slot_elems) != hipSuccess ||
         m->d_total.alloc(sizeof(double) * m->slot_elems) != hipSuccess ||
@@ -276,8 +287,8 @@ int mcmcpp_hip_moments_add_steps(mcmcpp_hip_moments* m, const void* steps, int64
     MOM_TRY(hipSetDevice(m->device));
     const size_t esize = m->dtype == MCMCPP_HIP_F64 ? 8 : 4;
     const size_t step_bytes = esize * (size_t)m->W * m->D;
-    // chunks of up to 64 MiB (at least one step)
-    int64_t per_chunk = (int64_t)(((size_t)64 << 20) / step_bytes);
+    // chunks of up to MCMCPP_HIP_MOMENTS_CHUNK_MB (at least one step)
+    int64_t per_chunk = (int64_t)(m->chunk_bytes / step_bytes);
     if (per_chunk < 1) per_chunk = 1;
     if (per_chunk > n_steps) per_chunk = n_steps;
     if (mcmcpp::grow(m->d_chunk, step_bytes * (size_t)per_chunk, m->stream)) return fail(m, MCMCPP_HIP_E_NOMEM, "moments_add_steps: cannot allocate the upload buffer");
