@@ -157,7 +157,9 @@ int mcmcpp_hip_register_calculator(int32_t calc_id, const void* table_f64, const
  *
  * Contract:
  *   - the callback runs on the thread that executes the run: for mcmcpp_hip_run_async that is the handle's worker thread;
- *   - it is called once per half-step with count = W/2; mcmcpp_hip_calc_logp calls it in chunks of at most W/2;
+ *   - it is called once per half-step with count = W/2; mcmcpp_hip_calc_logp calls it in chunks of at most W/2, and
+ *     mcmcpp_hip_calc_logp_device likewise, with pointers into the caller's own device arrays instead of the handle's
+ *     buffers (a callback must not assume it is handed device_proposals / device_logp);
  *   - it either enqueues its work on hip_stream or finishes that work before it returns;
  *   - it returns 0 on success.  Any other value ends the run with MCMCPP_HIP_E_CALLBACK (the message names the value), and
  *     the walker state counts as undefined until the next set_state.
@@ -203,6 +205,32 @@ int mcmcpp_hip_run(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, voi
 int mcmcpp_hip_run_async(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step);
 int mcmcpp_hip_wait_stored(mcmcpp_hip_sampler* h, int64_t count);
 int mcmcpp_hip_run_wait(mcmcpp_hip_sampler* h);
+
+/* mcmcpp_hip_run with the stored steps left in DEVICE memory: the same steps, the same stream, the same counters and the same
+ * walker state afterwards, but the chain never crosses the host link.  What follows a run -- covariance, histograms,
+ * autocorrelation times (the *_device entry points below), the log-posteriors of the stored rows
+ * (mcmcpp_hip_calc_logp_device), the caller's own kernels or torch -- reads it where it was written.
+ *   device_chain       caller-owned memory of the handle's device, 16-byte aligned, K*n_saved*W*D elements laid out
+ *                      [K][n_saved][W][D] exactly as mcmcpp_hip_run lays out chain_out (K = max(num_chains, 1)).  Nothing
+ *                      outside it is written.  NULL only with n_saved == 0.
+ *   accepted_per_step  HOST memory as for mcmcpp_hip_run (it is small), or NULL
+ * Synchronous: when it returns every stored step is complete in device_chain and visible to work on any stream.
+ * The launch that makes a stored step writes it to its final place: there is no ring, no staging buffer, no copy and no
+ * host wait for the chain inside the run, whichever kernels step the handle (every kernel forms the chain cell's address
+ * in 64 bits, so device_chain may lie anywhere and be of any size).
+ * Supported: stretch-move handles that hold a whole ensemble (several chains and per-chain parameters included), the
+ * differential-evolution mover and batch targets.  Returns MCMCPP_HIP_E_ARG (with a message) for a NULL pointer with
+ * n_saved > 0, a pointer that is not 16-byte aligned, one that hipPointerGetAttributes does not report as memory of the
+ * handle's device -- a host pointer, pinned or not, is refused before anything is launched, never dereferenced -- and a
+ * destination that does not end inside the allocation hipMemGetAddressRange reports around the pointer (the array lies
+ * in ONE allocation); MCMCPP_HIP_E_UNSUPPORTED for sharded handles (they store through mcmcpp_hip_bind_device_chain) and
+ * handles with a communicator; MCMCPP_HIP_E_STATE as mcmcpp_hip_run.
+ * run_device_async pairs with mcmcpp_hip_wait_stored and mcmcpp_hip_run_wait like mcmcpp_hip_run_async: wait_stored(c)
+ * returns when the first c stored steps of every chain are complete in device_chain; a copy or kernel enqueued on any
+ * stream after it has returned reads them.  (Argument errors of the asynchronous form are reported by run_wait.) */
+int mcmcpp_hip_run_device(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, void* device_chain, uint32_t* accepted_per_step);
+int mcmcpp_hip_run_device_async(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, void* device_chain,
+                                uint32_t* accepted_per_step);
 
 /* Pinned (page-locked, device-visible) host memory for Chain blocks (stands in for the allocation of
  * Chain/ChainBlock.h:115-131).  When chain_out of mcmcpp_hip_run lies in such memory the step launches forward stored
@@ -261,6 +289,18 @@ int mcmcpp_hip_set_chain_params(mcmcpp_hip_sampler* h, int32_t chain, const void
 /* mcmcpp_hip_calc_logp with chain `chain`'s parameters (same refusals as mcmcpp_hip_set_chain_params, except that a
  * calculator without parameters is evaluated: all its chains are the same). */
 int mcmcpp_hip_calc_logp_chain(mcmcpp_hip_sampler* h, int32_t chain, const void* positions, int64_t count, void* logp_out);
+
+/* mcmcpp_hip_calc_logp_chain with device input and device output and no copies: `count` D-vectors at device_positions
+ * (16-byte aligned when a row is a whole number of 16-byte pieces, element-aligned otherwise; e.g. the rows of a chain
+ * written by mcmcpp_hip_run_device), their log-posteriors to device_logp_out[count].  Returns when they are there.
+ * chain selects chain `chain`'s parameters (0 <= chain < K); differential-evolution handles evaluate with their create-time
+ * parameters and batch handles call the callback directly on the caller's rows (both pointers 16-byte aligned), in chunks
+ * of at most W/2 rows that are a whole number of 16-byte pieces of log-posteriors, so that the callback is handed 16-byte
+ * aligned pointers as in a run (W/2 below 16 / sizeof(element) cannot be cut so: its later chunks are element-aligned)
+ * -- for both, chain must be 0.  MCMCPP_HIP_E_ARG for a chain out of range or a pointer that is
+ * not memory of the handle's device (checked as for mcmcpp_hip_run_device). */
+int mcmcpp_hip_calc_logp_device(mcmcpp_hip_sampler* h, int32_t chain, const void* device_positions, int64_t count,
+                                void* device_logp_out);
 
 /* ---- measurement ---------------------------------------------------------------------------------- */
 
@@ -324,9 +364,14 @@ int mcmcpp_hip_moments_create(int32_t dtype, int32_t device, int32_t num_walkers
 void mcmcpp_hip_moments_destroy(mcmcpp_hip_moments* m);
 int mcmcpp_hip_moments_reset(mcmcpp_hip_moments* m);
 int mcmcpp_hip_moments_add_steps(mcmcpp_hip_moments* m, const void* steps, int64_t n_steps, int64_t step_stride);
-/* the same for n_steps contiguous stored steps that already live in device memory (e.g. a device chain bound with
- * mcmcpp_hip_bind_device_chain): no upload; returns when the sums are updated */
+/* the same for n_steps contiguous stored steps that already live in device memory (e.g. a chain written by
+ * mcmcpp_hip_run_device, or a device chain bound with mcmcpp_hip_bind_device_chain): no upload; returns when the sums are
+ * updated */
 int mcmcpp_hip_moments_add_device_steps(mcmcpp_hip_moments* m, const void* device_steps, int64_t n_steps);
+/* ... and with the slicing of add_steps: n_steps stored steps, consecutive ones step_stride steps apart in device memory
+ * (stride 1 is add_device_steps).  The steps used are gathered on the device into the accumulator's chunk buffer, in the
+ * chunks add_steps uploads: the sums are grouped as add_steps groups them. */
+int mcmcpp_hip_moments_add_device_steps_strided(mcmcpp_hip_moments* m, const void* device_steps, int64_t n_steps, int64_t step_stride);
 int mcmcpp_hip_moments_finish(mcmcpp_hip_moments* m, int64_t* num_points, void* mean, void* cov, void* corr);
 const char* mcmcpp_hip_moments_last_error(const mcmcpp_hip_moments* m);
 
@@ -346,8 +391,8 @@ const char* mcmcpp_hip_moments_last_error(const mcmcpp_hip_moments* m);
  * walker's function; uninitialised memory for the first), see INTEGRATION.md 4b. */
 int mcmcpp_hip_autocorr_times(int32_t dtype, int32_t device, const void* const* steps, int64_t n_steps, int32_t num_walkers, int32_t num_params,
                               int32_t walkers_to_use, int32_t window_scaling, void* times, void* functions);
-/* the same for a chain that already lives in device memory: n_steps contiguous stored steps ([n_steps][W][D], e.g. a device
- * chain bound with mcmcpp_hip_bind_device_chain); no upload */
+/* the same for a chain that already lives in device memory: n_steps contiguous stored steps ([n_steps][W][D], e.g. a chain
+ * written by mcmcpp_hip_run_device, or a device chain bound with mcmcpp_hip_bind_device_chain); no upload */
 int mcmcpp_hip_autocorr_times_device(int32_t dtype, int32_t device, const void* device_steps, int64_t n_steps, int32_t num_walkers,
                                      int32_t num_params, int32_t walkers_to_use, int32_t window_scaling, void* times, void* functions);
 const char* mcmcpp_hip_autocorr_last_error(void);
@@ -366,8 +411,9 @@ const char* mcmcpp_hip_autocorr_last_error(void);
  *   compute         n_steps pointers to the steps to use (host memory, the caller has applied sliceInterval); steps that
  *                   are contiguous in memory are uploaded in one copy.  Replaces the previous result.  A NaN sample fails
  *                   the call with MCMCPP_HIP_E_ARG; the handle stays usable.
- *   compute_device  n_steps contiguous steps [n][W][P] in device memory (e.g. a device chain bound with
- *                   mcmcpp_hip_bind_device_chain); every slice_interval-th from the first is used; no upload.
+ *   compute_device  n_steps contiguous steps [n][W][P] in device memory (e.g. a chain written by mcmcpp_hip_run_device, or a
+ *                   device chain bound with mcmcpp_hip_bind_device_chain); every slice_interval-th from the first is used;
+ *                   no upload.
  *   result          bounds [P][2] = (low edge, bin width) in T, as the reference's paramBounds after findBinning;
  *                   single [P][bins]; pairs [P(P-1)/2][bins][bins] (pair i > j at i(i-1)/2 + j, element [bin_i][bin_j]) or
  *                   NULL; clamped [P]; *num_points = samples used.  Any pointer may be NULL. */

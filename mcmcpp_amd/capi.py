@@ -26,6 +26,7 @@ EXPORTS = [
     "mcmcpp_hip_get_counters", "mcmcpp_hip_calc_logp", "mcmcpp_hip_set_chain_params", "mcmcpp_hip_calc_logp_chain", "mcmcpp_hip_last_run_timing", "mcmcpp_hip_last_run_host_timing",
     "mcmcpp_hip_comm_unique_id", "mcmcpp_hip_last_run_exchange", "mcmcpp_hip_run_async", "mcmcpp_hip_wait_stored", "mcmcpp_hip_run_wait",
     "mcmcpp_hip_host_alloc", "mcmcpp_hip_host_free",
+    "mcmcpp_hip_run_device", "mcmcpp_hip_run_device_async", "mcmcpp_hip_calc_logp_device", "mcmcpp_hip_moments_add_device_steps_strided",
     "mcmcpp_hip_half_step_async", "mcmcpp_hip_bind_device_chain", "mcmcpp_hip_device_positions",
     "mcmcpp_hip_shard_span", "mcmcpp_hip_synchronize",
     "mcmcpp_hip_moments_create", "mcmcpp_hip_moments_destroy", "mcmcpp_hip_moments_reset", "mcmcpp_hip_moments_add_steps",
@@ -101,6 +102,10 @@ def lib():
         L.mcmcpp_hip_comm_unique_id.argtypes = [vp]
         L.mcmcpp_hip_last_run_exchange.argtypes = [vp, dp, C.POINTER(i64), C.POINTER(i64)]
         L.mcmcpp_hip_run_async.argtypes = [vp, i64, i32, vp, vp]
+        if hasattr(L, "mcmcpp_hip_run_device"):  # (absent from earlier builds selected with MCMCPP_HIP_LIB)
+            L.mcmcpp_hip_run_device.argtypes = [vp, i64, i32, vp, vp]
+            L.mcmcpp_hip_run_device_async.argtypes = [vp, i64, i32, vp, vp]
+            L.mcmcpp_hip_calc_logp_device.argtypes = [vp, i32, vp, i64, vp]
         L.mcmcpp_hip_wait_stored.argtypes = [vp, i64]
         L.mcmcpp_hip_run_wait.argtypes = [vp]
         L.mcmcpp_hip_host_alloc.argtypes = [C.c_uint64]
@@ -120,6 +125,8 @@ def lib():
             L.mcmcpp_hip_moments_reset.argtypes = [vp]
             L.mcmcpp_hip_moments_add_steps.argtypes = [vp, vp, i64, i64]
             L.mcmcpp_hip_moments_add_device_steps.argtypes = [vp, vp, i64]
+            if hasattr(L, "mcmcpp_hip_moments_add_device_steps_strided"):
+                L.mcmcpp_hip_moments_add_device_steps_strided.argtypes = [vp, vp, i64, i64]
             L.mcmcpp_hip_moments_finish.argtypes = [vp, C.POINTER(i64), vp, vp, vp]
             L.mcmcpp_hip_moments_last_error.argtypes = [vp]
             L.mcmcpp_hip_moments_last_error.restype = C.c_char_p
@@ -169,6 +176,47 @@ def np_dtype(dtype):
 
 def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _is_tensor(x):
+    """A torch tensor?  (Without importing torch: whoever holds a tensor has imported it.)"""
+    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
+
+
+def _torch_dtype(dtype):
+    import torch
+    return torch.float64 if dtype == F64 else torch.float32
+
+
+def _after_torch(t):
+    """The library launches on streams of its own, which wait for nothing torch has enqueued.  Before a tensor's memory is
+    handed to it, the current torch stream of the tensor's device is therefore drained: the work that produces the tensor, a
+    copy that made it contiguous, and whatever last used the block the caching allocator gave a fresh tensor.  (Work the
+    caller has put on another torch stream is the caller's to order, as it is between two torch streams.)  The library's
+    calls return when their results are there, so nothing is needed behind them."""
+    import torch
+    torch.cuda.current_stream(t.device).synchronize()
+
+
+def _device_steps(steps, n_steps, W, D, dtype, device=None):
+    """(address, n_steps) of stored steps in device memory: a contiguous device tensor (n, W, D) of the handle's dtype (and
+    device, where known), or an integer address with n_steps given."""
+    if not _is_tensor(steps):
+        if n_steps is None:
+            raise ValueError("an integer device address needs n_steps")
+        return int(steps), int(n_steps)
+    if steps.dim() != 3 or tuple(steps.shape[1:]) != (W, D):
+        raise ValueError("device steps must have shape (n, %d, %d), not %s" % (W, D, tuple(steps.shape)))
+    if steps.dtype != _torch_dtype(dtype):
+        raise ValueError("device steps must be %s, not %s" % (_torch_dtype(dtype), steps.dtype))
+    if not steps.is_cuda or not steps.is_contiguous():
+        raise ValueError("device steps must be a contiguous tensor in device memory")
+    if device is not None and device >= 0 and steps.device.index != device:
+        raise ValueError("device steps are on device %d, the handle on device %d" % (steps.device.index, device))
+    if n_steps is not None and n_steps != steps.shape[0]:
+        raise ValueError("n_steps = %d, but the tensor holds %d steps" % (n_steps, steps.shape[0]))
+    _after_torch(steps)
+    return steps.data_ptr(), int(steps.shape[0])
 
 
 class HipError(RuntimeError):
@@ -243,6 +291,7 @@ class HipSampler:
         tt = torch.float64 if self.dtype == F64 else torch.float32
         n = self.W // 2
         # the proposals are formed in, and the log-posteriors read from, these tensors' storage
+        self._foreign = None  # calc_logp_device: (rows, out), the caller's tensors the callback is given pieces of
         self._prop = torch.empty((n, self.D), dtype=tt, device=dev)
         self._lp = torch.empty((n,), dtype=tt, device=dev)
         prop_ptr = self._prop.data_ptr()
@@ -250,14 +299,26 @@ class HipSampler:
 
         def trampoline(user, proposals, logp_out, count, num_params, hip_stream):
             try:
-                assert proposals == prop_ptr and num_params == self.D and 0 < count <= n
+                assert num_params == self.D and 0 < count <= n
+                if proposals == prop_ptr:
+                    x, lp = self._prop[:count], self._lp[:count]
+                else:
+                    # mcmcpp_hip_calc_logp_device: rows of the caller's own.  Torch cannot wrap a bare address, so the rows
+                    # must be a piece of the tensors HipSampler.calc_logp_device has announced
+                    if self._foreign is None:
+                        raise ValueError("a torch log_prob handle evaluates foreign rows through HipSampler.calc_logp_device only")
+                    rows, out = self._foreign
+                    first, rest = divmod(proposals - rows.data_ptr(), rows.element_size() * self.D)
+                    assert rest == 0 and 0 <= first and first + count <= rows.shape[0]
+                    assert logp_out == out.data_ptr() + first * out.element_size()
+                    x, lp = rows[first:first + count], out[first:first + count]
                 # (the current stream is thread-local: run_async calls from the handle's worker thread)
                 with torch.cuda.device(dev), torch.cuda.stream(ts):
-                    y = log_prob(self._prop[:count])
+                    y = log_prob(x)
                     if not isinstance(y, torch.Tensor) or tuple(y.shape) != (count,) or y.dtype != tt or y.device != dev:
                         raise TypeError("log_prob must return a tensor of shape (%d,), dtype %s on %s; got %s" % (
                             count, tt, dev, (tuple(y.shape), y.dtype, y.device) if isinstance(y, torch.Tensor) else type(y)))
-                    self._lp[:count].copy_(y)
+                    lp.copy_(y)
                 return 0
             except BaseException as e:  # (nothing may propagate through the C frames)
                 self._cb_error = e
@@ -309,6 +370,67 @@ class HipSampler:
         self._async_keep = (chain, acc)
         self._check(lib().mcmcpp_hip_run_async(self.h, n_saved, interval, _ptr(chain), _ptr(acc)))
         return chain, acc
+
+    def _device_out(self, n_saved, out):
+        """(address, what run_device returns) of a device destination: a fresh tensor, the caller's tensor, or (address, nbytes)"""
+        shape = ((self.K,) if self.K > 1 else ()) + (n_saved, self.W, self.D)
+        if out is None:
+            import torch
+            dev = torch.device("cuda", self.cfg.device if self.cfg.device >= 0 else torch.cuda.current_device())
+            out = torch.empty(shape, dtype=_torch_dtype(self.dtype), device=dev)
+        if _is_tensor(out):
+            if tuple(out.shape) != shape or out.dtype != _torch_dtype(self.dtype) or not out.is_cuda or not out.is_contiguous():
+                raise ValueError("out must be a contiguous device tensor of shape %s and dtype %s" % (shape, _torch_dtype(self.dtype)))
+            if self.cfg.device >= 0 and out.device.index != self.cfg.device:
+                raise ValueError("out is on device %d, the handle on device %d" % (out.device.index, self.cfg.device))
+            _after_torch(out)
+            return out.data_ptr(), out
+        ptr, nbytes = out
+        need = int(np.prod(shape)) * np.dtype(self.np_t).itemsize
+        if nbytes < need:
+            raise ValueError("out holds %d bytes, the run stores %d" % (nbytes, need))
+        return int(ptr), out
+
+    def run_device(self, n_saved, interval=1, out=None, want_accepted=True):
+        """run() with the stored steps left in device memory (mcmcpp_hip_run_device).  Returns (chain, acc): chain a torch
+        tensor (n_saved, W, D) -- (K, n_saved, W, D) with several chains -- on the handle's device, acc the per-step accepted
+        counts as numpy (None unless want_accepted).  out: a contiguous device tensor of that shape and dtype to store into,
+        or, for callers without torch, an (integer device address, nbytes) pair, which is then returned as it is."""
+        ptr, chain = self._device_out(n_saved, out)
+        lead = (self.K,) if self.K > 1 else ()
+        acc = np.zeros(lead + (n_saved * interval,), dtype=np.uint32) if want_accepted else None
+        self._check(lib().mcmcpp_hip_run_device(self.h, n_saved, interval, C.c_void_p(ptr), _ptr(acc)))
+        return chain, acc
+
+    def run_device_async(self, n_saved, interval=1, out=None, want_accepted=False):
+        """Start run_device on the handle's worker thread; wait_stored(c) returns when the first c stored steps of every chain
+        are complete in the returned device tensor, run_wait when the run is over."""
+        ptr, chain = self._device_out(n_saved, out)
+        lead = (self.K,) if self.K > 1 else ()
+        acc = np.zeros(lead + (n_saved * interval,), dtype=np.uint32) if want_accepted else None
+        self._async_keep = (chain, acc)
+        self._check(lib().mcmcpp_hip_run_device_async(self.h, n_saved, interval, C.c_void_p(ptr), _ptr(acc)))
+        return chain, acc
+
+    def calc_logp_device(self, x, chain=0):
+        """Log-posteriors of the rows of the device tensor x (..., D), e.g. of a chain run_device wrote, as a device tensor
+        (...,): no host copies (mcmcpp_hip_calc_logp_device; an x that is not contiguous is made so on the device first).
+        chain=k: with chain k's parameters.  A batch target -- C callback or torch log_prob -- is called on the rows
+        themselves, in chunks of at most W/2."""
+        import torch
+        if not _is_tensor(x) or x.dim() < 1 or x.shape[-1] != self.D or x.dtype != _torch_dtype(self.dtype) or not x.is_cuda:
+            raise ValueError("x must be a device tensor (..., %d) of dtype %s" % (self.D, _torch_dtype(self.dtype)))
+        rows = x.contiguous().view(-1, self.D)
+        out = torch.empty((rows.shape[0],), dtype=rows.dtype, device=rows.device)
+        _after_torch(rows)  # (x's producer, the copy behind contiguous(), the last user of out's block)
+        if self._torch_stream is not None:
+            self._foreign = (rows, out)
+        try:
+            self._check(lib().mcmcpp_hip_calc_logp_device(self.h, chain, C.c_void_p(rows.data_ptr()), rows.shape[0], C.c_void_p(out.data_ptr())))
+        finally:
+            if self._torch_stream is not None:
+                self._foreign = None
+        return out.view(x.shape[:-1])
 
     def wait_stored(self, count):
         self._check(lib().mcmcpp_hip_wait_stored(self.h, count))
@@ -387,7 +509,7 @@ class HipMoments:
     """Device-side Analysis::CovarianceMatrix (include/mcmcpp_hip.h, mcmcpp_hip_moments_*)."""
 
     def __init__(self, num_walkers, num_params, dtype=F64, device=-1):
-        self.W, self.D, self.dtype = num_walkers, num_params, dtype
+        self.W, self.D, self.dtype, self.device = num_walkers, num_params, dtype, device
         self.h = C.c_void_p()
         rc = lib().mcmcpp_hip_moments_create(dtype, device, num_walkers, num_params, C.byref(self.h))
         if rc != OK:
@@ -404,9 +526,15 @@ class HipMoments:
         used = (steps.shape[0] + slice_interval - 1) // slice_interval
         self._check(lib().mcmcpp_hip_moments_add_steps(self.h, _ptr(steps), used, slice_interval))
 
-    def add_device_steps(self, device_ptr, n_steps):
-        """n_steps contiguous stored steps in device memory (an integer address, e.g. torch.Tensor.data_ptr())."""
-        self._check(lib().mcmcpp_hip_moments_add_device_steps(self.h, C.c_void_p(device_ptr), n_steps))
+    def add_device_steps(self, steps, n_steps=None, slice_interval=1):
+        """Stored steps in device memory: a contiguous device tensor (n, W, D), or an integer address (e.g.
+        torch.Tensor.data_ptr()) of n_steps contiguous steps.  Every slice_interval-th step is used, starting with the first."""
+        ptr, n = _device_steps(steps, n_steps, self.W, self.D, self.dtype, self.device)
+        if slice_interval == 1:
+            self._check(lib().mcmcpp_hip_moments_add_device_steps(self.h, C.c_void_p(ptr), n))
+        else:
+            used = (n + slice_interval - 1) // slice_interval
+            self._check(lib().mcmcpp_hip_moments_add_device_steps_strided(self.h, C.c_void_p(ptr), used, slice_interval))
 
     def finish(self):
         t = np_dtype(self.dtype)
@@ -434,7 +562,7 @@ class HipHistograms:
     """Device-side Analysis::CornerHistograms / PercentileAndMaximumFinder (include/mcmcpp_hip.h, mcmcpp_hip_histograms_*)."""
 
     def __init__(self, num_walkers, num_params, bins, with_pairs=True, dtype=F64, device=-1):
-        self.W, self.P, self.bins, self.with_pairs, self.dtype = num_walkers, num_params, bins, bool(with_pairs), dtype
+        self.W, self.P, self.bins, self.with_pairs, self.dtype, self.device = num_walkers, num_params, bins, bool(with_pairs), dtype, device
         self.h = C.c_void_p()
         rc = lib().mcmcpp_hip_histograms_create(dtype, device, num_walkers, num_params, bins, 1 if with_pairs else 0, C.byref(self.h))
         if rc != OK:
@@ -458,9 +586,11 @@ class HipHistograms:
         self._keep = blocks
         self._check(lib().mcmcpp_hip_histograms_compute(self.h, ptrs, len(blocks)))
 
-    def compute_device(self, device_ptr, n_steps, slice_interval=1):
-        """n_steps contiguous stored steps in device memory (an integer address, e.g. torch.Tensor.data_ptr())."""
-        self._check(lib().mcmcpp_hip_histograms_compute_device(self.h, C.c_void_p(device_ptr), n_steps, slice_interval))
+    def compute_device(self, steps, n_steps=None, slice_interval=1):
+        """Stored steps in device memory: a contiguous device tensor (n, W, P), or an integer address (e.g.
+        torch.Tensor.data_ptr()) of n_steps contiguous steps."""
+        ptr, n = _device_steps(steps, n_steps, self.W, self.P, self.dtype, self.device)
+        self._check(lib().mcmcpp_hip_histograms_compute_device(self.h, C.c_void_p(ptr), n, slice_interval))
 
     def result(self, want_pairs=None):
         """(num_points, bounds[(P, 2)] in the chain's type, single[(P, bins)], pairs[(P(P-1)/2, bins, bins)] or None, clamped[P])"""
@@ -513,8 +643,25 @@ def autocorr_times(steps, walkers_to_use=0, window_scaling=4, want_functions=Fal
     return (times, functions) if want_functions else times
 
 
-def autocorr_times_device(device_ptr, n_steps, W, D, dtype=F64, walkers_to_use=0, window_scaling=4, device=-1):
-    """The same for n_steps contiguous stored steps in device memory (an integer address, e.g. torch.Tensor.data_ptr())."""
+def autocorr_times_device(steps, n_steps=None, W=None, D=None, dtype=None, walkers_to_use=0, window_scaling=4, device=-1):
+    """The same for stored steps in device memory: a contiguous device tensor (n, W, D) -- shape, dtype and device are the
+    tensor's, and are checked against W, D, dtype and device where those are given -- or an integer address (e.g.
+    torch.Tensor.data_ptr()) of n_steps contiguous steps of W x D elements (dtype: F64 unless given)."""
+    if _is_tensor(steps):
+        import torch
+        if steps.dim() != 3 or steps.dtype not in (torch.float64, torch.float32):
+            raise ValueError("device steps must be a float64 or float32 tensor (n, W, D)")
+        tensor_dtype = F64 if steps.dtype == torch.float64 else F32
+        if dtype is not None and dtype != tensor_dtype:
+            raise ValueError("device steps are %s, not the dtype asked for" % steps.dtype)
+        dtype = tensor_dtype
+        W, D = (steps.shape[1] if W is None else W), (steps.shape[2] if D is None else D)
+        if device < 0 and steps.is_cuda:
+            device = steps.device.index
+    elif W is None or D is None:
+        raise ValueError("an integer device address needs n_steps, W and D")
+    dtype = F64 if dtype is None else dtype
+    device_ptr, n_steps = _device_steps(steps, n_steps, W, D, dtype, device)
     times = np.zeros(D, np_dtype(dtype))
     rc = lib().mcmcpp_hip_autocorr_times_device(dtype, device, C.c_void_p(device_ptr), n_steps, W, D, walkers_to_use, window_scaling, _ptr(times), None)
     if rc != OK:

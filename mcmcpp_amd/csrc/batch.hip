@@ -308,12 +308,23 @@ public:
         return MCMCPP_HIP_OK;
     }
 
-    int run(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step) override
+    int run(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step) override { return run_to(n_saved, interval, chain_out, accepted_per_step, false); }
+
+    // The same run with the stored steps left in the caller's device memory: the run record points at device_chain, the accept
+    // launches write every stored step to its final place, the run is one "sub-chunk" with no chain buffer and no copy.
+    int run_device(int64_t n_saved, int32_t interval, void* device_chain, uint32_t* accepted_per_step) override
+    {
+        return run_to(n_saved, interval, device_chain, accepted_per_step, true);
+    }
+
+    int run_to(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, bool to_device)
     {
         if (!fn) return fail(MCMCPP_HIP_E_STATE, "run: no batch calculator (mcmcpp_hip_set_batch_calculator)");
         if (!have_state) return fail(MCMCPP_HIP_E_STATE, "run: set_state has not been called (or a run failed half way)");
         if (n_saved < 0 || interval < 1) return fail(MCMCPP_HIP_E_ARG, "run: n_saved >= 0 and interval >= 1 required");
         HIP_TRY(hipSetDevice(device));
+        if (to_device && n_saved > 0)
+            if (int rc = check_device_chain(chain_out, n_saved, 1)) return rc;
         const int64_t total = n_saved * (int64_t)interval;
         last_ms = 0.0;
         last_launches = 0;
@@ -322,7 +333,7 @@ public:
         const size_t step_bytes = sizeof(T) * (size_t)W * D;
         // stored steps go to a device buffer of sub_saved slots and from there to chain_out, a sub-chunk at a time
         int64_t sub_saved = n_saved;
-        if (chain_out)
+        if (chain_out && !to_device)
         {
             sub_saved = stored_steps_per_subchunk(chain_subchunk_bytes, step_bytes, n_saved);
             if (int rc = ensure(d_chain, step_bytes * (size_t)sub_saved)) return rc;
@@ -331,7 +342,7 @@ public:
         {
             if (int rc = ensure(d_acc, sizeof(uint32_t) * (size_t)total)) return rc;
         }
-        const int rc = run_steps(n_saved, interval, chain_out, accepted_per_step, sub_saved, step_bytes, total);
+        const int rc = run_steps(n_saved, interval, chain_out, accepted_per_step, sub_saved, step_bytes, total, to_device);
         if (rc != MCMCPP_HIP_OK)
         {
             abandon_state();
@@ -384,6 +395,34 @@ public:
             HIP_TRY(hipMemcpyAsync((T*)out + first, d_lp, sizeof(T) * (size_t)now, hipMemcpyDeviceToHost, stream));
             HIP_TRY(hipStreamSynchronize(stream));
         }
+        return MCMCPP_HIP_OK;
+    }
+
+    // the callback directly on the caller's device rows, in chunks of at most W/2 (what a callback is ever given), writing
+    // into the caller's device array: no copies.  A chunk is a whole number of 16-byte pieces of log-posteriors (and so of
+    // rows) wherever W/2 allows one, so that the callback sees both pointers 16-byte aligned, as it does in a run
+    int calc_logp_device(int32_t chain, const void* pos, int64_t count, void* out) override
+    {
+        if (!fn) return fail(MCMCPP_HIP_E_STATE, "calc_logp_device: no batch calculator (mcmcpp_hip_set_batch_calculator)");
+        if (chain != 0) return fail(MCMCPP_HIP_E_ARG, "calc_logp_device: chain %d, but a batch handle holds one ensemble (chain 0)", chain);
+        if (count < 0) return fail(MCMCPP_HIP_E_ARG, "calc_logp_device: count must not be negative");
+        if (count == 0) return MCMCPP_HIP_OK;
+        HIP_TRY(hipSetDevice(device));
+        if (int rc = check_device_range("calc_logp_device", "device_positions", pos, sizeof(T) * (size_t)count * D, 16)) return rc;
+        if (int rc = check_device_range("calc_logp_device", "device_logp_out", out, sizeof(T) * (size_t)count, 16)) return rc;
+        const int64_t per16 = 16 / (int64_t)sizeof(T);
+        const int64_t chunk = n >= per16 ? n - n % per16 : n;  // (W/2 < 4 fp32 walkers: element-aligned chunks, see the header)
+        for (int64_t first = 0; first < count; first += chunk)
+        {
+            const int64_t now = count - first < chunk ? count - first : chunk;
+            const int cb = fn(user, (const T*)pos + (size_t)first * D, (T*)out + first, now, D, (void*)stream);
+            if (cb != 0)
+            {
+                (void)hipStreamSynchronize(stream);
+                return fail(MCMCPP_HIP_E_CALLBACK, "calc_logp_device: the batch log-posterior callback returned %d", cb);
+            }
+        }
+        HIP_TRY(hipStreamSynchronize(stream));
         return MCMCPP_HIP_OK;
     }
 
@@ -467,7 +506,7 @@ private:
     }
 
     int run_steps(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, int64_t sub_saved, size_t step_bytes,
-                  int64_t total)
+                  int64_t total, bool to_device)
     {
         if (int rc = write_ctl()) return rc;  // step_in_run = 0, stream position from the host-side half-step count
         if (accepted_per_step) HIP_TRY(hipMemsetAsync(d_acc, 0, sizeof(uint32_t) * (size_t)total, stream));
@@ -482,7 +521,7 @@ private:
             const int64_t now = chain_out ? ((n_saved - first < sub_saved) ? n_saved - first : sub_saved) : n_saved;
             RunInfo* ri = &h_pinned->run;  // (the stream was synchronised behind the previous sub-chunk)
             *ri = idle_run_info();
-            ri->chain = chain_out ? d_chain.get() : nullptr;
+            ri->chain = !chain_out ? nullptr : to_device ? chain_out : d_chain.get();  // (a device destination: sub_saved = n_saved, first = 0)
             ri->accepted_per_step = accepted_per_step ? d_acc.get() : nullptr;
             ri->interval = interval;
             ri->chain_slot_base = -first;
@@ -507,7 +546,7 @@ private:
                 steps_since_reset += 1;
                 ++done_steps;
             }
-            if (chain_out)
+            if (chain_out && !to_device)
                 HIP_TRY(hipMemcpyAsync((char*)chain_out + step_bytes * (size_t)first, d_chain, step_bytes * (size_t)now, hipMemcpyDeviceToHost, stream));
             HIP_TRY(hipStreamSynchronize(stream));
             if (chain_out) publish_stored(first + now);

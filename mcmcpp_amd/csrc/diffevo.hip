@@ -205,12 +205,29 @@ public:
     int run(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step) override
     {
         run_touched = false;
-        const int rc = run_steps(n_saved, interval, chain_out, accepted_per_step);
+        const int rc = run_steps(n_saved, interval, chain_out, accepted_per_step, false);
         if (rc != MCMCPP_HIP_OK && run_touched) abandon_state();
         return rc;
     }
 
-    int run_steps(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step)
+    // The same run with the stored steps left in the caller's device memory: every piece of the run writes in place (its run
+    // record points at the piece's first stored step in device_chain), so there is no chain buffer of the handle's own and no
+    // copy.  The 256 MiB bound of a piece was the size of that buffer and goes with it: only the accepted counters (64 MiB)
+    // still cut such a run into pieces, and without them it is one piece.
+    int run_device(int64_t n_saved, int32_t interval, void* device_chain, uint32_t* accepted_per_step) override
+    {
+        run_touched = false;
+        if (!have_state) return fail(MCMCPP_HIP_E_STATE, "run_device: set_state has not been called");
+        if (n_saved < 0 || interval < 1) return fail(MCMCPP_HIP_E_ARG, "run_device: n_saved >= 0 and interval >= 1 required");
+        if (n_saved > 0)
+            if (int rc = check_device_chain(device_chain, n_saved, 1)) return rc;
+        const int rc = run_steps(n_saved, interval, n_saved > 0 ? device_chain : nullptr, accepted_per_step, true);
+        if (rc != MCMCPP_HIP_OK && run_touched) abandon_state();
+        return rc;
+    }
+
+    // to_device: chain_out is device memory of this device (run_device has checked it)
+    int run_steps(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, bool to_device)
     {
         if (!have_state) return fail(MCMCPP_HIP_E_STATE, "run: set_state has not been called");
         if (n_saved < 0 || interval < 1) return fail(MCMCPP_HIP_E_ARG, "run: n_saved >= 0 and interval >= 1 required");
@@ -229,7 +246,7 @@ public:
             const int64_t fit = ((int64_t)64 << 20) / per_stored;
             if (piece > fit) piece = fit < 1 ? 1 : fit;
         }
-        if (chain_out)
+        if (chain_out && !to_device)
         {
             const int64_t fit = (int64_t)(((size_t)256 << 20) / step_bytes);
             if (piece > fit) piece = fit < 1 ? 1 : fit;
@@ -248,7 +265,7 @@ public:
             {
                 DeRunInfo ri;
                 std::memset(&ri, 0, sizeof ri);
-                ri.chain = chain_out ? d_chain.get() : nullptr;
+                ri.chain = !chain_out ? nullptr : to_device ? static_cast<void*>(static_cast<char*>(chain_out) + (size_t)first * step_bytes) : d_chain.get();
                 ri.accepted = accepted_per_step ? d_acc.get() : nullptr;
                 ri.interval = (uint32_t)interval;
                 HIP_TRY(hipMemcpyAsync(d_run, &ri, sizeof ri, hipMemcpyHostToDevice, stream));
@@ -258,7 +275,7 @@ public:
             int rc = enqueue_steps(now * interval);
             if (rc) return rc;
             HIP_TRY(hipEventRecord(ev_t1[0], stream));
-            if (chain_out)
+            if (chain_out && !to_device)
                 HIP_TRY(hipMemcpyAsync(static_cast<char*>(chain_out) + (size_t)first * step_bytes, d_chain, (size_t)now * step_bytes, hipMemcpyDeviceToHost, stream));
             if (accepted_per_step)
                 HIP_TRY(hipMemcpyAsync(accepted_per_step + first * interval, d_acc, sizeof(uint32_t) * (size_t)(now * interval), hipMemcpyDeviceToHost, stream));
@@ -461,6 +478,12 @@ public:
     }
 
     int calc_logp(const void* pos, int64_t count, void* out) override { return kernel_calc_logp(calc_fn, d_params, pos, count, out); }
+    // (one ensemble, the create-time parameters: chain 0 only)
+    int calc_logp_device(int32_t chain, const void* pos, int64_t count, void* out) override
+    {
+        if (chain != 0) return fail(MCMCPP_HIP_E_ARG, "calc_logp_device: chain %d, but a differential-evolution handle holds one ensemble (chain 0)", chain);
+        return kernel_calc_logp_device(calc_fn, d_params, pos, count, out);
+    }
 
     int half_step_async(int32_t, int64_t) override { return unsupported("half_step_async"); }
     int bind_device_chain(void*, int64_t) override { return unsupported("bind_device_chain"); }

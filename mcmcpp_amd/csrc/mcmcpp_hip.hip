@@ -459,7 +459,26 @@ public:
     int run(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step) override
     {
         run_touched_device = false;
-        const int rc = comm ? run_split(n_saved, interval, chain_out, accepted_per_step) : run_whole(n_saved, interval, chain_out, accepted_per_step);
+        const int rc = comm ? run_split(n_saved, interval, chain_out, accepted_per_step) : run_whole(n_saved, interval, chain_out, accepted_per_step, false);
+        return end_of_run(rc);
+    }
+
+    // The same run with the stored steps left in the caller's device memory (mcmcpp_hip_run_device): chain k's run record
+    // points at its part of device_chain, so the launch that makes a stored step writes it to its final place -- the full-step
+    // and the half-step kernels alike, and the captured graphs as they are (they read the record from memory).
+    int run_device(int64_t n_saved, int32_t interval, void* device_chain, uint32_t* accepted_per_step) override
+    {
+        if (comm) return fail(MCMCPP_HIP_E_UNSUPPORTED, "run_device: not for a handle with a communicator (run delivers a split ensemble's stored steps)");
+        if (shard_count != n) return fail(MCMCPP_HIP_E_UNSUPPORTED, "run_device: a sharded handle stores into the chain given to bind_device_chain");
+        run_touched_device = false;
+        if (int rc = check_run(n_saved, interval, true)) return rc;
+        if (n_saved > 0)
+            if (int rc = check_device_chain(device_chain, n_saved, K)) return rc;
+        return end_of_run(run_whole(n_saved, interval, n_saved > 0 ? device_chain : nullptr, accepted_per_step, true));
+    }
+
+    int end_of_run(int rc)
+    {
         if (rc != MCMCPP_HIP_OK && run_touched_device)
         {
             abandon_state();
@@ -537,7 +556,8 @@ public:
         return MCMCPP_HIP_OK;
     }
 
-    int run_whole(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step)
+    // to_device: chain_out is device memory of this device (run_device has checked it)
+    int run_whole(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, bool to_device)
     {
         if (int rc = check_run(n_saved, interval, true)) return rc;
         const int64_t total = n_saved * (int64_t)interval;
@@ -551,7 +571,7 @@ public:
         // pinned host memory, no copy engine, no gap in the launch sequence
         const size_t step_bytes = sizeof(T) * (size_t)W * D;
         const ChainRequest want = {step_bytes, K, n_saved, interval, chain_out != nullptr, accepted_per_step != nullptr, full_fn != nullptr,
-                                   chain_subchunk_bytes, plan.graph_steps, knobs.trickle, knobs.pinned_direct};
+                                   chain_subchunk_bytes, plan.graph_steps, knobs.trickle, knobs.pinned_direct, to_device};
         // chain_out in pinned host memory (mcmcpp_hip_host_alloc: the facade's Chain blocks): the launches forward stored
         // steps straight into their final place -- no pinned twin of the device ring, no host copy
         void* direct_stage = pinned_question_matters(want) ? device_view_of_pinned(chain_out, step_bytes * (size_t)n_saved * K) : nullptr;
@@ -565,6 +585,8 @@ public:
         double launch_ms = 0.0;  // GPU time of the step launches alone (downloads excluded)
         if (cp.mode == ChainMode::Trickle)
             rc = run_trickle(n_saved, interval, (char*)chain_out, accepted_per_step != nullptr, step_bytes, cp, &launch_ms, (char*)direct_stage);
+        else if (cp.mode == ChainMode::Device)
+            rc = run_into_device_chain(n_saved, interval, (char*)chain_out, accepted_per_step != nullptr, step_bytes, cp, &launch_ms);
         StoredRange pending = {0, 0};  // sub-chunk whose staging still has to reach chain_out
         int pending_buf = 0;
         for (int64_t c = 0; c < cp.n_sub && rc == MCMCPP_HIP_OK; ++c)
@@ -1021,6 +1043,44 @@ public:
         return MCMCPP_HIP_OK;
     }
 
+    // The chain path of a device destination: one run record per chain for the whole run, then chunks of steps; a finished
+    // chunk only tells wait_stored how far the stored steps have come.  DeviceWindow (run_plan.hpp) keeps the schedule.
+    int run_into_device_chain(int64_t n_saved, int32_t interval, char* device_chain, bool want_accepted, size_t step_bytes, const ChainPlan& cp, double* launch_ms)
+    {
+        const int64_t total = n_saved * (int64_t)interval;
+        for (int k = 0; k < K; ++k)
+        {
+            RunInfo* ri = &h_pinned->chain_run[0][k];
+            // (chain_slot_base 0, slots never reused, nothing forwarded: run_info_of_run's record as it is)
+            *ri = run_info_of_run(device_chain + device_chain_offset(step_bytes, n_saved, k), want_accepted ? d_acc + (size_t)k * (size_t)total : nullptr, interval, step_bytes);
+            HIP_TRY(hipMemcpyAsync(run_of(k), ri, sizeof(RunInfo), hipMemcpyHostToDevice, stream));
+        }
+        DeviceWindow win(n_saved, interval, cp);
+        auto process_oldest = [&]() -> int {
+            const int e = win.event_slot(win.oldest);
+            float ms = 0.f;
+            HIP_TRY(hipEventSynchronize(ev_t1[e]));
+            HIP_TRY(hipEventElapsedTime(&ms, ev_t0[e], ev_t1[e]));
+            *launch_ms += ms;
+            publish_stored(win.process_oldest().to);
+            return MCMCPP_HIP_OK;
+        };
+        while (!win.all_enqueued())
+        {
+            while (win.must_process_oldest_first())
+                if (const int rc = process_oldest()) return rc;
+            const int64_t now = win.next_length();
+            const int e = win.event_slot(win.next_chunk);
+            HIP_TRY(hipEventRecord(ev_t0[e], stream));
+            if (const int rc = enqueue_steps(now)) return rc;
+            HIP_TRY(hipEventRecord(ev_t1[e], stream));
+            win.enqueued(now);
+        }
+        while (win.in_flight())
+            if (const int rc = process_oldest()) return rc;
+        return MCMCPP_HIP_OK;
+    }
+
     // Device-visible address of [p, p + bytes) when that range is pinned host memory (hipHostMalloc / mcmcpp_hip_host_alloc),
     // nullptr for pageable memory.
     void* device_view_of_pinned(void* p, size_t bytes)
@@ -1147,6 +1207,14 @@ public:
         if (chain < 0 || chain >= K) return fail(MCMCPP_HIP_E_ARG, "calc_logp_chain: chain %d outside 0..%d", chain, K - 1);
         const T* prm = d_chain_params ? d_chain_params + (size_t)chain_params_stride * (size_t)chain : d_params;
         return kernel_calc_logp(calc_fn, prm, pos, count, out);
+    }
+
+    // calc_logp_chain on rows that are in device memory already (a stored device chain), into device memory
+    int calc_logp_device(int32_t chain, const void* pos, int64_t count, void* out) override
+    {
+        if (chain < 0 || chain >= K) return fail(MCMCPP_HIP_E_ARG, "calc_logp_device: chain %d outside 0..%d", chain, K - 1);
+        const T* prm = d_chain_params ? d_chain_params + (size_t)chain_params_stride * (size_t)chain : d_params;
+        return kernel_calc_logp_device(calc_fn, prm, pos, count, out);
     }
 
     int half_step_async(int32_t color, int64_t save_slot) override
@@ -1721,10 +1789,25 @@ int mcmcpp_hip_run(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, voi
     NOT_WHILE_ASYNC("run");
     return h->run(n_saved, interval, chain_out, accepted_per_step);
 }
-int mcmcpp_hip_run_async(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step)
+int mcmcpp_hip_run_device(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, void* device_chain, uint32_t* accepted_per_step)
 {
     NEED_H;
-    if (h->async_active) return h->refuse("mcmcpp_hip_run_async: the previous asynchronous run has not been waited for (mcmcpp_hip_run_wait)");
+    NOT_WHILE_ASYNC("run_device");
+    return h->run_device(n_saved, interval, device_chain, accepted_per_step);
+}
+int mcmcpp_hip_calc_logp_device(mcmcpp_hip_sampler* h, int32_t chain, const void* device_positions, int64_t count, void* device_logp_out)
+{
+    NEED_H;
+    NOT_WHILE_ASYNC("calc_logp_device");
+    return h->calc_logp_device(chain, device_positions, count, device_logp_out);
+}
+// run_async / run_device_async: the run on the handle's worker thread
+static int start_async_run(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, bool to_device)
+{
+    NEED_H;
+    if (h->async_active)
+        return h->refuse(to_device ? "mcmcpp_hip_run_device_async: the previous asynchronous run has not been waited for (mcmcpp_hip_run_wait)"
+                                   : "mcmcpp_hip_run_async: the previous asynchronous run has not been waited for (mcmcpp_hip_run_wait)");
     h->refused = nullptr;
     {
         std::lock_guard<std::mutex> lock(h->async_mutex);
@@ -1736,7 +1819,7 @@ int mcmcpp_hip_run_async(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interva
     try
     {
         h->async_worker = std::thread([=]() {
-            const int rc = h->run(n_saved, interval, chain_out, accepted_per_step);
+            const int rc = to_device ? h->run_device(n_saved, interval, chain_out, accepted_per_step) : h->run(n_saved, interval, chain_out, accepted_per_step);
             {
                 std::lock_guard<std::mutex> lock(h->async_mutex);
                 h->async_rc = rc;
@@ -1753,6 +1836,14 @@ int mcmcpp_hip_run_async(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interva
         return h->fail(MCMCPP_HIP_E_NOMEM, "run_async: cannot start the worker thread");
     }
     return MCMCPP_HIP_OK;
+}
+int mcmcpp_hip_run_async(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step)
+{
+    return start_async_run(h, n_saved, interval, chain_out, accepted_per_step, false);
+}
+int mcmcpp_hip_run_device_async(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, void* device_chain, uint32_t* accepted_per_step)
+{
+    return start_async_run(h, n_saved, interval, device_chain, accepted_per_step, true);
 }
 int mcmcpp_hip_wait_stored(mcmcpp_hip_sampler* h, int64_t count)
 {

@@ -279,11 +279,10 @@ int mcmcpp_hip_moments_reset(mcmcpp_hip_moments* m)
     return MCMCPP_HIP_OK;
 }
 
-int mcmcpp_hip_moments_add_steps(mcmcpp_hip_moments* m, const void* steps, int64_t n_steps, int64_t step_stride)
+// add_steps and add_device_steps_strided: the steps used go into the chunk buffer (uploaded, or gathered on the device), a
+// chunk at a time, and are summed from there
+static int add_steps_through_chunks(mcmcpp_hip_moments* m, const char* what, const void* steps, int64_t n_steps, int64_t step_stride, hipMemcpyKind kind)
 {
-    if (!m) return MCMCPP_HIP_E_ARG;
-    if (n_steps < 0 || step_stride < 1 || (n_steps > 0 && !steps)) return fail(m, MCMCPP_HIP_E_ARG, "moments_add_steps: bad arguments");
-    if (n_steps == 0) return MCMCPP_HIP_OK;
     MOM_TRY(hipSetDevice(m->device));
     const size_t esize = m->dtype == MCMCPP_HIP_F64 ? 8 : 4;
     const size_t step_bytes = esize * (size_t)m->W * m->D;
@@ -291,18 +290,17 @@ int mcmcpp_hip_moments_add_steps(mcmcpp_hip_moments* m, const void* steps, int64
     int64_t per_chunk = (int64_t)(m->chunk_bytes / step_bytes);
     if (per_chunk < 1) per_chunk = 1;
     if (per_chunk > n_steps) per_chunk = n_steps;
-    if (mcmcpp::grow(m->d_chunk, step_bytes * (size_t)per_chunk, m->stream)) return fail(m, MCMCPP_HIP_E_NOMEM, "moments_add_steps: cannot allocate the upload buffer");
+    if (mcmcpp::grow(m->d_chunk, step_bytes * (size_t)per_chunk, m->stream)) return fail(m, MCMCPP_HIP_E_NOMEM, (std::string(what) + ": cannot allocate the chunk buffer").c_str());
     for (int64_t first = 0; first < n_steps; first += per_chunk)
     {
         const int64_t now = (n_steps - first < per_chunk) ? n_steps - first : per_chunk;
         const char* src = (const char*)steps + step_bytes * (size_t)(first * step_stride);
         MOM_TRY(hipStreamSynchronize(m->stream));  // the previous chunk's kernel has read the buffer
         if (step_stride == 1)
-            MOM_TRY(hipMemcpyAsync(m->d_chunk, src, step_bytes * (size_t)now, hipMemcpyHostToDevice, m->stream));
+            MOM_TRY(hipMemcpyAsync(m->d_chunk, src, step_bytes * (size_t)now, kind, m->stream));
         else
             for (int64_t k = 0; k < now; ++k)
-                MOM_TRY(hipMemcpyAsync((char*)m->d_chunk + step_bytes * (size_t)k, src + step_bytes * (size_t)(k * step_stride), step_bytes,
-                                       hipMemcpyHostToDevice, m->stream));
+                MOM_TRY(hipMemcpyAsync((char*)m->d_chunk + step_bytes * (size_t)k, src + step_bytes * (size_t)(k * step_stride), step_bytes, kind, m->stream));
         const long long n_samples = (long long)now * m->W;
         const int rc = m->dtype == MCMCPP_HIP_F64 ? accumulate<double>(m, (const double*)m->d_chunk.get(), n_samples)
                                                   : accumulate<float>(m, (const float*)m->d_chunk.get(), n_samples);
@@ -311,6 +309,23 @@ int mcmcpp_hip_moments_add_steps(mcmcpp_hip_moments* m, const void* steps, int64
     }
     MOM_TRY(hipStreamSynchronize(m->stream));
     return MCMCPP_HIP_OK;
+}
+
+int mcmcpp_hip_moments_add_steps(mcmcpp_hip_moments* m, const void* steps, int64_t n_steps, int64_t step_stride)
+{
+    if (!m) return MCMCPP_HIP_E_ARG;
+    if (n_steps < 0 || step_stride < 1 || (n_steps > 0 && !steps)) return fail(m, MCMCPP_HIP_E_ARG, "moments_add_steps: bad arguments");
+    if (n_steps == 0) return MCMCPP_HIP_OK;
+    return add_steps_through_chunks(m, "moments_add_steps", steps, n_steps, step_stride, hipMemcpyHostToDevice);
+}
+
+int mcmcpp_hip_moments_add_device_steps_strided(mcmcpp_hip_moments* m, const void* device_steps, int64_t n_steps, int64_t step_stride)
+{
+    if (!m) return MCMCPP_HIP_E_ARG;
+    if (n_steps < 0 || step_stride < 1 || (n_steps > 0 && !device_steps)) return fail(m, MCMCPP_HIP_E_ARG, "moments_add_device_steps_strided: bad arguments");
+    if (step_stride == 1) return mcmcpp_hip_moments_add_device_steps(m, device_steps, n_steps);
+    if (n_steps == 0) return MCMCPP_HIP_OK;
+    return add_steps_through_chunks(m, "moments_add_device_steps_strided", device_steps, n_steps, step_stride, hipMemcpyDeviceToDevice);
 }
 
 int mcmcpp_hip_moments_add_device_steps(mcmcpp_hip_moments* m, const void* device_steps, int64_t n_steps)

@@ -1,6 +1,7 @@
 // run_plan.hpp -- how a run() delivers its stored steps and cuts itself into chunks: ring size, chunk lengths, when the host
-// must wait, where a sub-chunk lands in the caller's array, where a split run cuts so that every rank cuts alike, and the
-// slot bound of its exchange blocks.  Pure functions and one small value type over plain numbers.  No HIP header: this file
+// must wait, where a sub-chunk lands in the caller's array, what a destination in device memory changes (run_device: no ring,
+// no staging, what wait_stored may hear), where a split run cuts so that every rank cuts alike, and the slot bound of its
+// exchange blocks.  Pure functions and one small value type over plain numbers.  No HIP header: this file
 // compiles with the host compiler alone, and tests/test_run_plan.py checks the schedules there, case by case.  The samplers
 // keep every HIP and RCCL call and ask here for the numbers.
 #pragma once
@@ -25,7 +26,9 @@ inline int64_t stored_steps_per_subchunk(size_t budget, size_t stored_step_bytes
 // Nothing: no chain_out, the steps run as one sub-chunk.  Subchunks: device chain halves -> pinned staging -> chain_out.
 // Trickle: the full-step launches forward stored steps themselves (trickle_stored_step) through a ring of `ring` slots on
 // the device -- into its pinned twin, or, when chain_out is pinned memory, straight into their final place (`direct`).
-enum class ChainMode { Nothing, Subchunks, Trickle };
+// Device: the destination is the caller's device memory (run_device).  The launch that makes a stored step writes it to its
+// final place: no ring, no staging, no sub-chunks, nothing forwarded, whichever kernels step the handle.
+enum class ChainMode { Nothing, Subchunks, Trickle, Device };
 
 struct ChainRequest
 {
@@ -38,11 +41,13 @@ struct ChainRequest
     size_t subchunk_bytes;   // MCMCPP_HIP_CHAIN_SUBCHUNK_MB in bytes
     int graph_steps;         // StepPlan::graph_steps
     long trickle, pinned_direct;  // the knobs
+    bool device_dest;        // chain_out is device memory of the handle's device (run_device)
 };
 
 inline ChainMode chain_mode(const ChainRequest& r)
 {
     if (!r.chain_out) return ChainMode::Nothing;
+    if (r.device_dest) return ChainMode::Device;
     return r.full_step && r.step_bytes % 16 == 0 && r.trickle != 0 ? ChainMode::Trickle : ChainMode::Subchunks;
 }
 // Is it worth asking the runtime whether chain_out is pinned memory?  (The answer goes into plan_chain.)
@@ -56,7 +61,7 @@ struct ChainPlan
     ChainMode mode;
     bool direct;                      // Trickle, straight into a pinned chain_out
     int64_t sub_saved, n_sub;         // stored steps per sub-chunk, sub-chunks (Trickle: none)
-    int64_t ring, chunk_steps;        // Trickle: ring slots (a power of two), ensemble steps per chunk
+    int64_t ring, chunk_steps;        // Trickle: ring slots (a power of two); Trickle, Device: ensemble steps per chunk
     size_t acc_entries, half_bytes, ring_bytes;  // ensure_run_buffers
     bool need_host_ring;
     int64_t slice_bytes;              // RunInfo::slice_bytes: what one launch forwards of a stored step, low bit = direct
@@ -75,8 +80,16 @@ inline ChainPlan plan_chain(const ChainRequest& r, bool chain_out_pinned)
     p.n_saved = r.n_saved;
     p.mode = chain_mode(r);
     p.direct = pinned_question_matters(r) && chain_out_pinned;
-    p.sub_saved = r.chain_out ? stored_steps_per_subchunk(r.subchunk_bytes, r.step_bytes * (size_t)r.chains, r.n_saved) : r.n_saved;
-    if (p.mode == ChainMode::Trickle)
+    p.sub_saved = r.chain_out && p.mode != ChainMode::Device ? stored_steps_per_subchunk(r.subchunk_bytes, r.step_bytes * (size_t)r.chains, r.n_saved) : r.n_saved;
+    if (p.mode == ChainMode::Device)
+    {
+        // Nothing has to be handed out, so a chunk only bounds how far the host enqueues ahead and how often wait_stored
+        // hears of progress: a graph replay's worth of steps, in whole intervals (a chunk ends on a stored step), at least one
+        int64_t per_chunk = (r.graph_steps > 0 ? r.graph_steps : 64) / (int64_t)r.interval;
+        if (per_chunk < 1) per_chunk = 1;
+        p.chunk_steps = per_chunk * r.interval;
+    }
+    else if (p.mode == ChainMode::Trickle)
     {
         p.ring = 4;
         while (p.ring < 64 && (size_t)(2 * p.ring) * r.step_bytes <= 2 * r.subchunk_bytes) p.ring *= 2;
@@ -94,9 +107,47 @@ inline ChainPlan plan_chain(const ChainRequest& r, bool chain_out_pinned)
         if (r.chain_out) p.half_bytes = r.step_bytes * (size_t)p.sub_saved * (size_t)r.chains;
     }
     p.acc_entries = r.want_accepted ? (size_t)(r.n_saved * (int64_t)r.interval) * (size_t)r.chains : 0;
-    p.need_host_ring = !p.direct;
+    p.need_host_ring = !p.direct && p.mode != ChainMode::Device;
     return p;
 }
+
+// ---- a device destination (run_device) ---------------------------------------------------------------------------------
+// Chain k's stored steps are the k-th run of n_saved steps of the caller's array, as in host memory
+inline size_t device_chain_offset(size_t step_bytes, int64_t n_saved, int k) { return step_bytes * (size_t)n_saved * (size_t)k; }
+
+// Stored step k is written, whole, by the launches of ensemble step (k + 1) * interval - 1: it is complete in the caller's
+// array when that step has finished.  The host enqueues chunks of steps, at most two in flight (the chunks' events rotate
+// over four slots), and announces what a finished chunk completed.  Nothing is left behind the final synchronisation.
+struct DeviceWindow
+{
+    int64_t n_saved, interval, chunk_steps;
+    int64_t enq = 0, announced = 0;      // ensemble steps enqueued; stored steps announced to wait_stored
+    int64_t chunk_end[4] = {0, 0, 0, 0};
+    int64_t next_chunk = 0, oldest = 0;  // chunks enqueued / chunks whose completion has been processed
+
+    DeviceWindow(int64_t n_saved_, int64_t interval_, const ChainPlan& p) : n_saved(n_saved_), interval(interval_), chunk_steps(p.chunk_steps) {}
+
+    int64_t total() const { return n_saved * interval; }
+    bool all_enqueued() const { return enq == total(); }
+    bool in_flight() const { return next_chunk > oldest; }
+    static int event_slot(int64_t chunk) { return (int)(chunk & 3); }
+    int64_t next_length() const { return total() - enq < chunk_steps ? total() - enq : chunk_steps; }
+    bool must_process_oldest_first() const { return next_chunk - oldest >= 2; }
+    void enqueued(int64_t now)
+    {
+        enq += now;
+        chunk_end[event_slot(next_chunk)] = enq;
+        ++next_chunk;
+    }
+    // the oldest chunk has finished: the stored steps it completed
+    StoredRange process_oldest()
+    {
+        const StoredRange r = {announced, chunk_end[event_slot(oldest)] / interval};
+        announced = r.to;
+        ++oldest;
+        return r;
+    }
+};
 
 // ---- the trickle window (Sampler::run_trickle) -------------------------------------------------------------------------
 // Stored step k is complete in the pinned ring when ensemble step (k + 2) * interval - 1 has finished (every launch forwards

@@ -71,6 +71,13 @@ struct mcmcpp_hip_sampler
     {
         return fail(MCMCPP_HIP_E_UNSUPPORTED, "calc_logp_chain: per-chain parameters are for stretch-move handles only (not differential evolution)");
     }
+    // stored steps and log-posteriors that stay in device memory (mcmcpp_hip_run_device, mcmcpp_hip_calc_logp_device): every
+    // mover overrides both
+    virtual int run_device(int64_t, int32_t, void*, uint32_t*) { return fail(MCMCPP_HIP_E_UNSUPPORTED, "run_device: not available for this handle"); }
+    virtual int calc_logp_device(int32_t, const void*, int64_t, void*)
+    {
+        return fail(MCMCPP_HIP_E_UNSUPPORTED, "calc_logp_device: not available for this handle");
+    }
     // calc_id MCMCPP_HIP_CALC_BATCH only (batch.hip)
     virtual int set_batch_calculator(mcmcpp_hip_batch_logp_fn, void*, void*, void*)
     {

@@ -291,6 +291,58 @@ protected:
         return MCMCPP_HIP_OK;
     }
 
+    // Does [p, p + bytes) lie inside ONE allocation of this handle's device, aligned to `align` bytes?  Asked of the runtime
+    // before anything is launched: hipPointerGetAttributes must report p as device memory of the device (a host pointer --
+    // pageable, pinned or managed -- is refused here, never dereferenced), and the range must end inside the allocation
+    // hipMemGetAddressRange reports around p.  MCMCPP_HIP_E_ARG with a message otherwise.
+    int check_device_range(const char* what, const char* name, const void* p, size_t bytes, size_t align)
+    {
+        if (!p) return fail(MCMCPP_HIP_E_ARG, "%s: %s is NULL", what, name);
+        if (((uintptr_t)p & (align - 1)) != 0) return fail(MCMCPP_HIP_E_ARG, "%s: %s must be %zu-byte aligned", what, name, align);
+        hipPointerAttribute_t at;
+        std::memset(&at, 0, sizeof at);
+        const hipError_t e = hipPointerGetAttributes(&at, p);
+        if (e != hipSuccess) (void)hipGetLastError();  // (some runtimes report pageable memory as an error)
+        if (e != hipSuccess || at.type != hipMemoryTypeDevice)
+            return fail(MCMCPP_HIP_E_ARG, "%s: %s is not device memory (%zu bytes from %p must lie in memory of device %d)", what, name, bytes, p, device);
+        if (at.device != device) return fail(MCMCPP_HIP_E_ARG, "%s: %s is memory of device %d, the handle runs on device %d", what, name, at.device, device);
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess)
+        {
+            (void)hipGetLastError();
+            return fail(MCMCPP_HIP_E_ARG, "%s: the runtime does not know the allocation %s lies in", what, name);
+        }
+        const size_t room = (size_t)((const char*)base + size - (const char*)p);
+        if ((const char*)p < (const char*)base || bytes > room)
+            return fail(MCMCPP_HIP_E_ARG, "%s: %s needs %zu bytes, but its allocation ends %zu bytes behind it", what, name, bytes, room);
+        return MCMCPP_HIP_OK;
+    }
+
+    // calc_logp_device by the calculator's own kernel: device rows in, device log-posteriors out, no copies.  Returns when
+    // the values are there.
+    int kernel_calc_logp_device(typename LaunchTable<T>::CalcFn calc_fn, const T* params, const void* pos, int64_t count, void* out)
+    {
+        if (count < 0) return fail(MCMCPP_HIP_E_ARG, "calc_logp_device: count must not be negative");
+        if (count == 0) return MCMCPP_HIP_OK;
+        HIP_TRY(hipSetDevice(device));
+        // (rows are read in 16-byte pieces where a row is a whole number of them)
+        if (int rc = check_device_range("calc_logp_device", "device_positions", pos, sizeof(T) * (size_t)count * D, vec_ok ? 16 : sizeof(T))) return rc;
+        if (int rc = check_device_range("calc_logp_device", "device_logp_out", out, sizeof(T) * (size_t)count, sizeof(T))) return rc;
+        const long long per_block = (long long)(64 / lpw) * kWavesPerBlock;
+        const unsigned grid = (unsigned)((count + per_block - 1) / per_block);
+        calc_fn((const T*)pos, (T*)out, params, count, D, vec_ok, grid, stream);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(stream));
+        return MCMCPP_HIP_OK;
+    }
+
+    // the destination of a run_device: K * n_saved stored steps of device memory, 16-byte aligned
+    int check_device_chain(const void* device_chain, int64_t n_saved, int chains)
+    {
+        return check_device_range("run_device", "device_chain", device_chain, sizeof(T) * (size_t)W * D * (size_t)n_saved * (size_t)chains, 16);
+    }
+
     // calc_logp by the calculator's own kernel (`calc` of its launch table)
     int kernel_calc_logp(typename LaunchTable<T>::CalcFn calc_fn, const T* params, const void* pos, int64_t count, void* out)
     {
@@ -329,7 +381,8 @@ protected:
         Host::stream_valid, Host::have_state, Host::d_pos, Host::d_logp, Host::d_nacc, Host::d_diag, Host::steps_since_reset, \
         Host::last_ms, Host::last_launches;                                                                                     \
     using Host::set_shape, Host::open_device, Host::open_stream, Host::quiesce, Host::abandon_state, Host::read_state,         \
-        Host::clear_accepted, Host::read_counters, Host::kernel_calc_logp;                                                      \
+        Host::clear_accepted, Host::read_counters, Host::kernel_calc_logp, Host::kernel_calc_logp_device, Host::check_device_range,   \
+        Host::check_device_chain;                                                   \
     using Host::fail, Host::error, Host::publish_stored, Host::host_enqueue_ms, Host::host_wall_ms
 
 }  // namespace mcmcpp
