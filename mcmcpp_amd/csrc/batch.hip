@@ -295,60 +295,10 @@ public:
     int set_state(const void* pos, const void* logp) override
     {
         if (!fn) return fail(MCMCPP_HIP_E_STATE, "set_state: no batch calculator (mcmcpp_hip_set_batch_calculator)");
-        if (!pos || !logp) return fail(MCMCPP_HIP_E_ARG, "set_state: null pointer");
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipMemcpyAsync(d_pos, pos, sizeof(T) * (size_t)W * D, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(d_logp, logp, sizeof(T) * (size_t)W, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemsetAsync(d_nacc, 0, sizeof(uint32_t) * (size_t)W, stream));
-        HIP_TRY(hipMemsetAsync(d_diag, 0, sizeof(Diag), stream));
+        if (int rc = upload_state(pos, logp)) return rc;
         half_steps = 0;
-        steps_since_reset = 0;
         if (int rc = write_ctl()) return rc;
         have_state = true;
-        return MCMCPP_HIP_OK;
-    }
-
-    int run(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step) override { return run_to(n_saved, interval, chain_out, accepted_per_step, false); }
-
-    // The same run with the stored steps left in the caller's device memory: the run record points at device_chain, the accept
-    // launches write every stored step to its final place, the run is one "sub-chunk" with no chain buffer and no copy.
-    int run_device(int64_t n_saved, int32_t interval, void* device_chain, uint32_t* accepted_per_step) override
-    {
-        return run_to(n_saved, interval, device_chain, accepted_per_step, true);
-    }
-
-    int run_to(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, bool to_device)
-    {
-        if (!fn) return fail(MCMCPP_HIP_E_STATE, "run: no batch calculator (mcmcpp_hip_set_batch_calculator)");
-        if (!have_state) return fail(MCMCPP_HIP_E_STATE, "run: set_state has not been called (or a run failed half way)");
-        if (n_saved < 0 || interval < 1) return fail(MCMCPP_HIP_E_ARG, "run: n_saved >= 0 and interval >= 1 required");
-        HIP_TRY(hipSetDevice(device));
-        if (to_device && n_saved > 0)
-            if (int rc = check_device_chain(chain_out, n_saved, 1)) return rc;
-        const int64_t total = n_saved * (int64_t)interval;
-        last_ms = 0.0;
-        last_launches = 0;
-        if (total == 0) return MCMCPP_HIP_OK;
-        const auto tp0 = std::chrono::steady_clock::now();
-        const size_t step_bytes = sizeof(T) * (size_t)W * D;
-        // stored steps go to a device buffer of sub_saved slots and from there to chain_out, a sub-chunk at a time
-        int64_t sub_saved = n_saved;
-        if (chain_out && !to_device)
-        {
-            sub_saved = stored_steps_per_subchunk(chain_subchunk_bytes, step_bytes, n_saved);
-            if (int rc = ensure(d_chain, step_bytes * (size_t)sub_saved)) return rc;
-        }
-        if (accepted_per_step)
-        {
-            if (int rc = ensure(d_acc, sizeof(uint32_t) * (size_t)total)) return rc;
-        }
-        const int rc = run_steps(n_saved, interval, chain_out, accepted_per_step, sub_saved, step_bytes, total, to_device);
-        if (rc != MCMCPP_HIP_OK)
-        {
-            abandon_state();
-            return rc;
-        }
-        host_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp0).count();
         return MCMCPP_HIP_OK;
     }
 
@@ -505,26 +455,40 @@ private:
         return MCMCPP_HIP_OK;
     }
 
-    int run_steps(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, int64_t sub_saved, size_t step_bytes,
-                  int64_t total, bool to_device)
+    RunFacts run_facts() const override
     {
+        RunFacts f = {};
+        f.mover = Mover::Batch;
+        f.callback_set = fn != nullptr;
+        return f;
+    }
+
+    // The run, a sub-chunk at a time (plan_batch_pieces): stored steps go to a device buffer of a sub-chunk's slots and from
+    // there to chain_out.  A destination in device memory: the run record points at it, the accept launches write every
+    // stored step to its final place, the run is one sub-chunk with no chain buffer and no copy.
+    int run_mover(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, bool to_device) override
+    {
+        const int64_t total = n_saved * (int64_t)interval;
+        const size_t step_bytes = sizeof(T) * (size_t)W * D;
+        const PiecePlan plan = plan_batch_pieces(chain_subchunk_bytes, step_bytes, n_saved, interval, chain_out != nullptr, to_device, accepted_per_step != nullptr);
+        if (int rc = ensure(d_chain, plan.chain_bytes)) return rc;
+        if (int rc = ensure(d_acc, sizeof(uint32_t) * plan.acc_entries)) return rc;
+        run_touched = true;  // (whatever fails from here on, write_ctl included, abandons the walker state)
         if (int rc = write_ctl()) return rc;  // step_in_run = 0, stream position from the host-side half-step count
         if (accepted_per_step) HIP_TRY(hipMemsetAsync(d_acc, 0, sizeof(uint32_t) * (size_t)total, stream));
         HIP_TRY(hipEventRecord(ev_t0, stream));
         const auto tp1 = std::chrono::steady_clock::now();
         uint64_t step = half_steps >> 1;  // ensemble steps since set_state: its low bit selects the record buffer
         int64_t done_steps = 0;
-        const int64_t n_sub = chain_out ? (n_saved + sub_saved - 1) / sub_saved : 1;
-        for (int64_t c = 0; c < n_sub; ++c)
+        for (int64_t c = 0; c < plan.n_pieces; ++c)
         {
-            const int64_t first = c * sub_saved;
-            const int64_t now = chain_out ? ((n_saved - first < sub_saved) ? n_saved - first : sub_saved) : n_saved;
+            const int64_t first = plan.piece(c).from, now = plan.piece(c).to - first;
             RunInfo* ri = &h_pinned->run;  // (the stream was synchronised behind the previous sub-chunk)
             *ri = idle_run_info();
-            ri->chain = !chain_out ? nullptr : to_device ? chain_out : d_chain.get();  // (a device destination: sub_saved = n_saved, first = 0)
+            ri->chain = !chain_out ? nullptr : to_device ? chain_out : d_chain.get();  // (a device destination is one sub-chunk: first = 0)
             ri->accepted_per_step = accepted_per_step ? d_acc.get() : nullptr;
             ri->interval = interval;
-            ri->chain_slot_base = -first;
+            ri->chain_slot_base = subchunk_slot_base(first);
             ri->step_bytes = (int64_t)step_bytes;
             HIP_TRY(hipMemcpyAsync(d_run, ri, sizeof(RunInfo), hipMemcpyHostToDevice, stream));
             for (int64_t s = 0; s < now * (int64_t)interval; ++s, ++step)

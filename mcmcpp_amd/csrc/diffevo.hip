@@ -5,7 +5,6 @@
 // head, the error flags and the per-run counters travel in device memory.
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -180,12 +179,7 @@ public:
 
     int set_state(const void* pos, const void* logp) override
     {
-        if (!pos || !logp) return fail(MCMCPP_HIP_E_ARG, "set_state: null pointer");
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipMemcpyAsync(d_pos, pos, sizeof(T) * (size_t)W * D, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(d_logp, logp, sizeof(T) * (size_t)W, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemsetAsync(d_nacc, 0, sizeof(uint32_t) * (size_t)W, stream));
-        HIP_TRY(hipMemsetAsync(d_diag, 0, sizeof(Diag), stream));
+        if (int rc = upload_state(pos, logp)) return rc;
         DeHead h;
         std::memset(&h, 0, sizeof h);
         h.state = state0;
@@ -194,78 +188,41 @@ public:
         HIP_TRY(hipMemcpyAsync(d_head, &h, sizeof h, hipMemcpyHostToDevice, stream));
         HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof(uint32_t) * 2 * kDeSegments * kDeCountStride, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        steps_since_reset = 0;
         half_steps = 0;
         primed = false;
         have_state = true;
         return MCMCPP_HIP_OK;
     }
 
-    // EnsembleSampler::runMCMC (EnsembleSampler.h:284-310): interval-1 unsaved ensemble steps, one saved, n_saved times
-    int run(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step) override
+    RunFacts run_facts() const override
     {
-        run_touched = false;
-        const int rc = run_steps(n_saved, interval, chain_out, accepted_per_step, false);
-        if (rc != MCMCPP_HIP_OK && run_touched) abandon_state();
-        return rc;
+        RunFacts f = {};
+        f.mover = Mover::DiffEvo;
+        return f;
     }
 
-    // The same run with the stored steps left in the caller's device memory: every piece of the run writes in place (its run
-    // record points at the piece's first stored step in device_chain), so there is no chain buffer of the handle's own and no
-    // copy.  The 256 MiB bound of a piece was the size of that buffer and goes with it: only the accepted counters (64 MiB)
-    // still cut such a run into pieces, and without them it is one piece.
-    int run_device(int64_t n_saved, int32_t interval, void* device_chain, uint32_t* accepted_per_step) override
+    // The run, a piece at a time (plan_de_pieces).  A destination in device memory: every piece writes in place (its run
+    // record points at the piece's first stored step in the caller's array), so there is no chain buffer of the handle's
+    // own and no copy.
+    int run_mover(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, bool to_device) override
     {
-        run_touched = false;
-        if (!have_state) return fail(MCMCPP_HIP_E_STATE, "run_device: set_state has not been called");
-        if (n_saved < 0 || interval < 1) return fail(MCMCPP_HIP_E_ARG, "run_device: n_saved >= 0 and interval >= 1 required");
-        if (n_saved > 0)
-            if (int rc = check_device_chain(device_chain, n_saved, 1)) return rc;
-        const int rc = run_steps(n_saved, interval, n_saved > 0 ? device_chain : nullptr, accepted_per_step, true);
-        if (rc != MCMCPP_HIP_OK && run_touched) abandon_state();
-        return rc;
-    }
-
-    // to_device: chain_out is device memory of this device (run_device has checked it)
-    int run_steps(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, bool to_device)
-    {
-        if (!have_state) return fail(MCMCPP_HIP_E_STATE, "run: set_state has not been called");
-        if (n_saved < 0 || interval < 1) return fail(MCMCPP_HIP_E_ARG, "run: n_saved >= 0 and interval >= 1 required");
-        HIP_TRY(hipSetDevice(device));
         const int64_t total = n_saved * (int64_t)interval;
-        last_ms = 0.0;
-        last_launches = 0;
-        if (total == 0) return MCMCPP_HIP_OK;
-        const auto t0 = std::chrono::steady_clock::now();
         const size_t step_bytes = sizeof(T) * (size_t)W * D;
-        // stored steps leave in pieces of at most 256 MiB of device chain and 64 MiB of accepted counters
-        int64_t piece = n_saved;
-        if (accepted_per_step)
-        {
-            const int64_t per_stored = (int64_t)interval * (int64_t)sizeof(uint32_t);
-            const int64_t fit = ((int64_t)64 << 20) / per_stored;
-            if (piece > fit) piece = fit < 1 ? 1 : fit;
-        }
-        if (chain_out && !to_device)
-        {
-            const int64_t fit = (int64_t)(((size_t)256 << 20) / step_bytes);
-            if (piece > fit) piece = fit < 1 ? 1 : fit;
-            if (const hipError_t e = grow(d_chain, (size_t)piece * step_bytes, stream))
-                return fail(MCMCPP_HIP_E_HIP, "hipMalloc(&d_chain, (size_t)piece * step_bytes) failed: %s", hipGetErrorString(e));
-        }
-        const int64_t acc_piece = accepted_per_step ? piece * (int64_t)interval : 0;
-        if (const hipError_t e = grow(d_acc, sizeof(uint32_t) * (size_t)acc_piece, stream))
-            return fail(MCMCPP_HIP_E_HIP, "hipMalloc(&d_acc, sizeof(uint32_t) * (size_t)acc_piece) failed: %s", hipGetErrorString(e));
+        const PiecePlan plan = plan_de_pieces(step_bytes, n_saved, interval, chain_out != nullptr, to_device, accepted_per_step != nullptr);
+        if (const hipError_t e = grow(d_chain, plan.chain_bytes, stream))
+            return fail(MCMCPP_HIP_E_HIP, "hipMalloc of %zu bytes of device chain failed: %s", plan.chain_bytes, hipGetErrorString(e));
+        if (const hipError_t e = grow(d_acc, sizeof(uint32_t) * plan.acc_entries, stream))
+            return fail(MCMCPP_HIP_E_HIP, "hipMalloc of %zu accepted counters failed: %s", plan.acc_entries, hipGetErrorString(e));
 
         run_touched = true;
         double gpu_ms = 0.0;
-        for (int64_t first = 0; first < n_saved; first += piece)
+        for (int64_t c = 0; c < plan.n_pieces; ++c)
         {
-            const int64_t now = n_saved - first < piece ? n_saved - first : piece;
+            const int64_t first = plan.piece(c).from, now = plan.piece(c).to - first;
             {
                 DeRunInfo ri;
                 std::memset(&ri, 0, sizeof ri);
-                ri.chain = !chain_out ? nullptr : to_device ? static_cast<void*>(static_cast<char*>(chain_out) + (size_t)first * step_bytes) : d_chain.get();
+                ri.chain = !chain_out ? nullptr : to_device ? static_cast<void*>(static_cast<char*>(chain_out) + device_piece_offset(step_bytes, first)) : d_chain.get();
                 ri.accepted = accepted_per_step ? d_acc.get() : nullptr;
                 ri.interval = (uint32_t)interval;
                 HIP_TRY(hipMemcpyAsync(d_run, &ri, sizeof ri, hipMemcpyHostToDevice, stream));
@@ -292,7 +249,6 @@ public:
         HIP_TRY(hipMemcpy(&h, d_head, sizeof h, hipMemcpyDeviceToHost));
         last_ms = gpu_ms;  // GPU time of the launches (planning included) between HIP events on the launch stream (transfers excluded)
         last_launches = 2 * total;
-        host_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         if (h.error)
             return fail(MCMCPP_HIP_E_UNSUPPORTED,
                         "differential evolution: the random stream could not be followed (flags %u: 1 = more than %d draws thrown away in one "
@@ -516,7 +472,6 @@ private:
     int resolve_capacity = 0, scan_blocks = 0;
     bool primed = false;    // batches 0 and 1 planned behind the last set_state
     Affine128 batch_jump;   // (D+3) * n * batch_max draws
-    bool run_touched = false;
     Event ev_t0[2], ev_t1[2];
     std::unordered_map<uint64_t, GraphExec> graph_cache;
 

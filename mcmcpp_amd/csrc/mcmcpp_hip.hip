@@ -456,47 +456,24 @@ public:
     // staging into the caller's (pageable) memory.  One stream on purpose: with a second active stream every
     // half-step launch of this latency-bound kernel was measured 1.5 us slower (5.8 -> 7.3 us).
     // Everything is ordered by events; nothing is allocated on the way.
-    int run(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step) override
+    // A destination in device memory (run_device): chain k's run record points at its part of the caller's array, so the
+    // launch that makes a stored step writes it to its final place -- the full-step and the half-step kernels alike, and
+    // the captured graphs as they are (they read the record from memory).
+    int run_mover(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, bool to_device) override
     {
-        run_touched_device = false;
-        const int rc = comm ? run_split(n_saved, interval, chain_out, accepted_per_step) : run_whole(n_saved, interval, chain_out, accepted_per_step, false);
-        return end_of_run(rc);
+        return comm ? run_split(n_saved, interval, chain_out, accepted_per_step) : run_whole(n_saved, interval, chain_out, accepted_per_step, to_device);
     }
-
-    // The same run with the stored steps left in the caller's device memory (mcmcpp_hip_run_device): chain k's run record
-    // points at its part of device_chain, so the launch that makes a stored step writes it to its final place -- the full-step
-    // and the half-step kernels alike, and the captured graphs as they are (they read the record from memory).
-    int run_device(int64_t n_saved, int32_t interval, void* device_chain, uint32_t* accepted_per_step) override
+    int run_chains() const override { return K; }
+    RunFacts run_facts() const override
     {
-        if (comm) return fail(MCMCPP_HIP_E_UNSUPPORTED, "run_device: not for a handle with a communicator (run delivers a split ensemble's stored steps)");
-        if (shard_count != n) return fail(MCMCPP_HIP_E_UNSUPPORTED, "run_device: a sharded handle stores into the chain given to bind_device_chain");
-        run_touched_device = false;
-        if (int rc = check_run(n_saved, interval, true)) return rc;
-        if (n_saved > 0)
-            if (int rc = check_device_chain(device_chain, n_saved, K)) return rc;
-        return end_of_run(run_whole(n_saved, interval, n_saved > 0 ? device_chain : nullptr, accepted_per_step, true));
+        RunFacts f = {};
+        f.mover = Mover::Stretch;
+        f.communicator = comm != nullptr;
+        f.sharded = shard_count != n;
+        f.half_done = (half_steps & 1) != 0;
+        return f;
     }
-
-    int end_of_run(int rc)
-    {
-        if (rc != MCMCPP_HIP_OK && run_touched_device)
-        {
-            abandon_state();
-            records_valid = false;
-        }
-        return rc;
-    }
-
-    // the checks every run() makes before it touches the device
-    int check_run(int64_t n_saved, int32_t interval, bool whole_only)
-    {
-        if (!have_state) return fail(MCMCPP_HIP_E_STATE, "run: set_state has not been called");
-        if (n_saved < 0 || interval < 1) return fail(MCMCPP_HIP_E_ARG, "run: n_saved >= 0 and interval >= 1 required");
-        if (whole_only && shard_count != n) return fail(MCMCPP_HIP_E_UNSUPPORTED, "run: a sharded handle is driven with half_step_async");
-        if (half_steps & 1) return fail(MCMCPP_HIP_E_STATE, "run: an ensemble step is half done (half_step_async)");
-        HIP_TRY(hipSetDevice(device));
-        return MCMCPP_HIP_OK;
-    }
+    void state_abandoned() override { records_valid = false; }
 
     // The start of a run on the device: the per-step counters cleared, the control records at step 0 of the run, the rows
     // marked as moved for the full-step kernels, the launch arguments.  split_record: the one run record of a split run
@@ -504,7 +481,7 @@ public:
     int begin_run(size_t acc_entries, const RunInfo* split_record)
     {
         if (acc_entries) HIP_TRY(hipMemsetAsync(d_acc, 0, sizeof(uint32_t) * acc_entries, stream));
-        run_touched_device = true;  // from here on an error leaves the device ahead of the host's bookkeeping
+        run_touched = true;  // from here on an error leaves the device ahead of the host's bookkeeping
         if (int rc = write_ctl(0)) return rc;  // step_in_run = 0, stream position from the host-side half-step count
         records_valid = false;  // (until this call has finished: an error on the way leaves them unknown)
         run_info_idle = false;
@@ -526,7 +503,7 @@ public:
     // two host timings.  records_left: did the last launch leave the draw records of the next ensemble step behind (full-step
     // launches: with partner2)?
     using TimePoint = std::chrono::steady_clock::time_point;
-    int finish_run(int64_t total, double gpu_ms, bool records_left, uint32_t* accepted_per_step, TimePoint tp0, TimePoint tp1, TimePoint tp2)
+    int finish_run(int64_t total, double gpu_ms, bool records_left, uint32_t* accepted_per_step, TimePoint tp1, TimePoint tp2)
     {
         last_ms = gpu_ms;
         last_launches = full_fn ? total : 2 * total;  // (a launch steps all chains)
@@ -536,9 +513,7 @@ public:
         records_step = half_steps >> 1;
         records_partner2 = full_fn != nullptr;  // (read only while records_valid)
         if (accepted_per_step) HIP_TRY(hipMemcpy(accepted_per_step, d_acc, sizeof(uint32_t) * (size_t)total * K, hipMemcpyDeviceToHost));
-        const TimePoint tp3 = std::chrono::steady_clock::now();
         host_enqueue_ms = std::chrono::duration<double, std::milli>(tp2 - tp1).count();
-        host_wall_ms = std::chrono::duration<double, std::milli>(tp3 - tp0).count();
         return MCMCPP_HIP_OK;
     }
 
@@ -556,15 +531,10 @@ public:
         return MCMCPP_HIP_OK;
     }
 
-    // to_device: chain_out is device memory of this device (run_device has checked it)
+    // to_device: chain_out is device memory of this device (the entry has checked it)
     int run_whole(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, bool to_device)
     {
-        if (int rc = check_run(n_saved, interval, true)) return rc;
         const int64_t total = n_saved * (int64_t)interval;
-        last_ms = 0.0;
-        last_launches = 0;
-        if (total == 0) return MCMCPP_HIP_OK;
-        const TimePoint tp0 = std::chrono::steady_clock::now();
 
         // how the stored steps reach the caller (run_plan.hpp): sub-chunks through staging, or -- full-step kernels -- the
         // launches forward them to pinned host memory themselves (trickle_stored_step): a ring on the device with a twin in
@@ -641,7 +611,7 @@ public:
         // the last launch left the records of the next ensemble step behind -- unless the records were made ahead in
         // batches, which leaves the two-buffer records alone
         // (the device-side RunInfo still points to run-scoped buffers; half_step_async replaces it before it launches)
-        return finish_run(total, launch_ms, plan.batch_draws == 0, accepted_per_step, tp0, tp1, tp2);
+        return finish_run(total, launch_ms, plan.batch_draws == 0, accepted_per_step, tp1, tp2);
     }
 
     // ---- one ensemble split over the ranks of an RCCL communicator (BASELINE config 5) -----------------
@@ -678,7 +648,7 @@ public:
     // fails on this rank only -- the caller agrees on it with the other ranks (agree_on_status) before the first launch.
     int prepare_split(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, int64_t* stage_slots_out)
     {
-        if (int rc = check_run(n_saved, interval, false)) return rc;
+        if (int rc = refuse_run(n_saved, interval, false)) return rc;
         const int64_t total = n_saved * (int64_t)interval;
         const size_t step_bytes = sizeof(T) * (size_t)W * D;
         // stored steps: device -> pinned staging on the launch stream, handed to the caller a staging buffer at a time
@@ -774,12 +744,9 @@ public:
     // chunks is what the last one needed, plus an eighth.
     int run_split(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step)
     {
-        last_ms = 0.0;
-        last_launches = 0;
-        host_enqueue_ms = host_wall_ms = exchange_us_per_step = 0.0;
+        host_enqueue_ms = exchange_us_per_step = 0.0;
         xchg_bytes_per_step = 0.0;
         xchg_rollbacks = 0;
-        const auto tp0 = std::chrono::steady_clock::now();
         int64_t stage_slots = 0;
         const int prep = prepare_split(n_saved, interval, chain_out, accepted_per_step, &stage_slots);
         const int64_t total = (n_saved > 0 && interval > 0) ? n_saved * (int64_t)interval : 0;
@@ -961,7 +928,7 @@ public:
         xchg_bytes_per_step = xbytes / (double)total;
         xchg_cap_slots = compact ? (int64_t)cap : 0;
         // (full-step scheme: the next run re-primes, the red records of other ranks' walkers are per step anyway)
-        return finish_run(total, run_ms, full_fn == nullptr, accepted_per_step, tp0, tp1, tp2);
+        return finish_run(total, run_ms, full_fn == nullptr, accepted_per_step, tp1, tp2);
     }
 
     // The chain path of the full-step kernels: the launches forward stored steps into the pinned ring (or into chain_out
@@ -1594,7 +1561,7 @@ private:
     DeviceBuffer<T> d_chain[2];
     PinnedBuffer<char> h_stage[2];
     DeviceBuffer<uint32_t> d_acc;
-    bool own_pos = false, run_touched_device = false;
+    bool own_pos = false;
     Event ev_t0[4], ev_t1[4];
     T *d_params = nullptr, *d_params_padded = nullptr;  // (row 0 of d_chain_params once a chain has parameters of its own)
     DeviceBuffer<T> d_chain_params;  // [K][chain_params_stride] per-chain parameters (set_chain_params), or empty: shared

@@ -1,9 +1,10 @@
 // run_plan.hpp -- how a run() delivers its stored steps and cuts itself into chunks: ring size, chunk lengths, when the host
 // must wait, where a sub-chunk lands in the caller's array, what a destination in device memory changes (run_device: no ring,
-// no staging, what wait_stored may hear), where a split run cuts so that every rank cuts alike, and the slot bound of its
-// exchange blocks.  Pure functions and one small value type over plain numbers.  No HIP header: this file
-// compiles with the host compiler alone, and tests/test_run_plan.py checks the schedules there, case by case.  The samplers
-// keep every HIP and RCCL call and ask here for the numbers.
+// no staging, what wait_stored may hear), the pieces of a differential-evolution run and the sub-chunks of a batch run, where
+// a split run cuts so that every rank cuts alike, and the slot bound of its exchange blocks.  Pure functions and a few small
+// value types over plain numbers.  No HIP header: this file compiles with the host compiler alone, and tests/test_run_plan.py,
+// tests/test_device_chain_plan.py and tests/test_run_entry.py check the schedules there, case by case.  The samplers keep
+// every HIP and RCCL call and ask here for the numbers.
 #pragma once
 
 #include <cstddef>
@@ -225,6 +226,71 @@ inline size_t subchunk_half_used(size_t step_bytes, int64_t sub_saved, int64_t n
 {
     return step_bytes * (size_t)sub_saved * (size_t)(chains - 1) + step_bytes * (size_t)now;
 }
+
+// ---- the pieces of a differential-evolution run and of a batch run (DeSampler::run_mover, BatchSampler::run_mover) --------
+// Both movers step a run a piece at a time and wait for the device behind every piece: its stored steps (and, DE, its
+// accepted counters) leave through buffers of the piece's size.  A destination in device memory needs no chain buffer.
+struct PiecePlan
+{
+    int64_t n_saved;
+    int64_t piece_saved, n_pieces;    // stored steps per piece (the last may be shorter); pieces (none for a run of nothing)
+    size_t chain_bytes, acc_entries;  // what to grow: the device chain of a host destination, the accepted counters
+
+    StoredRange piece(int64_t c) const
+    {
+        const int64_t first = c * piece_saved;
+        return {first, n_saved - first < piece_saved ? n_saved : first + piece_saved};
+    }
+};
+inline PiecePlan pieces_of(int64_t n_saved, int64_t piece_saved)
+{
+    PiecePlan p = {};
+    p.n_saved = n_saved;
+    p.piece_saved = piece_saved;
+    p.n_pieces = n_saved > 0 ? (n_saved + piece_saved - 1) / piece_saved : 0;
+    return p;
+}
+
+// DE: a piece is at most 256 MiB of the handle's device chain and 64 MiB of accepted counters, at least one stored step.
+// (Bounds of device buffers the handle keeps; split_stage_slots' 256 MiB bounds pinned host memory and is its own number.)
+// A device destination has no chain buffer, so only the counters cut it: without them it is one piece.
+constexpr size_t kDePieceChainBytes = (size_t)256 << 20, kDePieceCounterBytes = (size_t)64 << 20;
+inline PiecePlan plan_de_pieces(size_t step_bytes, int64_t n_saved, int32_t interval, bool chain, bool device_dest, bool want_accepted)
+{
+    const bool host_chain = chain && !device_dest;
+    int64_t piece = n_saved;
+    if (want_accepted)
+    {
+        const int64_t fit = (int64_t)(kDePieceCounterBytes / ((size_t)interval * sizeof(uint32_t)));
+        if (piece > fit) piece = fit < 1 ? 1 : fit;
+    }
+    if (host_chain)
+    {
+        const int64_t fit = (int64_t)(kDePieceChainBytes / step_bytes);
+        if (piece > fit) piece = fit < 1 ? 1 : fit;
+    }
+    PiecePlan p = pieces_of(n_saved, piece);
+    p.chain_bytes = host_chain ? (size_t)piece * step_bytes : 0;
+    p.acc_entries = want_accepted ? (size_t)(piece * (int64_t)interval) : 0;
+    return p;
+}
+// where a piece that starts at stored step `first` begins in the caller's device array (DE points its run record there)
+inline size_t device_piece_offset(size_t step_bytes, int64_t first) { return step_bytes * (size_t)first; }
+
+// Batch: the sub-chunks of a host chain (stored_steps_per_subchunk of `budget` bytes); one sub-chunk without a chain or into
+// device memory.  The accepted counters are kept for the whole run.
+inline PiecePlan plan_batch_pieces(size_t budget, size_t step_bytes, int64_t n_saved, int32_t interval, bool chain, bool device_dest, bool want_accepted)
+{
+    const bool host_chain = chain && !device_dest;
+    const int64_t sub_saved = host_chain ? stored_steps_per_subchunk(budget, step_bytes, n_saved) : n_saved;
+    PiecePlan p = pieces_of(n_saved, sub_saved);
+    p.chain_bytes = host_chain ? step_bytes * (size_t)sub_saved : 0;
+    p.acc_entries = want_accepted ? (size_t)(n_saved * (int64_t)interval) : 0;
+    return p;
+}
+// RunInfo::chain_slot_base of a sub-chunk that starts at stored step `first`: the kernels count a run's stored steps from 0,
+// the sub-chunk's chain (the handle's buffer, or the caller's whole device array with first = 0) starts at `first`
+inline int64_t subchunk_slot_base(int64_t first) { return -first; }
 
 // ---- split runs (Sampler::run_split) -----------------------------------------------------------------------------------
 // Slots of the pinned staging of stored steps: 256 MiB worth, at least one, at most the run's.  The same number on every

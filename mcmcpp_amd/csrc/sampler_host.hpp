@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -14,6 +15,7 @@
 
 #include "launch_table.hpp"
 #include "run_plan.hpp"
+#include "run_refusal.hpp"
 #include "sampler_base.hpp"
 #include "tie_eps.h"
 
@@ -151,8 +153,8 @@ mcmcpp_hip_sampler* make_handle(const mcmcpp_hip_config& cfg, int* rc)
     return s;
 }
 
-// The state and plumbing every sampler handle has.  Each mover keeps its precondition checks in its own overrides and
-// calls the helpers below from there.
+// The state and plumbing every sampler handle has, and the one entry of a run.  Each mover keeps the precondition checks of
+// its other calls in its own overrides and calls the helpers below from there.
 template <class T>
 class SamplerHost : public mcmcpp_hip_sampler
 {
@@ -184,7 +186,65 @@ public:
         return MCMCPP_HIP_OK;
     }
 
+    // EnsembleSampler::runMCMC (EnsembleSampler.h:284-310): interval-1 unsaved ensemble steps, one saved, n_saved times;
+    // run_device leaves the stored steps in the caller's device memory.  Both are run_entry, for every mover.
+    int run(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step) override
+    {
+        return run_entry(n_saved, interval, chain_out, accepted_per_step, false);
+    }
+    int run_device(int64_t n_saved, int32_t interval, void* device_chain, uint32_t* accepted_per_step) override
+    {
+        return run_entry(n_saved, interval, device_chain, accepted_per_step, true);
+    }
+
 protected:
+    // ---- what a mover decides about a run: nothing else of run_entry is its business --------------------------------------
+    // the ensembles whose stored steps a device destination holds
+    virtual int run_chains() const { return 1; }
+    // which mover it is and the facts only it knows (run_refusal.hpp); run_entry fills in the rest
+    virtual RunFacts run_facts() const = 0;
+    // The run itself, behind the checks: n_saved > 0 and the arguments are good -- unless the handle runs collectively
+    // (run_is_collective), which hears of its own refusal through refuse_run.  It sets run_touched in front of its first launch.
+    virtual int run_mover(int64_t n_saved, int32_t interval, void* chain, uint32_t* accepted_per_step, bool to_device) = 0;
+    // the run failed behind its first launch and the walker state has been abandoned
+    virtual void state_abandoned() {}
+
+    // the refusal of a run call, if any (run_refusal.hpp), with its message
+    int refuse_run(int64_t n_saved, int32_t interval, bool to_device, bool* collective = nullptr)
+    {
+        RunFacts f = run_facts();
+        f.to_device = to_device;
+        f.have_state = have_state;
+        f.bad_arguments = n_saved < 0 || interval < 1;
+        if (collective) *collective = run_is_collective(f);
+        const RunRefusal r = run_refusal(f);
+        return r == RunRefusal::None ? MCMCPP_HIP_OK : fail(run_refusal_code(r), "%s: %s", to_device ? "run_device" : "run", run_refusal_text(r));
+    }
+
+    int run_entry(int64_t n_saved, int32_t interval, void* chain, uint32_t* accepted_per_step, bool to_device)
+    {
+        run_touched = false;
+        bool collective = false;
+        const int refused = refuse_run(n_saved, interval, to_device, &collective);
+        if (refused && !collective) return refused;
+        HIP_TRY(hipSetDevice(device));
+        // the destination, asked of the runtime before anything is launched or allocated (nothing to store: NULL is fine)
+        if (to_device && n_saved > 0)
+            if (int rc = check_device_range("run_device", "device_chain", chain, sizeof(T) * (size_t)W * D * (size_t)n_saved * (size_t)run_chains(), 16)) return rc;
+        last_ms = 0.0;
+        last_launches = 0;
+        if (n_saved == 0 && !collective) return MCMCPP_HIP_OK;
+        const auto t0 = std::chrono::steady_clock::now();
+        const int rc = run_mover(n_saved, interval, chain, accepted_per_step, to_device);
+        host_wall_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        if (rc != MCMCPP_HIP_OK && run_touched)
+        {
+            abandon_state();
+            state_abandoned();
+        }
+        return rc;
+    }
+
     // W, D, n and the lane mapping of the kernels: LPW lanes x EPL elements cover the walker's D-vector padded to a power of
     // two (16 bytes per lane until a walker fills a wavefront)
     void set_shape(const mcmcpp_hip_config& c)
@@ -243,6 +303,19 @@ protected:
         (void)hipGetLastError();
         have_state = false;
         error = keep + " (the walker state on the device is no longer consistent: call set_state again)";
+    }
+
+    // set_state of one ensemble: positions, log-posteriors, zeroed accepted counters and diagnostics, enqueued on the stream
+    int upload_state(const void* pos, const void* logp)
+    {
+        if (!pos || !logp) return fail(MCMCPP_HIP_E_ARG, "set_state: null pointer");
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(hipMemcpyAsync(d_pos, pos, sizeof(T) * (size_t)W * D, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(d_logp, logp, sizeof(T) * (size_t)W, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemsetAsync(d_nacc, 0, sizeof(uint32_t) * (size_t)W, stream));
+        HIP_TRY(hipMemsetAsync(d_diag, 0, sizeof(Diag), stream));
+        steps_since_reset = 0;
+        return MCMCPP_HIP_OK;
     }
 
     // get_state of one ensemble
@@ -337,12 +410,6 @@ protected:
         return MCMCPP_HIP_OK;
     }
 
-    // the destination of a run_device: K * n_saved stored steps of device memory, 16-byte aligned
-    int check_device_chain(const void* device_chain, int64_t n_saved, int chains)
-    {
-        return check_device_range("run_device", "device_chain", device_chain, sizeof(T) * (size_t)W * D * (size_t)n_saved * (size_t)chains, 16);
-    }
-
     // calc_logp by the calculator's own kernel (`calc` of its launch table)
     int kernel_calc_logp(typename LaunchTable<T>::CalcFn calc_fn, const T* params, const void* pos, int64_t count, void* out)
     {
@@ -365,6 +432,7 @@ protected:
     int W = 0, D = 0, n = 0, lpw = 1, epl = 1, vec_ok = 0, device = -1;
     hipStream_t stream = nullptr;
     bool own_stream = false, stream_valid = false, have_state = false;
+    bool run_touched = false;  // the run in hand has launched: a failure from here on leaves the device ahead of the host's bookkeeping
     // the walkers: positions [W][D], log-posteriors [W], accepted counters [W] (the mover allocates them)
     T *d_pos = nullptr, *d_logp = nullptr;
     uint32_t* d_nacc = nullptr;
@@ -379,10 +447,10 @@ protected:
     using Host = SamplerHost<T>;                                                                                                \
     using Host::W, Host::D, Host::n, Host::lpw, Host::epl, Host::vec_ok, Host::device, Host::stream, Host::own_stream,        \
         Host::stream_valid, Host::have_state, Host::d_pos, Host::d_logp, Host::d_nacc, Host::d_diag, Host::steps_since_reset, \
-        Host::last_ms, Host::last_launches;                                                                                     \
+        Host::last_ms, Host::last_launches, Host::run_touched;                                                                                   \
     using Host::set_shape, Host::open_device, Host::open_stream, Host::quiesce, Host::abandon_state, Host::read_state,         \
         Host::clear_accepted, Host::read_counters, Host::kernel_calc_logp, Host::kernel_calc_logp_device, Host::check_device_range,   \
-        Host::check_device_chain;                                                   \
+        Host::upload_state, Host::refuse_run;                                       \
     using Host::fail, Host::error, Host::publish_stored, Host::host_enqueue_ms, Host::host_wall_ms
 
 }  // namespace mcmcpp

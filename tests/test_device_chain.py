@@ -250,6 +250,25 @@ def test_differential_evolution(name, n_saved, interval):
     _golden_twins(name, n_saved, interval)
 
 
+@pytest.mark.gpu
+def test_differential_evolution_across_a_piece_boundary():
+    """The largest stored step the mover accepts at the smallest step count: 2050 x 1024 fp64 (the smallest even W above 2 D)
+    is 16 793 600 bytes, so the 256 MiB of device chain behind a host destination hold 15 stored steps and a run of 17 leaves
+    in two pieces (15 + 2: plan_de_pieces, tests/test_run_entry.py).  The twin stores into device memory, which is one piece
+    by construction.  Chains, per-step accepted counts, final states and counters are identical; a run that set the mover's
+    error flag would have failed.  The other bound of a piece, 64 MiB of accepted counters, needs more than 2^24 ensemble
+    steps in one run -- minutes, not seconds, at any shape: the CPU grid of tests/test_run_entry.py is its check."""
+    W, D, n_saved = 2050, 1024, 17
+    assert (256 << 20) // (W * D * 8) == 15 < n_saved
+    pos, logp = _start(W, D, po.CALC_ISO_GAUSSIAN, None, po.F64)
+    make = lambda: capi.HipSampler(W, D, po.CALC_ISO_GAUSSIAN, None, seed=11, mover=capi.MOVER_DIFFERENTIAL_EVOLUTION)
+    dev = _twins(make, pos, logp, n_saved, 1)[0]
+    c = dev.counters()
+    assert c["near_ties"] == 0 and c["ensemble_steps"] == n_saved
+    # (the 320 MB destination goes back to the runtime: left in torch's cache, it would be carved up for later tests' tensors)
+    _torch().cuda.empty_cache()
+
+
 # ---- batch targets ------------------------------------------------------------------------------------------------------------
 
 from tests.test_batch_calc import CTarget, _torch_iso, cb_lib  # noqa: E402,F401  (the callback library's fixture and a torch target)
@@ -280,6 +299,21 @@ def test_batch_target_c_callback(cb_lib, monkeypatch):
     with pytest.raises(capi.HipError) as e:
         dev.calc_logp_device(out, chain=1)
     assert e.value.code == E_ARG and "chain" in str(e.value)
+
+
+@pytest.mark.gpu
+def test_batch_target_across_sub_chunks(cb_lib, monkeypatch):
+    """Nine stored steps, two ensemble steps apart: the host destination takes them in five sub-chunks (an eighth of the run,
+    rounded up, is two stored steps; the last sub-chunk holds one), the device destination in one.  Both are the chain of the
+    fused half-step kernels."""
+    W, D, seed, n_saved, interval = 64, 4, 29, 9, 2
+    pos, logp = _start(W, D, po.CALC_ISO_GAUSSIAN, None, po.F64)
+    tgt = CTarget(cb_lib, po.CALC_ISO_GAUSSIAN, D, None, po.F64)
+    make = lambda: capi.HipSampler(W, D, capi.CALC_BATCH, seed=seed, batch_callback=tgt.callback())
+    dev, _, chain = _twins(make, pos, logp, n_saved, interval)
+    f, (want_chain, _) = _fused_iso(W, D, seed, pos, logp, n_saved, interval, monkeypatch)
+    np.testing.assert_array_equal(chain, want_chain)
+    _same_handles(dev, f)
 
 
 @pytest.mark.gpu
