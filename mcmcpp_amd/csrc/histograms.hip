@@ -32,11 +32,13 @@
 #include <vector>
 
 #include "../../include/mcmcpp_hip.h"
+#include "hist_plan.hpp"
 #include "sampler_base.hpp"
 
 namespace
 {
 constexpr int kHistThreads = 256;
+static_assert(kHistThreads == mcmcpp::kHistPlanThreads, "hist_plan.hpp plans for the block size of these kernels");
 
 template <class T>
 __device__ __forceinline__ const T* sample_row(const T* base, long long step_stride, unsigned W, int P, unsigned s)
@@ -191,7 +193,7 @@ struct mcmcpp_hip_histograms
     long long npairs = 0;
     size_t chunk_bytes = 0;        // MCMCPP_HIP_HIST_CHUNK_MB
     size_t lds_limit = 0;          // dynamic LDS per block for the counters
-    int idx_bytes = 1;             // 1 / 2 / 4 (bins <= 256 / <= 65536 / more)
+    int idx_bytes = 1;             // 1 / 2 / 4 (hist_plan.hpp)
     mcmcpp::DeviceBuffer<unsigned long long> d_single, d_pairs, d_clamped;
     mcmcpp::DeviceBuffer<int> d_ij;      // [npairs][2]
     mcmcpp::DeviceBuffer<int> d_nan;
@@ -248,10 +250,8 @@ int bounds_pass(mcmcpp_hip_histograms* h, const Span<T>& sp, std::vector<T>& lo,
 {
     const unsigned n = (unsigned)(sp.n_steps * h->W);
     if (n == 0) return MCMCPP_HIP_OK;
-    unsigned blocks = (unsigned)h->cus * 2;
-    if (blocks > (n + 255) / 256) blocks = (n + 255) / 256;
-    const unsigned per = (n + blocks - 1) / blocks;
-    blocks = (n + per - 1) / per;
+    const mcmcpp::HistPlan plan = mcmcpp::hist_plan(n, h->P, h->bins, h->with_pairs, h->cus, h->lds_limit);
+    const unsigned blocks = plan.bounds_blocks, per = plan.bounds_per;
     const size_t pbytes = sizeof(T) * 2 * (size_t)blocks * h->P;
     int rc = ensure(h, h->d_part, pbytes, "the bounds partials");
     if (rc) return rc;
@@ -276,53 +276,25 @@ int count_pass_t(mcmcpp_hip_histograms* h, const Span<T>& sp)
 {
     const unsigned n = (unsigned)(sp.n_steps * h->W);
     if (n == 0) return MCMCPP_HIP_OK;
-    const size_t col = ((size_t)n + 15) & ~(size_t)15;
+    const mcmcpp::HistPlan plan = mcmcpp::hist_plan(n, h->P, h->bins, h->with_pairs, h->cus, h->lds_limit);
+    const size_t col = plan.col;
     int rc = ensure(h, h->d_idx, sizeof(I) * col * h->P, "the bin index buffer");
     if (rc) return rc;
     I* idx = (I*)h->d_idx.get();
     const int bins = h->bins;
+    hipLaunchKernelGGL((hist_bin_kernel<T, I>), dim3(plan.bin_blocks), dim3(kHistThreads), 0, h->stream, sp.base, sp.step_stride, (unsigned)h->W, h->P, n,
+                       (const T*)h->d_edges.get(), bins, idx, col, h->d_clamped);
+    HIST_TRY(hipGetLastError());
+    hipLaunchKernelGGL((hist_single_kernel<I>), dim3(plan.single_blocks, h->P), dim3(kHistThreads), plan.single_lds_bytes, h->stream, idx, col, n,
+                       plan.single_per, bins, plan.single_lds, h->d_single);
+    HIST_TRY(hipGetLastError());
+    const size_t b2 = (size_t)bins * bins;
+    for (long long i = 0; i < plan.pair_launches; ++i)  // (none without pairs; more than one past the grid.y limit)
     {
-        unsigned blocks = (n + kHistThreads - 1) / kHistThreads;
-        if (blocks > (unsigned)h->cus * 8) blocks = (unsigned)h->cus * 8;
-        hipLaunchKernelGGL((hist_bin_kernel<T, I>), dim3(blocks), dim3(kHistThreads), 0, h->stream, sp.base, sp.step_stride, (unsigned)h->W,
-                           h->P, n, (const T*)h->d_edges.get(), bins, idx, col, h->d_clamped);
+        const mcmcpp::HistPairLaunch l = plan.pair_launch(i);
+        hipLaunchKernelGGL((hist_pairs_kernel<I>), dim3(plan.pair_blocks, (unsigned)l.now), dim3(kHistThreads), plan.pair_lds_bytes, h->stream, idx, col, n,
+                           plan.pair_per, bins, h->d_ij + 2 * l.q0, plan.npairs - l.q0, plan.tile, plan.pair_lds, h->d_pairs + (size_t)l.q0 * b2);
         HIST_TRY(hipGetLastError());
-    }
-    // slices of samples: enough blocks to fill the device, each slice long enough to amortise its flush
-    auto slices_for = [&](long long columns, long long flush_cells) {
-        long long want = ((long long)h->cus * 4 + columns - 1) / columns;
-        const long long most = (long long)n / (flush_cells * 4 > 1024 ? flush_cells * 4 : 1024);
-        if (want > most) want = most;
-        if (want < 1) want = 1;
-        return (unsigned)want;
-    };
-    {
-        const int lds = (size_t)bins * 4 <= h->lds_limit;
-        const unsigned slices = slices_for(h->P, lds ? bins : 1);
-        const unsigned per = (n + slices - 1) / slices;
-        hipLaunchKernelGGL((hist_single_kernel<I>), dim3((n + per - 1) / per, h->P), dim3(kHistThreads), lds ? (size_t)bins * 4 : 0, h->stream,
-                           idx, col, n, per, bins, lds, h->d_single);
-        HIST_TRY(hipGetLastError());
-    }
-    if (h->with_pairs && h->npairs > 0)
-    {
-        const size_t b2 = (size_t)bins * bins;
-        const int lds = b2 * 4 <= h->lds_limit;
-        int tile = lds ? (int)(h->lds_limit / (b2 * 4)) : 1;
-        if (tile > 64) tile = 64;
-        // keep enough tiles to fill the device
-        while (tile > 1 && (h->npairs + tile - 1) / tile < (long long)h->cus * 2) tile /= 2;
-        const long long tiles = (h->npairs + tile - 1) / tile;
-        const unsigned slices = slices_for(tiles, lds ? (long long)(tile * b2) : 1);
-        const unsigned per = (n + slices - 1) / slices;
-        for (long long t0 = 0; t0 < tiles; t0 += 65535)  // grid.y limit
-        {
-            const long long now = (tiles - t0 < 65535) ? tiles - t0 : 65535;
-            const long long q0 = t0 * tile;
-            hipLaunchKernelGGL((hist_pairs_kernel<I>), dim3((n + per - 1) / per, (unsigned)now), dim3(kHistThreads), lds ? (size_t)tile * b2 * 4 : 0,
-                               h->stream, idx, col, n, per, bins, h->d_ij + 2 * q0, h->npairs - q0, tile, lds, h->d_pairs + (size_t)q0 * b2);
-            HIST_TRY(hipGetLastError());
-        }
     }
     return MCMCPP_HIP_OK;
 }
@@ -420,14 +392,8 @@ int after_bounds(mcmcpp_hip_histograms* h, const std::vector<T>& lo, const std::
     return MCMCPP_HIP_OK;
 }
 
-// samples per pass-2 chunk: bounded by the chunk size (through the index buffer) and by 32-bit sample indexing
-long long steps_per_chunk(const mcmcpp_hip_histograms* h, size_t step_bytes)
-{
-    long long k = (long long)(h->chunk_bytes / step_bytes);
-    const long long cap = ((long long)1 << 31) / h->W - 1;
-    if (k > cap) k = cap;
-    return k < 1 ? 1 : k;
-}
+// steps per chunk of either pass
+long long steps_per_chunk(const mcmcpp_hip_histograms* h, size_t step_bytes) { return mcmcpp::hist_steps_per_chunk(h->chunk_bytes, step_bytes, h->W); }
 
 template <class T>
 int compute_host(mcmcpp_hip_histograms* h, const void* const* steps, int64_t n_steps)
@@ -515,7 +481,7 @@ int mcmcpp_hip_histograms_create(int32_t dtype, int32_t device, int32_t num_walk
     hipDeviceProp_t prop;
     std::string why;
     if (int rc = mcmcpp::open_gfx950_device(device, &device, &prop, &why)) return fail(h, rc, "histograms_create: " + why);
-    const long long npairs = with_pairs ? (long long)num_params * (num_params - 1) / 2 : 0;
+    const long long npairs = mcmcpp::hist_npairs(num_params, with_pairs != 0);
     // the 64-bit result arrays; refuse what cannot be addressed before asking the allocator
     const double pair_bytes = (double)npairs * (double)bins * (double)bins * 8.0;
     const double single_bytes = (double)num_params * (double)bins * 8.0;
@@ -535,8 +501,8 @@ int mcmcpp_hip_histograms_create(int32_t dtype, int32_t device, int32_t num_walk
     h->with_pairs = with_pairs != 0;
     h->npairs = npairs;
     h->cus = prop.multiProcessorCount;
-    h->lds_limit = prop.sharedMemPerBlock < (size_t)65536 ? prop.sharedMemPerBlock : (size_t)65536;
-    h->idx_bytes = bins <= 256 ? 1 : (bins <= 65536 ? 2 : 4);
+    h->lds_limit = mcmcpp::hist_lds_limit(prop.sharedMemPerBlock);
+    h->idx_bytes = mcmcpp::hist_index_bytes(bins);
     size_t mb = 1024;
     if (const char* env = std::getenv("MCMCPP_HIP_HIST_CHUNK_MB"))
     {

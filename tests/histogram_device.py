@@ -14,6 +14,9 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 from mcmcpp_amd import capi  # noqa: E402
+from tests import histogram_restatement as hr  # noqa: E402
+
+EDGE_KS = 40  # random bin edges per parameter, beside the fixed ones
 
 
 def _dt(name):
@@ -48,6 +51,8 @@ def make_steps(spec):
     rng = np.random.default_rng(spec.get("seed", 1))
     n, W, P = spec["n"], spec["W"], spec["P"]
     x = (rng.standard_normal((n, W, P)) * rng.uniform(0.2, 4.0, P) + rng.uniform(-3, 3, P)).astype(t)
+    if n == 0:
+        return x
     if not spec.get("positive"):
         x = (x - (x.reshape(-1, P).max(axis=0) + t(0.5))).astype(t)  # <= 0: the reference's defined case
     else:
@@ -56,7 +61,38 @@ def make_steps(spec):
         x[..., p] = t(spec.get("constant_value", -1.75))
     for p in spec.get("zero", []):
         x[..., p] = t(0)
+    if spec.get("edges"):
+        place_edges(x, spec["bins"], spec.get("slice", 1))
     return x
+
+
+def place_edges(x, bins, slice_interval=1):
+    """Overwrites samples of the used steps of non-positive x with values on the bin edges and beside them: per parameter,
+    for k in 1, 2, 3, bins/3, bins/2, bins - 2, bins - 1, bins and EDGE_KS random k, the edge fl(lo + fl(k width)) as the
+    analysis classes compute it and its two neighbours in T.  Only values above the parameter's minimum and not above 0 are
+    placed, and never on the minimum's sample: the bounds stay what they were.  Returns the number of samples placed."""
+    T = x.dtype.type
+    P = x.shape[-1]
+    used = x[::slice_interval]
+    bounds = hr.find_binning(used, bins)
+    flat = used.reshape(-1, P).copy()
+    rng = np.random.default_rng(99)
+    placed = 0
+    for p in range(P):
+        lo, w = T(bounds[p, 0]), T(bounds[p, 1])
+        smallest, at = flat[:, p].min(), int(flat[:, p].argmin())
+        ks = sorted(set([1, 2, 3, bins // 3, bins // 2, bins - 2, bins - 1, bins] + [int(k) for k in rng.integers(1, bins, EDGE_KS)]))
+        vals = []
+        for k in ks:
+            e = T(lo + T(T(k) * w))
+            for v in (np.nextafter(e, T(-np.inf)), e, np.nextafter(e, T(np.inf))):
+                if v > smallest and v <= 0:
+                    vals.append(v)
+        rows = [r for r in rng.permutation(flat.shape[0]) if r != at][:len(vals)]
+        flat[rows, p] = vals[:len(rows)]
+        placed += len(rows)
+    x[::slice_interval] = flat.reshape(used.shape)
+    return placed
 
 
 def random_case(spec, out):
@@ -70,7 +106,7 @@ def random_case(spec, out):
     h.compute(steps, spec.get("slice", 1))
     _results("host_", h, out)
     if spec.get("device", True):
-        d = torch.from_numpy(steps).cuda()
+        d = torch.from_numpy(steps).cuda() if steps.shape[0] else torch.zeros(1, device="cuda")  # (no steps: any address)
         h.compute_device(d.data_ptr(), steps.shape[0], spec.get("slice", 1))
         torch.cuda.synchronize()
         _results("dev_", h, out)
@@ -129,10 +165,17 @@ def errors(spec, out):
     _results("later_", ok, out)
 
 
+def device_info(spec, out):
+    """what the library's launch plan depends on (mcmcpp_amd/csrc/hist_plan.hpp), of the device the cases run on"""
+    prop = torch.cuda.get_device_properties(0)
+    out["cus"] = np.int64(prop.multi_processor_count)
+    out["shared_mem_per_block"] = np.int64(prop.shared_memory_per_block)
+
+
 def main():
     spec = json.loads(sys.argv[1])
     out = {}
-    {"fixture": fixture, "random": random_case, "device_chain": device_chain, "errors": errors}[spec["kind"]](spec, out)
+    {"fixture": fixture, "random": random_case, "device_chain": device_chain, "errors": errors, "device_info": device_info}[spec["kind"]](spec, out)
     np.savez(sys.argv[2], **out)
     print("histogram_device OK")
 

@@ -94,10 +94,12 @@ def histograms(steps, bins, slice_interval=1, with_pairs=True):
     single = np.stack([np.bincount(b[:, p], minlength=bins) for p in range(P)]).astype(np.int64)
     pairs = None
     if with_pairs:
+        b2 = bins * bins
         pairs = np.zeros((P * (P - 1) // 2, bins, bins), np.int64)
         for i in range(1, P):
-            for j in range(i):
-                pairs[i * (i - 1) // 2 + j] = np.bincount(b[:, i] * bins + b[:, j], minlength=bins * bins).reshape(bins, bins)
+            # pairs (i, 0) .. (i, i - 1) lie side by side: one count over cell numbers j * bins^2 + bin_i * bins + bin_j
+            cells = b[:, i:i + 1] * bins + b[:, :i] + np.arange(i, dtype=np.int64) * b2
+            pairs[i * (i - 1) // 2:i * (i + 1) // 2] = np.bincount(cells.ravel(), minlength=i * b2).reshape(i, bins, bins)
     return dict(num_points=b.shape[0], bounds=bounds, single=single, pairs=pairs, clamped=clamped)
 
 

@@ -5,7 +5,10 @@ reference produced (tests/golden/make_golden.py autocorr) -- bit for bit: Detail
 series, and the whole AutoCorrCalc class with the oracle's defect emulation on (the reference adds every series onto
 the previous walker's result, AutoCorrCalc.h:239-245; see the .inc).
 GPU: mcmcpp_hip_autocorr_times against the oracle with the emulation off -- times AND averaged autocovariance
-functions bit for bit, both element types, transform in LDS and in global memory, walker subsets, scattered steps."""
+functions bit for bit, both element types, transform in LDS and in global memory, walker subsets, scattered steps,
+windows that close in the second and third tile of 256 lags (the window kernel carries its compensated sum from tile to
+tile), a parameter that never moves (0 / 0: NaN, its neighbours untouched), and the device-memory entry with a walker
+subset and another window."""
 import os
 
 import numpy as np
@@ -97,6 +100,76 @@ def test_device_autocorr_matches_the_oracle_bit_for_bit(n, W, D, phi, window, dt
     np.testing.assert_array_equal(got_t, want_t)
 
 
+LATE_WINDOWS = [  # n, W, D, phi, window, dtype, seed, (tile of 256 lags in which parameter 0's window closes)
+    (2048, 3, 2, (0.99, 0.5), 4, np.float64, 21, 1),
+    (4096, 4, 2, (0.99, 0.3), 4, np.float32, 22, 2),
+]
+
+
+def _closing_lag(function, window, T):
+    """the lag at which AutoCorrCalc's window closes over one averaged function, and the time it returns there: its loop
+    (AutoCorrCalc.h:170-207), in T"""
+    acs, c, factor = T(-function[0]), T(0), T(window)
+    for i in range(function.size):
+        value = T(T(T(2) * function[i]) - c)
+        temp = T(acs + value)
+        c = T(T(temp - acs) - value)
+        acs = temp
+        if T(i) > T(factor * acs):
+            return i, acs
+    return None, T(-acs)
+
+
+@pytest.mark.parametrize("n,W,D,phi,window,dt,seed,tile", LATE_WINDOWS)
+def test_late_window_cases_close_beyond_the_first_tile_of_lags(n, W, D, phi, window, dt, seed, tile):
+    """what the GPU cases below rest on, from the oracle alone: parameter 0's window closes past lag 255, parameter 1's before"""
+    dtype = po.F32 if dt == np.float32 else po.F64
+    times, functions = po.autocorr_times(ar_chain(n, W, D, seed, phi, dt), window, False, dtype, want_functions=True)
+    lag0, t0 = _closing_lag(functions[0], window, dt)
+    lag1, t1 = _closing_lag(functions[1], window, dt)
+    assert (t0, t1) == (times[0], times[1])  # the loop above is the oracle's
+    assert 256 <= lag0 < n and lag0 // 256 == tile
+    assert lag1 < 256
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,W,D,phi,window,dt,seed,tile", LATE_WINDOWS)
+def test_device_autocorr_window_closing_in_a_later_tile(n, W, D, phi, window, dt, seed, tile):
+    dtype = po.F32 if dt == np.float32 else po.F64
+    steps = ar_chain(n, W, D, seed, phi, dt)
+    want_t, want_f = po.autocorr_times(steps, window, False, dtype, want_functions=True)
+    got_t, got_f = capi.autocorr_times(steps, 0, window, want_functions=True)
+    np.testing.assert_array_equal(got_f, want_f)
+    np.testing.assert_array_equal(got_t, want_t)
+    assert np.all(got_t > 0)
+
+
+def _constant_parameter_chain():
+    steps = ar_chain(300, 4, 3, 5, (0.9, 0.5, 0.7))
+    steps[:, :, 1] = -1.25
+    return steps
+
+
+def test_oracle_gives_nan_for_a_parameter_that_never_moves():
+    """lag 0 of its autocovariance is 0 and the normalised function 0 / 0; the neighbours are what they are without it"""
+    steps = _constant_parameter_chain()
+    times, functions = po.autocorr_times(steps, 4, want_functions=True)
+    assert np.isnan(times[1]) and np.isnan(functions[1]).all()
+    np.testing.assert_array_equal(times[[0, 2]], po.autocorr_times(steps[:, :, [0, 2]], 4))
+    np.testing.assert_allclose(times[[0, 2]], [19.83, 4.17], atol=0.005)
+
+
+@pytest.mark.gpu
+def test_device_autocorr_of_a_parameter_that_never_moves():
+    steps = _constant_parameter_chain()
+    want_t, want_f = po.autocorr_times(steps, 4, want_functions=True)
+    got_t, got_f = capi.autocorr_times(steps, 0, 4, want_functions=True)
+    assert np.isnan(got_t[1]) and np.isnan(got_f[1]).all()
+    np.testing.assert_array_equal(got_f, want_f)  # (NaN equal to NaN; every other element bit for bit)
+    np.testing.assert_array_equal(got_t, want_t)
+    assert got_t[[0, 2]].tobytes() == want_t[[0, 2]].tobytes() and got_f[[0, 2]].tobytes() == want_f[[0, 2]].tobytes()
+
+
 @pytest.mark.gpu
 def test_device_passes_the_references_own_autocorr_test():
     """The reference's AcTime test (100 walkers x 5 AR(1) parameters x 262144 stored steps, 1 GB) on the device: bit
@@ -174,6 +247,31 @@ def test_device_resident_chain_gives_the_same_times():
     got = capi.autocorr_times_device(t.data_ptr(), 700, 12, 5)
     np.testing.assert_array_equal(got, capi.autocorr_times(steps, 0, 4))
     np.testing.assert_array_equal(got, po.autocorr_times(steps, 4))
+
+
+@pytest.mark.gpu
+def test_device_resident_fp32_chain_with_a_walker_subset():
+    import torch
+    n, W, D, use = 700, 12, 5, 5
+    steps = ar_chain(n, W, D, 8, (0.9, 0.5, 0.7, 0.2, 0.8), np.float32)
+    t = torch.from_numpy(steps).cuda()
+    got = capi.autocorr_times_device(t, walkers_to_use=use)
+    assert got.dtype == np.float32
+    np.testing.assert_array_equal(got, capi.autocorr_times(steps, use, 4))
+    idx = [(i * W) // use for i in range(use)]
+    np.testing.assert_array_equal(got, po.autocorr_times(steps[:, idx, :], 4, False, po.F32))
+
+
+@pytest.mark.gpu
+def test_device_resident_chain_with_another_window():
+    import torch
+    steps = ar_chain(700, 12, 5, 8, (0.9, 0.5, 0.7, 0.2, 0.8))
+    t = torch.from_numpy(steps).cuda()
+    got = capi.autocorr_times_device(t.data_ptr(), 700, 12, 5, window_scaling=3)
+    np.testing.assert_array_equal(got, capi.autocorr_times(steps, 0, 3))
+    want = po.autocorr_times(steps, 3)
+    np.testing.assert_array_equal(got, want)
+    assert not np.array_equal(want, po.autocorr_times(steps, 4))  # the window matters on this chain
 
 
 @pytest.mark.gpu

@@ -5,7 +5,11 @@ CPU: the restatement (tests/histogram_restatement.py) reproduces fixtures the re
 like the reference test's analysis section compiles against include/MCMCpp.
 GPU: the device (mcmcpp_hip_histograms_*, through the C ABI and through the facade headers) reproduces the fixtures
 exactly, and the restatement exactly on ragged and larger shapes, positive data (clamped bins), many upload chunks and a
-chain the sampler wrote into device memory.  Every GPU step runs in a child process under its own time limit."""
+chain the sampler wrote into device memory.  PATHS walks the launch paths of histograms.hip (mcmcpp_amd/csrc/hist_plan.hpp
+chooses among them by bins, pairs and the device's CU count): each case asks the plan which path its shape takes on the
+device at hand and fails where that is not the one it is named for.  Cases with `edges` put samples on the bin edges and
+one step of T beside them, where a bin decides between two counters.  Every GPU step runs in a child process under its own
+time limit."""
 import json
 import os
 import struct
@@ -18,6 +22,8 @@ import pytest
 from mcmcpp_amd import capi
 from tests import histogram_restatement as hr
 from tests.goldens import GOLDEN_DIR
+from tests.histogram_device import make_steps
+from tests.test_hist_plan import build_driver, plan_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURES = ["hist_skewed320x2", "hist_skewed320x2_f32", "hist_96x5_slice3", "hist_96x5_slice3_f32", "hist_40x3_bins2",
@@ -120,6 +126,78 @@ def test_exports_and_chunk_knob_are_declared():
     assert "MCMCPP_HIP_HIST_CHUNK_MB" in header
 
 
+# The launch paths of histograms.hip, by the plan's numbers on a device of 256 CUs and 64 KiB of LDS for a block.
+# name: (spec, element types, what the plan must say).  n = W x (steps used).
+PATHS = {
+    # 33 153 pairs in 519 tiles of 64, one pair in the last; hist_bounds_kernel's second round of parameters with pt = 2
+    "tile64_ragged": (dict(W=70, n=6, P=258, bins=4), ("f64", "f32"), dict(pair_lds=1, tile=64, tiles=519, last_count=1, pair_blocks=1)),
+    # 32 896 pairs in 514 full tiles; second round with pt = 1
+    "tile64_full": (dict(W=70, n=6, P=257, bins=4), ("f64", "f32"), dict(pair_lds=1, tile=64, tiles=514, last_count=64, pair_blocks=1)),
+    # the same tiles over two slices of 4500 samples (17 rounds of 256 threads and 148 more)
+    "tile64_two_slices": (dict(W=300, n=30, P=258, bins=4), ("f64",), dict(pair_lds=1, tile=64, tiles=519, last_count=1, pair_blocks=2, pair_per=4500)),
+    "tile8": (dict(W=100, n=6, P=92, bins=3), ("f64", "f32"), dict(pair_lds=1, tile=8, tiles=524, last_count=2)),
+    # two 90 x 90 histograms (64 800 bytes) just fit, three would not; 67 MB of counters
+    "tile2_lds_bound": (dict(W=100, n=6, P=47, bins=90), ("f64", "f32"), dict(pair_lds=1, tile=2, tiles=541, last_count=1, pair_lds_bytes=64800)),
+    "tile1_after_90": (dict(W=100, n=6, P=47, bins=91), ("f64", "f32"), dict(pair_lds=1, tile=1, tiles=1081, pair_lds_bytes=33124)),
+    "pairs_lds_exact": (dict(W=100, n=6, P=3, bins=128), ("f64", "f32"), dict(pair_lds=1, tile=1, pair_lds_bytes=65536)),
+    "pairs_global": (dict(W=100, n=6, P=3, bins=129), ("f64", "f32"), dict(pair_lds=0, tile=1, pair_lds_bytes=0)),
+    "single_lds_exact": (dict(W=250, n=20, P=2, bins=16384, pairs=False, edges=True), ("f64", "f32"), dict(single_lds=1, single_lds_bytes=65536, idx_bytes=2)),
+    "single_global": (dict(W=250, n=20, P=2, bins=16385, pairs=False, edges=True), ("f64", "f32"), dict(single_lds=0, single_lds_bytes=0, single_blocks=4)),
+    # the largest index a type holds (255, 65 535) and the first shape of the next type, with the top bins filled
+    "idx_u8_top": (dict(W=300, n=4, P=2, bins=256, edges=True), ("f64", "f32"), dict(idx_bytes=1, pair_lds=0)),
+    "idx_u16_first": (dict(W=300, n=4, P=2, bins=257, edges=True), ("f64", "f32"), dict(idx_bytes=2, pair_lds=0)),
+    "idx_u16_top": (dict(W=300, n=4, P=2, bins=65536, pairs=False, edges=True), ("f64", "f32"), dict(idx_bytes=2, single_lds=0)),
+    "idx_u32_first": (dict(W=300, n=4, P=2, bins=65537, pairs=False, edges=True), ("f64", "f32"), dict(idx_bytes=4, single_lds=0)),
+}
+PATH_CASES = [(name, dt) for name, (_, dts, _) in PATHS.items() for dt in dts]
+PATH_SEED = 7
+
+
+def _path_spec(name, dtype):
+    return dict(PATHS[name][0], kind="random", slice=1, seed=PATH_SEED, dtype=dtype)
+
+
+def _plan_on(exe, spec, cus, lds):
+    used = (spec["n"] + spec.get("slice", 1) - 1) // spec.get("slice", 1)
+    return plan_of(exe, n=spec["W"] * used, P=spec["P"], bins=spec["bins"], pairs=int(spec.get("pairs", True)), cus=cus, lds=lds)
+
+
+def test_the_path_cases_take_their_paths_on_256_cus():
+    """the table above, on the CU count and LDS size it was worked out for; between them the cases take every path the plan has
+    but the split of the pair launch along grid.y (tests/test_hist_plan.py: no case of a few seconds reaches it)"""
+    exe = build_driver()
+    plans = {}
+    for name, (spec, _, want) in PATHS.items():
+        plans[name] = p = _plan_on(exe, spec, 256, 65536)
+        assert {k: p[k] for k in want} == want, name
+        assert p["pair_launches"] == (1 if spec.get("pairs", True) else 0)
+    assert {p["tile"] for p in plans.values()} == {0, 1, 2, 8, 64}
+    assert {p["idx_bytes"] for p in plans.values()} == {1, 2, 4}
+    assert {(p["single_lds"], p["single_blocks"] > 1) for p in plans.values()} >= {(1, False), (0, True)}
+    assert {(p["pair_lds"], p["pair_blocks"] > 1) for p in plans.values() if p["npairs"]} >= {(1, False), (1, True), (0, False)}
+
+
+EDGE_SPECS = [dict(W=300, n=4, P=2, bins=b, slice=1, seed=PATH_SEED, dtype=dt) for dt in ("f64", "f32") for b in (256, 257, 16384, 16385, 65536, 65537)] + [
+    dict(W=250, n=20, P=2, bins=16384, slice=1, seed=PATH_SEED, dtype="f32"),
+    dict(W=97, P=7, n=10, bins=257, slice=3, dtype="f64", seed=104), dict(W=130, P=2, n=12, bins=100, slice=2, dtype="f32", seed=132)]
+
+
+@pytest.mark.parametrize("spec", EDGE_SPECS, ids=lambda s: "W%(W)dP%(P)dbins%(bins)d_%(dtype)s" % s)
+def test_edge_data_sits_on_the_bin_edges_and_leaves_the_bounds_alone(spec):
+    """what the GPU cases with `edges` rest on, from the restatement alone: they cannot pass for want of such samples"""
+    plain, x = make_steps(spec), make_steps(dict(spec, edges=True))
+    sl, bins, P = spec["slice"], spec["bins"], spec["P"]
+    assert (x <= 0).all() and (x != plain).sum() > 100 * P and (x[::sl] != plain[::sl]).sum() == (x != plain).sum()
+    r = hr.histograms(x, bins, sl, False)
+    assert _same(r["bounds"], hr.find_binning(plain[::sl], bins))  # the bounds are the undisturbed data's
+    assert (r["single"][:, -1] > 0).all()                            # the top bin of every parameter holds samples
+    np.testing.assert_array_equal(r["clamped"], [2] * P)             # the top edge and its upper neighbour, nothing else
+    T = x.dtype.type
+    q = ((x[::sl].reshape(-1, P) - r["bounds"][:, 0]) / r["bounds"][:, 1]).astype(T)
+    assert (np.abs(q - np.rint(q)) <= 2 * np.spacing(np.abs(q))).sum() > 100  # quotients within 2 ulp of an integer
+    assert (q == np.rint(q)).sum() > 20 and (np.rint(q) > q).sum() > 20      # on an edge exactly, and just below one
+
+
 # ---- GPU ----------------------------------------------------------------------------------------------------------
 
 def _device(spec, tmp_path, timeout=300):
@@ -208,8 +286,8 @@ def _check_against_restatement(d, steps, bins, sl, pairs, prefix):
 RAGGED = [
     # W not a multiple of 64; P in {1, 2, 7, 32, 33}; bins in {2, 100, 257, 10 000}; slice > 1
     dict(W=70, P=1, n=9, bins=2, slice=1, dtype="f64"),
-    dict(W=130, P=2, n=12, bins=100, slice=2, dtype="f32"),
-    dict(W=97, P=7, n=10, bins=257, slice=3, dtype="f64"),
+    dict(W=130, P=2, n=12, bins=100, slice=2, dtype="f32", edges=True),
+    dict(W=97, P=7, n=10, bins=257, slice=3, dtype="f64", edges=True),
     dict(W=200, P=32, n=6, bins=100, slice=1, dtype="f64"),
     dict(W=65, P=33, n=8, bins=16, slice=2, dtype="f32"),
     dict(W=150, P=7, n=7, bins=10000, slice=1, dtype="f32", pairs=False),
@@ -225,7 +303,60 @@ def test_device_equals_restatement_on_ragged_shapes(spec, tmp_path):
     steps = d["steps"]
     for prefix in ("host_", "dev_"):
         w = _check_against_restatement(d, steps, spec["bins"], spec["slice"], spec.get("pairs", True), prefix)
-        assert w["clamped"].sum() == 0
+        # (edge data: the top edge and its upper neighbour lie at `bins` and above -- test_edge_data_sits_on_the_bin_edges...)
+        np.testing.assert_array_equal(w["clamped"], [2 if spec.get("edges") else 0] * spec["P"])
+
+
+def _check_result(d, want, prefix):
+    assert d[prefix + "num_points"] == want["num_points"]
+    assert _same(d[prefix + "bounds"], want["bounds"])
+    np.testing.assert_array_equal(d[prefix + "single"], want["single"])
+    np.testing.assert_array_equal(d[prefix + "clamped"], want["clamped"])
+    if want["pairs"] is not None:
+        np.testing.assert_array_equal(d[prefix + "pairs"], want["pairs"])
+    else:
+        assert prefix + "pairs" not in d
+
+
+@pytest.fixture(scope="module")
+def device_plan(tmp_path_factory):
+    """spec -> the plan of its launches on the device the cases run on"""
+    info = _device(dict(kind="device_info"), tmp_path_factory.mktemp("device_info"))
+    exe = build_driver()
+    lds = int(subprocess.run([exe, "lds", "shared=%d" % int(info["shared_mem_per_block"])], capture_output=True, text=True, check=True).stdout)
+    return lambda spec: _plan_on(exe, spec, int(info["cus"]), lds)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,dtype", PATH_CASES, ids=["%s_%s" % c for c in PATH_CASES])
+def test_device_equals_restatement_on_every_launch_path(name, dtype, device_plan, tmp_path):
+    spec, named = _path_spec(name, dtype), PATHS[name][2]
+    plan = device_plan(spec)
+    assert {k: plan[k] for k in named} == named, "on this device %s takes another path than the one it is named for: %r" % (name, plan)
+    d = _device(spec, tmp_path)
+    steps = d["steps"]
+    assert _same(steps, make_steps(spec))
+    want = hr.histograms(steps, spec["bins"], 1, spec.get("pairs", True))
+    if spec.get("edges"):
+        assert (want["single"][:, -1] > 0).all() and (want["clamped"] == 2).all()
+    else:
+        assert want["clamped"].sum() == 0
+    for prefix in ("host_", "dev_"):
+        _check_result(d, want, prefix)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("n,sl", [(0, 1), (3, 5)], ids=["no_steps", "one_step_of_three"])
+def test_nothing_or_one_step_selected(n, sl, dtype, tmp_path):
+    """no stored step at all: empty histograms over the bounds the analysis classes' start values give; slice 5 of 3 steps: the first"""
+    spec = dict(kind="random", W=70, n=n, P=3, bins=16, slice=sl, dtype=dtype, seed=PATH_SEED)
+    d = _device(spec, tmp_path)
+    want = hr.histograms(d["steps"], 16, sl, True)
+    assert want["num_points"] == (70 if n else 0) and d["steps"].shape == (n, 70, 3)
+    for prefix in ("host_", "dev_"):
+        _check_result(d, want, prefix)
+        assert d[prefix + "single"].sum() == 3 * want["num_points"] and d[prefix + "pairs"].sum() == 3 * want["num_points"]
 
 
 @pytest.mark.gpu
