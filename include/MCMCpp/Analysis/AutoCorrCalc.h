@@ -11,7 +11,8 @@
  * The reference transforms one (walker, parameter) series after another on one core; here the chain is handed to
  * libmcmcpp_hip.so (include/mcmcpp_hip.h, mcmcpp_hip_autocorr_times): one workgroup per series, both FFTs in LDS, the
  * reference's own butterflies, sums and divisions in the reference's order -- the result is bit-identical to the
- * restatement in oracle/ that is pinned to the reference's Detail::AutoCov (tests/test_autocorr.py).
+ * restatement in oracle/ that is pinned to the reference's Detail::AutoCov (tests/test_autocorr.py).  The steps of a device
+ * chain (MCMCPP_CHAIN_MEMORY=device) are transformed where they lie (mcmcpp_hip_autocorr_times_device): the same bits, no upload.
  *
  * Two things are deliberately NOT taken over:
  *   - the reference's transferWalker adds every series onto what its scratch array holds -- the previous walker's
@@ -32,6 +33,7 @@
 
 #include "../Chain/ChainStepIterator.h"
 #include "../Device/HipBackend.h"
+#include "Detail/DeviceSpan.h"
 
 namespace MCMC
 {
@@ -55,7 +57,28 @@ public:
     void calcAutoCorrTimes(const IttType& start, const IttType& end, int numSamples, int numWalkersToUse = 0)
     {
         stepList.clear();
-        for (IttType itt(start); itt != end; ++itt) stepList.push_back(*itt);
+        Detail::DeviceSpan<ParamType> span;
+        if (Detail::deviceSpan(start, end, &span))
+        {
+            assert(static_cast<std::int64_t>(numSamples) == span.steps);
+            (void)numSamples;
+            const int rc = mcmcpp_hip_autocorr_times_device(Device::HipDtype<ParamType>::value, -1, span.first, span.steps, walkerCount, paramCount,
+                                                            numWalkersToUse == walkerCount ? 0 : numWalkersToUse, windowScaling, acorrTimeList.data(), nullptr);
+            if (rc != MCMCPP_HIP_OK)
+            {
+                std::fprintf(stderr, "MCMCpp (MI355X): mcmcpp_hip_autocorr_times_device failed with code %d: %s\n", rc, mcmcpp_hip_autocorr_last_error());
+                std::abort();
+            }
+            return;
+        }
+        std::vector<ParamType> staging;  // (a device chain with the device path switched off: copies of its steps)
+        if (!Detail::pointersStay(start))
+        {
+            const std::int64_t n = Detail::downloadSteps(start, end, 1, staging);
+            for (std::int64_t k = 0; k < n; ++k) stepList.push_back(staging.data() + static_cast<std::size_t>(k) * walkerCount * paramCount);
+        }
+        else
+            for (IttType itt(start); itt != end; ++itt) stepList.push_back(*itt);
         assert(static_cast<size_t>(numSamples) == stepList.size());
         (void)numSamples;
         const int rc = mcmcpp_hip_autocorr_times(Device::HipDtype<ParamType>::value, -1, stepList.data(), static_cast<std::int64_t>(stepList.size()), walkerCount,

@@ -13,7 +13,8 @@
  * sums as a rank-N update X^T X on the matrix cores and applies the reference's finalizeMatrix arithmetic
  * (CovarianceMatrix.h:178-224).  A parallel sum cannot keep the reference's order of additions, so the results
  * agree with it to rounding, not bit for bit (tests/test_moments.py states the tolerance).  Runs of steps that are
- * contiguous in the chain's memory are uploaded in one piece.  No GPU, no result: failures abort with the
+ * contiguous in the chain's memory are uploaded in one piece; the steps of a device chain (MCMCPP_CHAIN_MEMORY=device) are
+ * summed where they lie (mcmcpp_hip_moments_add_device_steps_strided: the same sums, grouped the same way).  No GPU, no result: failures abort with the
  * library's message, like everything else in this facade.
  */
 #ifndef MCMCPP_ANALYSIS_COVARIANCEMATRIX_H
@@ -27,6 +28,7 @@
 
 #include "../Chain/ChainStepIterator.h"
 #include "../Device/HipBackend.h"
+#include "Detail/DeviceSpan.h"
 
 namespace MCMC
 {
@@ -60,6 +62,24 @@ public:
         assert(sliceInterval >= 1);
         check("mcmcpp_hip_moments_reset", mcmcpp_hip_moments_reset(handle));
         const std::int64_t stepElems = static_cast<std::int64_t>(wCount) * pCount;
+        Detail::DeviceSpan<ParamType> span;
+        if (Detail::deviceSpan(start, end, &span))  // a device chain: no upload, sliceInterval is the stride
+        {
+            const std::int64_t used = (span.steps + sliceInterval - 1) / sliceInterval;
+            if (used == 0) return;
+            check("mcmcpp_hip_moments_add_device_steps_strided", mcmcpp_hip_moments_add_device_steps_strided(handle, span.first, used, sliceInterval));
+            check("mcmcpp_hip_moments_finish", mcmcpp_hip_moments_finish(handle, nullptr, nullptr, covarMat.data(), corrMat.data()));
+            return;
+        }
+        if (!Detail::pointersStay(start))  // a device chain with the device path switched off: the selected steps, downloaded
+        {
+            std::vector<ParamType> staging;
+            const std::int64_t used = Detail::downloadSteps(start, end, sliceInterval, staging);
+            if (used == 0) return;
+            check("mcmcpp_hip_moments_add_steps", mcmcpp_hip_moments_add_steps(handle, staging.data(), used, 1));
+            check("mcmcpp_hip_moments_finish", mcmcpp_hip_moments_finish(handle, nullptr, nullptr, covarMat.data(), corrMat.data()));
+            return;
+        }
         // gather runs of selected steps that lie sliceInterval steps apart in memory: one upload call per run
         ParamType* runStart = nullptr;
         ParamType* prev = nullptr;

@@ -1,7 +1,8 @@
 /*
  * Analysis/Detail/DeviceHistograms.h -- what CornerHistograms and PercentileAndMaximumFinder share: the
  * mcmcpp_hip_histograms handle (include/mcmcpp_hip.h), the selection of the steps the reference's loops use (every
- * sliceInterval'th step of [start, end), beginning with `start`), and the arrays the library returns.  Not part of the
+ * sliceInterval'th step of [start, end), beginning with `start`), and the arrays the library returns.  The steps of a device
+ * chain (MCMCPP_CHAIN_MEMORY=device) are counted where they lie (mcmcpp_hip_histograms_compute_device).  Not part of the
  * reference's API.
  */
 #ifndef MCMCPP_ANALYSIS_DETAIL_DEVICEHISTOGRAMS_H
@@ -16,6 +17,7 @@
 
 #include "../../Chain/ChainStepIterator.h"
 #include "../../Device/HipBackend.h"
+#include "DeviceSpan.h"
 
 namespace MCMC
 {
@@ -62,11 +64,26 @@ public:
     {
         assert(sliceInterval >= 1);
         std::vector<const void*> steps;
-        long long index = 0;
-        for (IttType itt(start); itt != end; ++itt, ++index)
-            if (index % sliceInterval == 0) steps.push_back(*itt);
-        check("mcmcpp_hip_histograms_compute",
-              mcmcpp_hip_histograms_compute(handle, steps.empty() ? nullptr : steps.data(), static_cast<std::int64_t>(steps.size())));
+        DeviceSpan<ParamType> span;
+        if (deviceSpan(start, end, &span) && span.steps > 0)
+            check("mcmcpp_hip_histograms_compute_device", mcmcpp_hip_histograms_compute_device(handle, span.first, span.steps, sliceInterval));
+        else
+        {
+            std::vector<ParamType> staging;  // (a device chain with the device path switched off: copies of the steps used)
+            if (!pointersStay(start))
+            {
+                const std::int64_t n = downloadSteps(start, end, sliceInterval, staging);
+                for (std::int64_t k = 0; k < n; ++k) steps.push_back(staging.data() + static_cast<std::size_t>(k) * wCount * pCount);
+            }
+            else
+            {
+                long long index = 0;
+                for (IttType itt(start); itt != end; ++itt, ++index)
+                    if (index % sliceInterval == 0) steps.push_back(*itt);
+            }
+            check("mcmcpp_hip_histograms_compute",
+                  mcmcpp_hip_histograms_compute(handle, steps.empty() ? nullptr : steps.data(), static_cast<std::int64_t>(steps.size())));
+        }
         std::int64_t n = 0;
         check("mcmcpp_hip_histograms_result", mcmcpp_hip_histograms_result(handle, &n, bounds.data(), single.data(),
                                                                              pairs ? twoAxis.data() : nullptr, clamped.data()));

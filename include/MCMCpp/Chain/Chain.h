@@ -9,12 +9,19 @@
  *   - whole steps arrive from the GPU, so besides the reference's per-walker storeWalker() there is a bulk
  *     path (stepsContiguousFrom / commitSteps) that lets the device-to-host copy land in place;
  *   - iterators address steps by global index instead of walking a linked list, which removes the
- *     off-by-one defects of the reference's ChainPsetIterator (ChainPsetIterator.h:131-142,154).
+ *     off-by-one defects of the reference's ChainPsetIterator (ChainPsetIterator.h:131-142,154);
+ *   - a third memory kind besides heap and pinned blocks: a DEVICE chain (Detail::BlockMemory::onDevice) is ONE contiguous
+ *     allocation [steps][W][D] of GPU memory, which the sampler's run writes in place and the analysis classes read in place
+ *     (deviceSteps()).  It grows by doubling, bounded by the same byte budget, and is compacted in place by a kernel.  The
+ *     iterators still hand out host pointers: dereferencing one downloads that step into a buffer the chain owns, keyed by
+ *     step index (the pointer holds until a different step is dereferenced), and hostBytesFetched() counts those bytes.
  */
 #ifndef MCMCPP_CHAIN_CHAIN_H
 #define MCMCPP_CHAIN_CHAIN_H
 
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <future>
 #include <vector>
@@ -36,6 +43,14 @@ enum class IncrementStatus : char
     EndOfChain        ///< the byte budget is exhausted: nothing more can be stored
 };
 
+/// A device chain's stored steps where they lie: `steps` committed steps of W*D values each behind `base` (DEVICE memory).
+template <class ParamType>
+struct DeviceSteps
+{
+    ParamType* base;
+    std::int64_t steps;
+};
+
 template <class ParamType>
 class Chain
 {
@@ -47,7 +62,7 @@ public:
     Chain(int numWalkers, int numParams, unsigned long long maxSize, unsigned long long blockBytes = Detail::DefaultBlockBytes,
           const Detail::BlockMemory& memory = Detail::BlockMemory())
         : blockMemory(memory), walkerCount(numWalkers), cellsPerWalker(numParams),
-          cellsPerStep(static_cast<std::int64_t>(numWalkers) * numParams), stepCount(0)
+          cellsPerStep(static_cast<std::int64_t>(numWalkers) * numParams), stepCount(0), firstReserve(0), fetchedStep(-1), fetchedBytes(0)
     {
         const unsigned long long stepBytes = static_cast<unsigned long long>(cellsPerStep) * sizeof(ParamType);
         maxSteps = static_cast<std::int64_t>(maxSize / stepBytes);
@@ -68,6 +83,12 @@ public:
     /// Copy one walker's parameters into the step being assembled.
     void storeWalker(int walkerNum, const ParamType* walkerData)
     {
+        if (onDevice())  // (assembled on the host; incrementChainStep uploads it)
+        {
+            if (assembling.empty()) assembling.resize(static_cast<std::size_t>(cellsPerStep));
+            std::memcpy(assembling.data() + static_cast<std::size_t>(walkerNum) * cellsPerWalker, walkerData, sizeof(ParamType) * cellsPerWalker);
+            return;
+        }
         ParamType* dst = writableStep();
         if (dst) std::memcpy(dst + static_cast<std::size_t>(walkerNum) * cellsPerWalker, walkerData, sizeof(ParamType) * cellsPerWalker);
     }
@@ -75,6 +96,14 @@ public:
     IncrementStatus incrementChainStep()
     {
         if (stepCount >= maxSteps) return IncrementStatus::EndOfChain;
+        if (onDevice())
+        {
+            if (!reserveSteps(1)) return IncrementStatus::EndOfChain;
+            if (assembling.empty()) assembling.resize(static_cast<std::size_t>(cellsPerStep));
+            deviceCopy(deviceStep(stepCount), assembling.data(), 1);
+            ++stepCount;
+            return stepCount >= maxSteps ? IncrementStatus::EndOfChain : IncrementStatus::NormalIncrement;
+        }
         if (!writableStep()) return IncrementStatus::EndOfChain;
         ++stepCount;
         blocks[static_cast<std::size_t>((stepCount - 1) / stepsPerBlock)]->setUsed((stepCount - 1) % stepsPerBlock + 1);
@@ -89,6 +118,12 @@ public:
     /// Pointer where the next stored step goes and how many consecutive steps fit there contiguously (0 when full).
     ParamType* stepsContiguousFrom(std::int64_t* contiguous)
     {
+        if (onDevice())  // a DEVICE pointer: behind the committed steps, as far as the allocation reaches
+        {
+            const bool room = stepCount < maxSteps && reserveSteps(1);
+            if (contiguous) *contiguous = room ? slab.capacity() - stepCount : 0;
+            return room ? deviceStep(stepCount) : nullptr;
+        }
         ParamType* p = (stepCount < maxSteps) ? writableStep() : nullptr;
         if (contiguous)
         {
@@ -107,8 +142,35 @@ public:
     /// Declare `count` steps written at the pointer handed out by stepsContiguousFrom.
     void commitSteps(std::int64_t count)
     {
+        if (onDevice())
+        {
+            stepCount = (count > slab.capacity() - stepCount) ? slab.capacity() : stepCount + count;
+            return;
+        }
         for (std::int64_t k = 0; k < count; ++k) incrementChainStep();
     }
+
+    /// A device chain makes room for `count` more steps now (a run knows how many it stores before it launches): the
+    /// allocation grows to what is needed or to twice its size, whichever is more, within the byte budget, and the committed
+    /// steps are copied over inside device memory.  False when not even one more step fits (budget or device memory
+    /// exhausted).  Host chains obtain their blocks as they go: nothing to do, true.
+    bool reserveSteps(std::int64_t count)
+    {
+        if (!onDevice()) return true;
+        std::int64_t need = (count > maxSteps - stepCount) ? maxSteps : stepCount + count;
+        if (need <= slab.capacity()) return slab.capacity() > stepCount;
+        std::int64_t want = slab.valid() ? 2 * slab.capacity() : firstReserve;
+        if (want < need) want = need;
+        if (want > maxSteps) want = maxSteps;
+        Detail::DeviceSlab<ParamType> bigger(blockMemory, want, cellsPerStep);
+        if (!bigger.valid() && want > need) bigger = Detail::DeviceSlab<ParamType>(blockMemory, need, cellsPerStep);
+        if (!bigger.valid()) return slab.capacity() > stepCount;
+        if (stepCount > 0) deviceCopy(bigger.get(), slab.get(), stepCount);
+        slab = static_cast<Detail::DeviceSlab<ParamType>&&>(bigger);  // (the old allocation goes with `bigger`)
+        return true;
+    }
+    /// Steps the first allocation of a device chain holds at the least (the samplers' test knob; 0: what is asked for).
+    void setFirstDeviceReservation(std::int64_t steps) { firstReserve = steps; }
 
     /// Obtain every block one block ahead of its use, on a helper thread (the samplers switch this on; off by default so
     /// that a Chain used alone never starts a thread).
@@ -120,11 +182,26 @@ public:
     int getWalkerCount() const { return walkerCount; }
     int getCellsPerWalker() const { return cellsPerWalker; }
     std::int64_t getCellsPerStep() const { return cellsPerStep; }
+    /// Heap, pinned blocks, or one device allocation.
+    Detail::MemoryKind memoryKind() const { return blockMemory.kind; }
+    /// A device chain's committed steps in place (base == nullptr for a host chain, or before anything is stored).
+    DeviceSteps<ParamType> deviceSteps() const
+    {
+        DeviceSteps<ParamType> d;
+        d.base = onDevice() ? slab.get() : nullptr;
+        d.steps = onDevice() ? stepCount : 0;
+        return d;
+    }
+    /// Device ordinal of a device chain (-1: the current device).
+    int deviceOrdinal() const { return blockMemory.device; }
+    /// Bytes copied from a device chain to the host so far (by dereferencing iterators / stepPtr).  0 for host chains.
+    unsigned long long hostBytesFetched() const { return fetchedBytes; }
 
     /// Forget every stored step, keep the memory (reference: Chain.h:255-266).
     void resetChain()
     {
         stepCount = 0;
+        fetchedStep = -1;
         for (ChainBlock<ParamType>* b : blocks) b->setUsed(0);
         if (nextBlock.valid()) delete nextBlock.get();  // (a block obtained ahead of a chain that starts over)
     }
@@ -133,6 +210,15 @@ public:
     /// (reference: Chain.h:268-305, same special cases).
     void resetChainForSubSampling(int burnInSamples, int interval)
     {
+        if (onDevice())  // the same selection, applied in place by a kernel; nothing comes to the host
+        {
+            long long kept = stepCount;
+            if (stepCount > 0 && blockMemory.compact(blockMemory.device, slab.get(), stepCount, cellsPerStep, burnInSamples, interval, &kept) != 0)
+                deviceDie("compacting");
+            stepCount = kept;
+            fetchedStep = -1;
+            return;
+        }
         if (burnInSamples == 0 && interval == 1) return;
         if (stepCount <= burnInSamples || (stepCount - burnInSamples) < interval)
         {
@@ -163,10 +249,35 @@ public:
     /// W*D contiguous values of stored step k (k < getStoredStepCount()).
     ParamType* stepPtr(std::int64_t k)
     {
+        if (onDevice())  // a HOST copy of that step, downloaded unless it is the one downloaded last
+        {
+            if (k < 0 || k >= stepCount) return nullptr;
+            if (k != fetchedStep)
+            {
+                if (fetched.empty()) fetched.resize(static_cast<std::size_t>(cellsPerStep));
+                deviceCopy(fetched.data(), deviceStep(k), 1);
+                fetchedStep = k;
+                fetchedBytes += static_cast<unsigned long long>(cellsPerStep) * sizeof(ParamType);
+            }
+            return fetched.data();
+        }
         return blocks[static_cast<std::size_t>(k / stepsPerBlock)]->step(k % stepsPerBlock);
     }
 
 private:
+    bool onDevice() const { return blockMemory.kind == Detail::MemoryKind::Device; }
+    ParamType* deviceStep(std::int64_t k) const { return slab.get() + static_cast<std::size_t>(k) * static_cast<std::size_t>(cellsPerStep); }
+    void deviceCopy(void* dst, const void* src, std::int64_t steps)
+    {
+        if (blockMemory.copy(dst, src, static_cast<unsigned long long>(steps) * static_cast<unsigned long long>(cellsPerStep) * sizeof(ParamType)) != 0)
+            deviceDie("copying steps of");
+    }
+    static void deviceDie(const char* what)
+    {
+        std::fprintf(stderr, "MCMCpp (MI355X): %s the device chain failed\n", what);
+        std::abort();
+    }
+
     /// Once the last block is half full, obtain the one behind it on a helper thread (a run that never gets that far never
     /// pays for a block it does not use).
     void maybePrefetch(std::int64_t stepsSoon)
@@ -227,6 +338,13 @@ private:
     std::int64_t stepsPerBlock;
     std::int64_t maxSteps;
     std::int64_t stepCount;
+    // ---- a device chain (blockMemory.kind == Device) uses these instead of blocks ----
+    Detail::DeviceSlab<ParamType> slab;  ///< the one allocation: its only owner
+    std::int64_t firstReserve;           ///< steps the first allocation holds at the least
+    std::vector<ParamType> assembling;   ///< the step storeWalker assembles, on the host
+    std::vector<ParamType> fetched;      ///< host copy of stored step `fetchedStep`
+    std::int64_t fetchedStep;
+    unsigned long long fetchedBytes;
 };
 
 }  // namespace Chain

@@ -23,15 +23,93 @@ namespace Detail
 /// Default slab size; the number of steps per block follows from it and the ensemble size.
 static const unsigned long long DefaultBlockBytes = 256ULL << 20;
 
+/// The three kinds of memory a Chain keeps its stored steps in.
+enum class MemoryKind : char
+{
+    Heap,    ///< the default
+    Pinned,  ///< blocks from a provider (the samplers: pinned host memory, MCMCPP_CHAIN_MEMORY=pinned)
+    Device   ///< ONE contiguous allocation of GPU memory (MCMCPP_CHAIN_MEMORY=device): the chain never crosses the host link
+};
+
 /// Where a block's memory comes from.  The default is the heap (64-byte aligned like the reference's autoAlignedAlloc,
 /// Utility/Misc.h:77-102); the MI355X samplers hand out pinned host memory (mcmcpp_hip_host_alloc) so that the step
 /// launches write stored steps straight into the block.  A failed `obtain` falls back to the heap.
+/// A device chain (onDevice) takes its allocation from obtainOn / release, moves bytes with copy (host or device memory on
+/// either side; 0 = done) and compacts itself with compact (Chain::resetChainForSubSampling in place; 0 = done).  The
+/// samplers bind the four to the C ABI (mcmcpp_hip_device_alloc / _free / _copy / _chain_compact); this header needs none of it.
 struct BlockMemory
 {
     void* (*obtain)(unsigned long long bytes);
     void (*release)(void*);
-    BlockMemory() : obtain(nullptr), release(nullptr) {}
-    BlockMemory(void* (*get)(unsigned long long), void (*put)(void*)) : obtain(get), release(put) {}
+    void* (*obtainOn)(int device, unsigned long long bytes);
+    int (*copy)(void* dst, const void* src, unsigned long long bytes);
+    int (*compact)(int device, void* steps, long long numSteps, long long cellsPerStep, int burnIn, int interval, long long* kept);
+    int device;  ///< device ordinal of a device chain (-1: the current device)
+    MemoryKind kind;
+    BlockMemory() : obtain(nullptr), release(nullptr), obtainOn(nullptr), copy(nullptr), compact(nullptr), device(-1), kind(MemoryKind::Heap) {}
+    BlockMemory(void* (*get)(unsigned long long), void (*put)(void*))
+        : obtain(get), release(put), obtainOn(nullptr), copy(nullptr), compact(nullptr), device(-1), kind(get && put ? MemoryKind::Pinned : MemoryKind::Heap)
+    {
+    }
+    static BlockMemory onDevice(int deviceOrdinal, void* (*get)(int, unsigned long long), void (*put)(void*),
+                                int (*move)(void*, const void*, unsigned long long),
+                                int (*compactFn)(int, void*, long long, long long, int, int, long long*))
+    {
+        BlockMemory m;
+        m.obtainOn = get;
+        m.release = put;
+        m.copy = move;
+        m.compact = compactFn;
+        m.device = deviceOrdinal;
+        m.kind = MemoryKind::Device;
+        return m;
+    }
+};
+
+/// The one owner of a device chain's allocation: `capacity` steps behind `cells`, given back by the destructor.  Move-only.
+template <class ParamType>
+class DeviceSlab
+{
+public:
+    DeviceSlab() : cells(nullptr), capacitySteps(0), releaseFn(nullptr) {}
+    DeviceSlab(const BlockMemory& mem, std::int64_t steps, std::int64_t cellsInStep) : cells(nullptr), capacitySteps(0), releaseFn(mem.release)
+    {
+        if (steps < 1 || !mem.obtainOn || !mem.release) return;
+        cells = static_cast<ParamType*>(mem.obtainOn(mem.device, static_cast<unsigned long long>(steps) * static_cast<unsigned long long>(cellsInStep) * sizeof(ParamType)));
+        if (cells) capacitySteps = steps;
+    }
+    ~DeviceSlab()
+    {
+        if (cells) releaseFn(cells);
+    }
+    DeviceSlab(const DeviceSlab&) = delete;
+    DeviceSlab& operator=(const DeviceSlab&) = delete;
+    DeviceSlab(DeviceSlab&& o) : cells(o.cells), capacitySteps(o.capacitySteps), releaseFn(o.releaseFn)
+    {
+        o.cells = nullptr;
+        o.capacitySteps = 0;
+    }
+    DeviceSlab& operator=(DeviceSlab&& o)  // (o gives back what this held)
+    {
+        ParamType* c = cells;
+        cells = o.cells;
+        o.cells = c;
+        const std::int64_t n = capacitySteps;
+        capacitySteps = o.capacitySteps;
+        o.capacitySteps = n;
+        void (*r)(void*) = releaseFn;
+        releaseFn = o.releaseFn;
+        o.releaseFn = r;
+        return *this;
+    }
+    bool valid() const { return cells != nullptr; }
+    ParamType* get() const { return cells; }
+    std::int64_t capacity() const { return capacitySteps; }
+
+private:
+    ParamType* cells;  ///< DEVICE memory: never dereferenced on the host
+    std::int64_t capacitySteps;
+    void (*releaseFn)(void*);
 };
 }
 

@@ -6,6 +6,9 @@
  * walker of the next step, regardless of step boundaries.  The reference's ++ visits one phantom cell at
  * a full-block boundary and its -- tests the wrong link (ChainPsetIterator.h:131-142,154); indexing by a
  * global 64-bit parameter-set number has neither problem.
+ *
+ * On a device chain (Chain.h) the dereference goes through the chain's one-step host buffer: walking the W parameter sets
+ * of a step downloads the step once.
  */
 #ifndef MCMCPP_CHAIN_CHAINPSETITERATOR_H
 #define MCMCPP_CHAIN_CHAINPSETITERATOR_H

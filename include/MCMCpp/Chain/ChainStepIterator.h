@@ -5,6 +5,11 @@
  * `*it` is a ParamType* to the W*D contiguous values of a step (walker-major), ++/-- move by one step,
  * +=/-= by many, and movement saturates at the ends of the chain (begin stays begin, end stays end)
  * instead of running off.  Addressing is a 64-bit global step index into the owning Chain.
+ *
+ * On a device chain (Chain.h) `*it` is still a host pointer: the dereference downloads that one step into a buffer the
+ * chain owns, keyed by step index -- dereferencing the same step again costs nothing, and the pointer holds until another
+ * step is dereferenced.  Movement and comparison touch no memory.  The analysis classes ask owner() whether the steps
+ * can be read where they lie.
  */
 #ifndef MCMCPP_CHAIN_CHAINSTEPITERATOR_H
 #define MCMCPP_CHAIN_CHAINSTEPITERATOR_H
@@ -44,6 +49,7 @@ public:
     /// All walkers of this step: W*D values, walker w at [w*D, (w+1)*D).
     ParamType* operator*() const { return chain->stepPtr(index); }
     std::int64_t stepIndex() const { return index; }
+    Chain<ParamType>* owner() const { return chain; }
 
 private:
     Chain<ParamType>* chain;

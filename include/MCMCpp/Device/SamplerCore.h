@@ -10,6 +10,9 @@
  *   - the PostStepAction runs once per ensemble step and sees the chain without the step being made
  *                                                                            (EnsembleSampler.h:291-293,356-359)
  *   - reset() forgets chain and counters, keeps positions and the random stream          (EnsembleSampler.h:312-322)
+ * Beyond the reference: with MCMCPP_CHAIN_MEMORY=device the chain is one allocation of GPU memory (Chain/Chain.h).  The run
+ * then stores through mcmcpp_hip_run_device, sliceAndBurnChain compacts it with a kernel and the analysis classes read it in
+ * place: no stored step crosses the host link unless an iterator is dereferenced.
  * Not kept: the parallel sampler's run-to-run non-determinism (ParallelEnsembleSampler.h:71-76) and its
  * sub-sampling defect (Threading/RedBlkCtrlerSpinLock.h:297-300) -- both samplers follow the sequential
  * trajectory, the only reproducible one.
@@ -80,10 +83,12 @@ public:
     SamplerCore(int randSeed, long long stream, int numWalker, int numParameter, const Mover& move,
                 unsigned long long maxChainSizeBytes, PostStepAction* stepAct, const Placement& where = Placement::fromEnvironment())
         : stepAction(stepAct),
-          markovChain(numWalker, numParameter, maxChainSizeBytes, Chain::Detail::DefaultBlockBytes, chainMemory()),
+          markovChain(numWalker, numParameter, maxChainSizeBytes, Chain::Detail::DefaultBlockBytes, chainMemory(where, numWalker, numParameter)),
           moveProposer(move), numParams(numParameter), numWalkers(numWalker), initialPlacementCounted(false)
     {
         markovChain.setBlockPrefetch(true);
+        if (const char* first = std::getenv("MCMCPP_CHAIN_DEVICE_FIRST_STEPS"))  // (tests: a small first allocation, so that a short chain grows)
+            markovChain.setFirstDeviceReservation(std::strtoll(first, nullptr, 10));
         assert(numWalkers % 2 == 0);             // EnsembleSampler.h:207
         assert(numWalkers > (2 * numParams));    // EnsembleSampler.h:208
         moveProposer.setPrng(randSeed, stream);  // EnsembleSampler.h:217 / RedBlkUpdater.h:86
@@ -146,6 +151,14 @@ public:
 
     void storeCurrentWalkerPositions()
     {
+        if (deviceChain())  // (one step, by way of the host: the chain's own upload path)
+        {
+            std::vector<ParamType> now(static_cast<std::size_t>(numWalkers) * numParams);
+            ranks[0].check("mcmcpp_hip_get_state", mcmcpp_hip_get_state(ranks[0].get(), now.data(), nullptr, nullptr));
+            for (int w = 0; w < numWalkers; ++w) markovChain.storeWalker(w, now.data() + static_cast<std::size_t>(w) * numParams);
+            markovChain.incrementChainStep();
+            return;
+        }
         std::int64_t room = 0;
         ParamType* dst = markovChain.stepsContiguousFrom(&room);
         if (!dst || room < 1) return;
@@ -157,6 +170,7 @@ public:
     bool run(int numSteps, int interval)
     {
         std::int64_t left = numSteps;
+        markovChain.reserveSteps(left);  // (a device chain grows once, in front of the run; host chains obtain blocks as they go)
         while (left > 0)
         {
             std::int64_t room = 0;
@@ -164,7 +178,26 @@ public:
             if (!dst || room < 1) return false;
             const std::int64_t now = left < room ? left : room;
             markovChain.expectSteps(now);
-            if (stepAction == nullptr && ranks.size() == 1)
+            if (deviceChain())
+            {
+                // dst is device memory: the launches store each step at its final place.  The PostStepAction sees the chain as
+                // on the host path (one call per ensemble step, without the step being made); what it dereferences is downloaded.
+                if (stepAction == nullptr)
+                    ranks[0].check("mcmcpp_hip_run_device", mcmcpp_hip_run_device(ranks[0].get(), now, interval, dst, nullptr));
+                else
+                {
+                    ranks[0].check("mcmcpp_hip_run_device_async", mcmcpp_hip_run_device_async(ranks[0].get(), now, interval, dst, nullptr));
+                    for (std::int64_t k = 0; k < now; ++k)
+                    {
+                        ranks[0].check("mcmcpp_hip_wait_stored", mcmcpp_hip_wait_stored(ranks[0].get(), k + 1));
+                        for (int j = 0; j < interval; ++j) stepAction->performAction(markovChain.getStepIteratorBegin(), markovChain.getStepIteratorEnd());
+                        markovChain.commitSteps(1);
+                    }
+                    ranks[0].check("mcmcpp_hip_run_wait", mcmcpp_hip_run_wait(ranks[0].get()));
+                }
+                if (stepAction == nullptr) markovChain.commitSteps(now);
+            }
+            else if (stepAction == nullptr && ranks.size() == 1)
             {
                 ranks[0].check("mcmcpp_hip_run", mcmcpp_hip_run(ranks[0].get(), now, interval, dst, nullptr));
                 markovChain.commitSteps(now);
@@ -251,15 +284,51 @@ public:
 protected:
     static void* pinnedObtain(unsigned long long bytes) { return mcmcpp_hip_host_alloc(bytes); }
     static void pinnedRelease(void* p) { mcmcpp_hip_host_free(p); }
+    static void* deviceObtain(int device, unsigned long long bytes) { return mcmcpp_hip_device_alloc(device, bytes); }
+    static void deviceRelease(void* p) { mcmcpp_hip_device_free(p); }
+    static int deviceCopy(void* dst, const void* src, unsigned long long bytes)
+    {
+        const int rc = mcmcpp_hip_device_copy(dst, src, bytes);
+        if (rc != MCMCPP_HIP_OK) std::fprintf(stderr, "MCMCpp (MI355X): mcmcpp_hip_device_copy failed with code %d: %s\n", rc, mcmcpp_hip_device_chain_last_error());
+        return rc;
+    }
+    static int deviceCompact(int device, void* steps, long long numSteps, long long cellsPerStep, int burnIn, int interval, long long* kept)
+    {
+        std::int64_t left = 0;
+        const int rc = mcmcpp_hip_device_chain_compact(HipDtype<ParamType>::value, device, steps, numSteps, cellsPerStep, burnIn, interval, &left);
+        if (rc != MCMCPP_HIP_OK)
+            std::fprintf(stderr, "MCMCpp (MI355X): mcmcpp_hip_device_chain_compact failed with code %d: %s\n", rc, mcmcpp_hip_device_chain_last_error());
+        *kept = left;
+        return rc;
+    }
+    bool deviceChain() const { return markovChain.memoryKind() == Chain::Detail::MemoryKind::Device; }
     /// Chain blocks come from the heap (stored steps pass through the library's pinned staging ring and are copied out by
     /// the host while the launches continue) unless MCMCPP_CHAIN_MEMORY=pinned asks for pinned host memory, into which the
     /// step launches write stored steps directly.  Measured at C2 (tools/bench_facade.cpp): pinned blocks win
     /// when the memory already exists (a chain that is reset and refilled); obtaining them costs as much as the page
     /// faults of fresh heap memory but stalls the launches while it lasts, so a growing chain is faster on the heap.
-    static Chain::Detail::BlockMemory chainMemory()
+    /// MCMCPP_CHAIN_MEMORY=device keeps the chain in ONE allocation of the sampler's GPU instead (Chain/Chain.h): the run stores
+    /// into it, sliceAndBurnChain and the analysis classes work on it where it lies.  Two cases keep a host chain and say so
+    /// once on stderr: a placement of more than one device (a handle with a communicator refuses mcmcpp_hip_run_device), and
+    /// an ensemble whose step is not a whole number of 16-byte pieces (fp32 with W*D = 2 mod 4: mcmcpp_hip_run_device wants
+    /// every run's first step 16-byte aligned).
+    static Chain::Detail::BlockMemory chainMemory(const Placement& where, int numWalker, int numParameter)
     {
         const char* v = std::getenv("MCMCPP_CHAIN_MEMORY");
         if (v && v[0] == 'p' && v[1] == 'i') return Chain::Detail::BlockMemory(&pinnedObtain, &pinnedRelease);
+        if (v && v[0] == 'd' && v[1] == 'e')
+        {
+            const bool split = where.count() > 1 || where.splitEnsemble;
+            const bool ragged = (static_cast<unsigned long long>(numWalker) * numParameter * sizeof(ParamType)) % 16 != 0;
+            if (!split && !ragged)
+                return Chain::Detail::BlockMemory::onDevice(where.device(0), &deviceObtain, &deviceRelease, &deviceCopy, &deviceCompact);
+            static bool said = false;
+            if (!said)
+                std::fprintf(stderr, "MCMCpp (MI355X): MCMCPP_CHAIN_MEMORY=device: this sampler keeps its chain in host memory (%s)\n",
+                             split ? "a placement of more than one device cannot store into device memory"
+                                   : "a device chain needs steps of a whole number of 16 bytes");
+            said = true;
+        }
         return Chain::Detail::BlockMemory();
     }
 

@@ -5,7 +5,9 @@
  * (ParamType, Mover, PostStepAction = NoAction), same constructor (EnsembleSampler.h:66-67) and the same
  * public methods (EnsembleSampler.h:89-176).  The step loop the reference runs on the host
  * (runMCMC -> performStep -> Mover::updateWalker, EnsembleSampler.h:284-360) is executed by gfx950 kernels
- * behind the C ABI of libmcmcpp_hip.so; the Chain and its iterators stay host objects.
+ * behind the C ABI of libmcmcpp_hip.so; the Chain and its iterators stay host objects.  With MCMCPP_CHAIN_MEMORY=device in
+ * the environment the chain's steps stay in GPU memory: sliceAndBurnChain and the Analysis classes work on them there, and the
+ * iterators download the step that is dereferenced (Chain/Chain.h).
  */
 #ifndef MCMCPP_ENSEMBLESAMPLER_H
 #define MCMCPP_ENSEMBLESAMPLER_H
@@ -77,6 +79,8 @@ public:
     // ---- additions of the device path (not in the reference) -------------------------------------------------
     using Core::currentState;
     using Core::diagnostics;
+    /// The chain itself: memoryKind(), deviceSteps() and hostBytesFetched() of a device chain (MCMCPP_CHAIN_MEMORY=device).
+    using Core::chain;
 
 private:
     int subSamplingInterval;

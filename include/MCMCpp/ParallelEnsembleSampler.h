@@ -127,6 +127,8 @@ public:
     }
     using Core::currentState;
     using Core::diagnostics;
+    /// The chain itself: memoryKind(), deviceSteps() and hostBytesFetched() of a device chain (MCMCPP_CHAIN_MEMORY=device).
+    using Core::chain;
     using Core::deviceCount;
 
 private:

@@ -238,6 +238,31 @@ int mcmcpp_hip_run_device_async(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t 
 void* mcmcpp_hip_host_alloc(uint64_t bytes);
 void mcmcpp_hip_host_free(void* p);
 
+/* Device memory for a Chain that never leaves the GPU (the facade's MCMCPP_CHAIN_MEMORY=device: one contiguous allocation
+ * [steps][W][D] that mcmcpp_hip_run_device writes and the *_device analysis entry points read).
+ *   device_alloc   `bytes` of memory of device `device` (-1 = the current one), or NULL when the allocation fails
+ *   device_free    gives it back (NULL is accepted)
+ *   device_copy    `bytes` from src to dst, each host or device memory (the runtime tells them apart); returns when the copy
+ *                  is done
+ * device_chain_last_error: the message of the last failure of these and of device_chain_compact on the calling thread. */
+void* mcmcpp_hip_device_alloc(int32_t device, uint64_t bytes);
+void mcmcpp_hip_device_free(void* p);
+int mcmcpp_hip_device_copy(void* dst, const void* src, uint64_t bytes);
+const char* mcmcpp_hip_device_chain_last_error(void);
+
+/* Chain::resetChainForSubSampling / sliceAndBurnChain (reference MCMCpp/Chain/Chain.h:268-305) on a chain in device memory:
+ * n_steps contiguous stored steps of step_elems elements each ([n_steps][W][D], step_elems = W*D), compacted in place.  The
+ * reference's selection: burn_in = 0 with interval = 1 changes nothing; no step is kept when none is left behind the burn-in
+ * or fewer than `interval` are; otherwise step burn_in + j*interval becomes step j.  *kept = the stored steps afterwards
+ * (may be NULL); steps behind them keep bytes of no meaning.  Destinations are moved in ascending waves, one launch each,
+ * none of which writes a step that it or a later one reads (mcmcpp_amd/csrc/chain_compact_plan.hpp): the result equals a
+ * copy into a fresh array, byte for byte.  Steps move in 16-byte pieces when a step is a whole number of them and
+ * device_steps is 16-byte aligned, element by element otherwise.  device: the device the memory belongs to (-1 = current).
+ * MCMCPP_HIP_E_ARG (with a message) for a pointer that is not memory of that device or n_steps steps that do not end inside
+ * its allocation: nothing is launched then.  Returns when the chain is compacted. */
+int mcmcpp_hip_device_chain_compact(int32_t dtype, int32_t device, void* device_steps, int64_t n_steps, int64_t step_elems,
+                                    int64_t burn_in, int64_t interval, int64_t* kept);
+
 /* Current walker state (what Walker::getCurrState / getCurrAuxData / getAcceptedProposals expose,
  * Walker/Walker.h:111-122).  n_accept[w] counts accepted proposals since set_state or reset_counters;
  * the reference additionally counts the initial placement (Walker.h:76,168) -- the facade adds it.

@@ -26,6 +26,8 @@ EXPORTS = [
     "mcmcpp_hip_get_counters", "mcmcpp_hip_calc_logp", "mcmcpp_hip_set_chain_params", "mcmcpp_hip_calc_logp_chain", "mcmcpp_hip_last_run_timing", "mcmcpp_hip_last_run_host_timing",
     "mcmcpp_hip_comm_unique_id", "mcmcpp_hip_last_run_exchange", "mcmcpp_hip_run_async", "mcmcpp_hip_wait_stored", "mcmcpp_hip_run_wait",
     "mcmcpp_hip_host_alloc", "mcmcpp_hip_host_free",
+    "mcmcpp_hip_device_alloc", "mcmcpp_hip_device_free", "mcmcpp_hip_device_copy", "mcmcpp_hip_device_chain_last_error",
+    "mcmcpp_hip_device_chain_compact",
     "mcmcpp_hip_run_device", "mcmcpp_hip_run_device_async", "mcmcpp_hip_calc_logp_device", "mcmcpp_hip_moments_add_device_steps_strided",
     "mcmcpp_hip_half_step_async", "mcmcpp_hip_bind_device_chain", "mcmcpp_hip_device_positions",
     "mcmcpp_hip_shard_span", "mcmcpp_hip_synchronize",
@@ -112,6 +114,15 @@ def lib():
         L.mcmcpp_hip_host_alloc.restype = vp
         L.mcmcpp_hip_host_free.argtypes = [vp]
         L.mcmcpp_hip_host_free.restype = None
+        if hasattr(L, "mcmcpp_hip_device_alloc"):  # (absent from earlier builds selected with MCMCPP_HIP_LIB)
+            L.mcmcpp_hip_device_alloc.argtypes = [i32, C.c_uint64]
+            L.mcmcpp_hip_device_alloc.restype = vp
+            L.mcmcpp_hip_device_free.argtypes = [vp]
+            L.mcmcpp_hip_device_free.restype = None
+            L.mcmcpp_hip_device_copy.argtypes = [vp, vp, C.c_uint64]
+            L.mcmcpp_hip_device_chain_last_error.argtypes = []
+            L.mcmcpp_hip_device_chain_last_error.restype = C.c_char_p
+            L.mcmcpp_hip_device_chain_compact.argtypes = [i32, i32, vp, i64, i64, i64, i64, C.POINTER(i64)]
         L.mcmcpp_hip_half_step_async.argtypes = [vp, i32, i64]
         L.mcmcpp_hip_bind_device_chain.argtypes = [vp, vp, i64]
         L.mcmcpp_hip_device_positions.argtypes = [vp]
@@ -168,6 +179,30 @@ def pinned_empty(shape, dtype=np.float64):
     # the memory goes back when nothing refers to the buffer any more (numpy keeps it alive through arr.base)
     weakref.finalize(buf, lib().mcmcpp_hip_host_free, p)
     return np.frombuffer(buf, dtype=dt).reshape(shape)
+
+
+def device_chain_compact(steps, burn_in, interval, n_steps=None, step_elems=None, dtype=None, device=-1):
+    """Chain::resetChainForSubSampling on stored steps in device memory, in place (mcmcpp_hip_device_chain_compact): a contiguous
+    float64 / float32 device tensor (n, W, D), or an integer address with n_steps, step_elems and dtype given.  Returns the number
+    of steps kept; they are the first ones of the array afterwards."""
+    if _is_tensor(steps):
+        import torch
+        if steps.dim() != 3 or steps.dtype not in (torch.float64, torch.float32) or not steps.is_cuda or not steps.is_contiguous():
+            raise ValueError("device steps must be a contiguous float64 or float32 device tensor (n, W, D)")
+        dtype = F64 if steps.dtype == torch.float64 else F32
+        n_steps, step_elems = steps.shape[0], steps.shape[1] * steps.shape[2]
+        device = steps.device.index if device < 0 else device
+        _after_torch(steps)
+        ptr = steps.data_ptr()
+    else:
+        if n_steps is None or step_elems is None or dtype is None:
+            raise ValueError("an integer device address needs n_steps, step_elems and dtype")
+        ptr = int(steps)
+    kept = C.c_int64(0)
+    rc = lib().mcmcpp_hip_device_chain_compact(dtype, device, C.c_void_p(ptr), n_steps, step_elems, burn_in, interval, C.byref(kept))
+    if rc != OK:
+        raise HipError(rc, (lib().mcmcpp_hip_device_chain_last_error() or b"").decode())
+    return kept.value
 
 
 def np_dtype(dtype):
