@@ -19,25 +19,29 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "exchange_plan.hpp"
+
 namespace mcmcpp
 {
 constexpr uint32_t kAcceptCountMask = 0x7fffffffu;  // (the top bit of an accepted counter is the full-step kernels' "moved" mark)
 
-// [header 16 B][idx: cap x u32][logp: cap x T][rows: cap x D x T], every piece 16-byte aligned
+// [header 16 B][idx: cap x u32][logp: cap x T][rows: cap x D x T], every piece 16-byte aligned (the offsets: exchange_plan.hpp)
 struct XBlockHeader
 {
     uint32_t count;  // walkers of the slice that moved (may exceed cap: overflow)
     uint32_t cap;
     uint32_t pad[2];
 };
-__host__ __device__ inline size_t xblock_align16(size_t b) { return (b + 15) & ~(size_t)15; }
-__host__ __device__ inline size_t xblock_idx_offset() { return sizeof(XBlockHeader); }
+static_assert(sizeof(XBlockHeader) == kXBlockHeaderBytes, "exchange_plan.hpp lays the block out behind a header of this size");
+// the offsets for an element type: thin wrappers of exchange_plan.hpp's functions of the same names, which take the element size
+// as a number (T cannot be deduced from the arguments, so the unqualified-looking calls below can only mean those; they are
+// qualified all the same).  The log-posteriors lie behind the indices, so their offset does not depend on T.
 template <class T>
-__host__ __device__ inline size_t xblock_logp_offset(uint32_t cap) { return xblock_idx_offset() + xblock_align16((size_t)cap * sizeof(uint32_t)); }
+MCMCPP_HD size_t xblock_logp_offset(uint32_t cap) { return ::mcmcpp::xblock_logp_offset(cap); }
 template <class T>
-__host__ __device__ inline size_t xblock_rows_offset(uint32_t cap) { return xblock_logp_offset<T>(cap) + xblock_align16((size_t)cap * sizeof(T)); }
+MCMCPP_HD size_t xblock_rows_offset(uint32_t cap) { return ::mcmcpp::xblock_rows_offset(cap, sizeof(T)); }
 template <class T>
-__host__ __device__ inline size_t xblock_bytes(uint32_t cap, int dims) { return xblock_rows_offset<T>(cap) + xblock_align16((size_t)cap * (size_t)dims * sizeof(T)); }
+MCMCPP_HD size_t xblock_bytes(uint32_t cap, int dims) { return ::mcmcpp::xblock_bytes(cap, dims, sizeof(T)); }
 
 // what the scatter kernels leave for the host (read once per chunk of steps)
 struct XStats
@@ -47,7 +51,7 @@ struct XStats
 };
 
 // own slice: seen[w] <- accepted counter of w (start of a run, after a roll-back)
-__global__ void __launch_bounds__(256) exchange_sync_seen_kernel(const uint32_t* n_accept, uint32_t* seen, int n, int shard_begin, int shard_count)
+__global__ void __launch_bounds__(kSyncSeenThreads) exchange_sync_seen_kernel(const uint32_t* n_accept, uint32_t* seen, int n, int shard_begin, int shard_count)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 2 * shard_count) return;
@@ -62,11 +66,10 @@ __global__ void __launch_bounds__(256) exchange_sync_seen_kernel(const uint32_t*
 // count, a prefix over the wavefronts): one atomic per wavefront on the same address costs ~12 ns each -- 1 024 of them
 // made this launch 17 us at C5's slice size, 64 make it 3.  The block's count must be zero on entry (the scatter kernel
 // of the previous exchange, or the host at the start of a chunk, sees to that).
-constexpr int kPackWalkersPerWave = 16;
-constexpr int kPackWavesPerBlock = 16;
+// (kPackWalkersPerWave, kPackWavesPerBlock and the grid: exchange_plan.hpp)
 template <class T>
-__global__ void __launch_bounds__(64 * kPackWavesPerBlock) exchange_pack_kernel(const T* pos, const T* logp, const uint32_t* n_accept, uint32_t* seen, char* block,
-                                                                                   uint32_t cap, int n, int dims, int shard_begin, int shard_count, int color0, int colors)
+__global__ void __launch_bounds__(kPackThreads) exchange_pack_kernel(const T* pos, const T* logp, const uint32_t* n_accept, uint32_t* seen, char* block,
+                                                                     uint32_t cap, int n, int dims, int shard_begin, int shard_count, int color0, int colors)
 {
     __shared__ uint32_t wave_count[kPackWavesPerBlock];
     __shared__ uint32_t block_base;
@@ -112,10 +115,10 @@ __global__ void __launch_bounds__(64 * kPackWavesPerBlock) exchange_pack_kernel(
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const bool vec = ((size_t)dims * sizeof(T)) % 16 == 0;
-    const int pieces = vec ? (int)((size_t)dims * sizeof(T) / 16) : dims;
-    int lpr = 1;  // lanes per row: a power of two, at most 64
-    while (lpr < pieces && lpr < 64) lpr <<= 1;
+    const XRowPieces row = exchange_row_pieces(dims, sizeof(T));
+    const bool vec = row.vec;
+    const int pieces = row.pieces;
+    const int lpr = exchange_lanes_per_row(pieces);  // lanes per row: a power of two, at most 64
     const int rows_per_round = 64 / lpr, sub = lane % lpr, rr = lane / lpr;
     for (uint32_t r0 = 0; r0 < mine; r0 += (uint32_t)rows_per_round)
     {
@@ -137,8 +140,8 @@ __global__ void __launch_bounds__(64 * kPackWavesPerBlock) exchange_pack_kernel(
 // this rank) goes to pos_a (and pos_b, logp_b unless null).  One workgroup row of 256 threads handles 256 / lanes_per_row
 // slots.  Thread 0 of the grid reads every header for the statistics and clears this rank's own count for the next pack.
 template <class T>
-__global__ void __launch_bounds__(256) exchange_scatter_kernel(char* blocks, size_t block_bytes, uint32_t cap, int ranks, int rank, int dims, T* pos_a, T* pos_b,
-                                                               T* logp_a, T* logp_b, XStats* stats)
+__global__ void __launch_bounds__(kScatterThreads) exchange_scatter_kernel(char* blocks, size_t block_bytes, uint32_t cap, int ranks, int rank, int dims, T* pos_a, T* pos_b,
+                                                                           T* logp_a, T* logp_b, XStats* stats)
 {
     if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
     {
@@ -156,11 +159,11 @@ __global__ void __launch_bounds__(256) exchange_scatter_kernel(char* blocks, siz
     const char* block = blocks + block_bytes * (size_t)peer;
     uint32_t count = reinterpret_cast<const XBlockHeader*>(block)->count;
     if (count > cap) count = cap;
-    const bool vec = ((size_t)dims * sizeof(T)) % 16 == 0;
-    const int pieces = vec ? (int)((size_t)dims * sizeof(T) / 16) : dims;
-    int lpr = 1;  // lanes per row: a power of two, at most 64
-    while (lpr < pieces && lpr < 64) lpr <<= 1;
-    const int rows_per_block = 256 / lpr;
+    const XRowPieces row = exchange_row_pieces(dims, sizeof(T));
+    const bool vec = row.vec;
+    const int pieces = row.pieces;
+    const int lpr = exchange_lanes_per_row(pieces);  // lanes per row: a power of two, at most 64
+    const int rows_per_block = exchange_scatter_rows_per_block(lpr);
     const uint32_t slot = blockIdx.x * (uint32_t)rows_per_block + threadIdx.x / (uint32_t)lpr;
     if (slot >= count) return;
     const int sub = threadIdx.x % lpr;

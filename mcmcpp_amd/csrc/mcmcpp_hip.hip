@@ -710,17 +710,12 @@ public:
     {
         const size_t bb = xblock_bytes<T>(cap, D);
         char* own = d_xblocks + bb * (size_t)cfg.comm_rank;
-        const int pack_waves = (colors * shard_count + kPackWalkersPerWave - 1) / kPackWalkersPerWave;
-        hipLaunchKernelGGL(exchange_pack_kernel<T>, dim3((unsigned)((pack_waves + kPackWavesPerBlock - 1) / kPackWavesPerBlock)), dim3(64 * kPackWavesPerBlock), 0, stream, (const T*)cur_pos, (const T*)cur_logp,
+        hipLaunchKernelGGL(exchange_pack_kernel<T>, dim3(exchange_pack_blocks(colors * shard_count)), dim3(kPackThreads), 0, stream, (const T*)cur_pos, (const T*)cur_logp,
                            (const uint32_t*)d_nacc, d_seen, own, cap, n, D, shard_begin, shard_count, color0, colors);
         HIP_TRY(hipGetLastError());
         NCCL_TRY(rccl->AllGather(own, d_xblocks, bb, ncclInt8, comm, stream));
-        const bool vec = ((size_t)D * sizeof(T)) % 16 == 0;
-        const int pieces = vec ? (int)((size_t)D * sizeof(T) / 16) : D;
-        int lpr = 1;
-        while (lpr < pieces && lpr < 64) lpr <<= 1;
-        const unsigned rows_per_block = 256u / (unsigned)lpr;
-        hipLaunchKernelGGL(exchange_scatter_kernel<T>, dim3((cap + rows_per_block - 1) / rows_per_block, (unsigned)(cfg.comm_world - 1)), dim3(256), 0, stream,
+        const XScatterGrid grid = exchange_scatter_grid(cap, D, sizeof(T), cfg.comm_world);
+        hipLaunchKernelGGL(exchange_scatter_kernel<T>, dim3(grid.x, grid.y), dim3(kScatterThreads), 0, stream,
                            d_xblocks, bb, cap, cfg.comm_world, cfg.comm_rank, D, cur_pos, other_pos, cur_logp, other_logp, d_xstats);
         HIP_TRY(hipGetLastError());
         return MCMCPP_HIP_OK;
@@ -729,7 +724,7 @@ public:
     // (seen counters of the own slice <- accepted counters; statistics and the own block's count <- 0)
     int exchange_reset(uint32_t cap)
     {
-        hipLaunchKernelGGL(exchange_sync_seen_kernel, dim3((unsigned)((2 * shard_count + 255) / 256)), dim3(256), 0, stream, (const uint32_t*)d_nacc, d_seen, n,
+        hipLaunchKernelGGL(exchange_sync_seen_kernel, dim3(exchange_sync_seen_blocks(shard_count)), dim3(kSyncSeenThreads), 0, stream, (const uint32_t*)d_nacc, d_seen, n,
                            shard_begin, shard_count);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemsetAsync(d_xstats, 0, sizeof(XStats), stream));

@@ -225,6 +225,18 @@ case("iso32768x64_G2_rank0_stores_half_scheme")(lambda: run_ranks(
 for _scheme in ("step", "half"):
     case("rosen296x3_G2_%s" % _scheme)(lambda scheme=_scheme: run_ranks(2, 296, 3, po.CALC_ROSENBROCK, scheme=scheme, runs=((25, 2), (7, 1))))
     case("iso340x5_f32_G5_%s" % _scheme)(lambda scheme=_scheme: run_ranks(5, 340, 5, po.CALC_ISO_GAUSSIAN, dtype=capi.F32, scheme=scheme, runs=((30, 1),)))
+# rows wider than the 64 lanes that copy them (tests/test_exchange_kernels.py steps pack and scatter alone at these shapes): 65
+# pieces of 16 bytes; 131 doubles copied one by one, 35 walkers per rank and colour; 256 pieces.  The last one again with blocks
+# of 8 slots and chunks of 3 steps: about a hundred walkers move per rank and step, so every chunk overflows and is rolled back.
+# (Seed 10 for the fp32 cases: with seed 9 the oracle flags one near tie in these seven steps.)
+for _scheme in ("step", "half"):
+    case("iso280x130_G2_%s" % _scheme)(lambda scheme=_scheme: run_ranks(2, 280, 130, po.CALC_ISO_GAUSSIAN, scheme=scheme, runs=((3, 2), (1, 1))))
+    case("iso280x131_G4_%s" % _scheme)(lambda scheme=_scheme: run_ranks(4, 280, 131, po.CALC_ISO_GAUSSIAN, scheme=scheme, runs=((3, 2), (1, 1))))
+    case("iso2100x1024_f32_G2_%s" % _scheme)(lambda scheme=_scheme: run_ranks(
+        2, 2100, 1024, po.CALC_ISO_GAUSSIAN, dtype=capi.F32, scheme=scheme, runs=((3, 2), (1, 1)), seed=10))
+    case("iso2100x1024_f32_G2_%s_forced_overflow" % _scheme)(lambda scheme=_scheme: run_ranks(
+        2, 2100, 1024, po.CALC_ISO_GAUSSIAN, dtype=capi.F32, scheme=scheme, runs=((3, 2), (1, 1)), seed=10,
+        env={"MCMCPP_HIP_COMM_COMPACT_CAP": "8", "MCMCPP_HIP_COMM_COMPACT_CHUNK": "3"}, expect=_expect_repeats))
 # walkers whose log-posterior is not finite (tests/test_nonfinite.py): they never move, so the compact exchange never sends their
 # rows -- every replica must still hold them, and the stated NaN / -inf log-posteriors, exactly as the oracle does
 for _scheme in ("step", "half"):
