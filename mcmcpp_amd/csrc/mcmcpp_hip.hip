@@ -26,18 +26,10 @@
 #include "../../include/mcmcpp_hip.h"
 #define MCMCPP_DEFINE_REDUCE_KERNEL
 #include "launch_table.hpp"
-#include "exchange_kernels.hpp"
-#include "rccl_dyn.hpp"
 #include "sampler_host.hpp"
+#include "split_exchange.hpp"
 
 using namespace mcmcpp;
-
-#define NCCL_TRY(expr)                                                                                          \
-    do                                                                                                          \
-    {                                                                                                           \
-        ncclResult_t r_ = (expr);                                                                               \
-        if (r_ != ncclSuccess) return fail(MCMCPP_HIP_E_COMM, "%s failed: %s", #expr, rccl->GetErrorString(r_)); \
-    } while (0)
 
 namespace
 {
@@ -157,14 +149,11 @@ void launch_accepted_reduce(const uint32_t* partials, int partial_slots, int par
 
 namespace
 {
-// The host's pinned scratch of one handle: records on their way to the device and status words on their way back.  The
-// host rewrites a slot only once the asynchronous copies that read it have been ordered (synchronised, or in the case of
-// the run records four sub-chunks of launches later: the sub-chunk loop rotates over them).
+// The host's pinned scratch of one handle: records on their way to the device.  The host rewrites a slot only once the
+// asynchronous copies that read it have been ordered (synchronised, or in the case of the run records four sub-chunks of
+// launches later: the sub-chunk loop rotates over them).
 struct PinnedScratch
 {
-    uint64_t status_out[6];                         // agree_on_status: the words every rank all-reduces
-    uint64_t status_back[6];                        // ... and what comes back
-    XStats xstats;                                  // split ensembles: the exchange statistics of the chunk in hand
     alignas(64) StepCtl ctl;                        // write_ctl, one chain
     alignas(64) RunInfo run[4];                     // one chain: a run's sub-chunks in turn (the split path uses [0])
     alignas(64) StepCtl chain_ctl[kMaxChains];      // write_ctl, several chains
@@ -184,8 +173,7 @@ public:
     Sampler() {}
     ~Sampler() override
     {
-        quiesce();  // (half_step_async work may still be in flight; the members free themselves behind this)
-        if (own_comm && comm && rccl) (void)rccl->CommDestroy(comm);
+        quiesce();  // (half_step_async work may still be in flight; the members free themselves behind this, xchg and its communicator first)
     }
 
     int init(const mcmcpp_hip_config& c)
@@ -206,7 +194,7 @@ public:
         if (int rc = resolve_shard(c)) return rc;
         hipDeviceProp_t prop;
         if (int rc = open_device(c, &prop)) return rc;
-        if (int rc = open_communicator(c)) return rc;
+        if (int rc = xchg.open(this, c)) return rc;  // split ensembles: the caller's communicator, or one from the caller's id
         K = c.num_chains > 1 ? c.num_chains : 1;
         if (K > kMaxChains) return fail(MCMCPP_HIP_E_ARG, "num_chains %d exceeds %d", K, kMaxChains);
         if (K > 1 && (shard_count != n || shard_begin != 0 || c.comm_world >= 1 || c.device_positions))
@@ -258,47 +246,10 @@ public:
         return MCMCPP_HIP_OK;
     }
 
-    // split ensembles: the caller's communicator, or one of the handle's own from the caller's id
-    int open_communicator(const mcmcpp_hip_config& c)
-    {
-        if (c.comm_world < 1) return MCMCPP_HIP_OK;
-        std::string why;
-        rccl = Rccl::get(&why);
-        if (!rccl) return fail(MCMCPP_HIP_E_COMM, "%s", why.c_str());
-        if (c.comm)
-        {
-            comm = static_cast<ncclComm_t>(c.comm);
-            int cnt = -1, rk = -1;
-            NCCL_TRY(rccl->CommCount(comm, &cnt));
-            NCCL_TRY(rccl->CommUserRank(comm, &rk));
-            if (cnt != c.comm_world || rk != c.comm_rank)
-                return fail(MCMCPP_HIP_E_ARG, "the communicator is rank %d of %d, the config says %d of %d", rk, cnt, c.comm_rank, c.comm_world);
-        }
-        else
-        {
-            ncclUniqueId id;
-            static_assert(sizeof(id) == MCMCPP_HIP_COMM_ID_BYTES, "mcmcpp_hip.h states the size of an RCCL id");
-            std::memcpy(&id, c.comm_id, sizeof id);
-            NCCL_TRY(rccl->CommInitRank(&comm, c.comm_world, id, c.comm_rank));
-            own_comm = true;
-        }
-        return MCMCPP_HIP_OK;
-    }
-
     // every buffer of the handle, sized by the plan
     int allocate(const mcmcpp_hip_config& c)
     {
         const size_t step_bytes = sizeof(T) * (size_t)W * D;
-        if (plan.compact_exchange)
-        {
-            snap.logp = step_bytes;
-            snap.nacc = snap.logp + sizeof(T) * (size_t)W;
-            snap.diag = snap.nacc + sizeof(uint32_t) * (size_t)W;
-            HIP_TRY(d_xblocks.alloc(xblock_bytes<T>(exchange_cap_full(), D) * (size_t)c.comm_world));
-            HIP_TRY(d_seen.alloc(sizeof(uint32_t) * (size_t)W));
-            HIP_TRY(d_xstats.alloc(sizeof(XStats)));
-            HIP_TRY(d_snap.alloc(snap.diag + sizeof(Diag)));
-        }
         for (int k = 0; k < 4; ++k)
         {
             HIP_TRY(hipEventCreate(ev_t0[k].replace()));
@@ -343,7 +294,6 @@ public:
             d_run = reinterpret_cast<RunInfo*>(piece + kRunBehindCtlBytes);
         }
         if (int rc = carve(&d_diag, sizeof(Diag))) return rc;
-        if (int rc = carve(&d_status, 8 * sizeof(uint64_t))) return rc;  // split ensembles: the status word the ranks agree on
         // the draw records (two buffers: see HalfStepArgs::draws) and, right behind them, the jump tables: one piece
         // whose layout follows from n alone (JumpTables), so that kernels reach the tables from the record pointer
         static_assert(sizeof(DrawRec<T>) == 32, "the table offsets assume 32-byte records");
@@ -370,7 +320,13 @@ public:
         if (int rc = carve(&d_partials, partials_bytes)) return rc;
         HIP_TRY(hipMemset(d_partials, 0, partials_bytes));
         chain_subchunk_bytes = (size_t)knobs.chain_subchunk_mb << 20;
-        return MCMCPP_HIP_OK;
+        // a rank of a split ensemble: the exchange side works on this replica (split_exchange.hpp)
+        SplitReplica<T> replica;
+        replica.owner = this, replica.device = device, replica.stream = stream;
+        replica.W = W, replica.D = D, replica.n = n, replica.shard_begin = shard_begin, replica.shard_count = shard_count;
+        replica.full_step = full_fn != nullptr, replica.compact = plan.compact_exchange;
+        replica.pos = d_pos, replica.pos_alt = d_pos_alt, replica.logp = d_logp, replica.nacc = d_nacc, replica.diag = d_diag;
+        return xchg.allocate(replica);
     }
 
     // what the kernels read and no run changes: calculator parameters, the random stream's seeds and jump tables
@@ -390,8 +346,8 @@ public:
         }
 
         // pcg64 stream (MultiSampler.h:54) and its jump tables
-        pcg_seed(c.seed, c.stream, &state0, &inc);
-        for (int k = 0; k < K; ++k)
+        pcg_seed(c.seed, c.stream, &state0_of[0], &inc);
+        for (int k = 1; k < K; ++k)
         {
             U128 inc_k;
             pcg_seed(c.seed + (uint64_t)k, c.stream, &state0_of[k], &inc_k);  // (same stream: the same increment)
@@ -412,9 +368,6 @@ public:
         }
         return MCMCPP_HIP_OK;
     }
-
-    // a block of the compact exchange that holds every walker of an exchange
-    uint32_t exchange_cap_full() const { return (uint32_t)((full_fn ? 2 : 1) * shard_count); }
 
     // Everything a step launch touches lives in ONE device allocation, carved here (one allocation, one free; tried as
     // a way to make the cold first accesses of a launch cheaper through fewer address translations: no measurable
@@ -443,7 +396,7 @@ public:
         half_steps = 0;
         steps_since_reset = 0;
         records_valid = false;
-        int rc = write_ctl(0);
+        int rc = write_ctl(half_steps, 0);
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(stream));
         have_state = true;
@@ -461,14 +414,14 @@ public:
     // the captured graphs as they are (they read the record from memory).
     int run_mover(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, bool to_device) override
     {
-        return comm ? run_split(n_saved, interval, chain_out, accepted_per_step) : run_whole(n_saved, interval, chain_out, accepted_per_step, to_device);
+        return xchg.active() ? run_split(n_saved, interval, chain_out, accepted_per_step) : run_whole(n_saved, interval, chain_out, accepted_per_step, to_device);
     }
     int run_chains() const override { return K; }
     RunFacts run_facts() const override
     {
         RunFacts f = {};
         f.mover = Mover::Stretch;
-        f.communicator = comm != nullptr;
+        f.communicator = xchg.active();
         f.sharded = shard_count != n;
         f.half_done = (half_steps & 1) != 0;
         return f;
@@ -482,7 +435,7 @@ public:
     {
         if (acc_entries) HIP_TRY(hipMemsetAsync(d_acc, 0, sizeof(uint32_t) * acc_entries, stream));
         run_touched = true;  // from here on an error leaves the device ahead of the host's bookkeeping
-        if (int rc = write_ctl(0)) return rc;  // step_in_run = 0, stream position from the host-side half-step count
+        if (int rc = write_ctl(half_steps, 0)) return rc;  // step_in_run = 0, stream position from the host-side half-step count
         records_valid = false;  // (until this call has finished: an error on the way leaves them unknown)
         run_info_idle = false;
         if (split_record) HIP_TRY(hipMemcpyAsync(d_run, split_record, sizeof(RunInfo), hipMemcpyHostToDevice, stream));
@@ -627,26 +580,12 @@ public:
     //     records of a rank's own walkers are also left behind by its draw wavefronts: same bits).
     //   half-step kernels (larger slices): the reference's scheme, one exchange of the updated colour per half-step.
     // The random stream is addressed by the global walker index, so the trajectory does not depend on the number of ranks.
-    int exchange_rows(T* pos_buf, T* logp_buf, int first_color, int colors)
-    {
-        NCCL_TRY(rccl->GroupStart());
-        for (int c = first_color; c < first_color + colors; ++c)
-        {
-            T* half = pos_buf + (size_t)c * n * D;
-            NCCL_TRY(rccl->AllGather(half + (size_t)shard_begin * D, half, (size_t)shard_count * D, RcclType<T>::value, comm, stream));
-            if (logp_buf)
-            {
-                T* lh = logp_buf + (size_t)c * n;
-                NCCL_TRY(rccl->AllGather(lh + shard_begin, lh, (size_t)shard_count, RcclType<T>::value, comm, stream));
-            }
-        }
-        NCCL_TRY(rccl->GroupEnd());
-        return MCMCPP_HIP_OK;
-    }
+    // The exchanges themselves, the communicator and every buffer only a split run uses are xchg's (split_exchange.hpp); the
+    // schedule of a run is SplitWindow's (run_plan.hpp).  Here are the step launches and the order of things.
 
     // Rank-local preparation of a split run: argument and state checks, staging and counter buffers.  Whatever fails here
     // fails on this rank only -- the caller agrees on it with the other ranks (agree_on_status) before the first launch.
-    int prepare_split(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step, int64_t* stage_slots_out)
+    int prepare_split(int64_t n_saved, int32_t interval, void* chain_out, int64_t* stage_slots_out)
     {
         if (int rc = refuse_run(n_saved, interval, false)) return rc;
         const int64_t total = n_saved * (int64_t)interval;
@@ -654,81 +593,86 @@ public:
         // stored steps: device -> pinned staging on the launch stream, handed to the caller a staging buffer at a time
         // (the same number of slots on every rank, whether it stores or not: every rank must cut its run into the same chunks)
         const int64_t stage_slots = split_stage_slots(step_bytes, n_saved);
-        if (chain_out && total > 0 && grow(h_split_stage, step_bytes * (size_t)stage_slots, stream))
-            return fail(MCMCPP_HIP_E_NOMEM, "run: cannot allocate %zu bytes of pinned staging", step_bytes * (size_t)stage_slots);
+        if (int rc = xchg.prepare_run(chain_out && total > 0 ? step_bytes * (size_t)stage_slots : 0)) return rc;
         *stage_slots_out = stage_slots;
         // (the per-step accepted counts are always kept on the device and all-reduced at the end of a split run, whether this
         //  rank's caller wants them or not: a collective must not depend on one rank's arguments)
-        (void)accepted_per_step;
-        const int rc = ensure_run_buffers(total > 0 ? (size_t)total : 0, 0, 0);
-        if (rc) return rc;
-        if (ev_x.empty())
+        return ensure_run_buffers(total > 0 ? (size_t)total : 0, 0, 0);
+    }
+
+    // what SplitWindow (run_plan.hpp) plans a run of `total` steps from
+    SplitRequest split_request(int64_t total, int32_t interval, bool any_rank_stores, bool stores, int64_t stage_slots) const
+    {
+        SplitRequest q = {};
+        q.total = total, q.interval = interval, q.any_rank_stores = any_rank_stores, q.stores = stores, q.stage_slots = stage_slots;
+        q.compact = plan.compact_exchange, q.cap_full = xchg.cap_full(), q.cap_learned = xchg.cap_learned;
+        q.comm_compact_cap = knobs.comm_compact_cap, q.comm_compact_chunk = knobs.comm_compact_chunk;
+        q.full_step = full_fn != nullptr, q.comm_world = cfg.comm_world, q.shard_count = shard_count, q.dims = D, q.elem_size = sizeof(T);
+        q.block_bytes = &mcmcpp::xblock_bytes;
+        return q;
+    }
+
+    // what a split run carries from step to step besides the handle's own counters
+    struct SplitRun
+    {
+        HalfStepArgs<T> fill_red;  // full-step scheme: the red draw records of ALL walkers, made per step
+        U128 red_base;             // engine state in front of the red half-step of the coming ensemble step
+        int unreduced = 0;         // steps whose per-wavefront accepted counts are still to be summed
+    };
+
+    // (the per-wavefront accepted counts are summed once per partial_slots steps, and at the end of a chunk)
+    void reduce_accepted_if_due(SplitRun& r, bool last_of_chunk)
+    {
+        if (++r.unreduced == plan.partial_slots || last_of_chunk)
         {
-            ev_x.resize(2 * kMaxExchangeSamples);
-            for (Event& e : ev_x) HIP_TRY(hipEventCreate(e.replace()));
+            launch_accepted_reduce(d_partials, plan.partial_slots, plan.partial_waves, r.unreduced, ctl_after((int64_t)run_step + 1), d_run, stream, K);
+            r.unreduced = 0;
         }
-        return MCMCPP_HIP_OK;
     }
 
-    // Every rank learns the worst status among the ranks (and that all were asked for the same number of steps) before any
-    // of them launches or exchanges anything: a rank that failed its preparation would otherwise leave the others waiting
-    // in their first all-gather for good.  One small all-reduce and one stream synchronisation per run.
-    int agree_on_status(int local_rc, int64_t total, int32_t interval, bool stores, bool* any_rank_stores)
+    // the position buffer that holds the ensemble behind the steps enqueued in this run so far
+    bool ensemble_in_alt() const { return full_fn && (run_step & 1); }
+
+    // One ensemble step of a split run with its exchange(s), blocks of `cap` slots; sample >= 0: its (red) exchange is timed
+    int enqueue_split_step(SplitRun& r, uint32_t cap, int sample, bool last_of_chunk)
     {
-        uint64_t* out = h_pinned->status_out;
-        const uint64_t* back = h_pinned->status_back;
-        out[0] = (uint64_t)local_rc;
-        out[1] = (uint64_t)total;
-        out[2] = ~(uint64_t)total;
-        out[3] = (uint64_t)(uint32_t)interval;
-        out[4] = ~(uint64_t)(uint32_t)interval;
-        out[5] = stores ? 1u : 0u;  // (stored steps are handed out a staging buffer at a time: where the chunks of the run end)
-        const std::string mine = error;
-        HIP_TRY(hipSetDevice(device));
-        HIP_TRY(hipMemcpyAsync(d_status, out, 6 * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-        NCCL_TRY(rccl->AllReduce(d_status, d_status, 6, ncclUint64, ncclMax, comm, stream));
-        HIP_TRY(hipMemcpyAsync(h_pinned->status_back, d_status, 6 * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (local_rc != MCMCPP_HIP_OK)
+        const int parity = (int)(enq_step & 1), pos_parity = (int)(run_step & 1);
+        if (full_fn)
         {
-            error = mine;
-            return local_rc;
+            r.fill_red.draw_parity = parity;
+            launch_fill_draws(r.fill_red, r.red_base, nullptr, stream);
+            enqueue_step(parity, pos_parity);
+            reduce_accepted_if_due(r, last_of_chunk);
+            HIP_TRY(hipGetLastError());
+            if (int rc = xchg.exchange(!pos_parity, 0, 2, cap, sample)) return rc;  // (the step wrote the buffer it did not read)
+            r.red_base = apply(half_jump, apply(half_jump, r.red_base));
         }
-        if (back[0] != 0) return fail((int)back[0], "run: the preparation of another rank of the split ensemble failed (code %d); nothing was launched", (int)back[0]);
-        if (back[1] != ~back[2] || back[3] != ~back[4])
-            return fail(MCMCPP_HIP_E_ARG, "run: the ranks of the split ensemble were asked for different numbers of steps or intervals; nothing was launched");
-        *any_rank_stores = back[5] != 0;
+        else
+        {
+            args_red.draw_parity = parity;
+            args_blk.draw_parity = parity;
+            half_fn(args_red, plan.grid_blocks_for(args_red.shard_count), stream);
+            HIP_TRY(hipGetLastError());
+            if (int rc = xchg.exchange(false, 0, 1, cap, sample)) return rc;
+            half_fn(args_blk, plan.grid_blocks_for(args_blk.shard_count), stream);
+            reduce_accepted_if_due(r, last_of_chunk);
+            HIP_TRY(hipGetLastError());
+            if (int rc = xchg.exchange(false, 1, 1, cap, -1)) return rc;
+        }
+        enq_step += 1;
+        run_step += 1;
         return MCMCPP_HIP_OK;
     }
 
-    static constexpr int kMaxExchangeSamples = 32;
-
-    // ---- the exchange of moved rows only (exchange_kernels.hpp) ----------------------------------------------------------
-    // pack -> one all-gather of G equal blocks of `cap` slots -> scatter into the replica (both position buffers when
-    // `other_pos` is given).  Colours [color0, color0 + colors) of this rank's slice.
-    int exchange_compact(T* cur_pos, T* other_pos, T* cur_logp, T* other_logp, int color0, int colors, uint32_t cap)
+    // Behind the roll-back of an overflowed chunk: the stream, the control record and the host's counters in front of step
+    // `step` of the run that started at half-step half_steps0; the repeated chunk starts at buffer 0 like a run does
+    int reposition_split(SplitRun& r, uint64_t half_steps0, int64_t step, int32_t interval)
     {
-        const size_t bb = xblock_bytes<T>(cap, D);
-        char* own = d_xblocks + bb * (size_t)cfg.comm_rank;
-        hipLaunchKernelGGL(exchange_pack_kernel<T>, dim3(exchange_pack_blocks(colors * shard_count)), dim3(kPackThreads), 0, stream, (const T*)cur_pos, (const T*)cur_logp,
-                           (const uint32_t*)d_nacc, d_seen, own, cap, n, D, shard_begin, shard_count, color0, colors);
-        HIP_TRY(hipGetLastError());
-        NCCL_TRY(rccl->AllGather(own, d_xblocks, bb, ncclInt8, comm, stream));
-        const XScatterGrid grid = exchange_scatter_grid(cap, D, sizeof(T), cfg.comm_world);
-        hipLaunchKernelGGL(exchange_scatter_kernel<T>, dim3(grid.x, grid.y), dim3(kScatterThreads), 0, stream,
-                           d_xblocks, bb, cap, cfg.comm_world, cfg.comm_rank, D, cur_pos, other_pos, cur_logp, other_logp, d_xstats);
-        HIP_TRY(hipGetLastError());
-        return MCMCPP_HIP_OK;
-    }
-
-    // (seen counters of the own slice <- accepted counters; statistics and the own block's count <- 0)
-    int exchange_reset(uint32_t cap)
-    {
-        hipLaunchKernelGGL(exchange_sync_seen_kernel, dim3(exchange_sync_seen_blocks(shard_count)), dim3(kSyncSeenThreads), 0, stream, (const uint32_t*)d_nacc, d_seen, n,
-                           shard_begin, shard_count);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemsetAsync(d_xstats, 0, sizeof(XStats), stream));
-        HIP_TRY(hipMemsetAsync(d_xblocks + xblock_bytes<T>(cap, D) * (size_t)cfg.comm_rank, 0, sizeof(XBlockHeader), stream));
+        records_valid = false;
+        if (int rc = write_ctl(half_steps0 + 2 * (uint64_t)step, (uint64_t)step, interval)) return rc;
+        enq_step = (half_steps0 >> 1) + (uint64_t)step;
+        run_step = 0;
+        r.red_base = engine_state_before(half_steps0 + 2 * (uint64_t)step);
         return MCMCPP_HIP_OK;
     }
 
@@ -736,194 +680,109 @@ public:
     // only at the end of a chunk, and only when it has a reason to: stored steps to hand out (a staging buffer's worth), or
     // -- exchanging moved rows only -- the overflow flag to look at.  A chunk whose blocks overflowed is rolled back to the
     // snapshot taken in front of it and repeated with blocks that hold a whole slice; the slot bound of the following
-    // chunks is what the last one needed, plus an eighth.
+    // chunks is what the last one needed, plus an eighth.  SplitWindow (run_plan.hpp) keeps that schedule.
     int run_split(int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step)
     {
         host_enqueue_ms = exchange_us_per_step = 0.0;
         xchg_bytes_per_step = 0.0;
         xchg_rollbacks = 0;
+        // ---- prepare, and agree with the other ranks
         int64_t stage_slots = 0;
-        const int prep = prepare_split(n_saved, interval, chain_out, accepted_per_step, &stage_slots);
+        const int prep = prepare_split(n_saved, interval, chain_out, &stage_slots);
         const int64_t total = (n_saved > 0 && interval > 0) ? n_saved * (int64_t)interval : 0;
         bool any_rank_stores = false;
-        int rc = agree_on_status(prep, total, interval, chain_out != nullptr, &any_rank_stores);
+        int rc = xchg.agree_on_status(prep, total, interval, chain_out != nullptr, &any_rank_stores);
         if (rc) return rc;
         if (total == 0) return MCMCPP_HIP_OK;
+
+        // ---- begin the run
         const size_t step_bytes = sizeof(T) * (size_t)W * D;
-        constexpr int kMaxSamples = kMaxExchangeSamples;
         h_pinned->run[0] = run_info_of_run(nullptr, d_acc, interval, step_bytes);  // (no chain: stored steps are copied from the replica after the exchange)
         if ((rc = begin_run((size_t)total, &h_pinned->run[0]))) return rc;
         const uint64_t half_steps0 = half_steps;  // (the member moves on when the run has succeeded)
-        // engine state in front of the red half-step of the coming ensemble step (what write_ctl put into the control record)
-        U128 red_base = apply(pcg_jump(inc, (unsigned __int128)3 * (unsigned)n * (unsigned __int128)half_steps0), state0);
-        HalfStepArgs<T> fill_red = make_args(0);
-        fill_red.shard_begin = 0;
-        fill_red.shard_count = n;
-
-        const bool compact = plan.compact_exchange;
-        const uint32_t cap_full = exchange_cap_full();
-        // the slot bound of the exchange blocks (run_plan.hpp): what MCMCPP_HIP_COMM_COMPACT_CAP sets, or learned from the run
-        const uint32_t cap_set = split_cap_set(knobs.comm_compact_cap, cap_full);
-        uint32_t cap = split_first_cap(compact, cap_set, xcap_learned, cap_full);
-        if (compact && full_fn)
-        {
-            // a remote walker's row must be current in BOTH buffers (the scatter keeps it so from here on)
-            HIP_TRY(hipMemcpyAsync(d_pos_alt, d_pos, step_bytes, hipMemcpyDeviceToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(d_logp + W, d_logp, sizeof(T) * (size_t)W, hipMemcpyDeviceToDevice, stream));
-        }
-
-        const int64_t sample_stride = total > kMaxSamples ? total / kMaxSamples : 1;
-        int samples = 0;
-        int64_t handed = 0;  // stored steps handed to the caller
-        double xbytes = 0.0;  // bytes this rank received in the exchanges of the steps that count
-        bool learning = compact && !cap_set && xcap_learned == 0;  // first chunk: short, whole-slice blocks
+        SplitRun r;
+        r.red_base = engine_state_before(half_steps0);  // (what write_ctl put into the control record)
+        r.fill_red = make_args(0);
+        r.fill_red.shard_begin = 0;
+        r.fill_red.shard_count = n;
+        SplitWindow win(split_request(total, interval, any_rank_stores, chain_out != nullptr, stage_slots));
+        if ((rc = xchg.begin_run())) return rc;
         HIP_TRY(hipEventRecord(ev_t0[0], stream));
         const auto tp1 = std::chrono::steady_clock::now();
-        int64_t s0 = 0;  // first step of the chunk in hand
-        while (s0 < total)
+
+        while (!win.done())
         {
-            // ---- how far this chunk goes (every rank cuts alike)
-            const int64_t len = split_chunk_length(total, s0, compact, learning, knobs.comm_compact_chunk, any_rank_stores, interval, stage_slots);
-            if (compact)
+            // ---- a chunk (every rank cuts alike): snapshot, the steps, the end of the chunk
+            if ((rc = xchg.begin_chunk(ensemble_in_alt(), win.cap))) return rc;
+            for (int64_t s = win.first(); s < win.end(); ++s)
             {
-                const bool in_alt = full_fn && (run_step & 1);
-                if ((rc = snapshot(in_alt ? d_pos_alt : d_pos, in_alt ? d_logp + W : d_logp))) return rc;
-                if ((rc = exchange_reset(cap))) return rc;
+                if ((rc = enqueue_split_step(r, win.cap, win.take_sample(s), s + 1 == win.end()))) return rc;
+                if (win.stores_step(s))
+                    HIP_TRY(hipMemcpyAsync(xchg.stage() + step_bytes * (size_t)win.take_stage_slot(), ensemble_in_alt() ? d_pos_alt : d_pos, step_bytes, hipMemcpyDeviceToHost, stream));
             }
-            int unreduced = 0;
-            // (the per-wavefront accepted counts are summed once per partial_slots steps, and at the end of a chunk)
-            auto reduce_accepted_if_due = [&](bool last_of_chunk) {
-                if (++unreduced == plan.partial_slots || last_of_chunk)
-                {
-                    launch_accepted_reduce(d_partials, plan.partial_slots, plan.partial_waves, unreduced, ctl_after((int64_t)run_step + 1), d_run, stream, K);
-                    unreduced = 0;
-                }
-            };
-            int64_t staged = handed;
-            const int samples_before = samples;
-            for (int64_t s = s0; s < s0 + len; ++s)
+            XStats seen = {};
+            if (plan.compact_exchange)
             {
-                const int parity = (int)(enq_step & 1), pos_parity = (int)(run_step & 1);
-                const bool sample = samples < kMaxSamples && s % sample_stride == 0;
-                const bool last_of_chunk = s + 1 == s0 + len;
-                T* cur_pos = d_pos;  // the replica that holds the ensemble after this step
-                if (full_fn)
-                {
-                    fill_red.draw_parity = parity;
-                    launch_fill_draws(fill_red, red_base, nullptr, stream);
-                    enqueue_step(parity, pos_parity);
-                    reduce_accepted_if_due(last_of_chunk);
-                    HIP_TRY(hipGetLastError());
-                    cur_pos = pos_parity ? d_pos : d_pos_alt;
-                    T* other_pos = pos_parity ? d_pos_alt : d_pos;
-                    T* cur_logp = pos_parity ? d_logp : d_logp + W;
-                    T* other_logp = pos_parity ? d_logp + W : d_logp;
-                    if (sample) HIP_TRY(hipEventRecord(ev_x[2 * samples], stream));
-                    rc = compact ? exchange_compact(cur_pos, other_pos, cur_logp, other_logp, 0, 2, cap) : exchange_rows(cur_pos, cur_logp, 0, 2);
-                    if (rc) return rc;
-                    if (sample) HIP_TRY(hipEventRecord(ev_x[2 * samples + 1], stream));
-                    red_base = apply(half_jump, apply(half_jump, red_base));
-                }
-                else
-                {
-                    args_red.draw_parity = parity;
-                    args_blk.draw_parity = parity;
-                    half_fn(args_red, plan.grid_blocks_for(args_red.shard_count), stream);
-                    HIP_TRY(hipGetLastError());
-                    if (sample) HIP_TRY(hipEventRecord(ev_x[2 * samples], stream));
-                    rc = compact ? exchange_compact(d_pos, nullptr, d_logp, nullptr, 0, 1, cap) : exchange_rows(d_pos, nullptr, 0, 1);
-                    if (rc) return rc;
-                    if (sample) HIP_TRY(hipEventRecord(ev_x[2 * samples + 1], stream));
-                    half_fn(args_blk, plan.grid_blocks_for(args_blk.shard_count), stream);
-                    reduce_accepted_if_due(last_of_chunk);
-                    HIP_TRY(hipGetLastError());
-                    rc = compact ? exchange_compact(d_pos, nullptr, d_logp, nullptr, 1, 1, cap) : exchange_rows(d_pos, nullptr, 1, 1);
-                    if (rc) return rc;
-                }
-                if (sample) ++samples;
-                enq_step += 1;
-                run_step += 1;
-                if (chain_out && (s + 1) % interval == 0)
-                {
-                    HIP_TRY(hipMemcpyAsync((char*)h_split_stage + step_bytes * (size_t)(staged - handed), cur_pos, step_bytes, hipMemcpyDeviceToHost, stream));
-                    ++staged;
-                }
-            }
-            // ---- end of the chunk
-            const bool more = s0 + len < total;
-            if (compact)
-            {
-                XStats* hx = &h_pinned->xstats;
-                HIP_TRY(hipMemcpyAsync(hx, d_xstats, sizeof(XStats), hipMemcpyDeviceToHost, stream));
-                HIP_TRY(hipStreamSynchronize(stream));
-                if (hx->overflow)
+                if ((rc = xchg.read_stats(&seen))) return rc;
+                if (seen.overflow)
                 {
                     // Some block of some exchange of this chunk was too small: whatever the chunk computed rests on a
-                    // replica that missed rows.  Back to the snapshot (rollback) and once more with blocks nothing can
-                    // overflow.  Every rank reads the same gathered headers, so every rank takes this branch together.
-                    ++xchg_rollbacks;
-                    if ((rc = rollback())) return rc;
-                    half_steps = half_steps0 + 2 * (uint64_t)s0;
-                    records_valid = false;
-                    rc = write_ctl((uint64_t)s0, interval);
-                    half_steps = half_steps0;
-                    if (rc) return rc;
-                    enq_step = (half_steps0 >> 1) + (uint64_t)s0;
-                    run_step = 0;
-                    red_base = apply(pcg_jump(inc, (unsigned __int128)3 * (unsigned)n * ((unsigned __int128)half_steps0 + 2 * (unsigned __int128)s0)), state0);
-                    samples = samples_before;
-                    cap = cap_full;
-                    continue;  // (the same chunk again)
+                    // replica that missed rows.  Back to the snapshot and once more with blocks nothing can overflow.
+                    // Every rank reads the same gathered headers, so every rank takes this branch together.
+                    const int64_t again_from = win.chunk_overflowed();
+                    if ((rc = xchg.rollback())) return rc;
+                    if ((rc = reposition_split(r, half_steps0, again_from, interval))) return rc;
+                    continue;
                 }
-                xbytes += split_bytes_compact(len, full_fn != nullptr, cfg.comm_world, xblock_bytes<T>(cap, D));
-                // the next chunk's bound: what this one needed, plus an eighth and a little
-                if (!cap_set) xcap_learned = split_next_cap(hx->max_count, cap_full);
-                cap = cap_set ? cap_set : xcap_learned;
-                learning = false;
             }
-            else
-                xbytes += split_bytes_whole(len, full_fn != nullptr, cfg.comm_world, shard_count, D, sizeof(T));
-            if (chain_out && staged > handed && (staged - handed == stage_slots || !more || compact))
+            win.chunk_held(seen.max_count);
+            xchg.cap_learned = win.cap_learned;
+            // ---- stored steps leave where the window says so
+            const StoredRange out = win.hand_out();
+            if (out.to > out.from)
             {
                 HIP_TRY(hipStreamSynchronize(stream));
-                std::memcpy((char*)chain_out + step_bytes * (size_t)handed, h_split_stage, step_bytes * (size_t)(staged - handed));
-                handed = staged;
-                publish_stored(handed);
+                std::memcpy((char*)chain_out + step_bytes * (size_t)out.from, xchg.stage(), step_bytes * (size_t)(out.to - out.from));
+                publish_stored(out.to);
             }
-            s0 += len;
         }
         const auto tp2 = std::chrono::steady_clock::now();
+
+        // ---- the end of the run
         if ((rc = bring_ensemble_home())) return rc;
         HIP_TRY(hipEventRecord(ev_t1[0], stream));
-        // every rank ends the run with the whole ensemble's log-posteriors and accepted counters (get_state is then the
-        // same on all ranks), and with the ensemble-wide accepted counts per step
-        NCCL_TRY(rccl->GroupStart());
-        for (int c = 0; c < 2; ++c)
-        {
-            if (!full_fn && !compact)  // (the exchanges of the other schemes carry the log-posteriors along)
-                NCCL_TRY(rccl->AllGather(d_logp + (size_t)c * n + shard_begin, d_logp + (size_t)c * n, (size_t)shard_count, RcclType<T>::value, comm, stream));
-            NCCL_TRY(rccl->AllGather(d_nacc + (size_t)c * n + shard_begin, d_nacc + (size_t)c * n, (size_t)shard_count, ncclUint32, comm, stream));
-        }
-        NCCL_TRY(rccl->AllReduce(d_acc, d_acc, (size_t)total, ncclUint32, ncclSum, comm, stream));
-        NCCL_TRY(rccl->GroupEnd());
+        if ((rc = xchg.finish_run(d_acc, total))) return rc;
         HIP_TRY(hipStreamSynchronize(stream));
         float run_ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&run_ms, ev_t0[0], ev_t1[0]));
-        {
-            float ms = 0.f;
-            double sum = 0.0;
-            for (int k = 0; k < samples; ++k)
-            {
-                HIP_TRY(hipEventElapsedTime(&ms, ev_x[2 * k], ev_x[2 * k + 1]));
-                sum += ms;
-            }
-            // (half-step scheme: the sampled exchange is the red one, the black one moves as much)
-            exchange_us_per_step = samples ? sum / samples * 1e3 * (full_fn ? 1.0 : 2.0) : 0.0;
-        }
-        xchg_bytes_per_step = xbytes / (double)total;
-        xchg_cap_slots = compact ? (int64_t)cap : 0;
+        if ((rc = xchg.exchange_us_per_step(win.samples, &exchange_us_per_step))) return rc;
+        xchg_bytes_per_step = win.bytes_per_step();
+        xchg_rollbacks = win.rollbacks;
+        xchg_cap_slots = win.cap_slots();
         // (full-step scheme: the next run re-primes, the red records of other ranks' walkers are per step anyway)
         return finish_run(total, run_ms, full_fn == nullptr, accepted_per_step, tp1, tp2);
+    }
+
+    // The two blocks the host loops of run_trickle and run_into_device_chain share (ChunkWindow, run_plan.hpp): the next
+    // chunk of `now` steps, enqueued between the two events of its slot ...
+    int enqueue_chunk(ChunkWindow& win, int64_t now)
+    {
+        const int e = win.event_slot(win.next_chunk);
+        HIP_TRY(hipEventRecord(ev_t0[e], stream));
+        if (const int rc = enqueue_steps(now)) return rc;
+        HIP_TRY(hipEventRecord(ev_t1[e], stream));
+        win.enqueued(now);
+        return MCMCPP_HIP_OK;
+    }
+    // ... and the wait for the oldest chunk in flight, whose GPU time joins *launch_ms
+    int wait_for_oldest_chunk(const ChunkWindow& win, double* launch_ms)
+    {
+        const int e = win.event_slot(win.oldest);
+        float ms = 0.f;
+        HIP_TRY(hipEventSynchronize(ev_t1[e]));
+        HIP_TRY(hipEventElapsedTime(&ms, ev_t0[e], ev_t1[e]));
+        *launch_ms += ms;
+        return MCMCPP_HIP_OK;
     }
 
     // The chain path of the full-step kernels: the launches forward stored steps into the pinned ring (or into chain_out
@@ -962,11 +821,7 @@ public:
                 }
         };
         auto process_oldest = [&]() -> int {
-            const int e = win.event_slot(win.oldest);
-            float ms = 0.f;
-            HIP_TRY(hipEventSynchronize(ev_t1[e]));
-            HIP_TRY(hipEventElapsedTime(&ms, ev_t0[e], ev_t1[e]));
-            *launch_ms += ms;
+            if (const int rc = wait_for_oldest_chunk(win, launch_ms)) return rc;
             copy_out(win.process_oldest(), win.all_enqueued());
             publish_stored(win.copied);
             return MCMCPP_HIP_OK;
@@ -979,12 +834,7 @@ public:
                 const int rc = process_oldest();
                 if (rc) return rc;
             }
-            const int e = win.event_slot(win.next_chunk);
-            HIP_TRY(hipEventRecord(ev_t0[e], stream));
-            const int rc = enqueue_steps(now);
-            if (rc) return rc;
-            HIP_TRY(hipEventRecord(ev_t1[e], stream));
-            win.enqueued(now);
+            if (const int rc = enqueue_chunk(win, now)) return rc;
         }
         // What the launches do not forward: the run's last stored step.  Its download is queued now, behind the last
         // launch, so that it runs while the host still copies out the steps before it.
@@ -1019,11 +869,7 @@ public:
         }
         DeviceWindow win(n_saved, interval, cp);
         auto process_oldest = [&]() -> int {
-            const int e = win.event_slot(win.oldest);
-            float ms = 0.f;
-            HIP_TRY(hipEventSynchronize(ev_t1[e]));
-            HIP_TRY(hipEventElapsedTime(&ms, ev_t0[e], ev_t1[e]));
-            *launch_ms += ms;
+            if (const int rc = wait_for_oldest_chunk(win, launch_ms)) return rc;
             publish_stored(win.process_oldest().to);
             return MCMCPP_HIP_OK;
         };
@@ -1032,11 +878,7 @@ public:
             while (win.must_process_oldest_first())
                 if (const int rc = process_oldest()) return rc;
             const int64_t now = win.next_length();
-            const int e = win.event_slot(win.next_chunk);
-            HIP_TRY(hipEventRecord(ev_t0[e], stream));
-            if (const int rc = enqueue_steps(now)) return rc;
-            HIP_TRY(hipEventRecord(ev_t1[e], stream));
-            win.enqueued(now);
+            if (const int rc = enqueue_chunk(win, now)) return rc;
         }
         while (win.in_flight())
             if (const int rc = process_oldest()) return rc;
@@ -1085,7 +927,7 @@ public:
         HIP_TRY(hipSetDevice(device));
         half_steps = 2 * steps_done;
         records_valid = false;
-        return write_ctl(0);  // repositions the stream and re-primes the draw records of the next two half-steps
+        return write_ctl(half_steps, 0);  // repositions the stream and re-primes the draw records of the next two half-steps
     }
 
     int reset_counters() override
@@ -1257,32 +1099,6 @@ private:
         return MCMCPP_HIP_OK;
     }
 
-    // d_snap <- everything a repeated chunk of a split run must find as this one found it (cur_pos, cur_logp: the buffers
-    // that hold the ensemble now)
-    int snapshot(const T* cur_pos, const T* cur_logp)
-    {
-        HIP_TRY(hipMemcpyAsync(d_snap, cur_pos, snap.logp, hipMemcpyDeviceToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(d_snap + snap.logp, cur_logp, sizeof(T) * (size_t)W, hipMemcpyDeviceToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(d_snap + snap.nacc, d_nacc, sizeof(uint32_t) * (size_t)W, hipMemcpyDeviceToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(d_snap + snap.diag, d_diag, sizeof(Diag), hipMemcpyDeviceToDevice, stream));
-        return MCMCPP_HIP_OK;
-    }
-
-    // ... and back -- into both buffers, so that the repeated chunk may start at buffer 0 like a run does
-    int rollback()
-    {
-        HIP_TRY(hipMemcpyAsync(d_pos, d_snap, snap.logp, hipMemcpyDeviceToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(d_logp, d_snap + snap.logp, sizeof(T) * (size_t)W, hipMemcpyDeviceToDevice, stream));
-        if (full_fn)
-        {
-            HIP_TRY(hipMemcpyAsync(d_pos_alt, d_snap, snap.logp, hipMemcpyDeviceToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(d_logp + W, d_snap + snap.logp, sizeof(T) * (size_t)W, hipMemcpyDeviceToDevice, stream));
-        }
-        HIP_TRY(hipMemcpyAsync(d_nacc, d_snap + snap.nacc, sizeof(uint32_t) * (size_t)W, hipMemcpyDeviceToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(d_diag, d_snap + snap.diag, sizeof(Diag), hipMemcpyDeviceToDevice, stream));
-        return MCMCPP_HIP_OK;
-    }
-
     // RunInfo used outside run(): the chain bound for half_step_async (if any), no per-step counters
     int upload_idle_run_info()
     {
@@ -1340,29 +1156,35 @@ private:
         return a;
     }
 
-    // device StepCtl[0] <- {stream position of half-step `half_steps`, counters}; half_steps must be even
-    // step_in_run > 0 (a chunk of a split run being repeated): the counters the kernels keep instead of dividing follow
-    int write_ctl(uint64_t step_in_run, int32_t interval = 1)
+    // the engine state of chain k in front of half-step h (a half-step draws 3 numbers per walker of its colour)
+    U128 engine_state_before(uint64_t h, int k = 0) const
     {
-        const Affine128 j = pcg_jump(inc, (unsigned __int128)3 * (unsigned)n * (unsigned __int128)half_steps);
+        return apply(pcg_jump(inc, (unsigned __int128)3 * (unsigned)n * (unsigned __int128)h), state0_of[k]);
+    }
+
+    // device StepCtl[0] <- {stream position of half-step `at`, counters}; `at` must be even (the host's half_steps, or -- a
+    // chunk of a split run being repeated -- where that chunk starts)
+    // step_in_run > 0 (such a chunk): the counters the kernels keep instead of dividing follow
+    int write_ctl(uint64_t at, uint64_t step_in_run, int32_t interval = 1)
+    {
         // the draw records of the next red and the next black half-step (afterwards the launches keep them going):
         // unless the launches of the previous call left exactly these behind
-        const bool refill = !(records_valid && records_step == (half_steps >> 1) && (!full_fn || records_partner2));
+        const bool refill = !(records_valid && records_step == (at >> 1) && (!full_fn || records_partner2));
         for (int k = 0; k < K; ++k)
         {
             StepCtl* c = K > 1 ? &h_pinned->chain_ctl[k] : &h_pinned->ctl;
-            c->state = apply(j, state0_of[k]);
+            c->state = engine_state_before(at, k);
             const U128 state1 = apply(half_jump, c->state);
             c->state2 = apply(half_jump, state1);
-            c->half_step = half_steps;
+            c->half_step = at;
             c->step_in_run = step_in_run;
             c->chain_slot = (long long)(step_in_run / (uint64_t)interval);
             c->save_phase = (uint32_t)(step_in_run % (uint64_t)interval);
             c->partial_slot = (uint32_t)(step_in_run % (uint64_t)plan.partial_slots);
-            HIP_TRY(hipMemcpyAsync(ctl_of(k) + (half_steps & 1), c, sizeof(StepCtl), hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(ctl_of(k) + (at & 1), c, sizeof(StepCtl), hipMemcpyHostToDevice, stream));
             if (refill)
             {
-                const int parity = (int)((half_steps >> 1) & 1);  // the buffer the coming ensemble step reads
+                const int parity = (int)((at >> 1) & 1);  // the buffer the coming ensemble step reads
                 HalfStepArgs<T> fr = make_args(0, parity), fb = make_args(1, parity);
                 fr.draws = fb.draws = d_draws + (size_t)k * 4 * (size_t)n;  // (the chain's own records; the tables are shared)
                 launch_fill_draws(fr, c->state, nullptr, stream);
@@ -1373,7 +1195,7 @@ private:
         if (refill)
         {
             records_valid = true;
-            records_step = half_steps >> 1;
+            records_step = at >> 1;
             records_partner2 = full_fn != nullptr;
         }
         HIP_TRY(hipStreamSynchronize(stream));
@@ -1527,18 +1349,6 @@ private:
 
     mcmcpp_hip_config cfg;
     Knobs knobs;
-    const Rccl* rccl = nullptr;  // split ensembles only
-    ncclComm_t comm = nullptr;
-    bool own_comm = false;
-    // split ensembles of more than one rank, exchanging moved rows only (exchange_kernels.hpp)
-    DeviceBuffer<char> d_xblocks;     // [comm_world][block]: this rank's block and, behind the all-gather, everybody's
-    DeviceBuffer<uint32_t> d_seen;    // [W]: a walker's accepted counter as of the last exchange (own slice)
-    DeviceBuffer<XStats> d_xstats;
-    DeviceBuffer<char> d_snap;        // positions | log-posteriors | counters | diagnostics in front of the chunk in hand
-    struct { size_t logp, nacc, diag; } snap = {};  // byte offsets into d_snap (the positions are at 0)
-    uint32_t xcap_learned = 0;        // the slot bound the last run ended with
-    PinnedBuffer<char> h_split_stage; // split ensembles: pinned staging of stored steps
-    std::vector<Event> ev_x;          // split ensembles: events around a sample of exchanges
     const LaunchTable<T>* table = nullptr;
     StepPlan plan;  // which kernels step this handle, their launch geometry and what follows from it (step_plan.hpp)
     typename LaunchTable<T>::HalfStepFn half_fn = nullptr;
@@ -1563,7 +1373,6 @@ private:
     int chain_params_stride = 0;
     StepCtl* d_ctl = nullptr;
     RunInfo* d_run = nullptr;
-    uint64_t* d_status = nullptr;
     DrawRec<T>* d_draws = nullptr;
     DeviceBuffer<DrawRec<T>> d_draws_batch;  // [batch_draws][2][n]: records made ahead of the matrix-core full-step launches
     DeviceBuffer<Affine128> d_step_jump;     // [batch_draws]
@@ -1573,7 +1382,7 @@ private:
     bool records_valid = false, records_partner2 = false, run_info_idle = false;
     uint64_t records_step = 0;
     PinnedBuffer<PinnedScratch> h_pinned;
-    U128 state0, inc;
+    U128 inc;
     U128 state0_of[kMaxChains];  // per chain (seed + k)
     int K = 1;                   // independent ensembles stepped by one launch
     Affine128 half_jump;
@@ -1582,6 +1391,9 @@ private:
     uint64_t half_steps = 0, enq_step = 0;
     void* bound_chain = nullptr;
     int64_t bound_slots = 0;
+    // a rank of a split ensemble: the communicator and everything only split runs use (declared last: it goes first, the
+    // communicator in front of every buffer)
+    SplitExchange<T> xchg;
 };
 
 int check_config(const mcmcpp_hip_config* c, std::string& err)

@@ -2,9 +2,12 @@
 // must wait, where a sub-chunk lands in the caller's array, what a destination in device memory changes (run_device: no ring,
 // no staging, what wait_stored may hear), the pieces of a differential-evolution run and the sub-chunks of a batch run, where
 // a split run cuts so that every rank cuts alike, and the slot bound of its exchange blocks.  Pure functions and a few small
-// value types over plain numbers.  No HIP header: this file compiles with the host compiler alone, and tests/test_run_plan.py,
-// tests/test_device_chain_plan.py and tests/test_run_entry.py check the schedules there, case by case.  The samplers keep
-// every HIP and RCCL call and ask here for the numbers.
+// value types over plain numbers: ChainPlan, PiecePlan, and the windows that keep the state of a run's host loop --
+// ChunkWindow (what the next two share), DeviceWindow, TrickleWindow, and SplitWindow, the whole schedule of a split run
+// (chunks, slot bound, roll-backs, staging, sampled exchanges, statistics).  No HIP header: this file compiles with the
+// host compiler alone, and tests/test_run_plan.py, tests/test_device_chain_plan.py and tests/test_run_entry.py check the
+// schedules there, case by case and over simulated runs.  The samplers keep every HIP and RCCL call and ask here for the
+// numbers.
 #pragma once
 
 #include <cstddef>
@@ -116,30 +119,40 @@ inline ChainPlan plan_chain(const ChainRequest& r, bool chain_out_pinned)
 // Chain k's stored steps are the k-th run of n_saved steps of the caller's array, as in host memory
 inline size_t device_chain_offset(size_t step_bytes, int64_t n_saved, int k) { return step_bytes * (size_t)n_saved * (size_t)k; }
 
-// Stored step k is written, whole, by the launches of ensemble step (k + 1) * interval - 1: it is complete in the caller's
-// array when that step has finished.  The host enqueues chunks of steps, at most two in flight (the chunks' events rotate
-// over four slots), and announces what a finished chunk completed.  Nothing is left behind the final synchronisation.
-struct DeviceWindow
+// What the two windows below share: a run of n_saved * interval ensemble steps is enqueued in chunks, a chunk's end is kept
+// until its completion has been processed, and the chunks' events rotate over four slots.
+struct ChunkWindow
 {
     int64_t n_saved, interval, chunk_steps;
-    int64_t enq = 0, announced = 0;      // ensemble steps enqueued; stored steps announced to wait_stored
+    int64_t enq = 0;                     // ensemble steps enqueued
     int64_t chunk_end[4] = {0, 0, 0, 0};
     int64_t next_chunk = 0, oldest = 0;  // chunks enqueued / chunks whose completion has been processed
 
-    DeviceWindow(int64_t n_saved_, int64_t interval_, const ChainPlan& p) : n_saved(n_saved_), interval(interval_), chunk_steps(p.chunk_steps) {}
+    ChunkWindow(int64_t n_saved_, int64_t interval_, int64_t chunk_steps_) : n_saved(n_saved_), interval(interval_), chunk_steps(chunk_steps_) {}
 
     int64_t total() const { return n_saved * interval; }
     bool all_enqueued() const { return enq == total(); }
     bool in_flight() const { return next_chunk > oldest; }
     static int event_slot(int64_t chunk) { return (int)(chunk & 3); }
-    int64_t next_length() const { return total() - enq < chunk_steps ? total() - enq : chunk_steps; }
-    bool must_process_oldest_first() const { return next_chunk - oldest >= 2; }
     void enqueued(int64_t now)
     {
         enq += now;
         chunk_end[event_slot(next_chunk)] = enq;
         ++next_chunk;
     }
+};
+
+// Stored step k is written, whole, by the launches of ensemble step (k + 1) * interval - 1: it is complete in the caller's
+// array when that step has finished.  The host enqueues chunks of steps, at most two in flight (the chunks' events rotate
+// over four slots), and announces what a finished chunk completed.  Nothing is left behind the final synchronisation.
+struct DeviceWindow : ChunkWindow
+{
+    int64_t announced = 0;  // stored steps announced to wait_stored
+
+    DeviceWindow(int64_t n_saved_, int64_t interval_, const ChainPlan& p) : ChunkWindow(n_saved_, interval_, p.chunk_steps) {}
+
+    int64_t next_length() const { return total() - enq < chunk_steps ? total() - enq : chunk_steps; }
+    bool must_process_oldest_first() const { return next_chunk - oldest >= 2; }
     // the oldest chunk has finished: the stored steps it completed
     StoredRange process_oldest()
     {
@@ -156,20 +169,14 @@ struct DeviceWindow
 // host enqueues chunks of steps, stays one chunk ahead of the one it waits for, hands out whatever has become complete and
 // never lets the launches run into a slot it has not copied yet.  The run's last stored step has no launches behind it:
 // it is fetched at the end (tail).
-struct TrickleWindow
+struct TrickleWindow : ChunkWindow
 {
-    int64_t n_saved, interval, ring, chunk_steps;
+    int64_t ring;
     bool direct;
-    int64_t enq = 0, copied = 0;         // ensemble steps enqueued; stored steps handed to the caller
-    int64_t chunk_end[4] = {0, 0, 0, 0};
-    int64_t next_chunk = 0, oldest = 0;  // chunks enqueued / chunks whose completion has been processed
+    int64_t copied = 0;  // stored steps handed to the caller
 
-    TrickleWindow(int64_t n_saved_, int64_t interval_, const ChainPlan& p) : n_saved(n_saved_), interval(interval_), ring(p.ring), chunk_steps(p.chunk_steps), direct(p.direct) {}
+    TrickleWindow(int64_t n_saved_, int64_t interval_, const ChainPlan& p) : ChunkWindow(n_saved_, interval_, p.chunk_steps), ring(p.ring), direct(p.direct) {}
 
-    int64_t total() const { return n_saved * interval; }
-    bool all_enqueued() const { return enq == total(); }
-    bool in_flight() const { return next_chunk > oldest; }
-    static int event_slot(int64_t chunk) { return (int)(chunk & 3); }
     int64_t ring_slot(int64_t stored_step) const { return stored_step & (ring - 1); }
 
     int64_t next_length() const
@@ -187,12 +194,6 @@ struct TrickleWindow
     bool must_process_oldest_before(int64_t now) const
     {
         return in_flight() && (next_chunk - oldest >= 2 || (!direct && enq + now > (copied + ring + 1) * interval));
-    }
-    void enqueued(int64_t now)
-    {
-        enq += now;
-        chunk_end[event_slot(next_chunk)] = enq;
-        ++next_chunk;
     }
     // the oldest chunk has finished: the stored steps that are fully forwarded now and were not handed out before
     StoredRange process_oldest()
@@ -303,7 +304,8 @@ inline int64_t split_stage_slots(size_t step_bytes, int64_t n_saved)
     return slots;
 }
 // How far the chunk that starts at step s0 goes.  Exchanging moved rows only: 16 steps while the slot bound is being
-// learned, compact_chunk otherwise (the host looks at the overflow flag at the end of a chunk).
+// learned, compact_chunk otherwise (the host looks at the overflow flag at the end of a chunk).  Some rank stores: until
+// the staging buffer is full.
 inline int64_t split_chunk_length(int64_t total, int64_t s0, bool compact, bool learning, long compact_chunk, bool any_rank_stores, int32_t interval,
                                   int64_t stage_slots)
 {
@@ -347,4 +349,106 @@ inline double split_bytes_whole(int64_t len, bool full_step, int comm_world, int
 {
     return (double)len * (double)(comm_world - 1) * (double)shard_count * 2.0 * (double)((size_t)dims + (full_step ? 1 : 0)) * elem_size;
 }
+
+// The schedule of one split run, as the host loop of Sampler::run_split plays it.  The run proceeds in chunks of steps; the
+// host looks at the device only at the end of a chunk.  Exchanging moved rows only (`compact`), a chunk whose blocks
+// overflowed is tried again from its first step with blocks of cap_full slots, and the bound of the following chunks is
+// what the last one needed (split_next_cap) unless the knob sets it.  Stored steps go to a pinned staging buffer of
+// stage_slots slots and leave it behind a chunk that held.  A sample of at most kSplitMaxSamples exchanges is timed.
+// Every rank of a run builds the same window but for `stores`, and `stores` moves no chunk boundary.
+constexpr int kSplitMaxSamples = 32;
+
+struct SplitRequest
+{
+    int64_t total;               // ensemble steps of the run (> 0)
+    int32_t interval;
+    bool any_rank_stores, stores;  // some rank hands stored steps to its caller / this one does
+    int64_t stage_slots;         // split_stage_slots
+    bool compact;                // the exchanges carry moved rows only (StepPlan::compact_exchange)
+    uint32_t cap_full;           // a block that holds every walker of an exchange
+    long comm_compact_cap, comm_compact_chunk;  // the knobs
+    uint32_t cap_learned;        // the bound the handle's last run ended with, or 0
+    // what split_bytes_* need
+    bool full_step;
+    int comm_world, shard_count, dims;
+    size_t elem_size;
+    size_t (*block_bytes)(uint32_t cap, int dims, size_t elem_size);  // xblock_bytes (exchange_plan.hpp)
+};
+
+struct SplitWindow
+{
+    SplitRequest r;
+    uint32_t cap_set, cap, cap_learned;  // the knob's bound or 0; the bound of the chunk in hand; the bound to keep for the next run
+    bool learning;                       // first chunk of a run that knows no bound: short, whole-slice blocks
+    int64_t sample_stride;
+    int64_t s0 = 0, len = 0;             // the chunk in hand: its first step, its length
+    int samples = 0, samples_before = 0; // exchanges sampled so far / in front of the chunk in hand
+    int64_t staged = 0, handed = 0;      // stored steps copied to staging / handed to the caller
+    double xbytes = 0.0;                 // bytes this rank received in the exchanges of the chunks that held
+    int64_t rollbacks = 0;               // chunk tries that overflowed
+
+    explicit SplitWindow(const SplitRequest& q)
+        : r(q), cap_set(split_cap_set(q.comm_compact_cap, q.cap_full)), cap_learned(q.cap_learned), learning(q.compact && !cap_set && q.cap_learned == 0),
+          sample_stride(q.total > kSplitMaxSamples ? q.total / kSplitMaxSamples : 1)
+    {
+        cap = split_first_cap(r.compact, cap_set, cap_learned, r.cap_full);
+        len = chunk_length();
+    }
+
+    bool done() const { return s0 == r.total; }
+    int64_t first() const { return s0; }
+    int64_t end() const { return s0 + len; }
+
+    // ---- the steps of the chunk in hand
+    // the sample slot of step s's (red) exchange, or -1: the exchange is not timed
+    int take_sample(int64_t s) { return samples < kSplitMaxSamples && s % sample_stride == 0 ? samples++ : -1; }
+    bool stores_step(int64_t s) const { return r.stores && (s + 1) % r.interval == 0; }
+    // the staging slot of the step that is stored next
+    int64_t take_stage_slot() { return staged++ - handed; }
+
+    // ---- the end of a try of the chunk in hand
+    // Some block overflowed: the same steps again with blocks nothing can overflow; what the failed try sampled and staged is
+    // forgotten.  Returns the step in front of which the stream and the counters have to be put back.
+    int64_t chunk_overflowed()
+    {
+        ++rollbacks;
+        samples = samples_before;
+        staged = handed;
+        cap = r.cap_full;
+        return s0;
+    }
+    // The chunk held (max_count: the most moved walkers any rank packed in one of its exchanges; whole slices: unused): its
+    // bytes count, the next chunk's bound is what this one needed, and the next chunk is in hand.
+    void chunk_held(uint32_t max_count)
+    {
+        if (r.compact)
+        {
+            xbytes += split_bytes_compact(len, r.full_step, r.comm_world, r.block_bytes(cap, r.dims, r.elem_size));
+            if (!cap_set) cap_learned = split_next_cap(max_count, r.cap_full);
+            cap = cap_set ? cap_set : cap_learned;
+            learning = false;
+        }
+        else
+            xbytes += split_bytes_whole(len, r.full_step, r.comm_world, r.shard_count, r.dims, r.elem_size);
+        s0 += len;
+        samples_before = samples;
+        len = chunk_length();
+    }
+    // Behind chunk_held: the staged steps the host hands to its caller now (it waits for the stream first), or none.  They
+    // leave when the staging buffer is full, at the end of the run, and -- the host has waited for the chunk anyway -- behind
+    // every chunk of moved rows.
+    StoredRange hand_out()
+    {
+        const StoredRange out = {handed, staged > handed && (staged - handed == r.stage_slots || done() || r.compact) ? staged : handed};
+        handed = out.to;
+        return out;
+    }
+
+    // ---- the end of the run
+    double bytes_per_step() const { return xbytes / (double)r.total; }
+    int64_t cap_slots() const { return r.compact ? (int64_t)cap : 0; }
+
+private:
+    int64_t chunk_length() const { return split_chunk_length(r.total, s0, r.compact, learning, r.comm_compact_chunk, r.any_rank_stores, r.interval, r.stage_slots); }
+};
 }  // namespace mcmcpp

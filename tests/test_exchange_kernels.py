@@ -265,17 +265,17 @@ def _body(text, head):
 
 
 def test_the_exchange_arithmetic_has_one_copy():
-    """The three kernels, exchange_compact and exchange_reset call exchange_plan.hpp; none of them states lanes per row, pieces or
+    """The three kernels, SplitExchange's exchange_compact and exchange_reset call exchange_plan.hpp; none of them states lanes per row, pieces or
     a grid itself.  (Only their own bodies are searched: the same idioms are at home elsewhere in these files.)"""
     kernels = open(os.path.join(CSRC, "exchange_kernels.hpp")).read()
-    host = open(os.path.join(CSRC, "mcmcpp_hip.hip")).read()
+    host = open(os.path.join(CSRC, "split_exchange.hpp")).read()  # (SplitExchange: the exchange side of a split handle)
     assert '#include "exchange_plan.hpp"' in kernels
     bodies = {
         "sync_seen": (_body(kernels, "exchange_sync_seen_kernel("), []),
         "pack": (_body(kernels, "exchange_pack_kernel("), ["exchange_row_pieces(dims, sizeof(T))", "exchange_lanes_per_row(pieces)"]),
         "scatter": (_body(kernels, "exchange_scatter_kernel("), ["exchange_row_pieces(dims, sizeof(T))", "exchange_lanes_per_row(pieces)",
                                                                  "exchange_scatter_rows_per_block(lpr)"]),
-        "exchange_compact": (_body(host, "int exchange_compact("), ["exchange_pack_blocks(colors * shard_count)", "exchange_scatter_grid(cap, D, sizeof(T), cfg.comm_world)",
+        "exchange_compact": (_body(host, "int exchange_compact("), ["exchange_pack_blocks(colors * shard_count)", "exchange_scatter_grid(cap, D, sizeof(T), world)",
                                                                     "dim3(kPackThreads)", "dim3(kScatterThreads)"]),
         "exchange_reset": (_body(host, "int exchange_reset("), ["exchange_sync_seen_blocks(shard_count)", "dim3(kSyncSeenThreads)"]),
     }
@@ -288,7 +288,7 @@ def test_the_exchange_arithmetic_has_one_copy():
     for used in ("exchange_pack_blocks(colors * shard_count)", "exchange_scatter_grid(cap, dims, sizeof(T), ranks)", "exchange_sync_seen_blocks(shard_count)"):
         assert used in shim, used
     hdrs = [line for line in open(os.path.join(CSRC, "Makefile")).read().split("\n") if line.startswith("HDRS")]
-    assert len(hdrs) == 1 and "exchange_plan.hpp" in hdrs[0].split()
+    assert len(hdrs) == 1 and "exchange_plan.hpp" in hdrs[0].split() and "split_exchange.hpp" in hdrs[0].split()
 
 
 def test_plan_constants(plan_exe):

@@ -8,10 +8,12 @@ run: the driver plays the host loop of Sampler::run_trickle with "process the ol
 
 The expected values were worked from the arithmetic run_whole / run_trickle / run_split held before it moved into the header
 (by hand; _earlier_trickle_chunks below is a transcription of that loop, kept as the second opinion of the sweep).  The header
-has to reproduce them.  fp64, one chain, graph_steps = 300 and a 32 MiB budget unless the case says otherwise."""
+has to reproduce them.  A split run's whole schedule is SplitWindow's: the driver plays Sampler::run_split through it, with the
+chunk tries that overflow and what each held chunk reports as the only inputs (split_sim, split_sweep).  fp64, one chain, graph_steps = 300 and a 32 MiB budget unless the case says otherwise."""
 import os
 import subprocess
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,10 +43,33 @@ def test_run_plan_header_includes_no_hip_header():
     assert includes == ["<cstddef>", "<cstdint>"]
 
 
+def _body(text, head):
+    """the braces that follow the one occurrence of `head` in `text`, and what they hold"""
+    assert text.count(head) == 1, head
+    at = text.index("{", text.index(head))
+    depth = 0
+    for i in range(at, len(text)):
+        depth += {"{": 1, "}": -1}.get(text[i], 0)
+        if depth == 0:
+            return text[at:i + 1]
+    raise AssertionError("unbalanced braces behind " + head)
+
+
 def test_the_sampler_holds_no_schedule_arithmetic():
     text = open(os.path.join(CSRC, "mcmcpp_hip.hip")).read()
     for gone in ("ring *= 2", "(ring - 2) / 2", "(copied + ring + 1)", "/ 8 + 64", "(size_t)256 << 20"):
         assert gone not in text, gone
+    # the exchange side of a split handle holds none of it either
+    exchange = open(os.path.join(CSRC, "split_exchange.hpp")).read()
+    for gone in ("/ 8 + 64", "(size_t)256 << 20", "% interval", "% sample_stride"):
+        assert gone not in exchange, gone
+    # run_split asks SplitWindow: no sampling or storing arithmetic, no staging bookkeeping, and the slot bound is never assigned
+    body = _body(text, "int run_split(")
+    assert "SplitWindow win(" in body
+    for gone in ("% interval", "% sample_stride", "staged - handed", "cap =", "cap_full;", "split_next_cap", "split_bytes_", "samples_before"):
+        assert gone not in body, gone
+    for used in ("win.chunk_overflowed()", "win.chunk_held(", "win.hand_out()", "win.take_sample(", "win.stores_step(", "win.take_stage_slot()"):
+        assert used in body, used
 
 
 # ---- simulated trickle runs ------------------------------------------------------------------------------------------------
@@ -269,6 +294,148 @@ def test_split_chunk_lengths(driver, args, want):
 ])
 def test_split_slot_bound(driver, args, want):
     assert _fields(driver("cap", **args)[0]) == want
+
+
+# ---- simulated split runs ---------------------------------------------------------------------------------------------------
+# (cap_full 200, 5 fp64 dimensions, 4 ranks: a block of 200 slots is 10 416 bytes, one of 192 slots 10 000, one of 128 slots 6 672, one of 64 slots 3 344)
+
+SPLIT_SIMS = [
+    # a learning run that stores every 3rd step into two staging slots; the second chunk overflows once
+    (dict(total=12, interval=3, compact=1, compact_chunk=4, stores=1, stage_slots=2, cap_full=200, overflow="1", max_counts="50,10"),
+     "C 0 6 200 | X 0 0 | X 1 1 | X 2 2 | S 2 0 | X 3 3 | X 4 4 | X 5 5 | S 5 1 | K 50 128 | H 0 2 | "
+     "C 6 4 128 | X 6 6 | X 7 7 | X 8 8 | S 8 0 | X 9 9 | R 6 | "
+     "C 6 4 200 | X 6 6 | X 7 7 | X 8 8 | S 8 0 | X 9 9 | K 10 128 | H 2 3 | "
+     "C 10 2 128 | X 10 10 | X 11 11 | S 11 0 | K 10 128 | H 3 4 | "
+     "end rollbacks=1 cap_slots=128 cap_to_keep=128 samples=12 bytes_per_step=29376"),   # (6 x 10416 + 4 x 10416 + 2 x 6672) x 3 / 12
+    # held, repeated, held, repeated: a bound of the last run, nothing stored, half-step scheme (two exchanges per step)
+    (dict(total=10, compact=1, compact_chunk=3, learned=64, cap_full=200, full_step=0, overflow="1,4", max_counts="0,100,0,0"),
+     "C 0 3 64 | X 0 0 | X 1 1 | X 2 2 | K 0 64 | C 3 3 64 | X 3 3 | X 4 4 | X 5 5 | R 3 | C 3 3 200 | X 3 3 | X 4 4 | X 5 5 | K 100 192 | "
+     "C 6 3 192 | X 6 6 | X 7 7 | X 8 8 | K 0 64 | C 9 1 64 | X 9 9 | R 9 | C 9 1 200 | X 9 9 | K 0 64 | "
+     "end rollbacks=2 cap_slots=64 cap_to_keep=64 samples=10 bytes_per_step=%.17g" % ((3 * 3344 + 3 * 10416 + 3 * 10000 + 1 * 10416) * 2 * 3 / 10)),
+    # whole slices, another rank stores: the chunks end where that rank's staging buffer is full, this one stages nothing
+    (dict(total=70, interval=7, any_rank_stores=1, stage_slots=4, shard_count=100),
+     "C 0 28 4096 | " + "".join("X %d %d | " % (k, 2 * k) for k in range(14)) + "K 0 4096 | C 28 28 4096 | " + "".join("X %d %d | " % (k, 2 * k) for k in range(14, 28))
+     + "K 0 4096 | C 56 14 4096 | " + "".join("X %d %d | " % (k, 2 * k) for k in range(28, 32)) + "K 0 4096 | "
+     "end rollbacks=0 cap_slots=0 cap_to_keep=0 samples=32 bytes_per_step=28800"),     # 3 x 100 x 2 x (5 + 1) x 8
+]
+
+
+@pytest.mark.parametrize("args,want", SPLIT_SIMS, ids=["learning_stores_one_repeat", "mixed_held_and_repeated", "whole_slices_another_rank_stores"])
+def test_split_window_simulated_runs(driver, args, want):
+    assert driver("split_sim", **args) == [want]
+
+
+def _next_cap(max_count, cap_full):
+    """split_next_cap, from the arithmetic run_split held: what the chunk needed, an eighth and 64 more, in whole 64s"""
+    want = (max_count + max_count // 8 + 64 + 63) // 64 * 64
+    return np.minimum(want, cap_full)
+
+
+def _block_bytes(cap, dims, elem):
+    a16 = lambda b: (b + 15) // 16 * 16
+    return 16 + a16(cap * 4) + a16(cap * elem) + a16(cap * dims * elem)
+
+
+def test_split_window_over_a_sweep(driver):
+    """Every schedule of: 1..60 steps x interval 1..7 (total // interval stored steps) x compact_chunk 3, 4, 7, 256 x 1, 2, 4 or
+    n_saved staging slots x {nobody stores, this rank stores, only another rank does} x {whole slices; moved rows with the bound set
+    by the knob or learned, and the first try of no chunk, of every chunk, of every 2nd or of every 3rd chunk overflowing}.  The
+    driver plays each through SplitWindow as run_split does and writes rows of 12 integers (run_plan_cases.cpp: sweep_one); the
+    properties are checked here over all of them at once."""
+    exe = os.path.join(BUILD, "run_plan_cases")  # (built by the fixture; this case's output is binary)
+    rows = np.frombuffer(subprocess.run([exe, "split_sweep"], capture_output=True, check=True).stdout, dtype=np.int32).reshape(-1, 12).astype(np.int64)
+    kind, sid = rows[:, 0], rows[:, 1]
+    H, E = rows[kind == 0], rows[kind == 3]
+    S = len(H)
+    assert (H[:, 1] == np.arange(S)).all() and (E[:, 1] == np.arange(S)).all()
+    total, interval, compact, chunk, slots, any_stores, stores, knob, pattern, cap_full = (H[:, c] for c in range(2, 12))
+    # the sweep is the one the docstring states: whole slices 60 x 7 x (1 + 2 x 4), moved rows 60 x 7 x 8 x 4 x (1 + 2 x 4)
+    assert S == 60 * 7 * 9 + 60 * 7 * 8 * 4 * 9
+    assert set(zip(total, interval)) == {(t, i) for t in range(1, 61) for i in range(1, 8)}
+    assert set(chunk[compact == 1]) == {3, 4, 7, 256} and set(pattern[compact == 1]) == {0, 1, 2, 3} and set(knob[compact == 1]) == {0, 96}
+    assert set(pattern[compact == 0]) == {0} and set(cap_full) == {200}
+    n_stored = np.where(stores == 1, total // interval, 0)
+    assert set(slots[any_stores == 1] - np.maximum(total // interval, 1)[any_stores == 1]) >= {0} and {1, 2, 4} <= set(slots)
+
+    T = rows[kind == 1]
+    t_sid, s0, length, cap, failed, smp_before, smp_after, staged, left, max_count, cap_next = (T[:, c] for c in range(1, 12))
+    end = s0 + length
+    same = t_sid[1:] == t_sid[:-1]  # a try and the next one belong to the same run
+    assert (length >= 1).all() and (end <= total[t_sid]).all()
+
+    # the held chunks cover [0, total) exactly once, in order
+    held = failed == 0
+    h_sid, h_s0, h_end = t_sid[held], s0[held], end[held]
+    first = np.r_[True, h_sid[1:] != h_sid[:-1]]
+    last = np.r_[h_sid[1:] != h_sid[:-1], True]
+    assert (h_sid[first] == np.arange(S)).all(), "every run has held chunks, and the runs come in order"
+    assert (h_s0[first] == 0).all() and (h_end[last] == total).all()
+    assert (h_s0[1:] == h_end[:-1])[~first[1:]].all()
+
+    # a repeated try covers the same steps as the failed one, with blocks of cap_full slots, and holds
+    f = np.flatnonzero(failed == 1)
+    assert len(f) > 100000 and (compact[t_sid[f]] == 1).all()
+    assert same[f].all() and (s0[f + 1] == s0[f]).all() and (length[f + 1] == length[f]).all() and (cap[f + 1] == cap_full[t_sid[f]]).all() and (failed[f + 1] == 0).all()
+    # ... the sample count is restored by it (and never exceeds 32), nothing of the failed try stays staged
+    assert (smp_before[f + 1] == smp_before[f]).all() and (smp_after[f + 1] == smp_after[f]).all()
+    assert (smp_after <= 32).all() and (smp_after >= smp_before).all() and (left[f] == 0).all()
+    h = np.flatnonzero(held)
+    carries = h[:-1][t_sid[h[:-1] + 1] == t_sid[h[:-1]]]
+    assert (smp_before[carries + 1] == smp_after[carries]).all()
+    stride = np.where(total > 32, total // 32, 1)
+    assert (E[:, 6] == np.minimum(32, (total + stride - 1) // stride)).all()
+    # rollbacks counts the failed tries: those the pattern asked for
+    assert (E[:, 2] == np.bincount(t_sid[f], minlength=S)).all()
+    n_chunks = np.bincount(h_sid, minlength=S)
+    assert (E[:, 2] == np.where(pattern > 0, n_chunks // np.maximum(pattern, 1), 0)).all()
+
+    # the bound: whole slices never use one; moved rows start with the set bound, or -- learning -- with whole-slice blocks and
+    # at most 16 steps; behind a held chunk it is the set bound or split_next_cap of what the chunk reported
+    first_try = np.r_[True, ~same]
+    assert (cap[compact[t_sid] == 0] == 200).all() and (E[:, 3][compact == 0] == 0).all()
+    learning_run = (compact == 1) & (knob == 0)
+    assert (cap[first_try] == np.where(compact == 0, 200, np.where(knob > 0, 96, 200))[t_sid[first_try]]).all()
+    learning = (s0 == 0) & learning_run[t_sid]  # (the tries of the first chunk of a run that knows no bound)
+    assert (length[learning] <= 16).all() and (cap[learning] == 200).all()
+    later = (compact[t_sid] == 1) & ~learning
+    assert (length[later] <= chunk[t_sid][later]).all()
+    hc = held & (compact[t_sid] == 1)
+    assert (cap_next[hc] == np.where(knob[t_sid[hc]] > 0, 96, _next_cap(max_count[hc], 200))).all()
+    assert (cap[carries + 1] == cap_next[carries]).all(), "the next chunk runs with the bound the held one left"
+    assert (cap_next[f] == 200).all()
+    last_try = np.r_[~same, True]
+    assert (E[:, 3][compact == 1] == cap_next[last_try][compact == 1]).all()                                # cap_slots
+    assert (E[:, 4][learning_run] == _next_cap(max_count[last_try], 200)[learning_run]).all()              # the bound to keep
+    assert (E[:, 4][~learning_run] == 0).all()
+
+    # staging: never more than stage_slots steps staged, nothing without `stores`, nothing left behind a chunk of moved rows
+    assert (staged <= slots[t_sid]).all() and (staged >= 0).all() and (staged[stores[t_sid] == 0] == 0).all()
+    assert (left[compact[t_sid] == 1] == 0).all() and (left < np.maximum(slots[t_sid], 1)).all()
+    # every stored step is handed out exactly once, in order, and only behind a held chunk that completed it
+    at = np.flatnonzero(kind == 2)
+    G = rows[at]
+    g_sid, g_from, g_to = G[:, 1], G[:, 2], G[:, 3]
+    g_first = np.r_[True, g_sid[1:] != g_sid[:-1]]
+    g_last = np.r_[g_sid[1:] != g_sid[:-1], True]
+    assert (np.unique(g_sid) == np.flatnonzero(n_stored > 0)).all()
+    assert (g_from[g_first] == 0).all() and (g_to[g_last] == n_stored[g_sid[g_last]]).all() and (g_to > g_from).all()
+    assert (g_from[1:] == g_to[:-1])[~g_first[1:]].all()
+    before = rows[at - 1]
+    assert (before[:, 0] == 1).all() and (before[:, 1] == g_sid).all() and (before[:, 5] == 0).all()
+    assert (g_to == (before[:, 2] + before[:, 3]) // interval[g_sid]).all() and (g_to - g_from <= slots[g_sid]).all()
+
+    # for a given any_rank_stores the cuts do not depend on whether this rank stores (the driver puts the two side by side)
+    mine, theirs = np.flatnonzero((any_stores == 1) & (stores == 1)), np.flatnonzero((any_stores == 1) & (stores == 0))
+    assert (theirs == mine + 1).all() and (H[mine][:, [2, 3, 4, 5, 6, 9, 10]] == H[theirs][:, [2, 3, 4, 5, 6, 9, 10]]).all()
+    cuts = [2, 3, 4, 5, 6, 7, 10, 11]
+    a, b = T[np.isin(t_sid, mine)][:, cuts], T[np.isin(t_sid, theirs)][:, cuts]
+    assert a.shape == b.shape and (a == b).all()
+
+    # bytes_per_step x total: the sum of split_bytes_* over the held chunks (4 ranks, 5 fp64 dimensions; full-step scheme when total is odd)
+    full = (total % 2)[h_sid]
+    assert (E[:, 7] == total % 2).all()
+    per_step = np.where(compact[h_sid] == 1, np.where(full == 1, 1, 2) * 3 * _block_bytes(cap[held], 5, 8), 3 * np.where(full == 1, 100, 200) * 2 * (5 + full) * 8)
+    assert (E[:, 5] == np.bincount(h_sid, weights=(h_end - h_s0) * per_step, minlength=S).astype(np.int64)).all()
 
 
 def test_split_bytes_received(driver):
