@@ -33,9 +33,13 @@
 //     mcmcpp_hip_register_calculator(1000, mcmcpp_hip_plugin_my_target_f64(), mcmcpp_hip_plugin_my_target_f32(), /*params*/ -1);
 //
 // after which `calc_id = 1000` (or a host Calculator class whose hipCalcId is 1000) selects it.
+//
+// An fp32 functor that takes a logarithm calls mcmcpp::glibc_logf (glibc_logf.hpp, included below) and its host twin the same
+// function through include/MCMCpp/Device/GlibcLogf.h: logf is one function on the host and another on the device.
 #pragma once
 
 #include "launch_build.hpp"
+#include "glibc_logf.hpp"  // (behind the HIP runtime header, which launch_build.hpp brings in)
 
 #define MCMCPP_HIP_PLUGIN_CALCULATOR(FUNCTOR_TEMPLATE, NAME)                                                     \
     extern "C" const void* mcmcpp_hip_plugin_##NAME##_f64(void)                                                   \
