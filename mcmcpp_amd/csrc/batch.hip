@@ -44,21 +44,14 @@ __global__ void __launch_bounds__(kBatchThreads) stretch_propose_kernel(const Ha
     const StepCtl ctl = *a.ctl_in;  // (wave-uniform)
     if (blockIdx.x == 0 && threadIdx.x == 0) hand_over<T>(a, ctl, *a.run, a.color, a.ctl_out);
 
-    const DrawRec<T>* recs = a.draws + ((size_t)a.draw_parity * 2 + (size_t)a.color) * (size_t)a.n;
-    DrawRec<T>* next = a.draws + ((size_t)(1 - a.draw_parity) * 2 + (size_t)a.color) * (size_t)a.n;
+    const DrawRec<T>* recs = a.draws + draw_buffer_index(a.draw_parity, a.color, a.n);
+    DrawRec<T>* next = a.draws + draw_buffer_index(1 - a.draw_parity, a.color, a.n);
     const DrawUse<T> rec(recs[lic]);
     T own[EPL], par[EPL];
     load_slice<T, EPL>(a.pos + (size_t)(half_base + lic) * a.dims, i0, a.dims, vec_ok, active, own);
     load_slice<T, EPL>(a.pos + (size_t)(other_base + (int)rec.partner) * a.dims, i0, a.dims, vec_ok, active, par);
-    // StretchMove.h:105-108  proposal = sel + z*(cur - sel)
     T p[EPL];
-#pragma unroll
-    for (int e = 0; e < EPL; ++e)
-    {
-        const T d = own[e] - par[e];
-        const T zd = rec.z * d;
-        p[e] = par[e] + zd;
-    }
+    stretch_propose(own, par, rec.z, p);
     if (active) store_slice<T, EPL>(prop + (size_t)li * a.dims, i0, a.dims, vec_ok, p);
 
     // the draws of this walker's next update (half-step + 2, base state ctl.state2): draw k by lane k of the group
@@ -68,13 +61,7 @@ __global__ void __launch_bounds__(kBatchThreads) stretch_propose_kernel(const Ha
         for (int k = sub; k < 3; k += LPW)
         {
             Affine128 j_a, j_b;
-            if (direct)
-                j_a = a.task_jump[3 * li + k];
-            else
-            {
-                j_a = a.jump_hi[li >> 8];
-                j_b = a.jump_lo[li & 255];
-            }
+            load_draw_jump<T>(a, direct, li, k, j_a, j_b);
             compute_draw<T>(a, ctl.state2, j_a, j_b, direct, k, next + li);
         }
     }
@@ -98,7 +85,7 @@ __global__ void __launch_bounds__(kBatchThreads) stretch_accept_kernel(const Hal
     const StepCtl ctl = *a.ctl_in;
     const RunInfo run = *a.run;
 
-    const DrawUse<T> rec(a.draws[((size_t)a.draw_parity * 2 + (size_t)a.color) * (size_t)a.n + lic]);
+    const DrawUse<T> rec(a.draws[draw_buffer_index(a.draw_parity, a.color, a.n) + lic]);
     T own[EPL], p[EPL];
     T* row = a.pos + (size_t)w * a.dims;
     load_slice<T, EPL>(prop + (size_t)lic * a.dims, i0, a.dims, vec_ok, active, p);
@@ -106,21 +93,10 @@ __global__ void __launch_bounds__(kBatchThreads) stretch_accept_kernel(const Hal
     const T lp_old = a.logp[w];
     const uint32_t nacc_old = a.n_accept[w];
 
-    // does this ensemble step go to the chain?  (EnsembleSampler.h:298-306: interval-1 unsaved, 1 saved)
-    long long save_slot = -1;
-    if (run.chain != nullptr && ctl.save_phase + 1u == (uint32_t)run.interval) save_slot = run.chain_slot_base + ctl.chain_slot;
+    const long long save_slot = stored_step_slot(run, ctl, true, false);  // (a batch run always saves by its control record)
     if (save_slot >= 0) load_slice<T, EPL>(row, i0, a.dims, vec_ok, active, own);
 
-    // StretchMove.h:112-113  accept iff lnU < (probScaling + newProb) - oldProb
-    const T zs = rec.zs, ln_u = rec.ln_u;
-    const T delta = zs + lp_new - lp_old;
-    const bool accept = active && (ln_u < delta);
-    if (active && sub == 0)
-    {
-        const T margin = dev_abs(ln_u - delta);
-        const T scale = dev_abs(ln_u) + dev_abs(zs) + dev_abs(lp_new) + dev_abs(lp_old);
-        if (near_tie(margin, a.tie_eps * scale)) count_near_tie(a.diag);
-    }
+    const bool accept = stretch_accept(a, rec.ln_u, rec.zs, lp_new, lp_old, active && sub == 0) && active;
     if (accept)
     {
         // Walker::jumpToNewPointSwap (Walker/Walker.h:172-179)
@@ -142,11 +118,7 @@ __global__ void __launch_bounds__(kBatchThreads) stretch_accept_kernel(const Hal
     }
     // per-wavefront accepted count (every wavefront of the grid writes its entry, zero or not)
     const unsigned accepted_here = (unsigned)__popcll(__ballot(accept && sub == 0));
-    if (a.partials != nullptr && run.accepted_per_step != nullptr && lane == 0)
-    {
-        const int wave = (int)blockIdx.x * (kBatchThreads / 64) + ((int)threadIdx.x >> 6);
-        a.partials[((size_t)ctl.partial_slot * 2 + (size_t)a.color) * (size_t)a.partial_waves + (size_t)wave] = accepted_here;
-    }
+    store_partial<T>(a, run, ctl, a.color, (int)blockIdx.x * (kBatchThreads / 64) + ((int)threadIdx.x >> 6), lane, accepted_here);
 }
 
 namespace
@@ -240,7 +212,7 @@ public:
         HIP_TRY(d_ctl.alloc(2 * sizeof(StepCtl)));
         HIP_TRY(d_run.alloc(sizeof(RunInfo)));
         HIP_TRY(d_own_diag.alloc(sizeof(Diag)));
-        HIP_TRY(d_draws.alloc(sizeof(DrawRec<T>) * 4 * (size_t)n));
+        HIP_TRY(d_draws.alloc(sizeof(DrawRec<T>) * draws_count(1, n)));
         HIP_TRY(d_partials.alloc(sizeof(uint32_t) * 2 * (size_t)partial_waves));
         d_logp = d_own_logp;
         d_nacc = d_own_nacc;
@@ -249,7 +221,7 @@ public:
         HIP_TRY(hipMemset(d_nacc, 0, sizeof(uint32_t) * (size_t)W));
         HIP_TRY(hipMemset(d_ctl, 0, 2 * sizeof(StepCtl)));
         HIP_TRY(hipMemset(d_diag, 0, sizeof(Diag)));
-        HIP_TRY(hipMemset(d_draws, 0, sizeof(DrawRec<T>) * 4 * (size_t)n));
+        HIP_TRY(hipMemset(d_draws, 0, sizeof(DrawRec<T>) * draws_count(1, n)));
         HIP_TRY(hipMemset(d_partials, 0, sizeof(uint32_t) * 2 * (size_t)partial_waves));
         HIP_TRY(h_pinned.alloc(sizeof(Pinned)));
         std::memset(h_pinned, 0, sizeof(Pinned));

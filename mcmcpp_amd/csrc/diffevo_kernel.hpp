@@ -160,12 +160,6 @@ struct DeArgs
     int partial_waves;  // updating wavefronts of a launch
 };
 
-// hot_bits of de_update_kernel: dims | colour << 12 | vec_ok << 14
-__host__ __device__ inline uint32_t de_hot_bits(int dims, int color, int vec_ok, int step = 0)
-{
-    return (uint32_t)dims | ((uint32_t)color << 12) | ((uint32_t)vec_ok << 14) | ((uint32_t)step << 16);
-}
-
 // The run record and the two lines of the launch description (kernarg) that hold DeArgs, in ONE batch of scalar loads with
 // one wait -- called behind the first round trip's vector loads, where the wait is free.  Left to the compiler these are cold
 // scalar misses issued where a field is first needed: behind the partner gather, with a wait that the matrix loads and the
@@ -195,7 +189,7 @@ __device__ __forceinline__ DeRunInfo de_load_run_and_warm_args(const DeRunInfo* 
 
 // ---- the update of one half-step ----------------------------------------------------------------------------------------
 // The hot_* arguments are what an updating wavefront needs before its second round trip; they travel in the 16 dwords
-// the command processor preloads into SGPRs (see HotBits in stretch_kernel.hpp), everything else in `a`.
+// the command processor preloads into SGPRs (see HotBits and DeHotBits in step_layout.hpp), everything else in `a`.
 // hot_recs: the n records of THIS half-step; hot_step: ensemble step inside the graph replay (0 for plain launches).
 template <class T, class Calc, int EPL, int LPW>
 __global__ void __launch_bounds__(64 * kWavesPerBlock)
@@ -205,13 +199,13 @@ de_update_kernel(T* hot_pos, T* hot_logp, uint32_t* hot_n_accept, const DeRec<T>
     constexpr int WPP = 64 / LPW;
     constexpr int kThreads = 64 * kWavesPerBlock;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int dims = (int)(hot_bits & 0xFFFu), n = hot_n;
+    const int dims = DeHotBits::dims(hot_bits), n = hot_n;
     const int lane = threadIdx.x & 63;
     const int wib = threadIdx.x >> 6;
-    const int color = (int)((hot_bits >> 12) & 1u);
+    const int color = DeHotBits::color(hot_bits);
     T* sh_stage = reinterpret_cast<T*>(smem + LdsLayout<T, Calc, EPL>::stage_offset());
     T* sh_block = reinterpret_cast<T*>(smem + LdsLayout<T, Calc, EPL>::block_offset());
-    const bool vec_ok = ((hot_bits >> 14) & 1u) != 0;
+    const bool vec_ok = DeHotBits::vec_ok(hot_bits) != 0;
     const bool has_block_scratch = Calc::block_scratch_elems(dims) != 0;
     const int sub = lane & (LPW - 1);
     const int wave = (int)blockIdx.x * kWavesPerBlock + wib;  // updating wavefront
@@ -284,17 +278,8 @@ de_update_kernel(T* hot_pos, T* hot_logp, uint32_t* hot_n_accept, const DeRec<T>
         const T p = moved + jit[e];
         prop[e] = (active && i0 + e < dims) ? p : (T)0;  // padded cells stay +0
     }
-    const T neg_exp = rec.neg_exp;
-
     const T lp_new = Calc::template eval<EPL, LPW>(ctx, a.calc_params, cregs, prop);
-    const T delta = lp_new - lp_old;
-    const bool accept = active && (delta > neg_exp);  // DifferentialEvolution.h:100
-    if (active && sub == 0)
-    {
-        const T margin = dev_abs(neg_exp - delta);
-        const T scale = dev_abs(neg_exp) + dev_abs(lp_new) + dev_abs(lp_old);
-        if (near_tie(margin, a.tie_eps * scale)) count_near_tie(a.diag);
-    }
+    const bool accept = de_accept(a, rec.neg_exp, lp_new, lp_old, active && sub == 0) && active;
     if (accept)
     {
         store_slice<T, EPL>(hot_pos + (size_t)w * dims, i0, dims, vec_ok, prop);
@@ -318,7 +303,7 @@ de_update_kernel(T* hot_pos, T* hot_logp, uint32_t* hot_n_accept, const DeRec<T>
     if (lane == 0)
     {
         uint32_t* partials = reinterpret_cast<uint32_t*>(hot_run + 1);
-        partials[((size_t)hot_step * 2 + (size_t)color) * (size_t)a.partial_waves + (size_t)wave] = acc;
+        partials[partial_index(0, 0, (uint32_t)hot_step, color, a.partial_waves, wave)] = acc;  // ([step in replay][colour][wavefront])
     }
 }
 
@@ -339,10 +324,10 @@ de_update_mfma_kernel(T* hot_pos, T* hot_logp, uint32_t* hot_n_accept, const DeR
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int kStageRows = sizeof(T) == 8 ? NW : 16;  // rows of the tile that hold walkers (mc_row)
     T* sh_x = reinterpret_cast<T*>(smem) + (threadIdx.x >> 6) * (kStageRows * kMcXS);
-    const int dims = (int)(hot_bits & 0xFFFu), n = hot_n;
-    const int hot_step = (int)(hot_bits >> 16);  // ensemble step inside the graph replay
+    const int dims = DeHotBits::dims(hot_bits), n = hot_n;
+    const int hot_step = DeHotBits::step(hot_bits);  // ensemble step inside the graph replay
     const int lane = threadIdx.x & 63;
-    const int color = (int)((hot_bits >> 12) & 1u);
+    const int color = DeHotBits::color(hot_bits);
     const int wave = (int)blockIdx.x * kWavesPerBlock + (int)(threadIdx.x >> 6);
     const int first = wave * NW;
     const bool wave_active = first < n;
@@ -444,15 +429,7 @@ de_update_mfma_kernel(T* hot_pos, T* hot_logp, uint32_t* hot_n_accept, const DeR
 #pragma unroll
     for (int q = 0; q < P; ++q)
     {
-        const T neg_exp = rec[q].neg_exp;
-        const T delta = lp_new[q] - lp_old[q];
-        const bool accept = active[q] && (delta > neg_exp);  // DifferentialEvolution.h:100
-        if (active[q] && sub == 0)
-        {
-            const T margin = dev_abs(neg_exp - delta);
-            const T scale = dev_abs(neg_exp) + dev_abs(lp_new[q]) + dev_abs(lp_old[q]);
-            if (near_tie(margin, a.tie_eps * scale)) count_near_tie(a.diag);
-        }
+        const bool accept = de_accept(a, rec[q].neg_exp, lp_new[q], lp_old[q], active[q] && sub == 0) && active[q];
         if (accept)
         {
             if (col_ok) *reinterpret_cast<V2*>(hot_pos + (size_t)w[q] * dims + i0) = Vec2<T>::make(prop[q][0], prop[q][1]);
@@ -472,7 +449,7 @@ de_update_mfma_kernel(T* hot_pos, T* hot_logp, uint32_t* hot_n_accept, const DeR
     if (lane == 0)
     {
         uint32_t* partials = reinterpret_cast<uint32_t*>(hot_run + 1);
-        partials[((size_t)hot_step * 2 + (size_t)color) * (size_t)a.partial_waves + (size_t)wave] = acc;
+        partials[partial_index(0, 0, (uint32_t)hot_step, color, a.partial_waves, wave)] = acc;  // ([step in replay][colour][wavefront])
     }
 }
 

@@ -52,9 +52,6 @@ __device__ __forceinline__ void hand_over_full(const HalfStepArgs<T>& a, const S
     *ctl_out = nx;  // (plain stores: written through, this and the partial counts below cost 0.2 us per launch)
 }
 
-// hot_bits of the full-step kernels: HotBits::pack(...) | pos_parity << 26
-__host__ __device__ inline uint32_t full_step_bits(uint32_t half_bits, int pos_parity) { return half_bits | ((uint32_t)pos_parity << 26); }
-
 // the workgroup's extra wavefronts: the draws of the NEXT ensemble step of every walker this workgroup updates
 // (`wpb` of each colour, starting at walker blockIdx.x * wpb); extra wavefronts 0, 1 make the red records of the first
 // and second half of those walkers, 2 and 3 the black ones
@@ -77,8 +74,7 @@ __device__ __forceinline__ void full_step_trickle_wave(const StepCtl* ctl_ptr, i
 {
     StepCtl ctl;
     RunInfo run;
-    const unsigned ctl_off = (unsigned)ctl_chain * (unsigned)kCtlChainStride;
-    load_records_and_warm_args<T>(ctl_ptr, ctl_off, ctl_ptr, ctl_off + (unsigned)kRunBehindCtlBytes - (unsigned)run_behind_ctl * (unsigned)sizeof(StepCtl), ctl, run);
+    load_records_and_warm_args<T>(ctl_ptr, ctl_chain_offset(ctl_chain), ctl_ptr, run_behind_ctl_offset(ctl_chain, run_behind_ctl), ctl, run);
     trickle_stored_step(run, ctl, lane);
 }
 
@@ -87,8 +83,7 @@ __device__ __forceinline__ void full_step_trickle_wave(const StepCtl* ctl_ptr, i
 // lives, so the ranks exchange rows once per ensemble step instead of once per half-step).  The bounds travel in the
 // 16 preloaded dwords; what they displaced is derived: the accepted counters lie right behind the two log-posterior
 // buffers ([2][W] elements, then [W] counters: one allocation), and the run record kRunBehindCtlBytes behind the
-// first control record.
-// (kRunBehindCtlBytes, stretch_kernel.hpp)
+// first control record (step_layout.hpp).
 
 template <class T, class Calc, int EPL, int LPW, bool MC = false>
 __global__ void __launch_bounds__(64 * (kWavesPerBlock + kFullDrawWaves))
@@ -98,27 +93,25 @@ stretch_full_step_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b, T* h
     const HalfStepArgs<T>& a = rest;
     constexpr int WPP = 64 / LPW;  // walkers of each colour per wavefront
     const int h_n = hot_n;
-    // chain blockIdx.y of (hot_bits >> 28) + 1 (ChainGeometry): every per-chain array at its fixed stride
-    const int chain = MC ? (int)blockIdx.y : 0, chains = MC ? (int)(hot_bits >> 28) + 1 : 1;  // (MC: see stretch_half_step_kernel)
+    // chain blockIdx.y of HotBits::chains (ChainGeometry): every per-chain array at its fixed stride
+    const int chain = MC ? (int)blockIdx.y : 0, chains = MC ? HotBits::chains(hot_bits) : 1;  // (MC: see stretch_half_step_kernel)
     const void* const draws_chain0 = hot_draws;
     if (MC && chain != 0)  // (a branch on purpose: chain 0 -- every single-ensemble launch -- skips the 64-bit products)
     {
-        hot_draws += (size_t)chain * 4 * (size_t)h_n;
-        hot_pos_a += (size_t)chain * 2 * (size_t)h_n * (size_t)(hot_bits & 0xFFFu);
-        hot_pos_b += (size_t)chain * 2 * (size_t)h_n * (size_t)(hot_bits & 0xFFFu);
-        hot_logp_a = reinterpret_cast<T*>(reinterpret_cast<char*>(hot_logp_a) + (size_t)chain * logp_chain_stride_bytes<T>(h_n));
+        step_to_chain<T>(chain, h_n, HotBits::dims(hot_bits), hot_draws, hot_pos_a, hot_logp_a);
+        hot_pos_b += pos_chain_offset(chain, h_n, HotBits::dims(hot_bits));
         // (the control record's address is not among the preloaded arguments: its chain offset travels as a load offset)
-        hot_run = reinterpret_cast<const RunInfo*>(reinterpret_cast<const char*>(hot_run) + (size_t)chain * kCtlChainStride);
+        hot_run = ctl_of_chain(hot_run, chain);
     }
-    const int h_dims = (int)(hot_bits & 0xFFFu);
-    const bool vec_ok = ((hot_bits >> 21) & 1u) != 0;
-    const int h_use_ctl_save = (int)((hot_bits >> 23) & 1u);
-    const int h_parity = (int)((hot_bits >> 24) & 1u);
-    const bool h_draw_wave = ((hot_bits >> 25) & 1u) != 0;
-    const bool h_flip = ((hot_bits >> 26) & 1u) != 0;
-    const DrawRec<T>* const dr_red = hot_draws + (size_t)h_parity * 2 * (size_t)h_n;
+    const int h_dims = HotBits::dims(hot_bits);
+    const bool vec_ok = HotBits::vec_ok(hot_bits) != 0;
+    const int h_use_ctl_save = HotBits::use_ctl_save(hot_bits);
+    const int h_parity = HotBits::draw_parity(hot_bits);
+    const bool h_draw_wave = HotBits::draw_wave(hot_bits) != 0;
+    const bool h_flip = HotBits::pos_parity(hot_bits) != 0;
+    const DrawRec<T>* const dr_red = hot_draws + draw_buffer_index(h_parity, 0, h_n);
     const DrawRec<T>* const dr_blk = dr_red + h_n;
-    DrawRec<T>* const dn_red = hot_draws + (size_t)(1 - h_parity) * 2 * (size_t)h_n;
+    DrawRec<T>* const dn_red = hot_draws + draw_buffer_index(1 - h_parity, 0, h_n);
     DrawRec<T>* const dn_blk = dn_red + h_n;
     const T* const pin = h_flip ? hot_pos_b : hot_pos_a;
     T* const pout = h_flip ? hot_pos_a : hot_pos_b;
@@ -136,7 +129,7 @@ stretch_full_step_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b, T* h
     const int wib = threadIdx.x >> 6;
     if (wib >= kWavesPerBlock)
     {
-        full_step_draw_wave<T>(a, jump_tables_behind(draws_chain0, h_n, ((hot_bits >> 27) & 1u) != 0, chains), hot_ctl_in, hot_run, Calc::block_scratch_elems(h_dims) != 0,
+        full_step_draw_wave<T>(a, jump_tables_behind(draws_chain0, h_n, HotBits::direct_jump(hot_bits) != 0, chains), hot_ctl_in, hot_run, Calc::block_scratch_elems(h_dims) != 0,
                                dn_red, h_n, sh_begin, sh_count, kWavesPerBlock * WPP, wib - kWavesPerBlock, lane, -1, chain);
         return;
     }
@@ -200,8 +193,8 @@ stretch_full_step_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b, T* h
     // a microsecond each; issued one by one where first needed they delayed the calculator by about that much).
     StepCtl ctl;  // wave-uniform
     RunInfo run;
-    load_records_and_warm_args<T>(hot_ctl_in, (unsigned)chain * (unsigned)kCtlChainStride, hot_run, 0u, ctl, run);
-    const StepCtl* const ctl_mine = reinterpret_cast<const StepCtl*>(reinterpret_cast<const char*>(hot_ctl_in) + (size_t)chain * kCtlChainStride);
+    load_records_and_warm_args<T>(hot_ctl_in, ctl_chain_offset(chain), hot_run, 0u, ctl, run);
+    const StepCtl* const ctl_mine = ctl_of_chain(hot_ctl_in, chain);
 
     // ---- in its shadow: the calculator's tables, the hand-over to the next launch ----
     const bool has_block_scratch = Calc::block_scratch_elems(h_dims) != 0;
@@ -213,8 +206,7 @@ stretch_full_step_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b, T* h
     if (blockIdx.x == 0 && threadIdx.x == 0) hand_over_full<T>(a, ctl, run, const_cast<StepCtl*>(ctl_mine) + (h_flip ? -1 : 1));
     if (!wave_active) return;
 
-    long long save_slot = -1;
-    if (h_use_ctl_save && run.chain != nullptr && ctl.save_phase + 1u == (uint32_t)run.interval) save_slot = (run.chain_slot_base + ctl.chain_slot) & run.slot_mask;
+    const long long save_slot = stored_step_slot(run, ctl, h_use_ctl_save != 0, true);
 
     if (!h_draw_wave)
     {
@@ -231,38 +223,16 @@ stretch_full_step_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b, T* h
             if (first + slot >= sh_count) continue;
             const int i = sh_begin + first + slot;
             Affine128 j_a, j_b;
-            if (direct)
-                j_a = a.task_jump[3 * i + k];
-            else
-            {
-                j_a = a.jump_hi[i >> 8];
-                j_b = a.jump_lo[i & 255];
-            }
+            load_draw_jump<T>(a, direct, i, k, j_a, j_b);
             compute_draw<T>(a, c ? base_b : ctl.state2, j_a, j_b, direct, k, (c ? dn_blk : dn_red) + i, c != 0, ctl.state2);
         }
     }
 
-    // One StretchMove::updateWalker (StretchMove.h:100-123) in two parts: the proposal, then calculator + accept test.
-    auto propose = [&](const T (&own)[EPL], const T (&par)[EPL], const DrawRec<T>& rec, T (&prop)[EPL]) {
-#pragma unroll
-        for (int e = 0; e < EPL; ++e)
-        {
-            const T d = own[e] - par[e];
-            const T zd = rec.z * d;
-            prop[e] = par[e] + zd;
-        }
-    };
+    // One StretchMove::updateWalker (StretchMove.h:100-123) in two parts: the proposal (stretch_propose), then calculator + accept test.
     // `fin` receives the walker's row after the update; returns accept, lp_out = its log-posterior afterwards.
     auto finish = [&](const T (&own)[EPL], const T (&prop)[EPL], const DrawRec<T>& rec, T lp_old, bool count_ties, T (&fin)[EPL], T& lp_out) -> bool {
         const T lp_new = Calc::template eval<EPL, LPW>(ctx, chain_calc_params<MC>(a, chain), cregs, prop);
-        const T delta = rec.zs + lp_new - lp_old;
-        const bool accept = rec.ln_u < delta;
-        if (count_ties && active && sub == 0)
-        {
-            const T margin = dev_abs(rec.ln_u - delta);
-            const T scale = dev_abs(rec.ln_u) + dev_abs(rec.zs) + dev_abs(lp_new) + dev_abs(lp_old);
-            if (near_tie(margin, a.tie_eps * scale)) count_near_tie(a.diag);
-        }
+        const bool accept = stretch_accept(a, rec.ln_u, rec.zs, lp_new, lp_old, count_ties && active && sub == 0);
 #pragma unroll
         for (int e = 0; e < EPL; ++e) fin[e] = accept ? prop[e] : own[e];
         lp_out = accept ? lp_new : lp_old;
@@ -291,15 +261,19 @@ stretch_full_step_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b, T* h
     // All three proposals' inputs are consumed before the first (conditional) store: a wait for loads placed behind
     // such a store would also wait for the store.
     T prop_x[EPL], prop_r[EPL];
-    propose(own_x, par_x, rec_x, prop_x);
-    propose(own_r, par_r, rec_r, prop_r);
+    // (cell by cell here: through stretch_propose, stretch_full_step_kernel<float, DenseGaussianFn<float>, 4, 1, true> takes a
+    //  97th VGPR and loses a wavefront per SIMD; tests/test_kernel_metadata.py holds it to 96)
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) prop_x[e] = stretch_proposal(own_x[e], par_x[e], rec_x.z);
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) prop_r[e] = stretch_proposal(own_r[e], par_r[e], rec_r.z);
 #pragma unroll
     for (int e = 0; e < EPL; ++e) asm volatile("" : "+v"(prop_x[e]), "+v"(prop_r[e]));
     T new_x[EPL], fin[EPL];
     T lp_x_new, lp_fin;
     finish(own_x, prop_x, rec_x, lp_x, false, new_x, lp_x_new);
     T prop_b[EPL];
-    propose(own_b, new_x, rec_b, prop_b);
+    stretch_propose(own_b, new_x, rec_b.z, prop_b);
     // ---- the group's red walker: its row goes out now and drains while the black update computes ----
     const bool acc_r = finish(own_r, prop_r, rec_r, lp_r, true, fin, lp_fin) && active;
     commit(ir, fin, lp_fin, acc_r, nacc_r);
@@ -308,12 +282,7 @@ stretch_full_step_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b, T* h
 
     const unsigned acc_red = (unsigned)__popcll(__ballot(acc_r && sub == 0));
     const unsigned acc_blk = (unsigned)__popcll(__ballot(acc_b && sub == 0));
-    if (a.partials != nullptr && run.accepted_per_step != nullptr && lane == 0)
-    {
-        uint32_t* p = a.partials + ((size_t)chain * (size_t)a.partial_slots + (size_t)ctl.partial_slot) * 2 * (size_t)a.partial_waves;
-        p[wave] = acc_red;
-        p[(size_t)a.partial_waves + wave] = acc_blk;
-    }
+    store_partials<T>(a, run, ctl, chain, wave, lane, acc_red, acc_blk);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -324,22 +293,8 @@ stretch_full_step_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b, T* h
 // barrier, so the draw wavefronts start at once.  First ONE full MFMA tile evaluates the 8 repeated partner
 // updates (rows 0..7) together with the 8 red owners' updates (rows 8..15), then a half tile the 8 black updates.
 // ---------------------------------------------------------------------------------------------------------
-// 16 bytes of a walker row of the `out` buffer (written through: see store_through)
-__device__ __forceinline__ void store_row_piece(double* p, double x0, double x1)
-{
-    typedef double v2d __attribute__((ext_vector_type(2)));
-    const v2d v = {x0, x1};
-    store_through16(p, v);
-}
-// (fp32: 8 bytes of a row)
-__device__ __forceinline__ void store_row_piece(float* p, float x0, float x1)
-{
-    typedef float v2f __attribute__((ext_vector_type(2)));
-    const v2f v = {x0, x1};
-    asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
-}
-
-// The same stores addressed as (uniform base, 32-bit byte offset): one register per address, no 64-bit arithmetic
+// 16 bytes (fp32: 8) of a walker row of the `out` buffer (written through: see store_through), addressed as (uniform base,
+// 32-bit byte offset): one register per address, no 64-bit arithmetic
 __device__ __forceinline__ void store_row_piece_at(char* base, uint32_t off, double x0, double x1)
 {
     typedef double v2d __attribute__((ext_vector_type(2)));
@@ -371,24 +326,26 @@ stretch_full_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b,
 
     const HalfStepArgs<T>& a = rest;
     const int h_n = hot_n;
-    const int h_dims = (int)(hot_bits & 0xFFFu);
-    // chain blockIdx.y of (hot_bits >> 28) + 1 (ChainGeometry): every per-chain array at its fixed stride
-    const int chain = MC ? (int)blockIdx.y : 0, chains = MC ? (int)(hot_bits >> 28) + 1 : 1;  // (MC: see stretch_half_step_kernel)
+    const int h_dims = HotBits::dims(hot_bits);
+    // chain blockIdx.y of HotBits::chains (ChainGeometry): every per-chain array at its fixed stride
+    const int chain = MC ? (int)blockIdx.y : 0, chains = MC ? HotBits::chains(hot_bits) : 1;  // (MC: see stretch_half_step_kernel)
     const void* const draws_chain0 = hot_draws;
     if (MC && chain != 0)  // (a branch on purpose: chain 0 -- every single-ensemble launch -- skips the 64-bit products)
     {
-        hot_draws += (size_t)chain * 4 * (size_t)h_n;
-        hot_pos_a += (size_t)chain * 2 * (size_t)h_n * (size_t)h_dims;
-        hot_pos_b += (size_t)chain * 2 * (size_t)h_n * (size_t)h_dims;
-        hot_logp_a = reinterpret_cast<T*>(reinterpret_cast<char*>(hot_logp_a) + (size_t)chain * logp_chain_stride_bytes<T>(h_n));
+        step_to_chain<T>(chain, h_n, h_dims, hot_draws, hot_pos_a, hot_logp_a);
+        hot_pos_b += pos_chain_offset(chain, h_n, h_dims);
         hot_matrix += (size_t)chain * (size_t)a.params_chain_stride;  // (the chain's own P^T; stride 0: shared)
     }
-    const int h_use_ctl_save = (int)((hot_bits >> 23) & 1u);
-    const int h_parity = (int)((hot_bits >> 24) & 1u);
-    const bool h_flip = ((hot_bits >> 26) & 1u) != 0;
-    const DrawRec<T>* const dr_red = hot_draws + (size_t)h_parity * 2 * (size_t)h_n;
+    const int h_use_ctl_save = HotBits::use_ctl_save(hot_bits);
+    const int h_parity = HotBits::draw_parity(hot_bits);
+    // (spelled out from the field's constants, not HotBits::pos_parity: decoded through a function, whatever its form, the run
+    //  record's load offset below takes one scalar instruction more in front of the scalar-load batch.  That is what keeps the
+    //  layout header and the decoders ALONE an instruction-neutral change, profiles/step_layout_refactor.txt 1a; the launch
+    //  times of this kernel were taken with this text)
+    const bool h_flip = ((hot_bits >> HotBits::PosParity::shift) & 1u) != 0;
+    const DrawRec<T>* const dr_red = hot_draws + draw_buffer_index(h_parity, 0, h_n);
     const DrawRec<T>* const dr_blk = dr_red + h_n;
-    DrawRec<T>* const dn_red = hot_draws + (size_t)(1 - h_parity) * 2 * (size_t)h_n;
+    DrawRec<T>* const dn_red = hot_draws + draw_buffer_index(1 - h_parity, 0, h_n);
     const T* const pin = h_flip ? hot_pos_b : hot_pos_a;
     T* const pout = h_flip ? hot_pos_a : hot_pos_b;
     T* const hot_logp_b = hot_logp_a + 2 * (size_t)h_n;  // (the two log-posterior buffers are one allocation: [2][W])
@@ -401,7 +358,7 @@ stretch_full_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b,
     const int lane = threadIdx.x & 63;
     if ((threadIdx.x >> 6) >= kWavesPerBlock)
     {
-        if ((hot_bits >> 20) & 1u)
+        if (HotBits::color(hot_bits))
         {
             // HalfStepArgs::draw_wave == 2: this step's records were made ahead of the launches (fill_draws_batch_kernel);
             // the one extra wavefront forwards this launch's slice of the last stored step and that is all
@@ -409,7 +366,7 @@ stretch_full_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b,
             return;
         }
         // (the run record is read at an offset from the control record's address, where it is needed)
-        full_step_draw_wave<T>(a, jump_tables_behind(draws_chain0, h_n, ((hot_bits >> 27) & 1u) != 0, chains), hot_ctl_in, nullptr, false, dn_red, h_n, sh_begin,
+        full_step_draw_wave<T>(a, jump_tables_behind(draws_chain0, h_n, HotBits::direct_jump(hot_bits) != 0, chains), hot_ctl_in, nullptr, false, dn_red, h_n, sh_begin,
                                sh_count, kWavesPerBlock * NW, (int)(threadIdx.x >> 6) - kWavesPerBlock, lane, h_flip ? 1 : 0, chain);
         return;
     }
@@ -491,23 +448,14 @@ stretch_full_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b,
     StepCtl ctl;
     RunInfo run;
     // (the chain's own records, the run record kRunBehindCtlBytes behind the first control record: offsets of the batch's loads)
-    load_records_and_warm_args<T>(hot_ctl_in, (unsigned)chain * (unsigned)kCtlChainStride, hot_ctl_in,
-                                  (unsigned)chain * (unsigned)kCtlChainStride + (unsigned)kRunBehindCtlBytes - (h_flip ? (unsigned)sizeof(StepCtl) : 0u), ctl, run);
-    const StepCtl* const ctl_mine = reinterpret_cast<const StepCtl*>(reinterpret_cast<const char*>(hot_ctl_in) + (size_t)chain * kCtlChainStride);
+    load_records_and_warm_args<T>(hot_ctl_in, ctl_chain_offset(chain), hot_ctl_in, run_behind_ctl_offset(chain, h_flip ? 1 : 0), ctl, run);
+    const StepCtl* const ctl_mine = ctl_of_chain(hot_ctl_in, chain);
     if (blockIdx.x == 0 && threadIdx.x == 0) hand_over_full<T>(a, ctl, run, const_cast<StepCtl*>(ctl_mine) + (h_flip ? -1 : 1));
-    long long save_slot = -1;
-    if (h_use_ctl_save && run.chain != nullptr && ctl.save_phase + 1u == (uint32_t)run.interval) save_slot = (run.chain_slot_base + ctl.chain_slot) & run.slot_mask;
+    const long long save_slot = stored_step_slot(run, ctl, h_use_ctl_save != 0, true);
 
     // accept test of walker slot q; fin = row afterwards
     auto decide = [&](int q, const T (&own)[2], const T (&prop)[2], const DrawRec<T>& rec, T lp_old, T lp_new, bool count_ties, T (&fin)[2], T& lp_fin) -> bool {
-        const T delta = rec.zs + lp_new - lp_old;
-        const bool accept = rec.ln_u < delta;
-        if (count_ties && active[q] && sub == 0)
-        {
-            const T margin = dev_abs(rec.ln_u - delta);
-            const T scale = dev_abs(rec.ln_u) + dev_abs(rec.zs) + dev_abs(lp_new) + dev_abs(lp_old);
-            if (near_tie(margin, a.tie_eps * scale)) count_near_tie(a.diag);
-        }
+        const bool accept = stretch_accept(a, rec.ln_u, rec.zs, lp_new, lp_old, count_ties && active[q] && sub == 0);
         fin[0] = accept ? prop[0] : own[0];
         fin[1] = accept ? prop[1] : own[1];
         lp_fin = accept ? lp_new : lp_old;
@@ -535,16 +483,10 @@ stretch_full_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b,
     T prop4[4][2], lp4[4];
 #pragma unroll
     for (int q = 0; q < 2; ++q)
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-        {
-            const T dx = own_x[q][e] - par_x[q][e];
-            const T zdx = rec_x[q].z * dx;
-            prop4[q][e] = par_x[q][e] + zdx;
-            const T dr = own_r[q][e] - par_r[q][e];
-            const T zdr = rec_r[q].z * dr;
-            prop4[2 + q][e] = par_r[q][e] + zdr;
-        }
+    {
+        stretch_propose(own_x[q], par_x[q], rec_x[q].z, prop4[q]);
+        stretch_propose(own_r[q], par_r[q], rec_r[q].z, prop4[2 + q]);
+    }
     mc_eval<4>(matB, sh_x, sub, grp, h_dims, prop4, lp4);
 
     // ---- the black walkers against their partners' results ----
@@ -553,13 +495,7 @@ stretch_full_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b,
     for (int q = 0; q < 2; ++q)
     {
         decide(q, own_x[q], prop4[q], rec_x[q], lp_x[q], lp4[q], false, new_x, lp_dummy);
-#pragma unroll
-        for (int e = 0; e < 2; ++e)
-        {
-            const T d = own_b[q][e] - new_x[e];
-            const T zd = rec_b[q].z * d;
-            prop_b[q][e] = new_x[e] + zd;
-        }
+        stretch_propose(own_b[q], new_x, rec_b[q].z, prop_b[q]);
     }
     // the red owners' rows go out now (every load has long been consumed) and drain while the black tile computes
     unsigned acc_red = 0, acc_blk = 0;
@@ -579,12 +515,7 @@ stretch_full_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos_a, T* hot_pos_b,
         commit(q, un + ir[q], fin, lp_fin, accb, nacc_b[q]);
         acc_blk += (unsigned)__popcll(__ballot(accb && sub == 0));
     }
-    if (a.partials != nullptr && run.accepted_per_step != nullptr && lane == 0)
-    {
-        uint32_t* p = a.partials + ((size_t)chain * (size_t)a.partial_slots + (size_t)ctl.partial_slot) * 2 * (size_t)a.partial_waves;
-        p[wave] = acc_red;
-        p[(size_t)a.partial_waves + wave] = acc_blk;
-    }
+    store_partials<T>(a, run, ctl, chain, wave, lane, acc_red, acc_blk);
 }
 
 }  // namespace mcmcpp

@@ -14,8 +14,7 @@ void launch_half(const HalfStepArgs<T>& a, unsigned grid, hipStream_t st)
 {
     const size_t lds = LdsLayout<T, Calc, EPL>::bytes(a.dims);
     const int chains = a.chains > 1 ? a.chains : 1;
-    const uint32_t bits = HotBits::pack(a.dims, a.passes, a.color, a.vec_ok, a.n_is_pow2, a.use_ctl_save, a.draw_parity, a.draw_wave, a.task_jump != nullptr) |
-                          ((uint32_t)(chains - 1) << 28);
+    const uint32_t bits = HotBits::pack(a.dims, a.passes, a.color, a.vec_ok, a.n_is_pow2, a.use_ctl_save, a.draw_parity, a.draw_wave, 0, a.task_jump != nullptr, chains);
 #define MCMCPP_LAUNCH_HALF(DW, MC, THREADS)                                                                                                              \
     hipLaunchKernelGGL((stretch_half_step_kernel<T, Calc, EPL, LPW, DW, MC>), dim3(grid, chains), dim3(THREADS), lds, st, a.draws, a.pos, a.logp, a.n_accept, a.n, \
                        bits, a.shard_begin, a.shard_count, a.ctl_in, a)
@@ -37,8 +36,7 @@ void launch_half_mfma(const HalfStepArgs<T>& a, unsigned grid, hipStream_t st)
     // (staging rows of the workgroup's wavefronts, then the 32 x 32 matrix shared by workgroups without a draw wavefront)
     const size_t lds = ((size_t)kWavesPerBlock * (sizeof(T) == 8 ? 4 * P : 16) * kMcXS + 1024) * sizeof(T);
     const int chains = a.chains > 1 ? a.chains : 1;
-    const uint32_t bits = HotBits::pack(a.dims, a.passes, a.color, a.vec_ok, a.n_is_pow2, a.use_ctl_save, a.draw_parity, a.draw_wave, a.task_jump != nullptr) |
-                          ((uint32_t)(chains - 1) << 28);
+    const uint32_t bits = HotBits::pack(a.dims, a.passes, a.color, a.vec_ok, a.n_is_pow2, a.use_ctl_save, a.draw_parity, a.draw_wave, 0, a.task_jump != nullptr, chains);
 #define MCMCPP_LAUNCH_HALF_MC(DW, MC, THREADS)                                                                                                            \
     hipLaunchKernelGGL((stretch_half_step_mfma_kernel<T, Calc, EPL, LPW, P, DW, MC, (LATE && !(DW))>), dim3(grid, chains), dim3(THREADS), lds, st, a.draws, a.pos, a.logp, a.n_accept, \
                        a.n, bits, a.shard_begin, a.shard_count, a.ctl_in, a.calc_params_padded, a)
@@ -68,8 +66,7 @@ void launch_full(const HalfStepArgs<T>& a, unsigned grid, hipStream_t st)
 {
     const size_t lds = LdsLayout<T, Calc, EPL>::bytes(a.dims);
     const int chains = a.chains > 1 ? a.chains : 1;
-    const uint32_t bits = full_step_bits(HotBits::pack(a.dims, 1, 0, a.vec_ok, a.n_is_pow2, a.use_ctl_save, a.draw_parity, a.draw_wave, a.task_jump != nullptr), a.pos_parity) |
-                          ((uint32_t)(chains - 1) << 28);
+    const uint32_t bits = HotBits::pack(a.dims, 1, 0, a.vec_ok, a.n_is_pow2, a.use_ctl_save, a.draw_parity, a.draw_wave, a.pos_parity, a.task_jump != nullptr, chains);
     if (chains > 1)
         hipLaunchKernelGGL((stretch_full_step_kernel<T, Calc, EPL, LPW, true>), dim3(grid, chains), dim3(64 * (kWavesPerBlock + (a.draw_wave ? kFullDrawWaves : 0))),
                            lds, st, a.draws, a.pos, a.pos_alt, a.logp, a.run, a.shard_begin, a.shard_count, a.n, bits, a.ctl_in, a);
@@ -87,8 +84,7 @@ void launch_full_mfma(const HalfStepArgs<T>& a, unsigned grid, hipStream_t st)
     //  such a launch has one extra wavefront per workgroup, the forwarder of stored steps, instead of the draw wavefronts)
     const int prefilled = a.draw_wave == 2 ? 1 : 0;
     const int extra_waves = prefilled ? 1 : kFullDrawWaves;
-    const uint32_t bits = full_step_bits(HotBits::pack(a.dims, 2, prefilled, a.vec_ok, a.n_is_pow2, a.use_ctl_save, a.draw_parity, 1, a.task_jump != nullptr), a.pos_parity) |
-                          ((uint32_t)(chains - 1) << 28);
+    const uint32_t bits = HotBits::pack(a.dims, 2, prefilled, a.vec_ok, a.n_is_pow2, a.use_ctl_save, a.draw_parity, 1, a.pos_parity, a.task_jump != nullptr, chains);
     // (logp_alt == logp + W, n_accept == logp + 2 W and the run record kRunBehindCtlBytes behind the control records: the
     //  kernel derives them and takes the padded matrix and the shard bounds as preloaded arguments instead)
     if (chains > 1)
@@ -112,7 +108,7 @@ void launch_de(const typename LaunchTable<T>::DeLaunch& l, const DeArgs<T>& a, u
 {
     const size_t lds = LdsLayout<T, Calc, EPL>::bytes(l.dims);
     hipLaunchKernelGGL((de_update_kernel<T, Calc, EPL, LPW>), dim3(grid), dim3(64 * kWavesPerBlock), lds, st, l.pos, l.logp, l.n_accept, l.recs, l.jump_small, l.run, l.n,
-                       de_hot_bits(l.dims, l.color, l.vec_ok), l.step, a);
+                       DeHotBits::pack(l.dims, l.color, l.vec_ok), l.step, a);
 }
 
 template <class T, class Calc, int EPL, int LPW, int P>
@@ -121,7 +117,7 @@ void launch_de_mfma(const typename LaunchTable<T>::DeLaunch& l, const DeArgs<T>&
     const size_t lds = ((size_t)kWavesPerBlock * (sizeof(T) == 8 ? 4 * P : 16) * kMcXS) * sizeof(T);
     // (the step inside the replay travels in the hot bits: the sixteenth preloaded dword pair is the matrix pointer)
     hipLaunchKernelGGL((de_update_mfma_kernel<T, Calc, EPL, LPW, P>), dim3(grid), dim3(64 * kWavesPerBlock), lds, st, l.pos, l.logp, l.n_accept, l.recs, l.jump_small, l.run,
-                       l.n, de_hot_bits(l.dims, l.color, l.vec_ok, l.step), l.matrix_padded, a);
+                       l.n, DeHotBits::pack(l.dims, l.color, l.vec_ok, l.step), l.matrix_padded, a);
 }
 
 template <class T, class Calc, int LPWLOG, int EPLSHIFT>

@@ -256,7 +256,7 @@ public:
             HIP_TRY(hipEventCreate(ev_t1[k].replace()));
         }
 
-        const size_t partials_bytes = sizeof(uint32_t) * (size_t)plan.partial_slots * 2 * (size_t)plan.partial_waves * K;
+        const size_t partials_bytes = sizeof(uint32_t) * partials_count(K, plan.partial_slots, plan.partial_waves);
         {
             // everything carved below (each piece rounded up to 256 bytes)
             static_assert(sizeof(Affine128) == kJumpEntryBytes, "the plan sizes the task table by this");
@@ -291,12 +291,11 @@ public:
             char* piece = nullptr;
             if (int rc = carve(&piece, (size_t)kCtlChainStride * (size_t)K)) return rc;
             d_ctl = reinterpret_cast<StepCtl*>(piece);
-            d_run = reinterpret_cast<RunInfo*>(piece + kRunBehindCtlBytes);
+            d_run = reinterpret_cast<RunInfo*>(offset_bytes(piece, kRunBehindCtlBytes));
         }
         if (int rc = carve(&d_diag, sizeof(Diag))) return rc;
         // the draw records (two buffers: see HalfStepArgs::draws) and, right behind them, the jump tables: one piece
         // whose layout follows from n alone (JumpTables), so that kernels reach the tables from the record pointer
-        static_assert(sizeof(DrawRec<T>) == 32, "the table offsets assume 32-byte records");
         {
             const bool task = plan.have_task_table;
             char* piece = nullptr;
@@ -306,7 +305,7 @@ public:
             d_jump_hi = reinterpret_cast<Affine128*>(piece + tables_offset_hi(n, task, K));
             d_jump_lo = reinterpret_cast<Affine128*>(piece + tables_offset_lo(n, task, K));
         }
-        HIP_TRY(hipMemset(d_draws, 0, sizeof(DrawRec<T>) * (size_t)W * 2 * K));
+        HIP_TRY(hipMemset(d_draws, 0, sizeof(DrawRec<T>) * draws_count(K, n)));
         HIP_TRY(hipMemset(d_logp, 0, logp_chain_stride_bytes<T>(n) * (size_t)K));
         HIP_TRY(hipMemset(d_diag, 0, sizeof(Diag)));
         HIP_TRY(hipMemset(d_ctl, 0, (size_t)kCtlChainStride * (size_t)K));
@@ -1111,10 +1110,10 @@ private:
     }
 
     // chain k's arrays (ChainGeometry; k = 0: the arrays themselves)
-    T* logp_of(int k) const { return reinterpret_cast<T*>(reinterpret_cast<char*>(d_logp) + logp_chain_stride_bytes<T>(n) * (size_t)k); }
+    T* logp_of(int k) const { return logp_of_chain<T>(d_logp, n, k); }
     uint32_t* nacc_of(int k) const { return reinterpret_cast<uint32_t*>(logp_of(k) + 2 * (size_t)W); }
-    StepCtl* ctl_of(int k) const { return reinterpret_cast<StepCtl*>(reinterpret_cast<char*>(d_ctl) + (size_t)kCtlChainStride * (size_t)k); }
-    RunInfo* run_of(int k) const { return reinterpret_cast<RunInfo*>(reinterpret_cast<char*>(d_run) + (size_t)kCtlChainStride * (size_t)k); }
+    StepCtl* ctl_of(int k) const { return ctl_of_chain(d_ctl, k); }
+    RunInfo* run_of(int k) const { return ctl_of_chain(d_run, k); }
 
     HalfStepArgs<T> make_args(int color, int parity) const
     {
@@ -1186,7 +1185,7 @@ private:
             {
                 const int parity = (int)((at >> 1) & 1);  // the buffer the coming ensemble step reads
                 HalfStepArgs<T> fr = make_args(0, parity), fb = make_args(1, parity);
-                fr.draws = fb.draws = d_draws + (size_t)k * 4 * (size_t)n;  // (the chain's own records; the tables are shared)
+                fr.draws = fb.draws = d_draws + draws_chain_offset(k, n);  // (the chain's own records; the tables are shared)
                 launch_fill_draws(fr, c->state, nullptr, stream);
                 launch_fill_draws(fb, state1, full_fn ? &c->state : nullptr, stream);
                 HIP_TRY(hipGetLastError());

@@ -33,6 +33,7 @@
 #include "fast_log.hpp"
 #include "glibc_logf.hpp"
 #include "pcg128.hpp"
+#include "step_layout.hpp"  // HotBits, ChainGeometry
 #include "step_plan.hpp"  // kWavesPerBlock: updating wavefronts per workgroup
 
 namespace mcmcpp
@@ -79,6 +80,9 @@ struct alignas(16) DrawRec
                        // red partner in the same ensemble step, so that both rows can be fetched in one round trip
 };
 
+static_assert(sizeof(StepCtl) == kStepCtlBytes, "ChainGeometry");
+static_assert(sizeof(DrawRec<double>) == kDrawRecBytes && sizeof(DrawRec<float>) == kDrawRecBytes, "ChainGeometry");
+
 // What a half-step update uses of its record.  The kernels keep THIS across their pass loop, not the 32-byte record: a
 // copied DrawRec<float> (20 bytes of fields, 12 of padding, partner2 unused here) is not taken apart into registers -- its
 // unused half stays a private array, which the back end "promotes" to LDS, and a kernel with such an array reads the
@@ -105,29 +109,14 @@ __device__ __forceinline__ void count_near_tie(Diag* diag)
     atomicAdd(&diag->near_ties, 1ULL);
 }
 
-// The jump tables live right behind the draw records, at offsets that follow from the number of walkers per colour
-// alone, so that a kernel can reach them from its preloaded record pointer without touching the kernarg segment
-// (a draw wavefront's first loads would otherwise wait for a cold scalar miss):
-//   [records: 4 n x 32 B][task_jump: 3 n entries, if built][jump_hi: ceil(n / 256) entries][jump_lo: 256 entries]
-// every piece rounded up to 256 bytes.
+// The jump tables behind the draw records (step_layout.hpp: tables_offset_*)
 struct JumpTables
 {
     const Affine128* task;  // nullptr when the table was not built (very large ensembles)
     const Affine128* hi;
     const Affine128* lo;
 };
-__host__ __device__ inline size_t round_up_256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-// (`chains` independent ensembles stepped by one launch share the tables: same stream increment, see ChainGeometry)
-__host__ __device__ inline size_t tables_offset_task(int n, int chains = 1) { return round_up_256((size_t)4 * (size_t)n * 32 * (size_t)chains); }
-__host__ __device__ inline size_t tables_offset_hi(int n, bool direct, int chains = 1)
-{
-    return tables_offset_task(n, chains) + (direct ? round_up_256((size_t)3 * (size_t)n * sizeof(Affine128)) : 0);
-}
-__host__ __device__ inline size_t tables_offset_lo(int n, bool direct, int chains = 1)
-{
-    return tables_offset_hi(n, direct, chains) + round_up_256((size_t)((n + 255) / 256) * sizeof(Affine128));
-}
-__host__ __device__ inline size_t tables_total_bytes(int n, bool direct, int chains = 1) { return tables_offset_lo(n, direct, chains) + 256 * sizeof(Affine128); }
+static_assert(sizeof(Affine128) == kJumpEntryBytes, "the table offsets assume this entry");
 __device__ __forceinline__ JumpTables jump_tables_behind(const void* draws_base, int n, bool direct, int chains = 1)
 {
     const char* b = static_cast<const char*>(draws_base);
@@ -137,25 +126,6 @@ __device__ __forceinline__ JumpTables jump_tables_behind(const void* draws_base,
     t.lo = reinterpret_cast<const Affine128*>(b + tables_offset_lo(n, direct, chains));
     return t;
 }
-
-// Several independent ensembles ("chains": BASELINE config 4 on one GPU) stepped by ONE launch: workgroup row
-// blockIdx.y is chain blockIdx.y.  Every per-chain array is the single-chain array repeated with a fixed stride that
-// follows from n and D alone, so the kernels need no further arguments (the chain count travels in the hot bits):
-//   positions (both buffers)   [chains][2n][D]
-//   log-posteriors + counters  [chains]{[2][2n] T, [2n] u32}
-//   control + run records      [chains]{StepCtl[2], pad to kRunBehindCtlBytes, RunInfo, pad to kCtlChainStride}
-//   draw records               [chains][2][2][n], then the shared jump tables
-//   partial accepted counts    [chains][partial_slots][2][partial_waves]
-// The chains differ in their seed (seed + chain: same stream increment, hence the same jump tables) and, once the host has
-// given any chain a parameter block of its own (mcmcpp_hip_set_chain_params), in their calculator parameters:
-//   calculator parameters      [chains][params_chain_stride]: the block (P^T for the dense target), zero padding to 256 bytes,
-//                              then -- dense target, D <= 32 -- the matrix-core kernels' zero-padded 32 x 32 P^T
-// calc_params and calc_params_padded point into row 0 and the MC kernels step both by chain * params_chain_stride (0: shared).
-constexpr int kCtlChainStride = 512;
-constexpr int kRunBehindCtlBytes = 256;
-constexpr int kMaxChains = 16;  // (four hot bits)
-template <class T>
-__host__ __device__ inline size_t logp_chain_stride_bytes(int n) { return (size_t)4 * (size_t)n * sizeof(T) + (size_t)2 * (size_t)n * sizeof(uint32_t); }
 
 // The launch description.  It travels by value in the kernarg segment (behind 64 bytes of preloaded hot arguments)
 // and is read with scalar loads where a field is first used; after a launch boundary every 64-byte line of it is a
@@ -363,6 +333,52 @@ __device__ __forceinline__ bool near_tie(T margin, T band)
     return margin <= band && margin < (T)__builtin_huge_val();
 }
 
+// The accept rules, one statement each for the full-step, batch accept and differential-evolution kernels (the two
+// half-step kernels keep the same text spelled out: DESIGN.md section 6).  `count`: this lane reports a near tie (one lane of an
+// active walker; the repeated partner updates of the full-step kernels report none).  `a`: HalfStepArgs or DeArgs (tie_eps,
+// diag).  Every + and - is rounded on its own, in this order (-ffp-contract=off), as the oracle has them.
+// StretchMove.h:112-113  accept iff lnU < (probScaling + newProb) - oldProb
+template <class T, class Args>
+__device__ __forceinline__ bool stretch_accept(const Args& a, T ln_u, T zs, T lp_new, T lp_old, bool count)
+{
+    const T delta = zs + lp_new - lp_old;
+    if (count)
+    {
+        const T margin = dev_abs(ln_u - delta);
+        const T scale = dev_abs(ln_u) + dev_abs(zs) + dev_abs(lp_new) + dev_abs(lp_old);
+        if (near_tie(margin, a.tie_eps * scale)) count_near_tie(a.diag);
+    }
+    return ln_u < delta;
+}
+// DifferentialEvolution.h:100  accept iff newProb - oldProb > -Exp(1)
+template <class T, class Args>
+__device__ __forceinline__ bool de_accept(const Args& a, T neg_exp, T lp_new, T lp_old, bool count)
+{
+    const T delta = lp_new - lp_old;
+    if (count)
+    {
+        const T margin = dev_abs(neg_exp - delta);
+        const T scale = dev_abs(neg_exp) + dev_abs(lp_new) + dev_abs(lp_old);
+        if (near_tie(margin, a.tie_eps * scale)) count_near_tie(a.diag);
+    }
+    return delta > neg_exp;
+}
+
+// StretchMove.h:105-108  proposal = sel + z*(cur - sel), one cell (padded cells stay +0) and a lane's cells
+template <class T>
+__device__ __forceinline__ T stretch_proposal(T own, T par, T z)
+{
+    const T d = own - par;
+    const T zd = z * d;
+    return par + zd;
+}
+template <class T, int N>
+__device__ __forceinline__ void stretch_propose(const T (&own)[N], const T (&par)[N], T z, T (&prop)[N])
+{
+#pragma unroll
+    for (int e = 0; e < N; ++e) prop[e] = stretch_proposal(own[e], par[e], z);
+}
+
 // dynamic LDS of one workgroup: [proposal stage (if the calculator wants it)][calculator tables]
 template <class T, class Calc, int EPL>
 struct LdsLayout
@@ -424,12 +440,6 @@ __device__ __forceinline__ void load_records_and_warm_args(const StepCtl* ctl_pt
         : "memory");
     ctl = __builtin_bit_cast(StepCtl, c);
     run = __builtin_bit_cast(RunInfo, r);
-}
-
-template <class T>
-__device__ __forceinline__ void load_records_and_warm_args(const StepCtl* ctl_ptr, const RunInfo* run_ptr, StepCtl& ctl, RunInfo& run)
-{
-    load_records_and_warm_args<T>(ctl_ptr, 0u, run_ptr, 0u, ctl, run);
 }
 
 // One random draw of one walker: task k of the walker at position i of the half (draw 3*i + k of the
@@ -522,22 +532,6 @@ __device__ __forceinline__ const T* chain_calc_params(const HalfStepArgs<T>& a, 
     return MC ? a.calc_params + (size_t)chain * (size_t)a.params_chain_stride : a.calc_params;
 }
 
-// Hot scalars of a launch, packed so that the arguments every wavefront needs before its first memory
-// access fit the 16 dwords the command processor preloads into SGPRs (-amdgpu-kernarg-preload-count=16);
-// everything else stays in the by-value HalfStepArgs and is fetched from the kernarg segment on demand.
-struct HotBits
-{
-    // (bit 26: full-step kernels' position-buffer parity; bit 27: the one-entry-per-draw jump table exists;
-    //  bits 28-31: chains - 1)
-    static __host__ __device__ uint32_t pack(int dims, int passes, int color, int vec_ok, int n_is_pow2, int use_ctl_save,
-                                             int draw_parity, int draw_wave, int direct_jump)
-    {
-        return (uint32_t)dims | ((uint32_t)passes << 12) | ((uint32_t)color << 20) | ((uint32_t)vec_ok << 21) |
-               ((uint32_t)n_is_pow2 << 22) | ((uint32_t)use_ctl_save << 23) | ((uint32_t)draw_parity << 24) |
-               ((uint32_t)draw_wave << 25) | ((uint32_t)direct_jump << 27);
-    }
-};
-
 // Hands the random stream and the step counters to the next half-step launch (one lane of the whole grid).
 template <class T>
 __device__ __forceinline__ void hand_over(const HalfStepArgs<T>& a, const StepCtl& ctl, const RunInfo& run, int color, StepCtl* ctl_out)
@@ -556,6 +550,60 @@ __device__ __forceinline__ void hand_over(const HalfStepArgs<T>& a, const StepCt
         nx.partial_slot = (ctl.partial_slot + 1u == (uint32_t)a.partial_slots) ? 0u : ctl.partial_slot + 1u;
     }
     *ctl_out = nx;
+}
+
+// Does this ensemble step go to the chain, and to which slot (-1: it does not)?  (EnsembleSampler.h:298-306: interval-1
+// unsaved, 1 saved.)  ring: the device chain is a ring of run.slot_mask + 1 slots (full-step kernels; the batch accept kernel's
+// slots are not reused).  The half-step kernels state the same rule themselves, with the sharded driver's direct slot in front.
+__device__ __forceinline__ long long stored_step_slot(const RunInfo& run, const StepCtl& ctl, bool use_ctl_save, bool ring)
+{
+    if (!(use_ctl_save && run.chain != nullptr && ctl.save_phase + 1u == (uint32_t)run.interval)) return -1;
+    return ring ? (run.chain_slot_base + ctl.chain_slot) & run.slot_mask : run.chain_slot_base + ctl.chain_slot;
+}
+
+// Per-wavefront accepted count of this launch, summed per ensemble step by accepted_reduce_kernel (one plain store per
+// wavefront: thousands of same-address atomics would serialise for ~12 ns each).  One colour of a handle's only ensemble
+// (the batch accept kernel; the half-step kernels store theirs themselves) ...
+template <class T>
+__device__ __forceinline__ void store_partial(const HalfStepArgs<T>& a, const RunInfo& run, const StepCtl& ctl, int color, int wave, int lane, unsigned accepted)
+{
+    if (a.partials != nullptr && run.accepted_per_step != nullptr && lane == 0)
+        a.partials[partial_index(0, a.partial_slots, ctl.partial_slot, color, a.partial_waves, wave)] = accepted;
+}
+// ... or both colours of chain `chain` (full-step launches)
+template <class T>
+__device__ __forceinline__ void store_partials(const HalfStepArgs<T>& a, const RunInfo& run, const StepCtl& ctl, int chain, int wave, int lane, unsigned acc_red, unsigned acc_blk)
+{
+    if (a.partials != nullptr && run.accepted_per_step != nullptr && lane == 0)
+    {
+        uint32_t* p = a.partials + partial_index(chain, a.partial_slots, ctl.partial_slot, 0, a.partial_waves, 0);
+        p[wave] = acc_red;
+        p[(size_t)a.partial_waves + wave] = acc_blk;
+    }
+}
+
+// The jump entry of draw k of walker i of the half: small ensembles jump with one table entry per draw (one 128-bit
+// multiply-add), large ones compose a two-level table (256-walker blocks x position inside the block) with the draw offset
+template <class T>
+__device__ __forceinline__ void load_draw_jump(const HalfStepArgs<T>& a, bool direct, int i, int k, Affine128& j_a, Affine128& j_b)
+{
+    if (direct)
+        j_a = a.task_jump[3 * i + k];
+    else
+    {
+        j_a = a.jump_hi[i >> 8];
+        j_b = a.jump_lo[i & 255];
+    }
+}
+
+// The preloaded pointers of chain 0 -> chain `chain`'s piece of each array (ChainGeometry).  Callers keep this behind
+// `if (MC && chain != 0)`: chain 0 -- every single-ensemble launch -- skips the 64-bit products.
+template <class T>
+__device__ __forceinline__ void step_to_chain(int chain, int n, int dims, DrawRec<T>*& draws, T*& pos, T*& logp)
+{
+    draws += draws_chain_offset(chain, n);
+    pos += pos_chain_offset(chain, n, dims);
+    logp = logp_of_chain<T>(logp, n, chain);
 }
 
 // Stored steps reach the host without a copy engine and without a gap in the launch sequence: every launch forwards
@@ -673,21 +721,21 @@ stretch_half_step_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, uint32_
     // `a` is the launch description in the kernarg segment; the h_* locals are the preloaded copies of the
     // fields every wavefront needs before its first memory access (same values, no kernarg fetch)
     const HalfStepArgs<T>& a = rest;
-    // chain blockIdx.y of (hot_bits >> 28) + 1 (ChainGeometry): every per-chain array at its fixed stride; a branch on
+    // chain blockIdx.y of HotBits::chains (ChainGeometry): every per-chain array at its fixed stride; a branch on
     // purpose -- chain 0, i.e. every single-ensemble launch, skips the 64-bit products
         // (MC: built for several chains per launch; the single-ensemble instantiation carries none of it -- measured 2 % of a
     //  65 536-walker launch otherwise)
-    const int chain = MC ? (int)blockIdx.y : 0, chains = MC ? (int)(hot_bits >> 28) + 1 : 1;
+    const int chain = MC ? (int)blockIdx.y : 0, chains = MC ? HotBits::chains(hot_bits) : 1;
     const void* const draws_chain0 = hot_draws;
     if (MC && chain != 0)
     {
         hot_draws += (size_t)chain * 4 * (size_t)hot_n;
-        hot_pos += (size_t)chain * 2 * (size_t)hot_n * (size_t)(hot_bits & 0xFFFu);
+        hot_pos += (size_t)chain * 2 * (size_t)hot_n * (size_t)HotBits::dims(hot_bits);
         hot_logp = reinterpret_cast<T*>(reinterpret_cast<char*>(hot_logp) + (size_t)chain * logp_chain_stride_bytes<T>(hot_n));
         hot_n_accept = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(hot_n_accept) + (size_t)chain * logp_chain_stride_bytes<T>(hot_n));
     }
-    const int h_color = (int)((hot_bits >> 20) & 1u);
-    const int h_parity = (int)((hot_bits >> 24) & 1u);
+    const int h_color = HotBits::color(hot_bits);
+    const int h_parity = HotBits::draw_parity(hot_bits);
     constexpr bool h_draw_wave = DW;  // (hot_bits bit 25 says the same)
     // draw records: this launch reads buffer `parity`, the draws of the colour's next update go to the other one
     const DrawRec<T>* const h_draws = hot_draws + ((size_t)h_parity * 2 + (size_t)h_color) * (size_t)hot_n;
@@ -696,10 +744,10 @@ stretch_half_step_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, uint32_
     T* const h_logp = hot_logp;
     uint32_t* const h_n_accept = hot_n_accept;
     const int h_n = hot_n;
-    const int h_dims = (int)(hot_bits & 0xFFFu);
-    const int h_passes = (int)((hot_bits >> 12) & 0xFFu);
-    const int h_vec_ok = (int)((hot_bits >> 21) & 1u);
-    const int h_use_ctl_save = (int)((hot_bits >> 23) & 1u);
+    const int h_dims = HotBits::dims(hot_bits);
+    const int h_passes = HotBits::passes(hot_bits);
+    const int h_vec_ok = HotBits::vec_ok(hot_bits);
+    const int h_use_ctl_save = HotBits::use_ctl_save(hot_bits);
     const int h_shard_begin = hot_shard_begin;
     const int h_shard_count = hot_shard_count;
     static_assert((LPW & (LPW - 1)) == 0 && LPW >= 1 && LPW <= 64, "LPW must be a power of two <= 64");
@@ -720,7 +768,7 @@ stretch_half_step_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, uint32_
         if (wib == kWavesPerBlock)
         {
             // the workgroup's extra wavefront: next draws of every walker this workgroup updates
-            draw_wave_body<T, 2>(a, jump_tables_behind(draws_chain0, hot_n, ((hot_bits >> 27) & 1u) != 0, chains), hot_ctl_in, Calc::block_scratch_elems(h_dims) != 0,
+            draw_wave_body<T, 2>(a, jump_tables_behind(draws_chain0, hot_n, HotBits::direct_jump(hot_bits) != 0, chains), hot_ctl_in, Calc::block_scratch_elems(h_dims) != 0,
                                  h_draws_next, h_draws_next, 1, h_shard_begin, h_shard_count, blockIdx.x * kWavesPerBlock * nw, kWavesPerBlock * nw, lane, false,
                                  nullptr, -1, chain);
             return;
@@ -940,14 +988,8 @@ __global__ void __launch_bounds__(256) fill_draws_kernel(const HalfStepArgs<T> a
     const int i = a.shard_begin + slot;
     const bool direct = a.task_jump != nullptr;
     Affine128 j_a, j_b;
-    if (direct)
-        j_a = a.task_jump[3 * i + k];
-    else
-    {
-        j_a = a.jump_hi[i >> 8];
-        j_b = a.jump_lo[i & 255];
-    }
-    compute_draw<T>(a, base, j_a, j_b, direct, k, a.draws + ((size_t)a.draw_parity * 2 + (size_t)a.color) * (size_t)a.n + i,
+    load_draw_jump<T>(a, direct, i, k, j_a, j_b);
+    compute_draw<T>(a, base, j_a, j_b, direct, k, a.draws + draw_buffer_index(a.draw_parity, a.color, a.n) + i,
                     with_partner2 != 0, red_base);
 }
 
@@ -969,16 +1011,10 @@ __global__ void __launch_bounds__(192) fill_draws_batch_kernel(const HalfStepArg
     const int i = a.shard_begin + slot;
     const bool direct = a.task_jump != nullptr;
     Affine128 j_a, j_b;
-    if (direct)
-        j_a = a.task_jump[3 * i + k];
-    else
-    {
-        j_a = a.jump_hi[i >> 8];
-        j_b = a.jump_lo[i & 255];
-    }
+    load_draw_jump<T>(a, direct, i, k, j_a, j_b);
     const U128 red_base = apply(step_jump[j], ctl->state);
     const U128 base = colour ? apply(a.half_jump, red_base) : red_base;
-    compute_draw<T>(a, base, j_a, j_b, direct, k, out + ((size_t)j * 2 + (size_t)colour) * (size_t)a.n + i, colour != 0, red_base);
+    compute_draw<T>(a, base, j_a, j_b, direct, k, out + draw_buffer_index(j, colour, a.n) + i, colour != 0, red_base);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1105,29 +1141,29 @@ stretch_half_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, ui
     T* sh_x = reinterpret_cast<T*>(smem) + (threadIdx.x >> 6) * (kStageRows * XS);
 
     const HalfStepArgs<T>& a = rest;
-    // chain blockIdx.y of (hot_bits >> 28) + 1 (ChainGeometry), as in the kernel above
+    // chain blockIdx.y of HotBits::chains (ChainGeometry), as in the kernel above
         // (MC: built for several chains per launch; the single-ensemble instantiation carries none of it -- measured 2 % of a
     //  65 536-walker launch otherwise)
-    const int chain = MC ? (int)blockIdx.y : 0, chains = MC ? (int)(hot_bits >> 28) + 1 : 1;
+    const int chain = MC ? (int)blockIdx.y : 0, chains = MC ? HotBits::chains(hot_bits) : 1;
     const void* const draws_chain0 = hot_draws;
     if (MC && chain != 0)
     {
         hot_draws += (size_t)chain * 4 * (size_t)hot_n;
-        hot_pos += (size_t)chain * 2 * (size_t)hot_n * (size_t)(hot_bits & 0xFFFu);
+        hot_pos += (size_t)chain * 2 * (size_t)hot_n * (size_t)HotBits::dims(hot_bits);
         hot_logp = reinterpret_cast<T*>(reinterpret_cast<char*>(hot_logp) + (size_t)chain * logp_chain_stride_bytes<T>(hot_n));
         hot_n_accept = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(hot_n_accept) + (size_t)chain * logp_chain_stride_bytes<T>(hot_n));
         hot_matrix += (size_t)chain * (size_t)a.params_chain_stride;  // (the chain's own P^T; stride 0: shared)
     }
-    const int h_color = (int)((hot_bits >> 20) & 1u);
-    const int h_parity = (int)((hot_bits >> 24) & 1u);
+    const int h_color = HotBits::color(hot_bits);
+    const int h_parity = HotBits::draw_parity(hot_bits);
     const DrawRec<T>* const h_draws = hot_draws + ((size_t)h_parity * 2 + (size_t)h_color) * (size_t)hot_n;
     DrawRec<T>* const h_draws_next = hot_draws + ((size_t)(1 - h_parity) * 2 + (size_t)h_color) * (size_t)hot_n;
     T* const h_pos = hot_pos;
     T* const h_logp = hot_logp;
     uint32_t* const h_n_accept = hot_n_accept;
     const int h_n = hot_n;
-    const int h_dims = (int)(hot_bits & 0xFFFu);
-    const int h_use_ctl_save = (int)((hot_bits >> 23) & 1u);
+    const int h_dims = HotBits::dims(hot_bits);
+    const int h_use_ctl_save = HotBits::use_ctl_save(hot_bits);
     const int h_shard_begin = hot_shard_begin;
     const int h_shard_count = hot_shard_count;
 
@@ -1137,7 +1173,7 @@ stretch_half_step_mfma_kernel(DrawRec<T>* hot_draws, T* hot_pos, T* hot_logp, ui
         if ((threadIdx.x >> 6) == kWavesPerBlock)
         {
             // the workgroup's extra wavefront: next draws of every walker this workgroup updates
-            draw_wave_body<T, 2>(a, jump_tables_behind(draws_chain0, hot_n, ((hot_bits >> 27) & 1u) != 0, chains), hot_ctl_in,
+            draw_wave_body<T, 2>(a, jump_tables_behind(draws_chain0, hot_n, HotBits::direct_jump(hot_bits) != 0, chains), hot_ctl_in,
                                  false /* no workgroup barrier in this kernel */, h_draws_next, h_draws_next, 1, h_shard_begin,
                                  h_shard_count, blockIdx.x * kWavesPerBlock * NW, kWavesPerBlock * NW, lane, false, nullptr, -1, chain);
             return;
@@ -1364,14 +1400,14 @@ accepted_reduce_kernel(const uint32_t* partials, int partial_slots, int partial_
 {
     __shared__ unsigned sums[4];
     // (blockIdx.y: the chain, see ChainGeometry)
-    partials += (size_t)blockIdx.y * (size_t)partial_slots * 2 * (size_t)partial_waves;
-    ctl_after = reinterpret_cast<const StepCtl*>(reinterpret_cast<const char*>(ctl_after) + (size_t)blockIdx.y * kCtlChainStride);
-    run_ptr = reinterpret_cast<const RunInfo*>(reinterpret_cast<const char*>(run_ptr) + (size_t)blockIdx.y * kCtlChainStride);
+    partials += partial_index((int)blockIdx.y, partial_slots, 0, 0, partial_waves, 0);
+    ctl_after = ctl_of_chain(ctl_after, (int)blockIdx.y);
+    run_ptr = ctl_of_chain(run_ptr, (int)blockIdx.y);
     const RunInfo run = *run_ptr;
     if (run.accepted_per_step == nullptr) return;
     const uint64_t done = ctl_after->step_in_run;
     const uint64_t step = done - (uint64_t)count + blockIdx.x;
-    const uint32_t* src = partials + (size_t)(step % (uint64_t)partial_slots) * 2 * (size_t)partial_waves;
+    const uint32_t* src = partials + partial_index(0, partial_slots, (uint32_t)(step % (uint64_t)partial_slots), 0, partial_waves, 0);
     unsigned s = 0;
     for (int k = threadIdx.x; k < 2 * partial_waves; k += blockDim.x) s += src[k];
     for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);

@@ -210,8 +210,8 @@ def _band_condition(d, dtype, tie_eps):
 def test_band_covers_fp64_distance(cases, dev):
     """The condition under which a decision can differ between device and oracle only where both flag a near tie.
 
-    Both sides compute, from identical u, z, lp_new, lp_old (stretch_kernel.hpp:872-881 and :1299-1305, full_step_kernel.hpp
-    :256-264 and :502-509, batch.hip:115-122; oracle update_walker):
+    Both sides compute, from identical u, z, lp_new, lp_old (stretch_accept in stretch_kernel.hpp, which the full-step and
+    batch accept kernels call and the two half-step kernels spell out; oracle update_walker):
         ln_u  = L(1 - u)                        the two L differ by at most d ulp:  |diff| <= d eps |ln_u|
         zs    = fl(L(z) * (D-1))                d eps |zs| carried through the product, + 1/2 ulp of each side's rounding:
                                                 |diff| <= (d + 1) eps |zs|
@@ -225,7 +225,7 @@ def test_band_covers_fp64_distance(cases, dev):
     My count of roundings is 3, the issue's: one for zs, one for each of the two sums.  The flag's own arithmetic (margin,
     scale: three sums, tie_eps * scale, each rounded; the two sides' scales differ by O(eps) of themselves) moves both sides
     of `margin <= tie_eps * scale` by a few eps RELATIVE: the factor (1 + 16 eps) on the left pays for it.  Differential
-    evolution (diffevo_kernel.hpp:287-296, :447-454) has no zs term and delta = fl(lp_new - lp_old) is the same on both
+    evolution (de_accept in stretch_kernel.hpp) has no zs term and delta = fl(lp_new - lp_old) is the same on both
     sides: d eps scale, covered by the same condition.
 
     fp64: d = 1, measured: the case program's largest distance between fast_log and glibc's log, over arguments on which

@@ -62,3 +62,7 @@ def test_step_kernels_carry_no_promoted_private_arrays_and_no_scratch(tmp_path):
     for k in mc16:
         late = k["name"].split(">(")[0].endswith("true")
         assert k["vgprs"] <= (128 if late else 168), (k["name"][:100], k["vgprs"])
+    # the plain full-step kernel of fp32 dense targets of up to 4 dimensions, several chains per launch: five wavefronts per SIMD
+    # (its proposals ahead of the register pin are written cell by cell for this: full_step_kernel.hpp)
+    d4 = [k for k in step if k["name"].startswith("stretch_full_step_kernel<float, DenseGaussianFn<float>, 4, 1, true>")]
+    assert len(d4) == 1 and d4[0]["vgprs"] <= 96, [(k["name"][:80], k["vgprs"]) for k in d4]
