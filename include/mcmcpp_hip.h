@@ -453,6 +453,38 @@ int mcmcpp_hip_histograms_result(const mcmcpp_hip_histograms* h, int64_t* num_po
                                  int64_t* pairs, int64_t* clamped);
 const char* mcmcpp_hip_histograms_last_error(const mcmcpp_hip_histograms* h);
 
+/* Exact order statistics and exact ranks of the parameters over stored steps (an extension: the reference has only the
+ * binned PercentileAndMaximumFinder above).  N = (steps used) x num_walkers samples per parameter.
+ *   order_statistics  values[p][k] (T, [num_params][n_ranks]) = the sample of parameter p that n_ranks[k] samples of p
+ *                     precede in the total order -inf < ... < -0 < +0 < ... < +inf: its bits are those of a sample in
+ *                     the data.  ranks[n_ranks]: 0 <= rank < N, the same for every parameter, in any order, repeats
+ *                     allowed; 1 <= n_ranks <= 64; 1 <= num_params <= 1024.  Found by most-significant-digit radix
+ *                     selection on order-preserving integer keys: integer counts only, so the result does not depend on
+ *                     scheduling, slicing or chunking.
+ *   rank_counts       below[p][q] / not_above[p][q] (int64, [num_params][n_query]; either may be NULL) = the number of
+ *                     samples x of parameter p with x < query[p][q] / x <= query[p][q], compared as numbers (-0 == +0).
+ *                     query is [num_params][n_query] in T; n_query >= 1.
+ *   steps             n_steps pointers to the steps to use (host memory, the caller has applied its slicing), uploaded in
+ *                     chunks of MCMCPP_HIP_QUANTILE_CHUNK_MB (read per call, default 1024): once when they fit one chunk,
+ *                     once per pass otherwise.
+ *   device_steps      n_steps contiguous steps [n_steps][W][P] in memory of the device, read where they lie; every
+ *                     slice_interval-th from the first is used.
+ * Free functions with a thread-local last error.  MCMCPP_HIP_E_ARG (with a message), before the device is opened, for a bad
+ * dtype, num_params, num_walkers, n_ranks or n_query, a NULL array, slice_interval < 1, N == 0, a rank outside [0, N) and a
+ * NaN query; and for a NaN sample, a device_steps that is not memory of that device, or steps that do not end inside its
+ * allocation.  Nothing is written to the outputs of a call that fails. */
+int mcmcpp_hip_order_statistics(int32_t dtype, int32_t device, const void* const* steps, int64_t n_steps, int32_t num_walkers,
+                                int32_t num_params, const int64_t* ranks, int32_t n_ranks, void* values);
+int mcmcpp_hip_order_statistics_device(int32_t dtype, int32_t device, const void* device_steps, int64_t n_steps,
+                                       int64_t slice_interval, int32_t num_walkers, int32_t num_params, const int64_t* ranks,
+                                       int32_t n_ranks, void* values);
+int mcmcpp_hip_rank_counts(int32_t dtype, int32_t device, const void* const* steps, int64_t n_steps, int32_t num_walkers,
+                           int32_t num_params, const void* query, int32_t n_query, int64_t* below, int64_t* not_above);
+int mcmcpp_hip_rank_counts_device(int32_t dtype, int32_t device, const void* device_steps, int64_t n_steps, int64_t slice_interval,
+                                  int32_t num_walkers, int32_t num_params, const void* query, int32_t n_query, int64_t* below,
+                                  int64_t* not_above);
+const char* mcmcpp_hip_order_statistics_last_error(void);
+
 int mcmcpp_hip_abi_version(void);
 
 #ifdef __cplusplus

@@ -36,6 +36,8 @@ EXPORTS = [
     "mcmcpp_hip_autocorr_times", "mcmcpp_hip_autocorr_times_device", "mcmcpp_hip_autocorr_last_error",
     "mcmcpp_hip_histograms_create", "mcmcpp_hip_histograms_destroy", "mcmcpp_hip_histograms_compute",
     "mcmcpp_hip_histograms_compute_device", "mcmcpp_hip_histograms_result", "mcmcpp_hip_histograms_last_error",
+    "mcmcpp_hip_order_statistics", "mcmcpp_hip_order_statistics_device", "mcmcpp_hip_rank_counts", "mcmcpp_hip_rank_counts_device",
+    "mcmcpp_hip_order_statistics_last_error",
 ]
 
 
@@ -155,6 +157,13 @@ def lib():
             L.mcmcpp_hip_histograms_result.argtypes = [vp, C.POINTER(i64), vp, vp, vp, vp]
             L.mcmcpp_hip_histograms_last_error.argtypes = [vp]
             L.mcmcpp_hip_histograms_last_error.restype = C.c_char_p
+        if hasattr(L, "mcmcpp_hip_order_statistics"):
+            L.mcmcpp_hip_order_statistics.argtypes = [i32, i32, C.POINTER(vp), i64, i32, i32, vp, i32, vp]
+            L.mcmcpp_hip_order_statistics_device.argtypes = [i32, i32, vp, i64, i64, i32, i32, vp, i32, vp]
+            L.mcmcpp_hip_rank_counts.argtypes = [i32, i32, C.POINTER(vp), i64, i32, i32, vp, i32, vp, vp]
+            L.mcmcpp_hip_rank_counts_device.argtypes = [i32, i32, vp, i64, i64, i32, i32, vp, i32, vp, vp]
+            L.mcmcpp_hip_order_statistics_last_error.argtypes = []
+            L.mcmcpp_hip_order_statistics_last_error.restype = C.c_char_p
         _lib = L
     return _lib
 
@@ -702,3 +711,110 @@ def autocorr_times_device(steps, n_steps=None, W=None, D=None, dtype=None, walke
     if rc != OK:
         raise HipError(rc, (lib().mcmcpp_hip_autocorr_last_error() or b"").decode())
     return times
+
+
+def _quantile_source(steps, slice_interval, dtype, device):
+    """What order_statistics and rank_counts hand the library: (dtype, device, W, P, N, call), where call(host_fn, device_fn,
+    *rest) runs the entry point that fits `steps` -- a numpy array [(n, W, P)] (host path: the pointers of every
+    slice_interval-th step) or a contiguous device tensor (n, W, P) (device path: read where it lies, no copy)."""
+    if slice_interval < 1:
+        raise ValueError("slice_interval must be at least 1")
+    if _is_tensor(steps):
+        import torch
+        if steps.dim() != 3 or steps.dtype not in (torch.float64, torch.float32):
+            raise ValueError("device steps must be a float64 or float32 tensor (n, W, P)")
+        tensor_dtype = F64 if steps.dtype == torch.float64 else F32
+        if dtype is not None and dtype != tensor_dtype:
+            raise ValueError("device steps are %s, not the dtype asked for" % steps.dtype)
+        n, W, P = (int(v) for v in steps.shape)
+        if device < 0 and steps.is_cuda:
+            device = steps.device.index
+        ptr, n = _device_steps(steps, None, W, P, tensor_dtype, device)
+
+        def call(host_fn, device_fn, *rest):
+            return device_fn(tensor_dtype, device, C.c_void_p(ptr), n, slice_interval, W, P, *rest)
+        return tensor_dtype, W, P, ((n + slice_interval - 1) // slice_interval) * W, call
+    steps = np.asarray(steps)
+    if dtype is None:
+        dtype = F32 if steps.dtype == np.float32 else F64
+    if steps.ndim != 3:
+        raise ValueError("steps must have shape (n, W, P), not %s" % (steps.shape,))
+    n, W, P = steps.shape
+    # (a step that is not contiguous by itself is copied; the steps need not lie one behind the other)
+    blocks = [np.ascontiguousarray(steps[k], dtype=np_dtype(dtype)) for k in range(0, n, slice_interval)]
+    ptrs = (C.c_void_p * max(1, len(blocks)))(*[b.ctypes.data for b in blocks])
+
+    def call(host_fn, device_fn, *rest):
+        return host_fn(dtype, device, ptrs, len(blocks), W, P, *rest)
+    return dtype, W, P, len(blocks) * W, call
+
+
+def _quantile_check(rc):
+    if rc != OK:
+        raise HipError(rc, (lib().mcmcpp_hip_order_statistics_last_error() or b"").decode())
+
+
+def order_statistics(steps, ranks, slice_interval=1, dtype=None, device=-1):
+    """Exact order statistics of every parameter over stored steps (include/mcmcpp_hip.h, mcmcpp_hip_order_statistics): values[(P,
+    len(ranks))], values[p][k] the sample of parameter p with 0-based rank ranks[k] among the N = (steps used) x W samples of p,
+    in the order -inf < ... < -0 < +0 < ... < +inf.  steps: a numpy array [(n, W, P)], or a contiguous torch tensor (n, W, P)
+    on the GPU, which is read where it lies.  Every slice_interval-th step is used, starting with the first."""
+    dtype, W, P, N, call = _quantile_source(steps, slice_interval, dtype, device)
+    ranks = np.ascontiguousarray(ranks, dtype=np.int64).ravel()
+    values = np.zeros((P, ranks.size), np_dtype(dtype))
+    _quantile_check(call(lib().mcmcpp_hip_order_statistics, lib().mcmcpp_hip_order_statistics_device, _ptr(ranks), ranks.size, _ptr(values)))
+    return values
+
+
+def rank_counts(steps, query, slice_interval=1, dtype=None, device=-1):
+    """(below, not_above), both int64 [(P, n_query)]: the samples x of parameter p with x < query[p][q] and with x <= query[p][q],
+    compared as numbers (-0 == +0), counted on the device (mcmcpp_hip_rank_counts).  steps as for order_statistics; query
+    [(P, n_query)], or [(n_query,)] for every parameter alike."""
+    dtype, W, P, N, call = _quantile_source(steps, slice_interval, dtype, device)
+    query = np.asarray(query, dtype=np_dtype(dtype))
+    if query.ndim == 1:
+        query = np.broadcast_to(query, (P, query.size))
+    if query.ndim != 2 or query.shape[0] != P:
+        raise ValueError("query must have shape (%d, n_query), not %s" % (P, query.shape))
+    query = np.ascontiguousarray(query)
+    below, not_above = np.zeros(query.shape, np.int64), np.zeros(query.shape, np.int64)
+    _quantile_check(call(lib().mcmcpp_hip_rank_counts, lib().mcmcpp_hip_rank_counts_device, _ptr(query), query.shape[1], _ptr(below), _ptr(not_above)))
+    return below, not_above
+
+
+def quantile_ranks(q, N):
+    """(h, lo, hi) of the quantiles q in [0, 1] among N samples: h = q (N - 1) in float64, lo = floor(h), hi = ceil(h)"""
+    q = np.asarray(q, dtype=np.float64).ravel()
+    if N < 1 or not np.all((q >= 0) & (q <= 1)):
+        raise ValueError("quantiles need at least one sample and 0 <= q <= 1")
+    h = q * np.float64(N - 1)
+    return h, np.floor(h).astype(np.int64), np.ceil(h).astype(np.int64)
+
+
+def quantile_rule(x_lo, x_hi, h, method, np_t):
+    """The value of a quantile from the order statistics of ranks floor(h) and ceil(h) ([(P, len(h))] each): "lower", "higher", or
+    "linear" = x_lo + (x_hi - x_lo) (h - floor(h)) in float64, rounded once to np_t."""
+    if method == "lower":
+        return x_lo.astype(np_t)
+    if method == "higher":
+        return x_hi.astype(np_t)
+    if method != "linear":
+        raise ValueError('method must be "linear", "lower" or "higher"')
+    lo, hi = x_lo.astype(np.float64), x_hi.astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        mid = lo + (hi - lo) * (h - np.floor(h))
+    return np.where(x_lo == x_hi, lo, mid).astype(np_t)  # (equal neighbours, infinite ones included, are the answer)
+
+
+def quantiles(steps, q, method="linear", slice_interval=1, dtype=None, device=-1):
+    """Exact quantiles q (in [0, 1]) of every parameter: [(P, len(q))], from the order statistics of ranks floor(h) and ceil(h),
+    h = q (N - 1): see quantile_rule for the three methods."""
+    if method not in ("linear", "lower", "higher"):
+        raise ValueError('method must be "linear", "lower" or "higher"')
+    dtype, W, P, N, _ = _quantile_source(steps, slice_interval, dtype, device)
+    h, lo, hi = quantile_ranks(q, N)
+    if not h.size:
+        return np.zeros((P, 0), np_dtype(dtype))
+    ranks, where = np.unique(np.concatenate([lo, hi]), return_inverse=True)  # (each rank is selected once)
+    x = order_statistics(steps, ranks, slice_interval, dtype, device)
+    return quantile_rule(x[:, where[:h.size]], x[:, where[h.size:]], h, method, np_dtype(dtype))
