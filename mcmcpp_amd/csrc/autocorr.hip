@@ -25,13 +25,11 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <memory>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/mcmcpp_hip.h"
-#include "sampler_base.hpp"
+#include "analysis_host.hpp"
 
 namespace
 {
@@ -277,18 +275,7 @@ inline void ac_sincos(float a, float* s, float* c) { ::sincosf(a, s, c); }
 
 thread_local std::string g_ac_error;
 
-int ac_fail(int code, const std::string& msg)
-{
-    g_ac_error = msg;
-    return code;
-}
-
-#define AC_TRY(expr)                                                                                          \
-    do                                                                                                        \
-    {                                                                                                         \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess) return ac_fail(MCMCPP_HIP_E_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
+int ac_fail(int code, const std::string& msg) { return mcmcpp::analysis_fail(g_ac_error, code, msg); }
 
 template <class T>
 // steps: n_steps host pointers, or nullptr when device_steps holds the whole [n_steps][W][D] chain in device memory
@@ -314,13 +301,8 @@ int autocorr_times(const void* const* steps, const T* device_steps, int64_t n_st
     mcmcpp::DeviceBuffer<T> d_upload, d_avg, d_tw, d_acov, d_sum, d_comp, d_times, d_scratch;
     mcmcpp::DeviceBuffer<int> d_idx;
     // (declared behind the buffers, so that on every way out the stream is idle and gone before they free themselves)
-    hipStream_t stream = nullptr;
-    AC_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    const auto sync_and_destroy = [](hipStream_t s) {
-        (void)hipStreamSynchronize(s);
-        (void)hipStreamDestroy(s);
-    };
-    const std::unique_ptr<std::remove_pointer_t<hipStream_t>, decltype(sync_and_destroy)> stream_owner(stream, sync_and_destroy);
+    mcmcpp::Stream stream;
+    ANALYSIS_TRY(g_ac_error, hipStreamCreateWithFlags(stream.replace(), hipStreamNonBlocking));
     // walkers per pass over the transforms: bounded by 1 GiB of functions and 2 GiB of global scratch
     size_t per_walker = sizeof(T) * (size_t)D * n;
     size_t per_walker_scratch = lds ? 0 : sizeof(T) * (size_t)D * 2 * fft;
@@ -334,18 +316,12 @@ int autocorr_times(const void* const* steps, const T* device_steps, int64_t n_st
         return ac_fail(MCMCPP_HIP_E_NOMEM, "autocorr_times: cannot allocate device memory for the chain and the work arrays");
 
     const T* d_steps = steps ? d_upload.get() : device_steps;
-    // upload: steps that follow each other in host memory go in one copy
-    for (int64_t s = 0; steps && s < n_steps;)
-    {
-        int64_t e = s + 1;
-        while (e < n_steps && static_cast<const T*>(steps[e]) == static_cast<const T*>(steps[e - 1]) + step_elems) ++e;
-        AC_TRY(hipMemcpyAsync(d_upload + (size_t)s * step_elems, steps[s], sizeof(T) * (size_t)(e - s) * step_elems, hipMemcpyHostToDevice, stream));
-        s = e;
-    }
-    AC_TRY(hipMemcpyAsync(d_tw, tw.data(), sizeof(T) * tw.size(), hipMemcpyHostToDevice, stream));
-    AC_TRY(hipMemcpyAsync(d_idx, walker_idx.data(), sizeof(int) * walker_idx.size(), hipMemcpyHostToDevice, stream));
-    AC_TRY(hipMemsetAsync(d_sum, 0, sizeof(T) * (size_t)D * n, stream));
-    AC_TRY(hipMemsetAsync(d_comp, 0, sizeof(T) * (size_t)D * n, stream));
+    // upload: one chunk, the whole chain
+    if (steps) ANALYSIS_TRY(g_ac_error, mcmcpp::copy_steps(d_upload.get(), [&](long long k) { return steps[k]; }, 0, n_steps, sizeof(T) * step_elems, hipMemcpyHostToDevice, stream));
+    ANALYSIS_TRY(g_ac_error, hipMemcpyAsync(d_tw, tw.data(), sizeof(T) * tw.size(), hipMemcpyHostToDevice, stream));
+    ANALYSIS_TRY(g_ac_error, hipMemcpyAsync(d_idx, walker_idx.data(), sizeof(int) * walker_idx.size(), hipMemcpyHostToDevice, stream));
+    ANALYSIS_TRY(g_ac_error, hipMemsetAsync(d_sum, 0, sizeof(T) * (size_t)D * n, stream));
+    ANALYSIS_TRY(g_ac_error, hipMemsetAsync(d_comp, 0, sizeof(T) * (size_t)D * n, stream));
 
     const long long series_total = (long long)use * D;
     hipLaunchKernelGGL(ac_chain_average_kernel<T>, dim3((unsigned)((series_total + kAcThreads - 1) / kAcThreads)), dim3(kAcThreads), 0, stream, d_steps, n,
@@ -364,10 +340,10 @@ int autocorr_times(const void* const* steps, const T* device_steps, int64_t n_st
                            D, cw, d_sum, d_comp);
     }
     hipLaunchKernelGGL(ac_window_kernel<T>, dim3((unsigned)D), dim3(kAcThreads), 0, stream, d_sum, n, use, window_scaling, d_times);
-    AC_TRY(hipGetLastError());
-    AC_TRY(hipMemcpyAsync(times, d_times, sizeof(T) * (size_t)D, hipMemcpyDeviceToHost, stream));
-    if (functions) AC_TRY(hipMemcpyAsync(functions, d_sum, sizeof(T) * (size_t)D * n, hipMemcpyDeviceToHost, stream));
-    AC_TRY(hipStreamSynchronize(stream));
+    ANALYSIS_TRY(g_ac_error, hipGetLastError());
+    ANALYSIS_TRY(g_ac_error, hipMemcpyAsync(times, d_times, sizeof(T) * (size_t)D, hipMemcpyDeviceToHost, stream));
+    if (functions) ANALYSIS_TRY(g_ac_error, hipMemcpyAsync(functions, d_sum, sizeof(T) * (size_t)D * n, hipMemcpyDeviceToHost, stream));
+    ANALYSIS_TRY(g_ac_error, hipStreamSynchronize(stream));
     return MCMCPP_HIP_OK;
 }
 }  // namespace

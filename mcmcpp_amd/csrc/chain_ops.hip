@@ -3,12 +3,11 @@
 // (mcmcpp_hip_device_alloc / _free), copies to, from and inside it (mcmcpp_hip_device_copy), and sliceAndBurnChain in place
 // (mcmcpp_hip_device_chain_compact, chain_compact_kernel).  Which steps are kept and which launches move them is
 // chain_compact_plan.hpp's; this file holds no selection rule of its own.
-#include <memory>
 #include <string>
 #include <type_traits>
 
+#include "analysis_host.hpp"
 #include "chain_compact_plan.hpp"
-#include "sampler_base.hpp"
 
 namespace
 {
@@ -47,53 +46,15 @@ __global__ void __launch_bounds__(kCompactThreads) chain_compact_kernel(T* steps
 
 thread_local std::string g_chain_error;
 
-int chain_fail(int code, const std::string& msg)
-{
-    g_chain_error = msg;
-    return code;
-}
-
-#define CHAIN_TRY(expr)                                                                                            \
-    do                                                                                                             \
-    {                                                                                                              \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess) return chain_fail(MCMCPP_HIP_E_HIP, std::string(#expr ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-// Does [p, p + bytes) lie inside one allocation of device `device`?  (As the samplers ask before run_device launches anything.)
-int check_chain_range(const void* p, size_t bytes, int device)
-{
-    hipPointerAttribute_t at;
-    std::memset(&at, 0, sizeof at);
-    const hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) (void)hipGetLastError();
-    if (e != hipSuccess || at.type != hipMemoryTypeDevice) return chain_fail(MCMCPP_HIP_E_ARG, "device_chain_compact: device_steps is not device memory");
-    if (at.device != device)
-        return chain_fail(MCMCPP_HIP_E_ARG, "device_chain_compact: device_steps is memory of device " + std::to_string(at.device) + ", not of device " + std::to_string(device));
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        return chain_fail(MCMCPP_HIP_E_ARG, "device_chain_compact: the runtime does not know the allocation device_steps lies in");
-    }
-    if ((const char*)p < (const char*)base || bytes > (size_t)((const char*)base + size - (const char*)p))
-        return chain_fail(MCMCPP_HIP_E_ARG, "device_chain_compact: n_steps steps do not end inside the allocation around device_steps");
-    return MCMCPP_HIP_OK;
-}
+int chain_fail(int code, const std::string& msg) { return mcmcpp::analysis_fail(g_chain_error, code, msg); }
 
 template <class T>
 int compact(T* steps, int64_t step_elems, int64_t burn_in, int64_t interval, int64_t kept)
 {
     const bool vec = (sizeof(T) * (size_t)step_elems) % 16 == 0 && ((uintptr_t)steps & 15) == 0;
     const long long per_step = vec ? (long long)(sizeof(T) * (size_t)step_elems / 16) : (long long)step_elems;
-    hipStream_t stream = nullptr;
-    CHAIN_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    const auto sync_and_destroy = [](hipStream_t s) {
-        (void)hipStreamSynchronize(s);
-        (void)hipStreamDestroy(s);
-    };
-    const std::unique_ptr<std::remove_pointer_t<hipStream_t>, decltype(sync_and_destroy)> stream_owner(stream, sync_and_destroy);
+    mcmcpp::Stream stream;
+    ANALYSIS_TRY(g_chain_error, hipStreamCreateWithFlags(stream.replace(), hipStreamNonBlocking));
     // blocks along a step: one per kCompactUnroll * kCompactThreads pieces, so that a thread holds kCompactUnroll pieces at once
     const long long per_block = (long long)kCompactUnroll * kCompactThreads;
     long long gx = (per_step + per_block - 1) / per_block;
@@ -111,9 +72,9 @@ int compact(T* steps, int64_t step_elems, int64_t burn_in, int64_t interval, int
         else
             hipLaunchKernelGGL((chain_compact_kernel<T, false>), grid, dim3(kCompactThreads), 0, stream, steps, per_step, (long long)step_elems,
                                (long long)burn_in, (long long)interval, (long long)wave.first, (long long)wave.count);
-        CHAIN_TRY(hipGetLastError());
+        ANALYSIS_TRY(g_chain_error, hipGetLastError());
     }
-    CHAIN_TRY(hipStreamSynchronize(stream));
+    ANALYSIS_TRY(g_chain_error, hipStreamSynchronize(stream));
     return MCMCPP_HIP_OK;
 }
 }  // namespace
@@ -148,8 +109,8 @@ int mcmcpp_hip_device_copy(void* dst, const void* src, uint64_t bytes)
 {
     if (bytes == 0) return MCMCPP_HIP_OK;
     if (!dst || !src) return chain_fail(MCMCPP_HIP_E_ARG, "device_copy: dst and src must not be NULL");
-    CHAIN_TRY(hipMemcpy(dst, src, (size_t)bytes, hipMemcpyDefault));
-    CHAIN_TRY(hipStreamSynchronize(nullptr));  // (a copy inside device memory may return before it is done)
+    ANALYSIS_TRY(g_chain_error, hipMemcpy(dst, src, (size_t)bytes, hipMemcpyDefault));
+    ANALYSIS_TRY(g_chain_error, hipStreamSynchronize(nullptr));  // (a copy inside device memory may return before it is done)
     return MCMCPP_HIP_OK;
 }
 
@@ -171,7 +132,7 @@ int mcmcpp_hip_device_chain_compact(int32_t dtype, int32_t device, void* device_
     std::string why;
     if (int rc = mcmcpp::open_gfx950_device(device, &device, &prop, &why)) return chain_fail(rc, "device_chain_compact: " + why);
     // every source lies below n_steps (the plan's rule) and every destination below its source: nothing outside these bytes is touched
-    if (int rc = check_chain_range(device_steps, elem * (size_t)step_elems * (size_t)n_steps, device)) return rc;
+    if (int rc = mcmcpp::check_device_steps(g_chain_error, "device_chain_compact", device_steps, elem * (size_t)step_elems * (size_t)n_steps, device)) return rc;
     if (dtype == MCMCPP_HIP_F64) return compact(static_cast<double*>(device_steps), step_elems, burn_in, interval, left);
     return compact(static_cast<float*>(device_steps), step_elems, burn_in, interval, left);
 }

@@ -24,7 +24,6 @@
 
 #include <cstdint>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <new>
@@ -32,8 +31,8 @@
 #include <vector>
 
 #include "../../include/mcmcpp_hip.h"
+#include "analysis_host.hpp"
 #include "hist_plan.hpp"
-#include "sampler_base.hpp"
 
 namespace
 {
@@ -201,33 +200,18 @@ struct mcmcpp_hip_histograms
     mcmcpp::DeviceBuffer<> d_part;       // bounds partials
     mcmcpp::DeviceBuffer<> d_chunk;      // host path upload buffer
     mcmcpp::DeviceBuffer<> d_idx;        // bin indices [P][col]
-    hipStream_t stream = nullptr;        // (destroyed after the buffers: mcmcpp_hip_histograms_destroy)
     bool have_result = false;
     long long points = 0;
     std::vector<unsigned char> bounds;  // [P][2] in T
+    // LAST: destroyed first, and idle by then -- nothing it enqueued still uses a buffer above when that frees itself
+    mcmcpp::Stream stream;
 };
 
 namespace
 {
 thread_local std::string g_hist_error;
 
-int fail(mcmcpp_hip_histograms* h, int code, const std::string& msg, hipError_t e = hipSuccess)
-{
-    std::string m = msg;
-    if (e != hipSuccess) m += std::string(": ") + hipGetErrorString(e);
-    if (h)
-        h->error = m;
-    else
-        g_hist_error = m;
-    return code;
-}
-
-#define HIST_TRY(expr)                                                     \
-    do                                                                     \
-    {                                                                      \
-        hipError_t e_ = (expr);                                            \
-        if (e_ != hipSuccess) return fail(h, MCMCPP_HIP_E_HIP, #expr, e_); \
-    } while (0)
+int fail(mcmcpp_hip_histograms* h, int code, const std::string& msg) { return mcmcpp::analysis_fail(h ? h->error : g_hist_error, code, msg); }
 
 int ensure(mcmcpp_hip_histograms* h, mcmcpp::DeviceBuffer<>& buf, size_t bytes, const char* what)
 {
@@ -236,17 +220,10 @@ int ensure(mcmcpp_hip_histograms* h, mcmcpp::DeviceBuffer<>& buf, size_t bytes, 
     return MCMCPP_HIP_OK;
 }
 
-// A source of selected samples: n_steps steps of W*P elements, step k at base + k * step_stride (elements)
-template <class T>
-struct Span
-{
-    const T* base;
-    long long step_stride;
-    long long n_steps;
-};
+using mcmcpp::StepSpan;
 
 template <class T>
-int bounds_pass(mcmcpp_hip_histograms* h, const Span<T>& sp, std::vector<T>& lo, std::vector<T>& hi)
+int bounds_pass(mcmcpp_hip_histograms* h, const StepSpan<T>& sp, std::vector<T>& lo, std::vector<T>& hi)
 {
     const unsigned n = (unsigned)(sp.n_steps * h->W);
     if (n == 0) return MCMCPP_HIP_OK;
@@ -257,10 +234,10 @@ int bounds_pass(mcmcpp_hip_histograms* h, const Span<T>& sp, std::vector<T>& lo,
     if (rc) return rc;
     hipLaunchKernelGGL((hist_bounds_kernel<T>), dim3(blocks), dim3(kHistThreads), 0, h->stream, sp.base, sp.step_stride, (unsigned)h->W, h->P,
                        n, per, (T*)h->d_part.get(), h->d_nan);
-    HIST_TRY(hipGetLastError());
+    ANALYSIS_TRY(h->error, hipGetLastError());
     std::vector<T> part(2 * (size_t)blocks * h->P);
-    HIST_TRY(hipMemcpyAsync(part.data(), h->d_part, pbytes, hipMemcpyDeviceToHost, h->stream));
-    HIST_TRY(hipStreamSynchronize(h->stream));
+    ANALYSIS_TRY(h->error, hipMemcpyAsync(part.data(), h->d_part, pbytes, hipMemcpyDeviceToHost, h->stream));
+    ANALYSIS_TRY(h->error, hipStreamSynchronize(h->stream));
     for (unsigned b = 0; b < blocks; ++b)
         for (int p = 0; p < h->P; ++p)
         {
@@ -272,7 +249,7 @@ int bounds_pass(mcmcpp_hip_histograms* h, const Span<T>& sp, std::vector<T>& lo,
 }
 
 template <class T, class I>
-int count_pass_t(mcmcpp_hip_histograms* h, const Span<T>& sp)
+int count_pass_t(mcmcpp_hip_histograms* h, const StepSpan<T>& sp)
 {
     const unsigned n = (unsigned)(sp.n_steps * h->W);
     if (n == 0) return MCMCPP_HIP_OK;
@@ -284,23 +261,23 @@ int count_pass_t(mcmcpp_hip_histograms* h, const Span<T>& sp)
     const int bins = h->bins;
     hipLaunchKernelGGL((hist_bin_kernel<T, I>), dim3(plan.bin_blocks), dim3(kHistThreads), 0, h->stream, sp.base, sp.step_stride, (unsigned)h->W, h->P, n,
                        (const T*)h->d_edges.get(), bins, idx, col, h->d_clamped);
-    HIST_TRY(hipGetLastError());
+    ANALYSIS_TRY(h->error, hipGetLastError());
     hipLaunchKernelGGL((hist_single_kernel<I>), dim3(plan.single_blocks, h->P), dim3(kHistThreads), plan.single_lds_bytes, h->stream, idx, col, n,
                        plan.single_per, bins, plan.single_lds, h->d_single);
-    HIST_TRY(hipGetLastError());
+    ANALYSIS_TRY(h->error, hipGetLastError());
     const size_t b2 = (size_t)bins * bins;
     for (long long i = 0; i < plan.pair_launches; ++i)  // (none without pairs; more than one past the grid.y limit)
     {
         const mcmcpp::HistPairLaunch l = plan.pair_launch(i);
         hipLaunchKernelGGL((hist_pairs_kernel<I>), dim3(plan.pair_blocks, (unsigned)l.now), dim3(kHistThreads), plan.pair_lds_bytes, h->stream, idx, col, n,
                            plan.pair_per, bins, h->d_ij + 2 * l.q0, plan.npairs - l.q0, plan.tile, plan.pair_lds, h->d_pairs + (size_t)l.q0 * b2);
-        HIST_TRY(hipGetLastError());
+        ANALYSIS_TRY(h->error, hipGetLastError());
     }
     return MCMCPP_HIP_OK;
 }
 
 template <class T>
-int count_pass(mcmcpp_hip_histograms* h, const Span<T>& sp)
+int count_pass(mcmcpp_hip_histograms* h, const StepSpan<T>& sp)
 {
     switch (h->idx_bytes)
     {
@@ -373,10 +350,10 @@ void finish_bounds(mcmcpp_hip_histograms* h, const std::vector<T>& lo_in, const 
 int reset_counts(mcmcpp_hip_histograms* h)
 {
     h->have_result = false;
-    HIST_TRY(hipMemsetAsync(h->d_single, 0, sizeof(unsigned long long) * (size_t)h->P * h->bins, h->stream));
-    if (h->d_pairs) HIST_TRY(hipMemsetAsync(h->d_pairs, 0, sizeof(unsigned long long) * (size_t)h->npairs * h->bins * h->bins, h->stream));
-    HIST_TRY(hipMemsetAsync(h->d_clamped, 0, sizeof(unsigned long long) * h->P, h->stream));
-    HIST_TRY(hipMemsetAsync(h->d_nan, 0, sizeof(int), h->stream));
+    ANALYSIS_TRY(h->error, hipMemsetAsync(h->d_single, 0, sizeof(unsigned long long) * (size_t)h->P * h->bins, h->stream));
+    if (h->d_pairs) ANALYSIS_TRY(h->error, hipMemsetAsync(h->d_pairs, 0, sizeof(unsigned long long) * (size_t)h->npairs * h->bins * h->bins, h->stream));
+    ANALYSIS_TRY(h->error, hipMemsetAsync(h->d_clamped, 0, sizeof(unsigned long long) * h->P, h->stream));
+    ANALYSIS_TRY(h->error, hipMemsetAsync(h->d_nan, 0, sizeof(int), h->stream));
     return MCMCPP_HIP_OK;
 }
 
@@ -384,85 +361,39 @@ template <class T>
 int after_bounds(mcmcpp_hip_histograms* h, const std::vector<T>& lo, const std::vector<T>& hi)
 {
     int nan = 0;
-    HIST_TRY(hipMemcpyAsync(&nan, h->d_nan, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIST_TRY(hipStreamSynchronize(h->stream));
+    ANALYSIS_TRY(h->error, hipMemcpyAsync(&nan, h->d_nan, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    ANALYSIS_TRY(h->error, hipStreamSynchronize(h->stream));
     if (nan) return fail(h, MCMCPP_HIP_E_ARG, "histograms: the selected samples contain a NaN (the reference would index with int(NaN))");
     finish_bounds<T>(h, lo, hi);
-    HIST_TRY(hipMemcpyAsync(h->d_edges, h->bounds.data(), h->bounds.size(), hipMemcpyHostToDevice, h->stream));
+    ANALYSIS_TRY(h->error, hipMemcpyAsync(h->d_edges, h->bounds.data(), h->bounds.size(), hipMemcpyHostToDevice, h->stream));
     return MCMCPP_HIP_OK;
 }
 
-// steps per chunk of either pass
-long long steps_per_chunk(const mcmcpp_hip_histograms* h, size_t step_bytes) { return mcmcpp::hist_steps_per_chunk(h->chunk_bytes, step_bytes, h->W); }
-
+// the bounds pass, the binning and the count pass over the source's chunks (a host selection of one chunk is uploaded once)
 template <class T>
-int compute_host(mcmcpp_hip_histograms* h, const void* const* steps, int64_t n_steps)
+int compute(mcmcpp_hip_histograms* h, mcmcpp::StepSource<T> src)
 {
-    const size_t step_elems = (size_t)h->W * h->P, step_bytes = sizeof(T) * step_elems;
-    const long long per = steps_per_chunk(h, step_bytes);
-    const long long first_chunk = n_steps < per ? n_steps : per;
-    int rc = ensure(h, h->d_chunk, step_bytes * (size_t)(first_chunk > 0 ? first_chunk : 1), "the upload buffer");
+    const long long per = mcmcpp::hist_steps_per_chunk(h->chunk_bytes, sizeof(T) * (size_t)h->W * h->P, h->W);
+    int rc = ensure(h, h->d_chunk, src.upload_bytes(per), "the upload buffer");
     if (rc) return rc;
-    auto upload = [&](long long k0, long long now) -> int {
-        HIST_TRY(hipStreamSynchronize(h->stream));  // the previous chunk's kernels have read the buffer
-        for (long long k = 0; k < now;)
-        {
-            // a run of steps that are contiguous in host memory goes in one copy
-            const char* src = (const char*)steps[k0 + k];
-            long long run = 1;
-            while (k + run < now && (const char*)steps[k0 + k + run] == src + step_bytes * (size_t)run) ++run;
-            HIST_TRY(hipMemcpyAsync((char*)h->d_chunk.get() + step_bytes * (size_t)k, src, step_bytes * (size_t)run, hipMemcpyHostToDevice, h->stream));
-            k += run;
-        }
-        return MCMCPP_HIP_OK;
-    };
     std::vector<T> lo(h->P, std::numeric_limits<T>::max()), hi(h->P, std::numeric_limits<T>::min());
-    const Span<T> whole{(const T*)h->d_chunk.get(), (long long)step_elems, 0};
-    for (long long k0 = 0; k0 < n_steps; k0 += per)
-    {
-        const long long now = (n_steps - k0 < per) ? n_steps - k0 : per;
-        if ((rc = upload(k0, now))) return rc;
-        Span<T> sp = whole;
-        sp.n_steps = now;
-        if ((rc = bounds_pass<T>(h, sp, lo, hi))) return rc;
-    }
+    if ((rc = src.for_each_chunk(per, [&](const StepSpan<T>& sp) { return bounds_pass<T>(h, sp, lo, hi); }))) return rc;
     if ((rc = after_bounds<T>(h, lo, hi))) return rc;
-    for (long long k0 = 0; k0 < n_steps; k0 += per)
-    {
-        const long long now = (n_steps - k0 < per) ? n_steps - k0 : per;
-        if (n_steps > per && (rc = upload(k0, now))) return rc;  // one chunk: still resident from the bounds pass
-        Span<T> sp = whole;
-        sp.n_steps = now;
-        if ((rc = count_pass<T>(h, sp))) return rc;
-    }
-    HIST_TRY(hipStreamSynchronize(h->stream));
-    h->points = (long long)n_steps * h->W;
+    if ((rc = src.for_each_chunk(per, [&](const StepSpan<T>& sp) { return count_pass<T>(h, sp); }))) return rc;
+    ANALYSIS_TRY(h->error, hipStreamSynchronize(h->stream));
+    h->points = src.used * h->W;
     h->have_result = true;
     return MCMCPP_HIP_OK;
 }
 
-template <class T>
-int compute_device(mcmcpp_hip_histograms* h, const T* d, int64_t n_steps, int64_t slice)
+// reset, then compute<T> of the handle's type: `used` host pointers, or every slice-th step behind device_steps
+int compute_entry(mcmcpp_hip_histograms* h, const void* const* steps, const void* device_steps, long long used, long long slice)
 {
-    const size_t step_elems = (size_t)h->W * h->P;
-    const long long used = (n_steps + slice - 1) / slice;
-    const long long per = steps_per_chunk(h, sizeof(T) * step_elems);
-    std::vector<T> lo(h->P, std::numeric_limits<T>::max()), hi(h->P, std::numeric_limits<T>::min());
-    int rc;
-    for (int pass = 0; pass < 2; ++pass)
-    {
-        for (long long k0 = 0; k0 < used; k0 += per)
-        {
-            const long long now = (used - k0 < per) ? used - k0 : per;
-            const Span<T> sp{d + (size_t)(k0 * slice) * step_elems, (long long)(slice * (long long)step_elems), now};
-            if ((rc = pass == 0 ? bounds_pass<T>(h, sp, lo, hi) : count_pass<T>(h, sp))) return rc;
-        }
-        if (pass == 0 && (rc = after_bounds<T>(h, lo, hi))) return rc;
-    }
-    HIST_TRY(hipStreamSynchronize(h->stream));
-    h->points = (long long)used * h->W;
-    h->have_result = true;
-    return MCMCPP_HIP_OK;
+    ANALYSIS_TRY(h->error, hipSetDevice(h->device));
+    if (int rc = reset_counts(h)) return rc;
+    if (h->dtype == MCMCPP_HIP_F64)
+        return compute<double>(h, {steps, static_cast<const double*>(device_steps), used, slice, h->W, h->P, h->stream, &h->d_chunk, &h->error});
+    return compute<float>(h, {steps, static_cast<const float*>(device_steps), used, slice, h->W, h->P, h->stream, &h->d_chunk, &h->error});
 }
 }  // namespace
 
@@ -503,20 +434,14 @@ int mcmcpp_hip_histograms_create(int32_t dtype, int32_t device, int32_t num_walk
     h->cus = prop.multiProcessorCount;
     h->lds_limit = mcmcpp::hist_lds_limit(prop.sharedMemPerBlock);
     h->idx_bytes = mcmcpp::hist_index_bytes(bins);
-    size_t mb = 1024;
-    if (const char* env = std::getenv("MCMCPP_HIP_HIST_CHUNK_MB"))
-    {
-        const long long v = std::atoll(env);
-        if (v >= 1) mb = (size_t)v;
-    }
-    h->chunk_bytes = mb << 20;
+    h->chunk_bytes = mcmcpp::chunk_bytes_from_env("MCMCPP_HIP_HIST_CHUNK_MB", 1024);
     const size_t esize = dtype == MCMCPP_HIP_F64 ? 8 : 4;
     auto bad = [&](int code, const std::string& what) {
         g_hist_error = what;
         mcmcpp_hip_histograms_destroy(h);
         return code;
     };
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return bad(MCMCPP_HIP_E_HIP, "histograms_create: cannot create a stream");
+    if (hipStreamCreateWithFlags(h->stream.replace(), hipStreamNonBlocking) != hipSuccess) return bad(MCMCPP_HIP_E_HIP, "histograms_create: cannot create a stream");
     if (h->d_single.alloc((size_t)single_bytes) != hipSuccess || h->d_clamped.alloc(8 * (size_t)num_params) != hipSuccess ||
         h->d_nan.alloc(sizeof(int)) != hipSuccess || h->d_edges.alloc(2 * esize * (size_t)num_params) != hipSuccess)
         return bad(MCMCPP_HIP_E_NOMEM, "histograms_create: cannot allocate device memory");
@@ -546,10 +471,7 @@ void mcmcpp_hip_histograms_destroy(mcmcpp_hip_histograms* h)
 {
     if (!h) return;
     hipSetDevice(h->device);
-    const hipStream_t stream = h->stream;
-    if (stream) hipStreamSynchronize(stream);
-    delete h;  // (the buffers free themselves)
-    if (stream) hipStreamDestroy(stream);
+    delete h;  // (the stream goes idle and away, then the buffers free themselves)
 }
 
 int mcmcpp_hip_histograms_compute(mcmcpp_hip_histograms* h, const void* const* steps, int64_t n_steps)
@@ -559,10 +481,7 @@ int mcmcpp_hip_histograms_compute(mcmcpp_hip_histograms* h, const void* const* s
     if (n_steps < 0 || (n_steps > 0 && !steps)) return fail(h, MCMCPP_HIP_E_ARG, "histograms_compute: bad arguments");
     for (int64_t k = 0; k < n_steps; ++k)
         if (!steps[k]) return fail(h, MCMCPP_HIP_E_ARG, "histograms_compute: a step pointer is NULL");
-    HIST_TRY(hipSetDevice(h->device));
-    int rc = reset_counts(h);
-    if (rc) return rc;
-    return h->dtype == MCMCPP_HIP_F64 ? compute_host<double>(h, steps, n_steps) : compute_host<float>(h, steps, n_steps);
+    return compute_entry(h, steps, nullptr, n_steps, 1);
 }
 
 int mcmcpp_hip_histograms_compute_device(mcmcpp_hip_histograms* h, const void* device_steps, int64_t n_steps, int64_t slice_interval)
@@ -571,11 +490,7 @@ int mcmcpp_hip_histograms_compute_device(mcmcpp_hip_histograms* h, const void* d
     h->have_result = false;
     if (n_steps < 0 || slice_interval < 1 || (n_steps > 0 && !device_steps))
         return fail(h, MCMCPP_HIP_E_ARG, "histograms_compute_device: bad arguments");
-    HIST_TRY(hipSetDevice(h->device));
-    int rc = reset_counts(h);
-    if (rc) return rc;
-    return h->dtype == MCMCPP_HIP_F64 ? compute_device<double>(h, (const double*)device_steps, n_steps, slice_interval)
-                                      : compute_device<float>(h, (const float*)device_steps, n_steps, slice_interval);
+    return compute_entry(h, nullptr, device_steps, (n_steps + slice_interval - 1) / slice_interval, slice_interval);
 }
 
 int mcmcpp_hip_histograms_result(const mcmcpp_hip_histograms* hc, int64_t* num_points, void* bounds, int64_t* single, int64_t* pairs,
@@ -585,12 +500,12 @@ int mcmcpp_hip_histograms_result(const mcmcpp_hip_histograms* hc, int64_t* num_p
     if (!h) return MCMCPP_HIP_E_ARG;
     if (!h->have_result) return fail(h, MCMCPP_HIP_E_STATE, "histograms_result: no successful compute since creation or the last failure");
     if (pairs && !h->with_pairs) return fail(h, MCMCPP_HIP_E_ARG, "histograms_result: this handle was created without pair histograms");
-    HIST_TRY(hipSetDevice(h->device));
-    if (single) HIST_TRY(hipMemcpyAsync(single, h->d_single, 8 * (size_t)h->P * h->bins, hipMemcpyDeviceToHost, h->stream));
+    ANALYSIS_TRY(h->error, hipSetDevice(h->device));
+    if (single) ANALYSIS_TRY(h->error, hipMemcpyAsync(single, h->d_single, 8 * (size_t)h->P * h->bins, hipMemcpyDeviceToHost, h->stream));
     if (pairs && h->npairs > 0)
-        HIST_TRY(hipMemcpyAsync(pairs, h->d_pairs, 8 * (size_t)h->npairs * h->bins * h->bins, hipMemcpyDeviceToHost, h->stream));
-    if (clamped) HIST_TRY(hipMemcpyAsync(clamped, h->d_clamped, 8 * (size_t)h->P, hipMemcpyDeviceToHost, h->stream));
-    HIST_TRY(hipStreamSynchronize(h->stream));
+        ANALYSIS_TRY(h->error, hipMemcpyAsync(pairs, h->d_pairs, 8 * (size_t)h->npairs * h->bins * h->bins, hipMemcpyDeviceToHost, h->stream));
+    if (clamped) ANALYSIS_TRY(h->error, hipMemcpyAsync(clamped, h->d_clamped, 8 * (size_t)h->P, hipMemcpyDeviceToHost, h->stream));
+    ANALYSIS_TRY(h->error, hipStreamSynchronize(h->stream));
     if (bounds) std::memcpy(bounds, h->bounds.data(), h->bounds.size());
     if (num_points) *num_points = h->points;
     return MCMCPP_HIP_OK;

@@ -20,14 +20,13 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "../../include/mcmcpp_hip.h"
-#include "sampler_base.hpp"
+#include "analysis_host.hpp"
 
 namespace
 {
@@ -165,30 +164,15 @@ struct mcmcpp_hip_moments
     size_t chunk_bytes = 0;     // MCMCPP_HIP_MOMENTS_CHUNK_MB
     mcmcpp::DeviceBuffer<double> d_partial, d_total;
     mcmcpp::DeviceBuffer<char> d_chunk;
-    hipStream_t stream = nullptr;  // (destroyed after the buffers: mcmcpp_hip_moments_destroy)
+    // LAST: destroyed first, and idle by then -- nothing it enqueued still uses a buffer above when that frees itself
+    mcmcpp::Stream stream;
 };
 
 namespace
 {
 thread_local std::string g_moments_error;
 
-int fail(mcmcpp_hip_moments* m, int code, const char* what, hipError_t e = hipSuccess)
-{
-    std::string msg = what;
-    if (e != hipSuccess) msg += std::string(": ") + hipGetErrorString(e);
-    if (m)
-        m->error = msg;
-    else
-        g_moments_error = msg;
-    return code;
-}
-
-#define MOM_TRY(expr)                                                  \
-    do                                                                 \
-    {                                                                  \
-        hipError_t e_ = (expr);                                        \
-        if (e_ != hipSuccess) return fail(m, MCMCPP_HIP_E_HIP, #expr, e_); \
-    } while (0)
+int fail(mcmcpp_hip_moments* m, int code, const std::string& msg) { return mcmcpp::analysis_fail(m ? m->error : g_moments_error, code, msg); }
 
 template <class T>
 int accumulate(mcmcpp_hip_moments* m, const T* dev_samples, long long n_samples)
@@ -207,7 +191,7 @@ int accumulate(mcmcpp_hip_moments* m, const T* dev_samples, long long n_samples)
     else
         hipLaunchKernelGGL((moments_generic_kernel<T>), dim3((unsigned)m->slots), dim3(256), sizeof(double) * 4 * (size_t)m->D, m->stream, dev_samples,
                            n_samples, m->D, m->dp, m->d_partial);
-    MOM_TRY(hipGetLastError());
+    ANALYSIS_TRY(m->error, hipGetLastError());
     return MCMCPP_HIP_OK;
 }
 }  // namespace
@@ -225,7 +209,7 @@ int mcmcpp_hip_moments_create(int32_t dtype, int32_t device, int32_t num_walkers
         return fail(m, MCMCPP_HIP_E_ARG, "moments_create: dtype must be F64/F32, num_walkers >= 1, 1 <= num_params <= 1024");
     hipDeviceProp_t prop;
     std::string why;
-    if (int rc = mcmcpp::open_gfx950_device(device, &device, &prop, &why)) return fail(m, rc, ("moments_create: " + why).c_str());
+    if (int rc = mcmcpp::open_gfx950_device(device, &device, &prop, &why)) return fail(m, rc, "moments_create: " + why);
     m = new (std::nothrow) mcmcpp_hip_moments();
     if (!m) return MCMCPP_HIP_E_NOMEM;
     m->dtype = dtype;
@@ -239,14 +223,8 @@ int mcmcpp_hip_moments_create(int32_t dtype, int32_t device, int32_t num_walkers
     m->slots = m->matrix_core ? prop.multiProcessorCount * kMomentWavesPerBlock * 2 : prop.multiProcessorCount;  // two workgroups per CU
     while (m->slots > kMomentWavesPerBlock && (size_t)m->slots * m->slot_elems * sizeof(double) > ((size_t)256 << 20)) m->slots /= 2;
     m->slots -= m->slots % kMomentWavesPerBlock;
-    size_t mb = 64;
-    if (const char* env = std::getenv("MCMCPP_HIP_MOMENTS_CHUNK_MB"))
-    {
-        const long long v = std::atoll(env);
-        if (v >= 1) mb = (size_t)v;
-    }
-    m->chunk_bytes = mb << 20;
-    if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess ||
+    m->chunk_bytes = mcmcpp::chunk_bytes_from_env("MCMCPP_HIP_MOMENTS_CHUNK_MB", 64);
+    if (hipStreamCreateWithFlags(m->stream.replace(), hipStreamNonBlocking) != hipSuccess ||
         m->d_partial.alloc(sizeof(double) * (size_t)m->slots * m->slot_elems) != hipSuccess ||
         m->d_total.alloc(sizeof(double) * m->slot_elems) != hipSuccess ||
         hipMemset(m->d_partial, 0, sizeof(double) * (size_t)m->slots * m->slot_elems) != hipSuccess)
@@ -263,18 +241,15 @@ void mcmcpp_hip_moments_destroy(mcmcpp_hip_moments* m)
 {
     if (!m) return;
     hipSetDevice(m->device);
-    const hipStream_t stream = m->stream;
-    if (stream) hipStreamSynchronize(stream);
-    delete m;  // (the buffers free themselves)
-    if (stream) hipStreamDestroy(stream);
+    delete m;  // (the stream goes idle and away, then the buffers free themselves)
 }
 
 int mcmcpp_hip_moments_reset(mcmcpp_hip_moments* m)
 {
     if (!m) return MCMCPP_HIP_E_ARG;
-    MOM_TRY(hipSetDevice(m->device));
-    MOM_TRY(hipMemsetAsync(m->d_partial, 0, sizeof(double) * (size_t)m->slots * m->slot_elems, m->stream));
-    MOM_TRY(hipStreamSynchronize(m->stream));
+    ANALYSIS_TRY(m->error, hipSetDevice(m->device));
+    ANALYSIS_TRY(m->error, hipMemsetAsync(m->d_partial, 0, sizeof(double) * (size_t)m->slots * m->slot_elems, m->stream));
+    ANALYSIS_TRY(m->error, hipStreamSynchronize(m->stream));
     m->points = 0;
     return MCMCPP_HIP_OK;
 }
@@ -283,31 +258,28 @@ int mcmcpp_hip_moments_reset(mcmcpp_hip_moments* m)
 // chunk at a time, and are summed from there
 static int add_steps_through_chunks(mcmcpp_hip_moments* m, const char* what, const void* steps, int64_t n_steps, int64_t step_stride, hipMemcpyKind kind)
 {
-    MOM_TRY(hipSetDevice(m->device));
+    ANALYSIS_TRY(m->error, hipSetDevice(m->device));
     const size_t esize = m->dtype == MCMCPP_HIP_F64 ? 8 : 4;
     const size_t step_bytes = esize * (size_t)m->W * m->D;
     // chunks of up to MCMCPP_HIP_MOMENTS_CHUNK_MB (at least one step)
     int64_t per_chunk = (int64_t)(m->chunk_bytes / step_bytes);
     if (per_chunk < 1) per_chunk = 1;
     if (per_chunk > n_steps) per_chunk = n_steps;
-    if (mcmcpp::grow(m->d_chunk, step_bytes * (size_t)per_chunk, m->stream)) return fail(m, MCMCPP_HIP_E_NOMEM, (std::string(what) + ": cannot allocate the chunk buffer").c_str());
+    if (mcmcpp::grow(m->d_chunk, step_bytes * (size_t)per_chunk, m->stream)) return fail(m, MCMCPP_HIP_E_NOMEM, std::string(what) + ": cannot allocate the chunk buffer");
     for (int64_t first = 0; first < n_steps; first += per_chunk)
     {
         const int64_t now = (n_steps - first < per_chunk) ? n_steps - first : per_chunk;
         const char* src = (const char*)steps + step_bytes * (size_t)(first * step_stride);
-        MOM_TRY(hipStreamSynchronize(m->stream));  // the previous chunk's kernel has read the buffer
-        if (step_stride == 1)
-            MOM_TRY(hipMemcpyAsync(m->d_chunk, src, step_bytes * (size_t)now, kind, m->stream));
-        else
-            for (int64_t k = 0; k < now; ++k)
-                MOM_TRY(hipMemcpyAsync((char*)m->d_chunk + step_bytes * (size_t)k, src + step_bytes * (size_t)(k * step_stride), step_bytes, kind, m->stream));
+        ANALYSIS_TRY(m->error, hipStreamSynchronize(m->stream));  // the previous chunk's kernel has read the buffer
+        // (stride 1: the chunk in one copy; a larger stride: a copy per step)
+        ANALYSIS_TRY(m->error, mcmcpp::copy_steps(m->d_chunk.get(), [&](long long k) { return src + step_bytes * (size_t)(k * step_stride); }, 0, now, step_bytes, kind, m->stream));
         const long long n_samples = (long long)now * m->W;
         const int rc = m->dtype == MCMCPP_HIP_F64 ? accumulate<double>(m, (const double*)m->d_chunk.get(), n_samples)
                                                   : accumulate<float>(m, (const float*)m->d_chunk.get(), n_samples);
         if (rc) return rc;
         m->points += n_samples;
     }
-    MOM_TRY(hipStreamSynchronize(m->stream));
+    ANALYSIS_TRY(m->error, hipStreamSynchronize(m->stream));
     return MCMCPP_HIP_OK;
 }
 
@@ -333,13 +305,13 @@ int mcmcpp_hip_moments_add_device_steps(mcmcpp_hip_moments* m, const void* devic
     if (!m) return MCMCPP_HIP_E_ARG;
     if (n_steps < 0 || (n_steps > 0 && !device_steps)) return fail(m, MCMCPP_HIP_E_ARG, "moments_add_device_steps: bad arguments");
     if (n_steps == 0) return MCMCPP_HIP_OK;
-    MOM_TRY(hipSetDevice(m->device));
+    ANALYSIS_TRY(m->error, hipSetDevice(m->device));
     const long long n_samples = (long long)n_steps * m->W;
     const int rc = m->dtype == MCMCPP_HIP_F64 ? accumulate<double>(m, (const double*)device_steps, n_samples)
                                               : accumulate<float>(m, (const float*)device_steps, n_samples);
     if (rc) return rc;
     m->points += n_samples;
-    MOM_TRY(hipStreamSynchronize(m->stream));
+    ANALYSIS_TRY(m->error, hipStreamSynchronize(m->stream));
     return MCMCPP_HIP_OK;
 }
 
@@ -347,13 +319,13 @@ int mcmcpp_hip_moments_finish(mcmcpp_hip_moments* m, int64_t* num_points, void* 
 {
     if (!m) return MCMCPP_HIP_E_ARG;
     if (m->points < 1) return fail(m, MCMCPP_HIP_E_STATE, "moments_finish: no samples have been added");
-    MOM_TRY(hipSetDevice(m->device));
+    ANALYSIS_TRY(m->error, hipSetDevice(m->device));
     hipLaunchKernelGGL(moments_reduce_kernel, dim3((unsigned)((m->slot_elems + 255) / 256)), dim3(256), 0, m->stream, m->d_partial, m->slots,
                        (long long)m->slot_elems, m->d_total);
-    MOM_TRY(hipGetLastError());
+    ANALYSIS_TRY(m->error, hipGetLastError());
     std::vector<double> tot(m->slot_elems);
-    MOM_TRY(hipMemcpyAsync(tot.data(), m->d_total, sizeof(double) * m->slot_elems, hipMemcpyDeviceToHost, m->stream));
-    MOM_TRY(hipStreamSynchronize(m->stream));
+    ANALYSIS_TRY(m->error, hipMemcpyAsync(tot.data(), m->d_total, sizeof(double) * m->slot_elems, hipMemcpyDeviceToHost, m->stream));
+    ANALYSIS_TRY(m->error, hipStreamSynchronize(m->stream));
     if (num_points) *num_points = m->points;
     // CovarianceMatrix::finalizeMatrix (CovarianceMatrix.h:178-224), in fp64; narrowed to the chain's type at the end
     const int D = m->D, dp = m->dp;

@@ -22,17 +22,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <cstdlib>
 #include <cstring>
 #include <limits>
-#include <memory>
 #include <string>
-#include <type_traits>
 #include <vector>
 
 #include "../../include/mcmcpp_hip.h"
+#include "analysis_host.hpp"
 #include "quantile_plan.hpp"
-#include "sampler_base.hpp"
 
 namespace
 {
@@ -203,107 +200,22 @@ quant_rank_kernel(const T* base, long long step_stride, unsigned W, int P, unsig
 
 thread_local std::string g_quant_error;
 
-int quant_fail(int code, const std::string& msg, hipError_t e = hipSuccess)
-{
-    g_quant_error = msg;
-    if (e != hipSuccess) g_quant_error += std::string(": ") + hipGetErrorString(e);
-    return code;
-}
+int quant_fail(int code, const std::string& msg) { return mcmcpp::analysis_fail(g_quant_error, code, msg); }
 
-#define QUANT_TRY(expr)                                                     \
-    do                                                                      \
-    {                                                                       \
-        hipError_t e_ = (expr);                                             \
-        if (e_ != hipSuccess) return quant_fail(MCMCPP_HIP_E_HIP, #expr, e_); \
-    } while (0)
+using mcmcpp::StepSpan;
 
-// Does [p, p + bytes) lie inside one allocation of device `device`?  (As the samplers ask before run_device launches anything.)
-int check_device_steps(const char* what, const void* p, size_t bytes, int device)
-{
-    const std::string w(what);
-    hipPointerAttribute_t at;
-    std::memset(&at, 0, sizeof at);
-    const hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) (void)hipGetLastError();  // (some runtimes report pageable memory as an error)
-    if (e != hipSuccess || at.type != hipMemoryTypeDevice) return quant_fail(MCMCPP_HIP_E_ARG, w + ": device_steps is not device memory");
-    if (at.device != device)
-        return quant_fail(MCMCPP_HIP_E_ARG, w + ": device_steps is memory of device " + std::to_string(at.device) + ", not of device " + std::to_string(device));
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        return quant_fail(MCMCPP_HIP_E_ARG, w + ": the runtime does not know the allocation device_steps lies in");
-    }
-    if ((const char*)p < (const char*)base || bytes > (size_t)((const char*)base + size - (const char*)p))
-        return quant_fail(MCMCPP_HIP_E_ARG, w + ": n_steps steps do not end inside the allocation around device_steps");
-    return MCMCPP_HIP_OK;
-}
-
-// A source of selected samples: n_steps steps of W*P elements, step k at base + k * step_stride (elements)
+// One call's steps, how many of them make a chunk, and what the plans ask about the device
 template <class T>
-struct Span
+struct Source : mcmcpp::StepSource<T>
 {
-    const T* base;
-    long long step_stride;
-    long long n_steps;
-};
+    long long per;
+    int cus;
+    size_t lds_limit;
 
-// One call's view of the device and of the steps it uses
-template <class T>
-struct Source
-{
-    const char* what = "";
-    int W = 0, P = 0, cus = 0;
-    size_t lds_limit = 0, chunk_bytes = 0;
-    hipStream_t stream = nullptr;
-    const void* const* host_steps = nullptr;  // host path: `used` pointers
-    const T* device_steps = nullptr;          // device path: every slice-th of the steps behind it
-    long long used = 0, slice = 1;
-    mcmcpp::DeviceBuffer<> d_chunk;
-    bool resident = false;  // a host selection of one chunk, uploaded already
-
-    int upload(long long k0, long long now)
-    {
-        const size_t step_bytes = sizeof(T) * (size_t)W * P;
-        QUANT_TRY(hipStreamSynchronize(stream));  // the previous chunk's kernel has read the buffer
-        for (long long k = 0; k < now;)
-        {
-            // a run of steps that are contiguous in host memory goes in one copy
-            const char* src = (const char*)host_steps[k0 + k];
-            long long run = 1;
-            while (k + run < now && (const char*)host_steps[k0 + k + run] == src + step_bytes * (size_t)run) ++run;
-            QUANT_TRY(hipMemcpyAsync((char*)d_chunk.get() + step_bytes * (size_t)k, src, step_bytes * (size_t)run, hipMemcpyHostToDevice, stream));
-            k += run;
-        }
-        return MCMCPP_HIP_OK;
-    }
-
-    // f(span) for every chunk of the selection, in order
     template <class F>
     int for_each_chunk(F&& f)
     {
-        const size_t step_elems = (size_t)W * P;
-        const long long per = mcmcpp::quantile_steps_per_chunk(device_steps ? std::numeric_limits<size_t>::max() : chunk_bytes, sizeof(T) * step_elems, W);
-        if (!device_steps && !d_chunk)
-            if (d_chunk.alloc(sizeof(T) * step_elems * (size_t)(used < per ? used : per)) != hipSuccess)
-                return quant_fail(MCMCPP_HIP_E_NOMEM, std::string(what) + ": cannot allocate the upload buffer");
-        for (long long k0 = 0; k0 < used; k0 += per)
-        {
-            const long long now = (used - k0 < per) ? used - k0 : per;
-            Span<T> sp;
-            if (device_steps)
-                sp = Span<T>{device_steps + (size_t)(k0 * slice) * step_elems, (long long)(slice * (long long)step_elems), now};
-            else
-            {
-                if (!resident)
-                    if (int rc = upload(k0, now)) return rc;
-                resident = used <= per;
-                sp = Span<T>{(const T*)d_chunk.get(), (long long)step_elems, now};
-            }
-            if (int rc = f(sp)) return rc;
-        }
-        return MCMCPP_HIP_OK;
+        return mcmcpp::StepSource<T>::for_each_chunk(per, f);
     }
 };
 
@@ -323,7 +235,7 @@ int order_statistics(Source<T>& src, const int64_t* ranks, int R, T* values)
     mcmcpp::DeviceBuffer<unsigned long long> d_cnt;
     mcmcpp::DeviceBuffer<int> d_nan;
     if (d_nan.alloc(sizeof(int)) != hipSuccess) return quant_fail(MCMCPP_HIP_E_NOMEM, "order_statistics: cannot allocate device memory");
-    QUANT_TRY(hipMemsetAsync(d_nan, 0, sizeof(int), src.stream));
+    ANALYSIS_TRY(g_quant_error, hipMemsetAsync(d_nan, 0, sizeof(int), src.stream));
     std::vector<K> table;
     std::vector<unsigned long long> cnt;
     for (int pass = 0; pass < passes; ++pass)
@@ -336,24 +248,24 @@ int order_statistics(Source<T>& src, const int64_t* ranks, int R, T* values)
             for (int k = 0; k < R; ++k) table[(size_t)p * groups + group[(size_t)p * R + k]] = prefix[(size_t)p * R + k];
         if (mcmcpp::grow(d_pref, sizeof(K) * sets, src.stream) != hipSuccess || mcmcpp::grow(d_cnt, 8 * sets * cells, src.stream) != hipSuccess)
             return quant_fail(MCMCPP_HIP_E_NOMEM, "order_statistics: cannot allocate the " + std::to_string(8 * sets * cells) + "-byte counters");
-        QUANT_TRY(hipMemcpyAsync(d_pref, table.data(), sizeof(K) * sets, hipMemcpyHostToDevice, src.stream));
-        QUANT_TRY(hipMemsetAsync(d_cnt, 0, 8 * sets * cells, src.stream));
-        int rc = src.for_each_chunk([&](const Span<T>& sp) -> int {
+        ANALYSIS_TRY(g_quant_error, hipMemcpyAsync(d_pref, table.data(), sizeof(K) * sets, hipMemcpyHostToDevice, src.stream));
+        ANALYSIS_TRY(g_quant_error, hipMemsetAsync(d_cnt, 0, 8 * sets * cells, src.stream));
+        int rc = src.for_each_chunk([&](const StepSpan<T>& sp) -> int {
             const unsigned n = (unsigned)(sp.n_steps * src.W);
             const mcmcpp::QuantPlan plan = mcmcpp::quantile_plan(n, P, groups, key_bits, dg.bits, src.cus, src.lds_limit);
             const auto kernel = plan.lds ? quant_count_kernel<T, true> : quant_count_kernel<T, false>;
             hipLaunchKernelGGL(kernel, dim3(plan.blocks, (unsigned)plan.ptiles), dim3(kQuantThreads), plan.lds_bytes, src.stream, sp.base, sp.step_stride,
                                (unsigned)src.W, P, n, plan.per, plan.tile, groups, dg.shift, dg.bits, pass > 0 ? 1 : 0, (const K*)d_pref.get(), d_cnt.get(),
                                d_nan.get());
-            QUANT_TRY(hipGetLastError());
+            ANALYSIS_TRY(g_quant_error, hipGetLastError());
             return MCMCPP_HIP_OK;
         });
         if (rc) return rc;
         cnt.resize(sets * cells);
-        QUANT_TRY(hipMemcpyAsync(cnt.data(), d_cnt, 8 * sets * cells, hipMemcpyDeviceToHost, src.stream));
+        ANALYSIS_TRY(g_quant_error, hipMemcpyAsync(cnt.data(), d_cnt, 8 * sets * cells, hipMemcpyDeviceToHost, src.stream));
         int nan = 0;
-        if (pass == 0) QUANT_TRY(hipMemcpyAsync(&nan, d_nan, sizeof(int), hipMemcpyDeviceToHost, src.stream));
-        QUANT_TRY(hipStreamSynchronize(src.stream));
+        if (pass == 0) ANALYSIS_TRY(g_quant_error, hipMemcpyAsync(&nan, d_nan, sizeof(int), hipMemcpyDeviceToHost, src.stream));
+        ANALYSIS_TRY(g_quant_error, hipStreamSynchronize(src.stream));
         if (nan) return quant_fail(MCMCPP_HIP_E_ARG, "order_statistics: the selected samples contain a NaN (it has no place in the order)");
         // the scan: the digit whose cumulative count first exceeds the remaining rank
         for (int p = 0; p < P; ++p)
@@ -394,23 +306,23 @@ int rank_counts(Source<T>& src, const T* query, int Q, int64_t* below, int64_t* 
     mcmcpp::DeviceBuffer<int> d_nan;
     if (d_query.alloc(sizeof(T) * cells) != hipSuccess || d_cnt.alloc(16 * cells) != hipSuccess || d_nan.alloc(sizeof(int)) != hipSuccess)
         return quant_fail(MCMCPP_HIP_E_NOMEM, "rank_counts: cannot allocate device memory");
-    QUANT_TRY(hipMemcpyAsync(d_query, query, sizeof(T) * cells, hipMemcpyHostToDevice, src.stream));
-    QUANT_TRY(hipMemsetAsync(d_cnt, 0, 16 * cells, src.stream));
-    QUANT_TRY(hipMemsetAsync(d_nan, 0, sizeof(int), src.stream));
-    int rc = src.for_each_chunk([&](const Span<T>& sp) -> int {
+    ANALYSIS_TRY(g_quant_error, hipMemcpyAsync(d_query, query, sizeof(T) * cells, hipMemcpyHostToDevice, src.stream));
+    ANALYSIS_TRY(g_quant_error, hipMemsetAsync(d_cnt, 0, 16 * cells, src.stream));
+    ANALYSIS_TRY(g_quant_error, hipMemsetAsync(d_nan, 0, sizeof(int), src.stream));
+    int rc = src.for_each_chunk([&](const StepSpan<T>& sp) -> int {
         const unsigned n = (unsigned)(sp.n_steps * src.W);
         const mcmcpp::QuantRankPlan plan = mcmcpp::quantile_rank_plan(n, P, src.cus);
         hipLaunchKernelGGL((quant_rank_kernel<T>), dim3(plan.blocks, (unsigned)plan.ptiles), dim3(kQuantThreads), 0, src.stream, sp.base, sp.step_stride,
                            (unsigned)src.W, P, n, plan.per, plan.tile, (const T*)d_query.get(), Q, d_cnt.get(), d_cnt.get() + cells, d_nan.get());
-        QUANT_TRY(hipGetLastError());
+        ANALYSIS_TRY(g_quant_error, hipGetLastError());
         return MCMCPP_HIP_OK;
     });
     if (rc) return rc;
     std::vector<int64_t> cnt(2 * cells);
     int nan = 0;
-    QUANT_TRY(hipMemcpyAsync(cnt.data(), d_cnt, 16 * cells, hipMemcpyDeviceToHost, src.stream));
-    QUANT_TRY(hipMemcpyAsync(&nan, d_nan, sizeof(int), hipMemcpyDeviceToHost, src.stream));
-    QUANT_TRY(hipStreamSynchronize(src.stream));
+    ANALYSIS_TRY(g_quant_error, hipMemcpyAsync(cnt.data(), d_cnt, 16 * cells, hipMemcpyDeviceToHost, src.stream));
+    ANALYSIS_TRY(g_quant_error, hipMemcpyAsync(&nan, d_nan, sizeof(int), hipMemcpyDeviceToHost, src.stream));
+    ANALYSIS_TRY(g_quant_error, hipStreamSynchronize(src.stream));
     if (nan) return quant_fail(MCMCPP_HIP_E_ARG, "rank_counts: the selected samples contain a NaN (it is neither below nor above a value)");
     if (below) std::memcpy(below, cnt.data(), 8 * cells);
     if (not_above) std::memcpy(not_above, cnt.data() + cells, 8 * cells);
@@ -446,34 +358,18 @@ bool any_nan(const void* v, size_t count)
 template <class T>
 int run_request(const Request& r, int device, const hipDeviceProp_t& prop, long long used)
 {
-    Source<T> src;
-    src.what = r.what;
-    src.W = r.W;
-    src.P = r.P;
-    src.cus = prop.multiProcessorCount;
-    src.lds_limit = mcmcpp::hist_lds_limit(prop.sharedMemPerBlock);
-    size_t mb = 1024;
-    if (const char* env = std::getenv("MCMCPP_HIP_QUANTILE_CHUNK_MB"))
-    {
-        const long long v = std::atoll(env);
-        if (v >= 1) mb = (size_t)v;
-    }
-    src.chunk_bytes = mb << 20;
-    src.host_steps = r.steps;
-    src.device_steps = static_cast<const T*>(r.device_steps);
-    src.used = used;
-    src.slice = r.slice;
+    const size_t step_bytes = sizeof(T) * (size_t)r.W * r.P;
     if (r.on_device)
-        if (int rc = check_device_steps(r.what, r.device_steps, sizeof(T) * (size_t)r.n_steps * r.W * r.P, device)) return rc;
-    hipStream_t stream = nullptr;
-    QUANT_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-    const auto sync_and_destroy = [](hipStream_t s) {
-        (void)hipStreamSynchronize(s);
-        (void)hipStreamDestroy(s);
-    };
-    // (destroyed before src: the stream is idle when the upload buffer goes)
-    const std::unique_ptr<std::remove_pointer_t<hipStream_t>, decltype(sync_and_destroy)> stream_owner(stream, sync_and_destroy);
-    src.stream = stream;
+        if (int rc = mcmcpp::check_device_steps(g_quant_error, r.what, r.device_steps, step_bytes * (size_t)r.n_steps, device)) return rc;
+    mcmcpp::DeviceBuffer<> d_chunk;
+    mcmcpp::Stream stream;  // (behind the upload buffer: the stream is idle and gone when the buffer goes)
+    ANALYSIS_TRY(g_quant_error, hipStreamCreateWithFlags(stream.replace(), hipStreamNonBlocking));
+    // (a device chain is read in place: 32-bit sample indexing alone bounds its chunks)
+    const size_t chunk_bytes = r.on_device ? std::numeric_limits<size_t>::max() : mcmcpp::chunk_bytes_from_env("MCMCPP_HIP_QUANTILE_CHUNK_MB", 1024);
+    Source<T> src{{r.steps, static_cast<const T*>(r.device_steps), used, r.slice, r.W, r.P, stream, &d_chunk, &g_quant_error},
+                  mcmcpp::quantile_steps_per_chunk(chunk_bytes, step_bytes, r.W), prop.multiProcessorCount, mcmcpp::hist_lds_limit(prop.sharedMemPerBlock)};
+    if (mcmcpp::grow(d_chunk, src.upload_bytes(src.per), stream) != hipSuccess)
+        return quant_fail(MCMCPP_HIP_E_NOMEM, std::string(r.what) + ": cannot allocate the upload buffer");
     return r.ranks ? order_statistics<T>(src, r.ranks, r.n_ranks, static_cast<T*>(r.values))
                    : rank_counts<T>(src, static_cast<const T*>(r.query), r.n_query, r.below, r.not_above);
 }

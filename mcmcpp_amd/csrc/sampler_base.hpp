@@ -118,8 +118,8 @@ struct mcmcpp_hip_sampler
 namespace mcmcpp
 {
 // ---- Owners of the HIP resources the handles hold ("Who frees what") ----------------------------
-// Every device buffer, pinned host buffer, event and instantiated graph of the library belongs to one of these, and they
-// are the only code that gives one back to the runtime.  Move-only.  A handle quiesces its stream in its destructor's
+// Every device buffer, pinned host buffer, event, instantiated graph and stream of the library belongs to one of these, and
+// they are the only code that gives one back to the runtime.  Move-only.  A handle quiesces its stream in its destructor's
 // body; its members then free themselves, before the stream goes with the base class.
 
 inline void free_device(void* p)
@@ -230,6 +230,49 @@ private:
 };
 using Event = HipHandle<hipEvent_t, hipEventDestroy>;
 using GraphExec = HipHandle<hipGraphExec_t, hipGraphExecDestroy>;
+
+// A stream of the library's own making (hipStreamCreateWithFlags(s.replace(), ...)): synchronised, then destroyed, with its
+// owner.  Whatever the stream's work used must outlive it: a function declares its Stream behind its buffers, a handle
+// struct as its last member.
+inline hipError_t destroy_idle_stream(hipStream_t s)
+{
+    (void)hipStreamSynchronize(s);
+    return hipStreamDestroy(s);
+}
+using Stream = HipHandle<hipStream_t, destroy_idle_stream>;
+
+// What the runtime knows about a pointer that a caller says is device memory: one probe for every entry point that takes
+// such a pointer.  Each caller words its own refusal.
+struct DeviceRange
+{
+    enum Kind
+    {
+        NotDevice,     // a host pointer (pageable, pinned or managed) or one the runtime has never seen: never dereferenced
+        OtherDevice,   // device memory of `device`, which is not the one asked about
+        NoAllocation,  // the runtime does not know the allocation around it
+        Found          // `room` bytes lie between the pointer and the end of its allocation
+    } kind;
+    int device;
+    size_t room;
+};
+inline DeviceRange probe_device_range(const void* p, int device)
+{
+    hipPointerAttribute_t at;
+    std::memset(&at, 0, sizeof at);
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) (void)hipGetLastError();  // (some runtimes report pageable memory as an error)
+    if (e != hipSuccess || at.type != hipMemoryTypeDevice) return {DeviceRange::NotDevice, -1, 0};
+    if (at.device != device) return {DeviceRange::OtherDevice, at.device, 0};
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        return {DeviceRange::NoAllocation, at.device, 0};
+    }
+    // (a pointer below the base the runtime reports has no room at all)
+    return {DeviceRange::Found, at.device, (const char*)p < (const char*)base ? 0 : (size_t)((const char*)base + size - (const char*)p)};
+}
 
 inline Affine128 compose(const Affine128& g, const Affine128& f)  // g after f
 {

@@ -159,11 +159,6 @@ template <class T>
 class SamplerHost : public mcmcpp_hip_sampler
 {
 public:
-    ~SamplerHost() override
-    {
-        if (own_stream && stream) (void)hipStreamDestroy(stream);
-    }
-
     int last_run_timing(double* ms, int64_t* launches) override
     {
         if (ms) *ms = last_ms;
@@ -272,7 +267,8 @@ protected:
             stream = (hipStream_t)c.hip_stream;
         else
         {
-            HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+            HIP_TRY(hipStreamCreateWithFlags(owned_stream.replace(), hipStreamNonBlocking));
+            stream = owned_stream;
             own_stream = true;
         }
         stream_valid = true;
@@ -365,30 +361,23 @@ protected:
     }
 
     // Does [p, p + bytes) lie inside ONE allocation of this handle's device, aligned to `align` bytes?  Asked of the runtime
-    // before anything is launched: hipPointerGetAttributes must report p as device memory of the device (a host pointer --
-    // pageable, pinned or managed -- is refused here, never dereferenced), and the range must end inside the allocation
-    // hipMemGetAddressRange reports around p.  MCMCPP_HIP_E_ARG with a message otherwise.
+    // before anything is launched (probe_device_range, sampler_base.hpp): p must be device memory of the device (a host pointer
+    // -- pageable, pinned or managed -- is refused here, never dereferenced), and the range must end inside the allocation
+    // around p.  MCMCPP_HIP_E_ARG with a message otherwise.
     int check_device_range(const char* what, const char* name, const void* p, size_t bytes, size_t align)
     {
         if (!p) return fail(MCMCPP_HIP_E_ARG, "%s: %s is NULL", what, name);
         if (((uintptr_t)p & (align - 1)) != 0) return fail(MCMCPP_HIP_E_ARG, "%s: %s must be %zu-byte aligned", what, name, align);
-        hipPointerAttribute_t at;
-        std::memset(&at, 0, sizeof at);
-        const hipError_t e = hipPointerGetAttributes(&at, p);
-        if (e != hipSuccess) (void)hipGetLastError();  // (some runtimes report pageable memory as an error)
-        if (e != hipSuccess || at.type != hipMemoryTypeDevice)
-            return fail(MCMCPP_HIP_E_ARG, "%s: %s is not device memory (%zu bytes from %p must lie in memory of device %d)", what, name, bytes, p, device);
-        if (at.device != device) return fail(MCMCPP_HIP_E_ARG, "%s: %s is memory of device %d, the handle runs on device %d", what, name, at.device, device);
-        hipDeviceptr_t base = nullptr;
-        size_t size = 0;
-        if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess)
+        const DeviceRange r = probe_device_range(p, device);
+        switch (r.kind)
         {
-            (void)hipGetLastError();
-            return fail(MCMCPP_HIP_E_ARG, "%s: the runtime does not know the allocation %s lies in", what, name);
+        case DeviceRange::NotDevice:
+            return fail(MCMCPP_HIP_E_ARG, "%s: %s is not device memory (%zu bytes from %p must lie in memory of device %d)", what, name, bytes, p, device);
+        case DeviceRange::OtherDevice: return fail(MCMCPP_HIP_E_ARG, "%s: %s is memory of device %d, the handle runs on device %d", what, name, r.device, device);
+        case DeviceRange::NoAllocation: return fail(MCMCPP_HIP_E_ARG, "%s: the runtime does not know the allocation %s lies in", what, name);
+        case DeviceRange::Found: break;
         }
-        const size_t room = (size_t)((const char*)base + size - (const char*)p);
-        if ((const char*)p < (const char*)base || bytes > room)
-            return fail(MCMCPP_HIP_E_ARG, "%s: %s needs %zu bytes, but its allocation ends %zu bytes behind it", what, name, bytes, room);
+        if (bytes > r.room) return fail(MCMCPP_HIP_E_ARG, "%s: %s needs %zu bytes, but its allocation ends %zu bytes behind it", what, name, bytes, r.room);
         return MCMCPP_HIP_OK;
     }
 
@@ -431,6 +420,7 @@ protected:
 
     int W = 0, D = 0, n = 0, lpw = 1, epl = 1, vec_ok = 0, device = -1;
     hipStream_t stream = nullptr;
+    Stream owned_stream;  // `stream`, where the handle made it (own_stream); goes with this base, after the mover's members
     bool own_stream = false, stream_valid = false, have_state = false;
     bool run_touched = false;  // the run in hand has launched: a failure from here on leaves the device ahead of the host's bookkeeping
     // the walkers: positions [W][D], log-posteriors [W], accepted counters [W] (the mover allocates them)

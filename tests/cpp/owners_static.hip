@@ -16,5 +16,6 @@ static_assert(move_only<DeviceBuffer<double>>(), "DeviceBuffer<double>");
 static_assert(move_only<PinnedBuffer<char>>(), "PinnedBuffer");
 static_assert(move_only<Event>(), "Event");
 static_assert(move_only<GraphExec>(), "GraphExec");
+static_assert(move_only<Stream>(), "Stream");
 
 int main() { return 0; }

@@ -1,5 +1,5 @@
 """The HIP resources of the library have one owner each (CPU test: no GPU needed).  Device buffers, pinned host buffers,
-events and instantiated graphs are held by the owner types of mcmcpp_amd/csrc/sampler_base.hpp, which are the only code
+events, instantiated graphs and streams are held by the owner types of mcmcpp_amd/csrc/sampler_base.hpp, which are the only code
 that gives them back to the runtime; a hand-written free anywhere else is a second free list to keep in step."""
 import os
 import re
@@ -8,7 +8,7 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "mcmcpp_amd", "csrc")
 OWNER_HEADER = "sampler_base.hpp"
-FREES = re.compile(r"hipFree\(|hipHostFree\(|hipEventDestroy|hipGraphExecDestroy")
+FREES = re.compile(r"hipFree\(|hipHostFree\(|hipEventDestroy|hipGraphExecDestroy|hipStreamDestroy")
 
 
 def test_only_the_owner_header_frees():
@@ -25,7 +25,7 @@ def test_only_the_owner_header_frees():
     assert not offenders, "HIP resources freed outside %s:\n%s" % (OWNER_HEADER, "\n".join(offenders))
     with open(os.path.join(CSRC, OWNER_HEADER)) as f:
         header = f.read()
-    assert all(s in header for s in ("hipFree(", "hipHostFree(", "hipEventDestroy", "hipGraphExecDestroy"))
+    assert all(s in header for s in ("hipFree(", "hipHostFree(", "hipEventDestroy", "hipGraphExecDestroy", "hipStreamDestroy"))
 
 
 def test_owners_are_move_only(tmp_path):
