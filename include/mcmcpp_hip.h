@@ -485,6 +485,50 @@ int mcmcpp_hip_rank_counts_device(int32_t dtype, int32_t device, const void* dev
                                   int64_t* not_above);
 const char* mcmcpp_hip_order_statistics_last_error(void);
 
+/* The Gelman-Rubin potential scale reduction (split R-hat, BDA3 form) of every parameter, with the walkers of num_chains
+ * independent chains as sequences (an extension: the reference has no such class).  Chains of one handle (num_chains, chain k
+ * seeded seed + k) or of several handles: have they converged to the same distribution?
+ *   input           K = num_chains chains of n used steps of W walkers x P parameters in T; all arithmetic and all outputs
+ *                   are double (a float sample converts exactly), every + - x / rounded on its own.
+ *   sequences       with split != 0 every walker gives two sequences of L = floor(n / 2) steps: used steps [0, L) and
+ *                   [n - L, n) (for odd n the middle step is dropped); without, one of L = n.  H = 2 or 1; M = K H W
+ *                   sequences, sequence m = (k H + h) W + w.  L >= 2 and M >= 2.
+ *   sum_fixed       the one shape of every sum below, so that a result is a function of the data alone (not of scheduling,
+ *                   CU count, chunk size, or where the chain lies): v[0..N) is cut into consecutive slices of
+ *                   slice_len(N) = max(1024, ceil(N / 64) rounded up to a multiple of 64) terms (the last may be short; at
+ *                   most 64 slices); a slice is summed in ascending order from +0; the slice sums are added in ascending
+ *                   order.  No floating-point atomics.
+ *   per sequence    c = its first sample, d_s = x_s - c; S1 = sum_fixed(d), S2 = sum_fixed(d d) over its L steps;
+ *                   q = S1 / L; sequence_mean[m][p] = c + q; sequence_m2[m][p] = max(S2 - S1 q, 0).
+ *   per parameter   v_m = sequence_m2 / (L - 1); within = sum_fixed(v_m) / M; mean = sum_fixed(sequence_mean) / M;
+ *                   e_m = sequence_mean - mean; between = sum_fixed(e_m e_m) / (M - 1) (B / L in BDA3's notation);
+ *                   varplus = (within (L - 1)) / L + between; rhat = sqrt(varplus / within).
+ *   per chain       chain_mean[k][p] = sum_fixed of sequence_mean over the chain's H W sequences in m order, over H W;
+ *                   chain_within[k][p] the same of v_m: they tell which ensemble disagrees.
+ *   non-finite      samples propagate by IEEE rules; a constant parameter has within = 0 and rhat = NaN.
+ *   steps           num_chains x n_steps host pointers, chain k's step s at steps[k n_steps + s] (the caller has applied
+ *                   its slicing), uploaded chain by chain in chunks of MCMCPP_HIP_RHAT_CHUNK_MB (read per call, default
+ *                   1024); the chunks do not change a bit of the result.
+ *   device_steps    chain k starts k x chain_stride_steps steps behind the pointer (0: n_steps; else >= n_steps, e.g. to
+ *                   skip a burn-in by offsetting the pointer into the [K][n_saved][W][P] array run_device wrote); of each
+ *                   chain's n_steps steps every slice_interval-th from the first is used; read where they lie.
+ *   outputs         rhat, mean, within, between [P]; chain_mean, chain_within [K][P]; sequence_mean, sequence_m2 [M][P];
+ *                   *sequence_length = L, *num_sequences = M.  Any of them may be NULL.
+ * Free functions with a thread-local last error.  MCMCPP_HIP_E_ARG (with a message), before the device is opened, for a bad
+ * dtype, num_chains or num_params outside 1..1024, num_walkers < 1, W P >= 2^31, slice_interval < 1, a chain_stride_steps
+ * below n_steps, a NULL array or step pointer, L < 2 and M < 2; and for a device_steps that is not memory of that device, or
+ * chains that do not all end inside its allocation.  Nothing is written to the outputs of a call that fails. */
+int mcmcpp_hip_gelman_rubin(int32_t dtype, int32_t device, const void* const* steps, int32_t num_chains, int64_t n_steps,
+                            int32_t num_walkers, int32_t num_params, int32_t split, double* rhat, double* mean, double* within,
+                            double* between, double* chain_mean, double* chain_within, double* sequence_mean,
+                            double* sequence_m2, int64_t* sequence_length, int64_t* num_sequences);
+int mcmcpp_hip_gelman_rubin_device(int32_t dtype, int32_t device, const void* device_steps, int32_t num_chains,
+                                   int64_t chain_stride_steps, int64_t n_steps, int64_t slice_interval, int32_t num_walkers,
+                                   int32_t num_params, int32_t split, double* rhat, double* mean, double* within, double* between,
+                                   double* chain_mean, double* chain_within, double* sequence_mean, double* sequence_m2,
+                                   int64_t* sequence_length, int64_t* num_sequences);
+const char* mcmcpp_hip_gelman_rubin_last_error(void);
+
 int mcmcpp_hip_abi_version(void);
 
 #ifdef __cplusplus

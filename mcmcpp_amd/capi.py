@@ -38,6 +38,7 @@ EXPORTS = [
     "mcmcpp_hip_histograms_compute_device", "mcmcpp_hip_histograms_result", "mcmcpp_hip_histograms_last_error",
     "mcmcpp_hip_order_statistics", "mcmcpp_hip_order_statistics_device", "mcmcpp_hip_rank_counts", "mcmcpp_hip_rank_counts_device",
     "mcmcpp_hip_order_statistics_last_error",
+    "mcmcpp_hip_gelman_rubin", "mcmcpp_hip_gelman_rubin_device", "mcmcpp_hip_gelman_rubin_last_error",
 ]
 
 
@@ -164,6 +165,12 @@ def lib():
             L.mcmcpp_hip_rank_counts_device.argtypes = [i32, i32, vp, i64, i64, i32, i32, vp, i32, vp, vp]
             L.mcmcpp_hip_order_statistics_last_error.argtypes = []
             L.mcmcpp_hip_order_statistics_last_error.restype = C.c_char_p
+        if hasattr(L, "mcmcpp_hip_gelman_rubin"):
+            outputs = [vp] * 10  # eight double arrays, *sequence_length, *num_sequences
+            L.mcmcpp_hip_gelman_rubin.argtypes = [i32, i32, C.POINTER(vp), i32, i64, i32, i32, i32] + outputs
+            L.mcmcpp_hip_gelman_rubin_device.argtypes = [i32, i32, vp, i32, i64, i64, i64, i32, i32, i32] + outputs
+            L.mcmcpp_hip_gelman_rubin_last_error.argtypes = []
+            L.mcmcpp_hip_gelman_rubin_last_error.restype = C.c_char_p
         _lib = L
     return _lib
 
@@ -818,3 +825,81 @@ def quantiles(steps, q, method="linear", slice_interval=1, dtype=None, device=-1
     ranks, where = np.unique(np.concatenate([lo, hi]), return_inverse=True)  # (each rank is selected once)
     x = order_statistics(steps, ranks, slice_interval, dtype, device)
     return quantile_rule(x[:, where[:h.size]], x[:, where[h.size:]], h, method, np_dtype(dtype))
+
+
+def _rhat_device_source(steps, chain_stride_steps, dtype, device):
+    """(dtype, device, address, K, chain_stride_steps, n, W, P) of a device tensor (K, n, W, P) or (n, W, P): every chain
+    contiguous, the chains a whole number of steps apart (a view such as chain[:, burn_in:] of a contiguous tensor is)"""
+    import torch
+    if steps.dim() not in (3, 4) or steps.dtype not in (torch.float64, torch.float32):
+        raise ValueError("device steps must be a float64 or float32 tensor (K, n, W, P) or (n, W, P)")
+    tensor_dtype = F64 if steps.dtype == torch.float64 else F32
+    if dtype is not None and dtype != tensor_dtype:
+        raise ValueError("device steps are %s, not the dtype asked for" % steps.dtype)
+    if steps.dim() == 3:
+        steps = steps[None]
+    K, n, W, P = (int(v) for v in steps.shape)
+    if not steps.is_cuda or not steps[0].is_contiguous():
+        raise ValueError("device steps must lie in device memory, every chain contiguous")
+    stride = int(steps.stride(0)) if K > 1 else n * W * P
+    if stride % (W * P) or stride < n * W * P:
+        raise ValueError("the chains of the device steps must be a whole number of steps apart, and not overlap")
+    if chain_stride_steps is not None and K > 1 and chain_stride_steps != stride // (W * P):
+        raise ValueError("chain_stride_steps = %d, but the tensor's chains are %d steps apart" % (chain_stride_steps, stride // (W * P)))
+    if device >= 0 and steps.device.index != device:
+        raise ValueError("device steps are on device %d, not on device %d" % (steps.device.index, device))
+    _after_torch(steps)
+    return tensor_dtype, steps.device.index, steps.data_ptr(), K, stride // (W * P), n, W, P
+
+
+def gelman_rubin(steps, split=True, slice_interval=1, chain_stride_steps=None, dtype=None, device=-1, want_sequences=False):
+    """The Gelman-Rubin split R-hat of every parameter, with the walkers of K chains as sequences (include/mcmcpp_hip.h,
+    mcmcpp_hip_gelman_rubin: an extension).  steps: a numpy array [(K, n, W, P)] or [(n, W, P)] (one chain); a list of K lists of
+    step arrays [(W, P)]; or a torch tensor of those shapes on the GPU, read where it lies (every chain contiguous: the view
+    chain[:, burn_in:] of what run_device wrote qualifies, its chains chain_stride_steps apart).  Every slice_interval-th step
+    of a chain is used, from its first.  Returns a dict: rhat, mean, within, between [(P,)], chain_mean, chain_within [(K, P)],
+    sequence_length, num_sequences, and with want_sequences sequence_mean, sequence_m2 [(M, P)]; all float64."""
+    if slice_interval < 1:
+        raise ValueError("slice_interval must be at least 1")
+    L_ = lib()
+    if _is_tensor(steps):
+        dtype, device, ptr, K, stride, n, W, P = _rhat_device_source(steps, chain_stride_steps, dtype, device)
+
+        def call(*outputs):
+            return L_.mcmcpp_hip_gelman_rubin_device(dtype, device, C.c_void_p(ptr), K, stride, n, slice_interval, W, P, int(bool(split)), *outputs)
+    else:
+        if chain_stride_steps is not None:
+            raise ValueError("chain_stride_steps belongs to steps in device memory")
+        if isinstance(steps, np.ndarray):
+            if steps.ndim not in (3, 4):
+                raise ValueError("steps must have shape (K, n, W, P) or (n, W, P), not %s" % (steps.shape,))
+            chains = [steps] if steps.ndim == 3 else list(steps)
+        else:
+            chains = [list(c) for c in steps]
+        if not chains or any(len(c) != len(chains[0]) for c in chains):
+            raise ValueError("every chain must hold the same number of steps")
+        if dtype is None:
+            dtype = F32 if len(chains[0]) and np.asarray(chains[0][0]).dtype == np.float32 else F64
+        # (a step that is not contiguous by itself is copied; the steps need not lie one behind the other)
+        blocks = [np.ascontiguousarray(c[s], dtype=np_dtype(dtype)) for c in chains for s in range(0, len(c), slice_interval)]
+        K, n = len(chains), len(blocks) // len(chains)
+        if not blocks or blocks[0].ndim != 2 or any(b.shape != blocks[0].shape for b in blocks):
+            raise ValueError("every step must have the same shape (W, P)")
+        W, P = blocks[0].shape
+        ptrs = (C.c_void_p * len(blocks))(*[b.ctypes.data for b in blocks])
+
+        def call(*outputs):
+            return L_.mcmcpp_hip_gelman_rubin(dtype, device, ptrs, K, n, W, P, int(bool(split)), *outputs)
+    used = (n + slice_interval - 1) // slice_interval if _is_tensor(steps) else n
+    M = K * (2 if split else 1) * W
+    out = dict(rhat=np.zeros(P), mean=np.zeros(P), within=np.zeros(P), between=np.zeros(P), chain_mean=np.zeros((K, P)), chain_within=np.zeros((K, P)))
+    if want_sequences:
+        out.update(sequence_mean=np.zeros((M, P)), sequence_m2=np.zeros((M, P)))
+    length, count = C.c_int64(0), C.c_int64(0)
+    rc = call(*([_ptr(out[k]) for k in ("rhat", "mean", "within", "between", "chain_mean", "chain_within")] +
+                [_ptr(out.get("sequence_mean")), _ptr(out.get("sequence_m2")), C.cast(C.byref(length), C.c_void_p), C.cast(C.byref(count), C.c_void_p)]))
+    if rc != OK:
+        raise HipError(rc, (L_.mcmcpp_hip_gelman_rubin_last_error() or b"").decode())
+    assert count.value == M and length.value == (used // 2 if split else used)
+    out.update(sequence_length=length.value, num_sequences=count.value)
+    return out
