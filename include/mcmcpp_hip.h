@@ -529,6 +529,59 @@ int mcmcpp_hip_gelman_rubin_device(int32_t dtype, int32_t device, const void* de
                                    int64_t* sequence_length, int64_t* num_sequences);
 const char* mcmcpp_hip_gelman_rubin_last_error(void);
 
+/* The effective sample size and the integrated autocorrelation time of every parameter over the same sequences: the
+ * multi-sequence estimator of BDA3 / Stan that goes with the split R-hat above (an extension: autocorr_times above is the
+ * reference's class, one pooled chain, and knows nothing of the between-chain variance).  Everything in fp64, each + - x /
+ * rounded on its own, no fma.
+ *   phase 1         sequences, split, H, L, M, the order m = (k H + h) W + w, sum_fixed, sequence_mean, within, between,
+ *                   varplus, rhat and mean are exactly those of the Gelman-Rubin call above: these outputs equal that call's
+ *                   on the same input bit for bit.
+ *   per sequence m, parameter p, lag t
+ *                   e_s = x_s - sequence_mean[m][p];  A_m[t] = e_0 e_t + e_1 e_(t+1) + ... + e_(L-1-t) e_(L-1), added in
+ *                   ascending s from +0: a plain ascending sum (the slices of sum_fixed are not used along s).
+ *   per parameter and lag
+ *                   S[t] = sum_fixed over m of A_m[t];  gamma[t] = (S[t] / M) / L;  rho[0] = 1;  for t >= 1
+ *                   rho[t] = 1 - (within - gamma[t]) / varplus.
+ *   window          cap = L - 1 when max_lag = 0, otherwise min(max_lag, L - 1);  kmax = floor((cap - 1) / 2);
+ *                   P_k = rho[2k] + rho[2k+1].  Walk k = 0, 1, ..., kmax; stop, with closed = 1, at the first k >= 1 for which
+ *                   `P_k >= 0` is false (a NaN stops the walk).  Otherwise Q_0 = P_0, Q_k = P_k if P_k < Q_(k-1), else
+ *                   Q_(k-1), and total = Q_0 + Q_1 + ... in ascending k.  lags_used = 2 x (pairs summed); closed = 0 when
+ *                   kmax was summed without a stop.
+ *   result          tau = -1 + 2 total; if tau < 1 / log10(N), tau = 1 / log10(N), with N = M L as a double and the host
+ *                   libm's log10 (a NaN tau stays);  ess = N / tau.  A constant parameter has varplus = 0: its rho, tau and
+ *                   ess are NaN by IEEE rules.  Non-finite samples propagate.
+ *   functions       n_functions >= 0: rho and autocov (= gamma), both [P][n_functions].  Every lag
+ *                   t < min(n_functions, cap + 1) is evaluated and returned whether or not the window closed before it;
+ *                   entries past that are NaN.
+ *   rounds          lags are evaluated in rounds of whole blocks of 32: the first covers MCMCPP_HIP_ESS_FIRST_LAGS lags
+ *                   (default 64; at least min(n_functions, cap + 1)); while a parameter's window is neither closed nor at
+ *                   its cap, the next round is twice as long.  A round holds no more lags than fit MCMCPP_HIP_ESS_WORK_MB
+ *                   (default 1024) of lagged products, 8 M P bytes a lag, and one block at the least.  Both are read per
+ *                   call, and neither they nor the CU count nor where the chain lies change a bit of any output.
+ *   steps           as for the Gelman-Rubin call (phase 1 uploads them in its chunks).  For the lagged products one
+ *                   (chain, half) of L steps is the unit of upload; the units stay in device memory across the rounds where
+ *                   they all fit and are uploaded again every round where they do not.  MCMCPP_HIP_E_NOMEM (with a message)
+ *                   when one unit and one block of lagged products cannot be allocated.
+ *   device_steps    as for the Gelman-Rubin call: chain_stride_steps, slice_interval, read where they lie.
+ *   outputs         ess, tau [P] double; lags_used, closed [P] int64; rho, autocov [P][n_functions]; rhat, mean, within,
+ *                   between [P]; *sequence_length = L, *num_sequences = M.  Any of them may be NULL.
+ * Free functions with a thread-local last error.  MCMCPP_HIP_E_ARG (with a message), before the device is opened, for every
+ * argument the Gelman-Rubin call refuses, and for max_lag < 0 and n_functions < 0; and for a device_steps that is not memory
+ * of that device, or chains that do not all end inside its allocation.  Nothing is written to the outputs of a call that
+ * fails. */
+int mcmcpp_hip_effective_sample_size(int32_t dtype, int32_t device, const void* const* steps, int32_t num_chains, int64_t n_steps,
+                                     int32_t num_walkers, int32_t num_params, int32_t split, int64_t max_lag, int64_t n_functions,
+                                     double* ess, double* tau, int64_t* lags_used, int64_t* closed, double* rho, double* autocov,
+                                     double* rhat, double* mean, double* within, double* between, int64_t* sequence_length,
+                                     int64_t* num_sequences);
+int mcmcpp_hip_effective_sample_size_device(int32_t dtype, int32_t device, const void* device_steps, int32_t num_chains,
+                                            int64_t chain_stride_steps, int64_t n_steps, int64_t slice_interval, int32_t num_walkers,
+                                            int32_t num_params, int32_t split, int64_t max_lag, int64_t n_functions, double* ess,
+                                            double* tau, int64_t* lags_used, int64_t* closed, double* rho, double* autocov,
+                                            double* rhat, double* mean, double* within, double* between, int64_t* sequence_length,
+                                            int64_t* num_sequences);
+const char* mcmcpp_hip_effective_sample_size_last_error(void);
+
 int mcmcpp_hip_abi_version(void);
 
 #ifdef __cplusplus

@@ -39,6 +39,7 @@ EXPORTS = [
     "mcmcpp_hip_order_statistics", "mcmcpp_hip_order_statistics_device", "mcmcpp_hip_rank_counts", "mcmcpp_hip_rank_counts_device",
     "mcmcpp_hip_order_statistics_last_error",
     "mcmcpp_hip_gelman_rubin", "mcmcpp_hip_gelman_rubin_device", "mcmcpp_hip_gelman_rubin_last_error",
+    "mcmcpp_hip_effective_sample_size", "mcmcpp_hip_effective_sample_size_device", "mcmcpp_hip_effective_sample_size_last_error",
 ]
 
 
@@ -171,6 +172,12 @@ def lib():
             L.mcmcpp_hip_gelman_rubin_device.argtypes = [i32, i32, vp, i32, i64, i64, i64, i32, i32, i32] + outputs
             L.mcmcpp_hip_gelman_rubin_last_error.argtypes = []
             L.mcmcpp_hip_gelman_rubin_last_error.restype = C.c_char_p
+        if hasattr(L, "mcmcpp_hip_effective_sample_size"):
+            outputs = [vp] * 12  # ess, tau, lags_used, closed, rho, autocov, rhat, mean, within, between, *sequence_length, *num_sequences
+            L.mcmcpp_hip_effective_sample_size.argtypes = [i32, i32, C.POINTER(vp), i32, i64, i32, i32, i32, i64, i64] + outputs
+            L.mcmcpp_hip_effective_sample_size_device.argtypes = [i32, i32, vp, i32, i64, i64, i64, i32, i32, i32, i64, i64] + outputs
+            L.mcmcpp_hip_effective_sample_size_last_error.argtypes = []
+            L.mcmcpp_hip_effective_sample_size_last_error.restype = C.c_char_p
         _lib = L
     return _lib
 
@@ -852,6 +859,37 @@ def _rhat_device_source(steps, chain_stride_steps, dtype, device):
     return tensor_dtype, steps.device.index, steps.data_ptr(), K, stride // (W * P), n, W, P
 
 
+def _rhat_sources(steps, slice_interval, chain_stride_steps, dtype, device):
+    """What gelman_rubin and effective_sample_size hand to the library: (on_device, dtype, device, source, K, chain stride, n,
+    W, P, keep).  On the device `source` is the address and n counts stored steps; on the host it is the array of step
+    pointers, sliced already, n counts used steps, and `keep` holds the arrays they point into."""
+    if slice_interval < 1:
+        raise ValueError("slice_interval must be at least 1")
+    if _is_tensor(steps):
+        dtype, device, ptr, K, stride, n, W, P = _rhat_device_source(steps, chain_stride_steps, dtype, device)
+        return True, dtype, device, C.c_void_p(ptr), K, stride, n, W, P, steps
+    if chain_stride_steps is not None:
+        raise ValueError("chain_stride_steps belongs to steps in device memory")
+    if isinstance(steps, np.ndarray):
+        if steps.ndim not in (3, 4):
+            raise ValueError("steps must have shape (K, n, W, P) or (n, W, P), not %s" % (steps.shape,))
+        chains = [steps] if steps.ndim == 3 else list(steps)
+    else:
+        chains = [list(c) for c in steps]
+    if not chains or any(len(c) != len(chains[0]) for c in chains):
+        raise ValueError("every chain must hold the same number of steps")
+    if dtype is None:
+        dtype = F32 if len(chains[0]) and np.asarray(chains[0][0]).dtype == np.float32 else F64
+    # (a step that is not contiguous by itself is copied; the steps need not lie one behind the other)
+    blocks = [np.ascontiguousarray(c[s], dtype=np_dtype(dtype)) for c in chains for s in range(0, len(c), slice_interval)]
+    K, n = len(chains), len(blocks) // len(chains)
+    if not blocks or blocks[0].ndim != 2 or any(b.shape != blocks[0].shape for b in blocks):
+        raise ValueError("every step must have the same shape (W, P)")
+    W, P = blocks[0].shape
+    ptrs = (C.c_void_p * len(blocks))(*[b.ctypes.data for b in blocks])
+    return False, dtype, device, ptrs, K, 0, n, W, P, blocks
+
+
 def gelman_rubin(steps, split=True, slice_interval=1, chain_stride_steps=None, dtype=None, device=-1, want_sequences=False):
     """The Gelman-Rubin split R-hat of every parameter, with the walkers of K chains as sequences (include/mcmcpp_hip.h,
     mcmcpp_hip_gelman_rubin: an extension).  steps: a numpy array [(K, n, W, P)] or [(n, W, P)] (one chain); a list of K lists of
@@ -859,38 +897,14 @@ def gelman_rubin(steps, split=True, slice_interval=1, chain_stride_steps=None, d
     chain[:, burn_in:] of what run_device wrote qualifies, its chains chain_stride_steps apart).  Every slice_interval-th step
     of a chain is used, from its first.  Returns a dict: rhat, mean, within, between [(P,)], chain_mean, chain_within [(K, P)],
     sequence_length, num_sequences, and with want_sequences sequence_mean, sequence_m2 [(M, P)]; all float64."""
-    if slice_interval < 1:
-        raise ValueError("slice_interval must be at least 1")
+    on_device, dtype, device, source, K, stride, n, W, P, _keep = _rhat_sources(steps, slice_interval, chain_stride_steps, dtype, device)
     L_ = lib()
-    if _is_tensor(steps):
-        dtype, device, ptr, K, stride, n, W, P = _rhat_device_source(steps, chain_stride_steps, dtype, device)
 
-        def call(*outputs):
-            return L_.mcmcpp_hip_gelman_rubin_device(dtype, device, C.c_void_p(ptr), K, stride, n, slice_interval, W, P, int(bool(split)), *outputs)
-    else:
-        if chain_stride_steps is not None:
-            raise ValueError("chain_stride_steps belongs to steps in device memory")
-        if isinstance(steps, np.ndarray):
-            if steps.ndim not in (3, 4):
-                raise ValueError("steps must have shape (K, n, W, P) or (n, W, P), not %s" % (steps.shape,))
-            chains = [steps] if steps.ndim == 3 else list(steps)
-        else:
-            chains = [list(c) for c in steps]
-        if not chains or any(len(c) != len(chains[0]) for c in chains):
-            raise ValueError("every chain must hold the same number of steps")
-        if dtype is None:
-            dtype = F32 if len(chains[0]) and np.asarray(chains[0][0]).dtype == np.float32 else F64
-        # (a step that is not contiguous by itself is copied; the steps need not lie one behind the other)
-        blocks = [np.ascontiguousarray(c[s], dtype=np_dtype(dtype)) for c in chains for s in range(0, len(c), slice_interval)]
-        K, n = len(chains), len(blocks) // len(chains)
-        if not blocks or blocks[0].ndim != 2 or any(b.shape != blocks[0].shape for b in blocks):
-            raise ValueError("every step must have the same shape (W, P)")
-        W, P = blocks[0].shape
-        ptrs = (C.c_void_p * len(blocks))(*[b.ctypes.data for b in blocks])
-
-        def call(*outputs):
-            return L_.mcmcpp_hip_gelman_rubin(dtype, device, ptrs, K, n, W, P, int(bool(split)), *outputs)
-    used = (n + slice_interval - 1) // slice_interval if _is_tensor(steps) else n
+    def call(*outputs):
+        if on_device:
+            return L_.mcmcpp_hip_gelman_rubin_device(dtype, device, source, K, stride, n, slice_interval, W, P, int(bool(split)), *outputs)
+        return L_.mcmcpp_hip_gelman_rubin(dtype, device, source, K, n, W, P, int(bool(split)), *outputs)
+    used = (n + slice_interval - 1) // slice_interval if on_device else n
     M = K * (2 if split else 1) * W
     out = dict(rhat=np.zeros(P), mean=np.zeros(P), within=np.zeros(P), between=np.zeros(P), chain_mean=np.zeros((K, P)), chain_within=np.zeros((K, P)))
     if want_sequences:
@@ -901,5 +915,29 @@ def gelman_rubin(steps, split=True, slice_interval=1, chain_stride_steps=None, d
     if rc != OK:
         raise HipError(rc, (L_.mcmcpp_hip_gelman_rubin_last_error() or b"").decode())
     assert count.value == M and length.value == (used // 2 if split else used)
+    out.update(sequence_length=length.value, num_sequences=count.value)
+    return out
+
+
+def effective_sample_size(steps, split=True, max_lag=0, n_functions=0, slice_interval=1, chain_stride_steps=None, dtype=None, device=-1):
+    """The effective sample size and integrated autocorrelation time of every parameter over the walkers of K chains
+    (include/mcmcpp_hip.h, mcmcpp_hip_effective_sample_size: the multi-sequence estimator that goes with the split R-hat; an
+    extension).  steps: as for gelman_rubin.  max_lag: 0, or the largest lag the window may reach.  n_functions: how many lags
+    of rho and autocov to return.  Returns a dict: ess, tau (float64), lags_used, closed (int64) [(P,)]; rho, autocov
+    [(P, n_functions)]; rhat, mean, within, between [(P,)]; sequence_length, num_sequences."""
+    if max_lag < 0 or n_functions < 0:
+        raise ValueError("max_lag and n_functions must not be negative")
+    on_device, dtype, device, source, K, stride, n, W, P, _keep = _rhat_sources(steps, slice_interval, chain_stride_steps, dtype, device)
+    L_ = lib()
+    out = dict(ess=np.zeros(P), tau=np.zeros(P), lags_used=np.zeros(P, np.int64), closed=np.zeros(P, np.int64), rho=np.zeros((P, n_functions)),
+               autocov=np.zeros((P, n_functions)), rhat=np.zeros(P), mean=np.zeros(P), within=np.zeros(P), between=np.zeros(P))
+    length, count = C.c_int64(0), C.c_int64(0)
+    outputs = [_ptr(a) if a.size else None for a in out.values()] + [C.cast(C.byref(length), C.c_void_p), C.cast(C.byref(count), C.c_void_p)]
+    if on_device:
+        rc = L_.mcmcpp_hip_effective_sample_size_device(dtype, device, source, K, stride, n, slice_interval, W, P, int(bool(split)), max_lag, n_functions, *outputs)
+    else:
+        rc = L_.mcmcpp_hip_effective_sample_size(dtype, device, source, K, n, W, P, int(bool(split)), max_lag, n_functions, *outputs)
+    if rc != OK:
+        raise HipError(rc, (L_.mcmcpp_hip_effective_sample_size_last_error() or b"").decode())
     out.update(sequence_length=length.value, num_sequences=count.value)
     return out

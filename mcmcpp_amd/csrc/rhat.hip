@@ -17,7 +17,8 @@
 //   * rhat_slice_sums_kernel / rhat_slice_join_kernel: sum_fixed over m of a function of [M][P], per parameter and per chain:
 //     the means and within-variances first, then the squared deviations from the mean in a second pass.
 // The last step, P square roots, is the host's.  A device chain is read in place; host chains are uploaded chain by chain in
-// chunks of MCMCPP_HIP_RHAT_CHUNK_MB (read per call, default 1024).
+// chunks of MCMCPP_HIP_RHAT_CHUNK_MB (read per call, default 1024).  The argument check and everything up to the figures in
+// device memory are also the first phase of mcmcpp_hip_effective_sample_size (ess.hip), which calls them through rhat_state.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -30,6 +31,7 @@
 #include "../../include/mcmcpp_hip.h"
 #include "analysis_host.hpp"
 #include "rhat_plan.hpp"
+#include "rhat_state.hpp"
 
 namespace
 {
@@ -281,8 +283,7 @@ rhat_slice_join_kernel(const double* __restrict__ in_a, const double* __restrict
 
 thread_local std::string g_rhat_error;
 
-int rhat_fail(int code, const std::string& msg) { return mcmcpp::analysis_fail(g_rhat_error, code, msg); }
-
+using mcmcpp::RhatRequest;
 using mcmcpp::StepSpan;
 
 struct Outputs
@@ -290,20 +291,6 @@ struct Outputs
     double *rhat, *mean, *within, *between, *chain_mean, *chain_within, *sequence_mean, *sequence_m2;
     int64_t *sequence_length, *num_sequences;
 };
-
-struct Request
-{
-    const char* what;
-    int32_t dtype, device;
-    const void* const* steps;
-    const void* device_steps;
-    bool on_device;
-    int32_t K;
-    int64_t chain_stride_steps, n_steps, slice;
-    int32_t W, P, split;
-    Outputs out;
-};
-
 
 template <class T, int V>
 void launch_series(const mcmcpp::RhatSeriesPlan& plan, hipStream_t stream, const StepSpan<T>& sp, long long chain_stride, long long E, long long n, long long L,
@@ -315,38 +302,41 @@ void launch_series(const mcmcpp::RhatSeriesPlan& plan, hipStream_t stream, const
 
 // sum_fixed over the N items of each of G segments of [M][P]: means and within-variances (center == nullptr), or squared
 // deviations from center[P]; into out_a, out_b [G][P], over div
-int sum_over_sequences(hipStream_t stream, const double* seq_mean, const double* seq_m2, const double* center, int P, long long N, int G, double Lm1, double div,
-                       double* part, size_t part_stride, double* out_a, double* out_b)
+int sum_over_sequences(std::string& slot, hipStream_t stream, const double* seq_mean, const double* seq_m2, const double* center, int P, long long N, int G, double Lm1,
+                       double div, double* part, size_t part_stride, double* out_a, double* out_b)
 {
     const mcmcpp::RhatSumPlan plan = mcmcpp::rhat_sum_plan(N, P, G);
     const auto kernel = center ? rhat_slice_sums_kernel<1> : rhat_slice_sums_kernel<0>;
     hipLaunchKernelGGL(kernel, dim3(plan.blocks, plan.segments), dim3(kRhatThreads), 0, stream, seq_mean, seq_m2, center, P, N, plan.slen, plan.slices, Lm1, part,
                        part + part_stride);
-    ANALYSIS_TRY(g_rhat_error, hipGetLastError());
+    ANALYSIS_TRY(slot, hipGetLastError());
     hipLaunchKernelGGL(rhat_slice_join_kernel, dim3((unsigned)((G * P + kRhatThreads - 1) / kRhatThreads)), dim3(kRhatThreads), 0, stream, (const double*)part,
                        center ? (const double*)nullptr : (const double*)(part + part_stride), P, G, plan.slices, div, out_a, out_b);
-    ANALYSIS_TRY(g_rhat_error, hipGetLastError());
+    ANALYSIS_TRY(slot, hipGetLastError());
     return MCMCPP_HIP_OK;
 }
 
 template <class T>
-int run_request(const Request& r, int device, const hipDeviceProp_t& prop, long long n, const mcmcpp::RhatShape& shape)
+int run_state(std::string& slot, const RhatRequest& r, int device, const hipDeviceProp_t& prop, long long n, const mcmcpp::RhatShape& shape, hipStream_t stream,
+              mcmcpp::RhatState& st)
 {
     const int K = r.K, P = r.P, H = shape.H;
     const long long E = (long long)r.W * P, L = shape.L, M = shape.M;
     const size_t step_bytes = sizeof(T) * (size_t)E;
     const long long chain_stride_steps = r.chain_stride_steps ? r.chain_stride_steps : r.n_steps;
     if (r.on_device)
-        if (int rc = mcmcpp::check_device_steps(g_rhat_error, r.what, r.device_steps, step_bytes * (size_t)((K - 1) * chain_stride_steps + r.n_steps), device)) return rc;
-    mcmcpp::DeviceBuffer<> d_chunk;
-    mcmcpp::DeviceBuffer<double> d_first, d_state, d_seq, d_part, d_res;
-    mcmcpp::Stream stream;  // (behind the buffers: the stream is idle and gone when they go)
-    ANALYSIS_TRY(g_rhat_error, hipStreamCreateWithFlags(stream.replace(), hipStreamNonBlocking));
+        if (int rc = mcmcpp::check_device_steps(slot, r.what, r.device_steps, step_bytes * (size_t)((K - 1) * chain_stride_steps + r.n_steps), device)) return rc;
+    mcmcpp::DeviceBuffer<>& d_chunk = st.chunk;
+    mcmcpp::DeviceBuffer<double>& d_first = st.first;
+    mcmcpp::DeviceBuffer<double>& d_state = st.state;
+    mcmcpp::DeviceBuffer<double>& d_seq = st.seq;
+    mcmcpp::DeviceBuffer<double>& d_part = st.part;
+    mcmcpp::DeviceBuffer<double>& d_res = st.res;
     // a device chain is read in place, all chains in one launch; host chains are uploaded chain by chain, a chunk at a time
     const long long per = r.on_device ? n : mcmcpp::rhat_steps_per_chunk(mcmcpp::chunk_bytes_from_env("MCMCPP_HIP_RHAT_CHUNK_MB", 1024), step_bytes);
     const size_t series = (size_t)M * P;
     if (mcmcpp::grow(d_chunk, r.on_device ? 0 : step_bytes * (size_t)(n < per ? n : per), stream) != hipSuccess)
-        return rhat_fail(MCMCPP_HIP_E_NOMEM, std::string(r.what) + ": cannot allocate the upload buffer");
+        return mcmcpp::analysis_fail(slot, MCMCPP_HIP_E_NOMEM, std::string(r.what) + ": cannot allocate the upload buffer");
     const int vec = mcmcpp::rhat_vector_width(sizeof(T), E, r.on_device ? (uintptr_t)r.device_steps : (uintptr_t)d_chunk.get());
     const mcmcpp::RhatSeriesPlan plan = mcmcpp::rhat_series_plan(E, vec, L, r.on_device ? K * H : H, mcmcpp::rhat_plan_cus(prop.multiProcessorCount));
     const size_t part_all = (size_t)mcmcpp::rhat_sum_plan(M, P, 1).slices * P, part_chain = (size_t)K * mcmcpp::rhat_sum_plan((long long)H * r.W, P, K).slices * P;
@@ -354,18 +344,18 @@ int run_request(const Request& r, int device, const hipDeviceProp_t& prop, long 
     const size_t res = 3 * (size_t)P + 2 * (size_t)K * P;  // mean, within, between [P]; chain_mean, chain_within [K][P]
     if (d_first.alloc(8 * series) != hipSuccess || d_state.alloc(8 * series * 2 * plan.slots) != hipSuccess || d_seq.alloc(8 * series * 2) != hipSuccess ||
         d_part.alloc(8 * part * 2) != hipSuccess || d_res.alloc(8 * res) != hipSuccess)
-        return rhat_fail(MCMCPP_HIP_E_NOMEM,
-                         std::string(r.what) + ": cannot allocate the " + std::to_string(8 * series * (3 + 2 * (size_t)plan.slots)) + "-byte state of the sequences");
+        return mcmcpp::analysis_fail(slot, MCMCPP_HIP_E_NOMEM,
+                                     std::string(r.what) + ": cannot allocate the " + std::to_string(8 * series * (3 + 2 * (size_t)plan.slots)) + "-byte state of the sequences");
 
     constexpr int kPiece = mcmcpp::kRhatVectorBytes / (int)sizeof(T);
     const auto launch = vec == 1 ? launch_series<T, 1> : launch_series<T, kPiece>;
     for (int k = 0; k < (r.on_device ? 1 : K); ++k)
     {
-        mcmcpp::StepSource<T> src{r.on_device ? nullptr : r.steps + (size_t)k * n, static_cast<const T*>(r.device_steps), n, r.slice, r.W, P, stream, &d_chunk, &g_rhat_error};
+        mcmcpp::StepSource<T> src{r.on_device ? nullptr : r.steps + (size_t)k * n, static_cast<const T*>(r.device_steps), n, r.slice, r.W, P, stream, &d_chunk, &slot};
         long long g0 = 0;
         int rc = src.for_each_chunk(per, [&](const StepSpan<T>& sp) -> int {
             launch(plan, stream, sp, chain_stride_steps * E, E, n, L, H, g0, k * H, d_first.get(), d_state.get());
-            ANALYSIS_TRY(g_rhat_error, hipGetLastError());
+            ANALYSIS_TRY(slot, hipGetLastError());
             g0 += sp.n_steps;
             return MCMCPP_HIP_OK;
         });
@@ -375,45 +365,75 @@ int run_request(const Request& r, int device, const hipDeviceProp_t& prop, long 
     double *mean = d_res.get(), *within = mean + P, *between = within + P, *chain_mean = between + P, *chain_within = chain_mean + (size_t)K * P;
     hipLaunchKernelGGL(rhat_sequence_kernel, dim3((unsigned)((series + kRhatThreads - 1) / kRhatThreads)), dim3(kRhatThreads), 0, stream, (const double*)d_first.get(),
                        (const double*)d_state.get(), E, (long long)series, plan.slots, plan.own ? 1 : plan.slices, (double)L, seq_mean, seq_m2);
-    ANALYSIS_TRY(g_rhat_error, hipGetLastError());
+    ANALYSIS_TRY(slot, hipGetLastError());
     const double Lm1 = (double)(L - 1);
-    if (int rc = sum_over_sequences(stream, seq_mean, seq_m2, nullptr, P, M, 1, Lm1, (double)M, d_part.get(), part, mean, within)) return rc;
-    if (int rc = sum_over_sequences(stream, seq_mean, seq_m2, nullptr, P, (long long)H * r.W, K, Lm1, (double)((long long)H * r.W), d_part.get(), part, chain_mean, chain_within))
+    if (int rc = sum_over_sequences(slot, stream, seq_mean, seq_m2, nullptr, P, M, 1, Lm1, (double)M, d_part.get(), part, mean, within)) return rc;
+    if (int rc = sum_over_sequences(slot, stream, seq_mean, seq_m2, nullptr, P, (long long)H * r.W, K, Lm1, (double)((long long)H * r.W), d_part.get(), part, chain_mean,
+                                    chain_within))
         return rc;
-    if (int rc = sum_over_sequences(stream, seq_mean, seq_m2, mean, P, M, 1, Lm1, (double)(M - 1), d_part.get(), part, between, nullptr)) return rc;
-
-    std::vector<double> h_res(res), h_seq;
-    ANALYSIS_TRY(g_rhat_error, hipMemcpyAsync(h_res.data(), d_res, 8 * res, hipMemcpyDeviceToHost, stream));
-    const bool want_seq = r.out.sequence_mean || r.out.sequence_m2;
-    if (want_seq)
-    {
-        h_seq.resize(2 * series);
-        ANALYSIS_TRY(g_rhat_error, hipMemcpyAsync(h_seq.data(), d_seq, 16 * series, hipMemcpyDeviceToHost, stream));
-    }
-    ANALYSIS_TRY(g_rhat_error, hipStreamSynchronize(stream));
-    // the call has succeeded: the outputs
-    const double *h_mean = h_res.data(), *h_within = h_mean + P, *h_between = h_within + P;
-    if (r.out.rhat)
-        for (int p = 0; p < P; ++p)
-        {
-            const double varplus = (h_within[p] * Lm1) / (double)L + h_between[p];
-            r.out.rhat[p] = std::sqrt(varplus / h_within[p]);
-        }
-    if (r.out.mean) std::memcpy(r.out.mean, h_mean, 8 * (size_t)P);
-    if (r.out.within) std::memcpy(r.out.within, h_within, 8 * (size_t)P);
-    if (r.out.between) std::memcpy(r.out.between, h_between, 8 * (size_t)P);
-    if (r.out.chain_mean) std::memcpy(r.out.chain_mean, h_between + P, 8 * (size_t)K * P);
-    if (r.out.chain_within) std::memcpy(r.out.chain_within, h_between + P + (size_t)K * P, 8 * (size_t)K * P);
-    if (r.out.sequence_mean) std::memcpy(r.out.sequence_mean, h_seq.data(), 8 * series);
-    if (r.out.sequence_m2) std::memcpy(r.out.sequence_m2, h_seq.data() + series, 8 * series);
-    if (r.out.sequence_length) *r.out.sequence_length = L;
-    if (r.out.num_sequences) *r.out.num_sequences = M;
+    if (int rc = sum_over_sequences(slot, stream, seq_mean, seq_m2, mean, P, M, 1, Lm1, (double)(M - 1), d_part.get(), part, between, nullptr)) return rc;
+    st.h_res.resize(res);
+    ANALYSIS_TRY(slot, hipMemcpyAsync(st.h_res.data(), d_res, 8 * res, hipMemcpyDeviceToHost, stream));
     return MCMCPP_HIP_OK;
 }
 
-int rhat_entry(const Request& r)
+int run_request(const RhatRequest& r, const Outputs& out, int device, const hipDeviceProp_t& prop, long long n, const mcmcpp::RhatShape& shape)
+{
+    const int K = r.K, P = r.P;
+    const long long L = shape.L, M = shape.M;
+    const size_t series = (size_t)M * P;
+    mcmcpp::RhatState st;
+    mcmcpp::Stream stream;  // (behind the buffers: the stream is idle and gone when they go)
+    ANALYSIS_TRY(g_rhat_error, hipStreamCreateWithFlags(stream.replace(), hipStreamNonBlocking));
+    if (int rc = mcmcpp::rhat_sequences_state(g_rhat_error, r, device, prop, n, shape, stream, st)) return rc;
+    std::vector<double> h_seq;
+    const std::vector<double>& h_res = st.h_res;
+    if (out.sequence_mean || out.sequence_m2)
+    {
+        h_seq.resize(2 * series);
+        ANALYSIS_TRY(g_rhat_error, hipMemcpyAsync(h_seq.data(), st.seq, 16 * series, hipMemcpyDeviceToHost, stream));
+    }
+    ANALYSIS_TRY(g_rhat_error, hipStreamSynchronize(stream));
+    // the call has succeeded: the outputs
+    const double Lm1 = (double)(L - 1);
+    const double *h_mean = h_res.data(), *h_within = h_mean + P, *h_between = h_within + P;
+    if (out.rhat)
+        for (int p = 0; p < P; ++p)
+        {
+            const double varplus = (h_within[p] * Lm1) / (double)L + h_between[p];
+            out.rhat[p] = std::sqrt(varplus / h_within[p]);
+        }
+    if (out.mean) std::memcpy(out.mean, h_mean, 8 * (size_t)P);
+    if (out.within) std::memcpy(out.within, h_within, 8 * (size_t)P);
+    if (out.between) std::memcpy(out.between, h_between, 8 * (size_t)P);
+    if (out.chain_mean) std::memcpy(out.chain_mean, h_between + P, 8 * (size_t)K * P);
+    if (out.chain_within) std::memcpy(out.chain_within, h_between + P + (size_t)K * P, 8 * (size_t)K * P);
+    if (out.sequence_mean) std::memcpy(out.sequence_mean, h_seq.data(), 8 * series);
+    if (out.sequence_m2) std::memcpy(out.sequence_m2, h_seq.data() + series, 8 * series);
+    if (out.sequence_length) *out.sequence_length = L;
+    if (out.num_sequences) *out.num_sequences = M;
+    return MCMCPP_HIP_OK;
+}
+
+int rhat_entry(const RhatRequest& r, const Outputs& out)
+{
+    long long n = 0;
+    mcmcpp::RhatShape shape;
+    if (int rc = mcmcpp::rhat_check_request(g_rhat_error, r, &n, &shape)) return rc;
+    hipDeviceProp_t prop;
+    std::string why;
+    int device = r.device;
+    if (int rc = mcmcpp::open_gfx950_device(device, &device, &prop, &why)) return mcmcpp::analysis_fail(g_rhat_error, rc, std::string(r.what) + ": " + why);
+    return run_request(r, out, device, prop, n, shape);
+}
+}  // namespace
+
+namespace mcmcpp
+{
+int rhat_check_request(std::string& slot, const RhatRequest& r, long long* n_out, RhatShape* shape_out)
 {
     const std::string w(r.what);
+    const auto rhat_fail = [&](int code, const std::string& msg) { return analysis_fail(slot, code, msg); };
     if (r.dtype != MCMCPP_HIP_F64 && r.dtype != MCMCPP_HIP_F32) return rhat_fail(MCMCPP_HIP_E_ARG, w + ": dtype must be MCMCPP_HIP_F64 or MCMCPP_HIP_F32");
     if (r.K < 1 || r.K > mcmcpp::kRhatMaxChains) return rhat_fail(MCMCPP_HIP_E_ARG, w + ": 1 <= num_chains <= " + std::to_string(mcmcpp::kRhatMaxChains));
     if (r.P < 1 || r.P > mcmcpp::kRhatMaxParams) return rhat_fail(MCMCPP_HIP_E_ARG, w + ": 1 <= num_params <= " + std::to_string(mcmcpp::kRhatMaxParams));
@@ -431,13 +451,17 @@ int rhat_entry(const Request& r)
     if (shape.L < 2)
         return rhat_fail(MCMCPP_HIP_E_ARG, w + ": a sequence needs two steps (L >= 2): " + std::to_string(n) + " used steps give L = " + std::to_string(shape.L));
     if (shape.M < 2) return rhat_fail(MCMCPP_HIP_E_ARG, w + ": two sequences at the least (M >= 2): one chain of one walker, unsplit, is one");
-    hipDeviceProp_t prop;
-    std::string why;
-    int device = r.device;
-    if (int rc = mcmcpp::open_gfx950_device(device, &device, &prop, &why)) return rhat_fail(rc, w + ": " + why);
-    return r.dtype == MCMCPP_HIP_F64 ? run_request<double>(r, device, prop, n, shape) : run_request<float>(r, device, prop, n, shape);
+    *n_out = n;
+    *shape_out = shape;
+    return MCMCPP_HIP_OK;
 }
-}  // namespace
+
+int rhat_sequences_state(std::string& slot, const RhatRequest& r, int device, const hipDeviceProp_t& prop, long long n, const RhatShape& shape, hipStream_t stream,
+                         RhatState& st)
+{
+    return r.dtype == MCMCPP_HIP_F64 ? run_state<double>(slot, r, device, prop, n, shape, stream, st) : run_state<float>(slot, r, device, prop, n, shape, stream, st);
+}
+}  // namespace mcmcpp
 
 extern "C"
 {
@@ -447,8 +471,8 @@ int mcmcpp_hip_gelman_rubin(int32_t dtype, int32_t device, const void* const* st
                             int32_t split, double* rhat, double* mean, double* within, double* between, double* chain_mean, double* chain_within,
                             double* sequence_mean, double* sequence_m2, int64_t* sequence_length, int64_t* num_sequences)
 {
-    return rhat_entry(Request{"gelman_rubin", dtype, device, steps, nullptr, false, num_chains, 0, n_steps, 1, num_walkers, num_params, split,
-                              Outputs{rhat, mean, within, between, chain_mean, chain_within, sequence_mean, sequence_m2, sequence_length, num_sequences}});
+    return rhat_entry(RhatRequest{"gelman_rubin", dtype, device, steps, nullptr, false, num_chains, 0, n_steps, 1, num_walkers, num_params, split},
+                      Outputs{rhat, mean, within, between, chain_mean, chain_within, sequence_mean, sequence_m2, sequence_length, num_sequences});
 }
 
 int mcmcpp_hip_gelman_rubin_device(int32_t dtype, int32_t device, const void* device_steps, int32_t num_chains, int64_t chain_stride_steps, int64_t n_steps,
@@ -456,8 +480,8 @@ int mcmcpp_hip_gelman_rubin_device(int32_t dtype, int32_t device, const void* de
                                    double* between, double* chain_mean, double* chain_within, double* sequence_mean, double* sequence_m2,
                                    int64_t* sequence_length, int64_t* num_sequences)
 {
-    return rhat_entry(Request{"gelman_rubin_device", dtype, device, nullptr, device_steps, true, num_chains, chain_stride_steps, n_steps, slice_interval, num_walkers,
-                              num_params, split,
-                              Outputs{rhat, mean, within, between, chain_mean, chain_within, sequence_mean, sequence_m2, sequence_length, num_sequences}});
+    return rhat_entry(RhatRequest{"gelman_rubin_device", dtype, device, nullptr, device_steps, true, num_chains, chain_stride_steps, n_steps, slice_interval,
+                                  num_walkers, num_params, split},
+                      Outputs{rhat, mean, within, between, chain_mean, chain_within, sequence_mean, sequence_m2, sequence_length, num_sequences});
 }
 }
