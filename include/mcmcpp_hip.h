@@ -582,6 +582,81 @@ int mcmcpp_hip_effective_sample_size_device(int32_t dtype, int32_t device, const
                                             int64_t* num_sequences);
 const char* mcmcpp_hip_effective_sample_size_last_error(void);
 
+/* The normal scores of the draws of every parameter: the rank-normalisation of Vehtari, Gelman, Simpson, Carpenter and
+ * Buerkner (2021), on which the rank-normalised R-hat and the bulk-ESS below rest (an extension).  Ranks are integers, found
+ * exactly by a stable radix sort on the device; everything after them is fp64, each + - x / rounded on its own, no fma.
+ *   draws           the sequences, split, H, L and M are exactly those of the Gelman-Rubin call above.  With split and an odd
+ *                   number n of used steps the middle used step belongs to no sequence and is not ranked.  A parameter has
+ *                   S = M L draws, 2 <= S <= 2^31 - 1.  Step j of chain k of the output is the j-th used step of that chain
+ *                   that belongs to a sequence: scores is a chain [K][H L][W][P] whose own split halves are the sequences.
+ *   order           x_(i), i = 0 .. S - 1: the i-th smallest draw of the parameter in the total order of
+ *                   mcmcpp_hip_order_statistics (-inf < ... < -0 < +0 < ... < +inf).  A float draw converts to double exactly.
+ *   quantile q      h = q (S - 1) in double, lo = floor(h), hi = ceil(h); x_(lo) where x_(lo) == x_(hi), else
+ *                   x_(lo) + (x_(hi) - x_(lo)) (h - floor(h)).  median = quantile 0.5, q05 = quantile 0.05, q95 = quantile 0.95.
+ *   value ranked    fold == 0: v = x.  fold != 0: v = |x - median| in double.
+ *   rank            values compare as numbers (-0 == +0).  below = #{v' < v}, equal = #{v' == v} over the S draws;
+ *                   r = below + (equal + 1) / 2: the average rank, exact in double.
+ *   score           p = (r - 0.375) / (S + 0.25);  z = mcmcpp::normal_score(p) of mcmcpp_amd/csrc/normal_score.hpp: Wichura's
+ *                   AS 241 (PPND16) in the evaluation order that header's comment states, with a logarithm of its own.  The
+ *                   device and the host produce the same bits.  All S draws equal: every z is +0.
+ *   knobs           parameters are ranked a tile at a time, as many as fit MCMCPP_HIP_RANK_WORK_MB (read per call, default
+ *                   1024; one parameter at the least: 2 S (key bytes + 4) bytes and the digit tables).  Host chains are
+ *                   uploaded once, as the sequences' steps, in copy groups of MCMCPP_HIP_RHAT_CHUNK_MB.  Neither changes a bit.
+ *   memory          held in device memory together: the fp64 chain of scores, 8 K H L W P bytes (the caller's for the device
+ *                   form of the normal scores, the library's otherwise); for host chains their upload as well, (element size)
+ *                   x K H L W P bytes -- MCMCPP_HIP_RHAT_CHUNK_MB groups the copies and bounds no memory, unlike in the R-hat
+ *                   and ESS calls, which stream host chains through; and the sort workspace.  MCMCPP_HIP_E_NOMEM, with the
+ *                   byte count, when one of them cannot be had.
+ *   median          a quantile interpolated between -inf and a larger order statistic, or up to +inf from a smaller one, is
+ *                   NaN or infinite by IEEE rules (-inf + inf), and is returned so for fold == 0.  A fold about a median
+ *                   that is not finite would make every |x - median| NaN or infinite: it fails the call.
+ *   steps, device_steps
+ *                   as for the Gelman-Rubin call.
+ *   outputs         scores [K][H L][W][P] double, required: host memory for mcmcpp_hip_normal_scores, caller-owned memory
+ *                   of that device for mcmcpp_hip_normal_scores_device (checked to be such, and large enough); median, q05,
+ *                   q95 [P] double; *sequence_length = L, *num_sequences = M; these may be NULL.
+ * MCMCPP_HIP_E_ARG (with a message) for every argument the Gelman-Rubin call refuses, for S > 2^31 - 1, for S x num_params > 256 x (2^31 - 1) (a launch grid), a NULL scores, a
+ * scores of the device form that is not memory of that device or too small, a NaN draw (it has no place in the order), and,
+ * folded, a median that is not finite (the folded values would be NaN).  MCMCPP_HIP_E_NOMEM, with the byte count, when the
+ * workspace of one parameter cannot be allocated.  Nothing is written to any output of a call that fails.  The thread-local
+ * last error is mcmcpp_hip_rank_diagnostics_last_error's. */
+int mcmcpp_hip_normal_scores(int32_t dtype, int32_t device, const void* const* steps, int32_t num_chains, int64_t n_steps,
+                             int32_t num_walkers, int32_t num_params, int32_t split, int32_t fold, double* scores, double* median,
+                             double* q05, double* q95, int64_t* sequence_length, int64_t* num_sequences);
+int mcmcpp_hip_normal_scores_device(int32_t dtype, int32_t device, const void* device_steps, int32_t num_chains,
+                                    int64_t chain_stride_steps, int64_t n_steps, int64_t slice_interval, int32_t num_walkers,
+                                    int32_t num_params, int32_t split, int32_t fold, double* scores, double* median, double* q05,
+                                    double* q95, int64_t* sequence_length, int64_t* num_sequences);
+
+/* Rank-normalised split R-hat, bulk-ESS and tail-ESS of every parameter (Vehtari et al. 2021; what Stan, ArviZ and `posterior`
+ * report), defined by composition of the calls above:
+ *   rhat_rank, ess_bulk, closed_bulk
+ *                   the rhat, ess and closed that mcmcpp_hip_effective_sample_size_device(MCMCPP_HIP_F64, ...) returns on the
+ *                   scores of fold = 0, read as K chains of H L steps with the same split and max_lag.
+ *   rhat_folded     the rhat of mcmcpp_hip_gelman_rubin_device on the scores of fold = 1.
+ *   ess_tail_lower, ess_tail_upper
+ *                   that ESS call's ess on the fp64 chain [K][H L][W][P] of the indicators 1.0 / 0.0 of x <= q05 and of
+ *                   x <= q95, compared in double (not rank-normalised, as in `posterior`).  A constant indicator gives NaN by
+ *                   the ESS call's rule.  closed_tail = 1 where both windows closed.
+ *   ess_tail        NaN if either is NaN, else the smaller.   rhat: NaN if rhat_rank or rhat_folded is NaN, else the larger.
+ * The results are bit for bit those of the existing entry points on those chains, so they depend on the data alone.
+ *   outputs         rhat, rhat_rank, rhat_folded, ess_bulk, ess_tail, ess_tail_lower, ess_tail_upper, median, q05, q95 [P]
+ *                   double; closed_bulk, closed_tail [P] int64; *sequence_length, *num_sequences.  Any of them may be NULL.
+ * Failures as for the normal scores (there is no scores argument), and max_lag < 0.  Nothing is written to the outputs of a
+ * call that fails. */
+int mcmcpp_hip_rank_diagnostics(int32_t dtype, int32_t device, const void* const* steps, int32_t num_chains, int64_t n_steps,
+                                int32_t num_walkers, int32_t num_params, int32_t split, int64_t max_lag, double* rhat,
+                                double* rhat_rank, double* rhat_folded, double* ess_bulk, double* ess_tail, double* ess_tail_lower,
+                                double* ess_tail_upper, double* median, double* q05, double* q95, int64_t* closed_bulk,
+                                int64_t* closed_tail, int64_t* sequence_length, int64_t* num_sequences);
+int mcmcpp_hip_rank_diagnostics_device(int32_t dtype, int32_t device, const void* device_steps, int32_t num_chains,
+                                       int64_t chain_stride_steps, int64_t n_steps, int64_t slice_interval, int32_t num_walkers,
+                                       int32_t num_params, int32_t split, int64_t max_lag, double* rhat, double* rhat_rank,
+                                       double* rhat_folded, double* ess_bulk, double* ess_tail, double* ess_tail_lower,
+                                       double* ess_tail_upper, double* median, double* q05, double* q95, int64_t* closed_bulk,
+                                       int64_t* closed_tail, int64_t* sequence_length, int64_t* num_sequences);
+const char* mcmcpp_hip_rank_diagnostics_last_error(void);
+
 int mcmcpp_hip_abi_version(void);
 
 #ifdef __cplusplus

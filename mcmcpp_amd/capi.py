@@ -40,6 +40,8 @@ EXPORTS = [
     "mcmcpp_hip_order_statistics_last_error",
     "mcmcpp_hip_gelman_rubin", "mcmcpp_hip_gelman_rubin_device", "mcmcpp_hip_gelman_rubin_last_error",
     "mcmcpp_hip_effective_sample_size", "mcmcpp_hip_effective_sample_size_device", "mcmcpp_hip_effective_sample_size_last_error",
+    "mcmcpp_hip_normal_scores", "mcmcpp_hip_normal_scores_device", "mcmcpp_hip_rank_diagnostics", "mcmcpp_hip_rank_diagnostics_device",
+    "mcmcpp_hip_rank_diagnostics_last_error",
 ]
 
 
@@ -178,6 +180,15 @@ def lib():
             L.mcmcpp_hip_effective_sample_size_device.argtypes = [i32, i32, vp, i32, i64, i64, i64, i32, i32, i32, i64, i64] + outputs
             L.mcmcpp_hip_effective_sample_size_last_error.argtypes = []
             L.mcmcpp_hip_effective_sample_size_last_error.restype = C.c_char_p
+        if hasattr(L, "mcmcpp_hip_normal_scores"):
+            outputs = [vp] * 6  # scores, median, q05, q95, *sequence_length, *num_sequences
+            L.mcmcpp_hip_normal_scores.argtypes = [i32, i32, C.POINTER(vp), i32, i64, i32, i32, i32, i32] + outputs
+            L.mcmcpp_hip_normal_scores_device.argtypes = [i32, i32, vp, i32, i64, i64, i64, i32, i32, i32, i32] + outputs
+            outputs = [vp] * 14  # ten double arrays, closed_bulk, closed_tail, *sequence_length, *num_sequences
+            L.mcmcpp_hip_rank_diagnostics.argtypes = [i32, i32, C.POINTER(vp), i32, i64, i32, i32, i32, i64] + outputs
+            L.mcmcpp_hip_rank_diagnostics_device.argtypes = [i32, i32, vp, i32, i64, i64, i64, i32, i32, i32, i64] + outputs
+            L.mcmcpp_hip_rank_diagnostics_last_error.argtypes = []
+            L.mcmcpp_hip_rank_diagnostics_last_error.restype = C.c_char_p
         _lib = L
     return _lib
 
@@ -939,5 +950,59 @@ def effective_sample_size(steps, split=True, max_lag=0, n_functions=0, slice_int
         rc = L_.mcmcpp_hip_effective_sample_size(dtype, device, source, K, n, W, P, int(bool(split)), max_lag, n_functions, *outputs)
     if rc != OK:
         raise HipError(rc, (L_.mcmcpp_hip_effective_sample_size_last_error() or b"").decode())
+    out.update(sequence_length=length.value, num_sequences=count.value)
+    return out
+
+
+def _rank_check(rc):
+    if rc != OK:
+        raise HipError(rc, (lib().mcmcpp_hip_rank_diagnostics_last_error() or b"").decode())
+
+
+def normal_scores(steps, split=True, fold=False, slice_interval=1, chain_stride_steps=None, dtype=None, device=-1):
+    """The normal scores of the draws of every parameter (include/mcmcpp_hip.h, mcmcpp_hip_normal_scores: the rank-normalisation
+    of Vehtari et al. 2021; an extension).  steps: as for gelman_rubin.  fold: rank |x - median| instead of x.  Returns a dict:
+    scores, float64 [(K, H L, W, P)], the chain of the sequences' steps -- a numpy array for host steps, a torch tensor on the
+    steps' device for device steps; median, q05, q95 [(P,)] float64; sequence_length, num_sequences."""
+    on_device, dtype, device, source, K, stride, n, W, P, _keep = _rhat_sources(steps, slice_interval, chain_stride_steps, dtype, device)
+    used = (n + slice_interval - 1) // slice_interval if on_device else n
+    HL = used // 2 * 2 if split else used
+    out = dict(median=np.zeros(P), q05=np.zeros(P), q95=np.zeros(P))
+    length, count = C.c_int64(0), C.c_int64(0)
+    tail = [_ptr(out[k]) for k in ("median", "q05", "q95")] + [C.cast(C.byref(length), C.c_void_p), C.cast(C.byref(count), C.c_void_p)]
+    L_ = lib()
+    if on_device:
+        import torch
+        scores = torch.empty((K, max(HL, 0), W, P), dtype=torch.float64, device=steps.device)
+        _after_torch(scores)
+        _rank_check(L_.mcmcpp_hip_normal_scores_device(dtype, device, source, K, stride, n, slice_interval, W, P, int(bool(split)), int(bool(fold)),
+                                                       C.c_void_p(scores.data_ptr()), *tail))
+    else:
+        scores = np.zeros((K, max(HL, 0), W, P))
+        _rank_check(L_.mcmcpp_hip_normal_scores(dtype, device, source, K, n, W, P, int(bool(split)), int(bool(fold)), _ptr(scores), *tail))
+    out.update(scores=scores, sequence_length=length.value, num_sequences=count.value)
+    return out
+
+
+RANK_DIAGNOSTICS_KEYS = ("rhat", "rhat_rank", "rhat_folded", "ess_bulk", "ess_tail", "ess_tail_lower", "ess_tail_upper", "median", "q05", "q95",
+                         "closed_bulk", "closed_tail")
+
+
+def rank_diagnostics(steps, split=True, max_lag=0, slice_interval=1, chain_stride_steps=None, dtype=None, device=-1):
+    """Rank-normalised split R-hat, bulk-ESS and tail-ESS of every parameter (include/mcmcpp_hip.h, mcmcpp_hip_rank_diagnostics;
+    an extension).  steps: as for gelman_rubin.  Returns a dict: rhat, rhat_rank, rhat_folded, ess_bulk, ess_tail,
+    ess_tail_lower, ess_tail_upper, median, q05, q95 (float64), closed_bulk, closed_tail (int64) [(P,)]; sequence_length,
+    num_sequences."""
+    if max_lag < 0:
+        raise ValueError("max_lag must not be negative")
+    on_device, dtype, device, source, K, stride, n, W, P, _keep = _rhat_sources(steps, slice_interval, chain_stride_steps, dtype, device)
+    out = {k: np.zeros(P, np.int64 if k.startswith("closed") else np.float64) for k in RANK_DIAGNOSTICS_KEYS}
+    length, count = C.c_int64(0), C.c_int64(0)
+    outputs = [_ptr(a) for a in out.values()] + [C.cast(C.byref(length), C.c_void_p), C.cast(C.byref(count), C.c_void_p)]
+    L_ = lib()
+    if on_device:
+        _rank_check(L_.mcmcpp_hip_rank_diagnostics_device(dtype, device, source, K, stride, n, slice_interval, W, P, int(bool(split)), max_lag, *outputs))
+    else:
+        _rank_check(L_.mcmcpp_hip_rank_diagnostics(dtype, device, source, K, n, W, P, int(bool(split)), max_lag, *outputs))
     out.update(sequence_length=length.value, num_sequences=count.value)
     return out
