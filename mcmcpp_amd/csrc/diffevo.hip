@@ -13,7 +13,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "diffevo_plan.hpp"
+#include "diffevo_planner.hpp"
 #include "launch_table.hpp"
 #include "sampler_host.hpp"
 
@@ -60,36 +60,12 @@ public:
         if (int rc = open_device(c, &prop)) return rc;
         if (int rc = open_stream(c)) return rc;
 
-        scan_run = (int)knobs.de_scan_run.value_or(kDeScanRun);
-        if (scan_run < 1) scan_run = 1;
-        batch_max = (int)knobs.de_batch.value_or(kDeBatchMax);
-        // the batch: as many half-steps as the position counters (32 bits), the resolver's lists and a sensible amount of
-        // record memory (256 MiB) allow
-        const unsigned per = (unsigned)D + 3u;
-        {
-            long long b = batch_max < 1 ? 1 : (batch_max > kDeBatchMax ? kDeBatchMax : batch_max);
-            const long long by_positions = ((1LL << 30) - 2 * (kDeShiftMax + 1)) / ((long long)per * n);
-            const long long by_lists = (kDeMaxBad * 5LL / 8 - 2 * (kDeShiftMax + 1) / n) / per;
-            const long long by_records = (8LL << 20) / n;
-            b = b < by_positions ? b : by_positions;
-            b = b < by_lists ? b : by_lists;
-            b = b < by_records ? b : by_records;
-            if (b < 1)
-                return fail(MCMCPP_HIP_E_UNSUPPORTED, "differential evolution: %d walkers x %d parameters exceed what the stream planner holds (per half-step: 2^30 stream "
-                            "positions, 8 Mi updates)", W, D);
-            batch_max = (int)b;
-        }
-        const size_t updates_max = (size_t)batch_max * n;
-        positions_max = (long long)per * (long long)(updates_max - 1) + 2 * (kDeShiftMax + 1);  // (what a scan looks at)
-        // one stream position in n is bad: a batch lists about (D + 3) of them per half-step (and as many again as the
-        // kDeShiftMax positions behind its end hold, which matters for tiny ensembles), spread evenly over the lists
-        {
-            const long long expected = positions_max / n + 1;
-            bad_capacity = (int)(4 * ((expected + kDeSegments - 1) / kDeSegments) + 64);
-            const long long cap = 2 * expected + 512;
-            resolve_capacity = cap > kDeMaxBad ? kDeMaxBad : (int)cap;
-        }
-        scan_blocks = (int)(((positions_max + scan_run - 1) / scan_run + kDePlanThreads - 1) / kDePlanThreads);
+        // the batch of half-steps the stream is planned by, and every size that follows from it (de_batch_plan.hpp)
+        const DeBatchPlan bp = plan_de_batch(n, D, knobs.de_batch.has_value(), knobs.de_batch.value_or(0), knobs.de_scan_run.has_value(), knobs.de_scan_run.value_or(0));
+        if (!bp.ok)
+            return fail(MCMCPP_HIP_E_UNSUPPORTED, "differential evolution: %d walkers x %d parameters exceed what the stream planner holds (one half-step exceeds %s)", W, D,
+                        de_batch_bound_text(bp.bound));
+        batch_max = bp.batch_max;
 
         HIP_TRY(d_own_pos.alloc(sizeof(T) * (size_t)W * D));
         HIP_TRY(d_own_logp.alloc(sizeof(T) * (size_t)W));
@@ -99,11 +75,7 @@ public:
         d_logp = d_own_logp;
         d_nacc = d_own_nacc;
         d_diag = d_own_diag;
-        HIP_TRY(d_counts.alloc(sizeof(uint32_t) * 2 * kDeSegments * kDeCountStride));  // two sets of lists (launch_boundary)
-        HIP_TRY(hipMemset(d_counts, 0, sizeof(uint32_t) * 2 * kDeSegments * kDeCountStride));
-        HIP_TRY(d_bad.alloc(sizeof(DeBad) * 2 * kDeSegments * (size_t)bad_capacity));
-        HIP_TRY(hipMemset(d_bad, 0, sizeof(DeBad) * 2 * kDeSegments * (size_t)bad_capacity));
-        HIP_TRY(d_recs.alloc(sizeof(DeRec<T>) * updates_max));  // the records of the batch being stepped through
+        HIP_TRY(d_recs.alloc(sizeof(DeRec<T>) * (size_t)bp.updates_max));  // the records of the batch being stepped through
         for (int k = 0; k < 2; ++k)
         {
             HIP_TRY(hipEventCreate(ev_t0[k].replace()));
@@ -116,8 +88,6 @@ public:
         const int per_block = walkers_per_block;
         update_blocks = (n + per_block - 1) / per_block;
         partial_waves = update_blocks * kWavesPerBlock;
-        HIP_TRY(d_head.alloc(sizeof(DeHead)));
-        HIP_TRY(d_batch.alloc(sizeof(DeBatch) * 2));  // batch b resolves into record b & 1
         // the run record and, right behind it, the wavefronts' accepted counts of a replay: one allocation (the update kernel
         // reaches both through one preloaded pointer)
         {
@@ -139,31 +109,10 @@ public:
             }
         }
 
-        // the stream (MultiSampler.h:54) and its jump tables: D + 3 draws per update
+        // the stream (MultiSampler.h:54); the planner's buffers and jump tables
         pcg_seed(c.seed, c.stream, &state0, &inc);
-        {
-            const size_t scan_lanes = ((size_t)positions_max + scan_run - 1) / scan_run;
-            const std::vector<Affine128> small = jump_powers(pcg_jump(inc, 1), (size_t)kDeShiftMax + (size_t)D + 2);
-            const std::vector<Affine128> lo = jump_powers(pcg_jump(inc, per), 256);
-            const std::vector<Affine128> hi = jump_powers(pcg_jump(inc, (unsigned __int128)per * 256u), (updates_max + 255) / 256);
-            const std::vector<Affine128> slo = jump_powers(pcg_jump(inc, (unsigned)scan_run), 256);
-            const std::vector<Affine128> shi = jump_powers(pcg_jump(inc, (unsigned __int128)scan_run * 256u), (scan_lanes + 255) / 256);
-            std::vector<Affine128> all;  // one allocation
-            all.insert(all.end(), small.begin(), small.end());
-            all.insert(all.end(), slo.begin(), slo.end());
-            all.insert(all.end(), lo.begin(), lo.end());
-            all.insert(all.end(), hi.begin(), hi.end());
-            all.insert(all.end(), shi.begin(), shi.end());
-            HIP_TRY(d_tables.alloc(sizeof(Affine128) * all.size()));
-            HIP_TRY(hipMemcpy(d_tables, all.data(), sizeof(Affine128) * all.size(), hipMemcpyHostToDevice));
-            d_jump_small = d_tables;
-            d_scan_lo = d_jump_small + small.size();
-            d_jump_lo = d_scan_lo + slo.size();
-            d_jump_hi = d_jump_lo + lo.size();
-            d_scan_hi = d_jump_hi + hi.size();
-        }
-        batch_jump = pcg_jump(inc, (unsigned __int128)per * (unsigned)n * (unsigned)batch_max);
-        threshold = (uint64_t)(0 - (uint64_t)n) % (uint64_t)n;
+        planner.take(bp, state0, inc);
+        HIP_TRY(planner.create());
         gamma = (T)(2.38 / std::sqrt((double)(2 * D)));  // DifferentialEvolution.h:57
 
         args.calc_params = d_params;
@@ -180,13 +129,7 @@ public:
     int set_state(const void* pos, const void* logp) override
     {
         if (int rc = upload_state(pos, logp)) return rc;
-        DeHead h;
-        std::memset(&h, 0, sizeof h);
-        h.state = state0;
-        h.provisional[0] = state0;  // (batches 0 and 1 are scanned before anything has been resolved)
-        h.provisional[1] = apply(batch_jump, state0);
-        HIP_TRY(hipMemcpyAsync(d_head, &h, sizeof h, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof(uint32_t) * 2 * kDeSegments * kDeCountStride, stream));
+        HIP_TRY(planner.rewind(stream));
         HIP_TRY(hipStreamSynchronize(stream));
         half_steps = 0;
         primed = false;
@@ -246,7 +189,7 @@ public:
         }
         steps_since_reset += (uint64_t)total;
         DeHead h;
-        HIP_TRY(hipMemcpy(&h, d_head, sizeof h, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&h, planner.d_head, sizeof h, hipMemcpyDeviceToHost));
         last_ms = gpu_ms;  // GPU time of the launches (planning included) between HIP events on the launch stream (transfers excluded)
         last_launches = 2 * total;
         if (h.error)
@@ -257,54 +200,10 @@ public:
         return MCMCPP_HIP_OK;
     }
 
-    // The boundary launch in front of a batch: the resolve of batch `resolve_batch` (scanned before), the records of batch
-    // `record_batch` (resolved before) and the scan of batch `scan_batch`; any of them < 0: not in this launch (priming).
-    void launch_boundary(long long resolve_batch, long long record_batch, long long scan_batch)
-    {
-        const unsigned per = (unsigned)D + 3u;
-        DePlanArgs p;
-        std::memset(&p, 0, sizeof p);
-        p.head = d_head;
-        p.scan_hi = d_scan_hi;
-        p.scan_lo = d_scan_lo;
-        p.jump_hi = d_jump_hi;
-        p.jump_lo = d_jump_lo;
-        p.jump_small = d_jump_small;
-        p.batch_jump = batch_jump;
-        p.inc = inc;
-        p.threshold = threshold;
-        p.n = n;
-        p.dims = D;
-        p.updates = n * batch_max;
-        p.positions = (int)((long long)per * (long long)(p.updates - 1) + kDeShiftMax + 1);
-        p.scan_positions = p.positions + kDeShiftMax + 1;
-        p.scan_run = scan_run;
-        p.seg_len = (p.scan_positions + kDeSegments - 1) / kDeSegments;
-        p.bad_capacity = bad_capacity;
-        // two sets of lists: batch b is scanned into set b & 1 (its resolve runs beside the scan of batch b + 1)
-        const long long sb = scan_batch >= 0 ? scan_batch : resolve_batch + 1;
-        p.scan_parity = (int)(sb & 1);
-        p.bad = d_bad + (size_t)(sb & 1) * kDeSegments * (size_t)bad_capacity;
-        p.counts = d_counts + (size_t)(sb & 1) * kDeSegments * kDeCountStride;
-        p.resolve_bad = d_bad + (size_t)((sb + 1) & 1) * kDeSegments * (size_t)bad_capacity;
-        p.resolve_counts = d_counts + (size_t)((sb + 1) & 1) * kDeSegments * kDeCountStride;
-        p.batch = d_batch + (resolve_batch >= 0 ? (resolve_batch & 1) : 0);
-        const int resolve = resolve_batch >= 0 ? 1 : 0;
-        const int record_blocks = record_batch >= 0 ? (p.updates + kDePlanThreads - 1) / kDePlanThreads : 0;
-        const int scan_now = scan_batch >= 0 ? scan_blocks : 0;
-        size_t lds = record_blocks ? sizeof(DePlan) * kDeMaxEvents : 0;
-        const size_t need = resolve ? de_resolve_lds_bytes(resolve_capacity, D + 3) : 0;
-        lds = need > lds ? need : lds;
-        hipLaunchKernelGGL((de_boundary_kernel<T>), dim3((unsigned)(resolve + record_blocks + scan_now)), dim3(kDePlanThreads), lds, stream, p, resolve, resolve_capacity,
-                           record_blocks, d_batch + (record_batch >= 0 ? (record_batch & 1) : 0), d_recs);
-    }
-
-    // Behind a set_state: batch 0 scanned and resolved, batch 1 scanned -- what the boundary in front of a batch finds
-    // (see enqueue_replay).
+    // Behind a set_state: batch 0 scanned and resolved, batch 1 scanned (see enqueue_replay)
     int prime()
     {
-        launch_boundary(-1, -1, 0);
-        launch_boundary(0, -1, 1);
+        planner.prime(stream);
         HIP_TRY(hipGetLastError());
         primed = true;
         return MCMCPP_HIP_OK;
@@ -320,7 +219,7 @@ public:
         l.pos = d_pos;
         l.logp = d_logp;
         l.n_accept = d_nacc;
-        l.jump_small = d_jump_small;
+        l.jump_small = planner.d_jump_small;
         l.run = d_run;
         l.n = n;
         l.dims = D;
@@ -331,7 +230,7 @@ public:
             const uint64_t h = h0 + (uint64_t)i;
             const uint64_t b = h / (uint64_t)batch_max;
             const int j = (int)(h % (uint64_t)batch_max);
-            if (j == 0) launch_boundary((long long)b + 1, (long long)b, (long long)b + 2);
+            if (j == 0) planner.launch_boundary((long long)b + 1, (long long)b, (long long)b + 2, d_recs, stream);
             l.recs = d_recs + (size_t)j * (size_t)n;
             l.color = (int)(h & 1);
             l.step = i >> 1;
@@ -423,7 +322,7 @@ public:
             {
                 std::vector<DeBatch> rec(1);
                 const uint64_t b = half_steps / (uint64_t)batch_max;
-                HIP_TRY(hipMemcpy(rec.data(), d_batch + (b & 1), sizeof(DeBatch), hipMemcpyDeviceToHost));
+                HIP_TRY(hipMemcpy(rec.data(), planner.d_batch + (b & 1), sizeof(DeBatch), hipMemcpyDeviceToHost));
                 const uint64_t done = (half_steps % (uint64_t)batch_max) * (uint64_t)n;  // updates of this batch behind us
                 uint64_t shift = 0;
                 for (uint32_t e = 0; e < rec[0].events && e < (uint32_t)kDeMaxEvents && (uint64_t)rec[0].plan[e].m < done; ++e) shift = rec[0].plan[e].shift_after;
@@ -457,27 +356,18 @@ private:
     DeviceBuffer<T> d_params, d_params_padded, d_chain;
     bool matrix_core = false;
     DeviceBuffer<uint32_t> d_acc;
-    DeviceBuffer<DeHead> d_head;
-    DeviceBuffer<DeBatch> d_batch;
-    DeviceBuffer<Affine128> d_tables;  // jump_small, scan_lo, jump_lo, jump_hi, scan_hi
-    DeviceBuffer<uint32_t> d_counts;
-    DeviceBuffer<DeBad> d_bad;
-    Affine128 *d_scan_lo = nullptr, *d_scan_hi = nullptr;
-    int bad_capacity = 0, scan_run = kDeScanRun, batch_max = kDeBatchMax;
-    long long positions_max = 0;
+    DePlanner<T> planner;  // the stream head, the batch records, the lists and the tables; the boundary launch
+    int batch_max = kDeBatchMax;
     DeviceBuffer<DeRec<T>> d_recs;
     DeviceBuffer<DeRunInfo> d_run;
     DeArgs<T> args;
     int update_blocks = 0, partial_waves = 0, graph_steps = 128, replay_steps_max = 128;
-    int resolve_capacity = 0, scan_blocks = 0;
     bool primed = false;    // batches 0 and 1 planned behind the last set_state
-    Affine128 batch_jump;   // (D+3) * n * batch_max draws
     Event ev_t0[2], ev_t1[2];
     std::unordered_map<uint64_t, GraphExec> graph_cache;
 
-    Affine128 *d_jump_lo = nullptr, *d_jump_hi = nullptr, *d_jump_small = nullptr;
     U128 state0, inc;
-    uint64_t threshold = 0, half_steps = 0;
+    uint64_t half_steps = 0;
     T gamma = 0;
 };
 }  // namespace

@@ -39,22 +39,11 @@
 // failed run: never a silently different chain.
 #pragma once
 
+#include "de_batch_plan.hpp"  // the planner's constants (kDe*) and its host-side sizing
 #include "stretch_kernel.hpp"
 
 namespace mcmcpp
 {
-constexpr int kDeBatchMax = 64;     // half-steps one plan covers at most
-constexpr int kDeShiftMax = 4095;   // thrown-away draws inside one batch that are followed exactly (expected: about one per half-step)
-constexpr int kDeWindow = 32;       // raw draws one update's integer part may consume (2 + up to 30 thrown away: even two
-                                    // walkers per half, where every second ind2 collides, overrun once in 1e9 updates)
-constexpr int kDeOverrun = 255;     // E of a start whose update would not fit that window
-constexpr int kDeSegments = 64;     // bad-position lists of a batch (by position)
-constexpr int kDeCountStride = 32;  // uint32 between two list counters: one 128-byte line each
-constexpr int kDeMaxBad = 8192;     // bad positions of a batch the resolver holds (about (D + 3) per half-step)
-constexpr int kDeMaxEvents = 1024;  // events of a batch
-constexpr int kDeScanRun = 8;       // consecutive stream positions one scanning lane steps through (default)
-constexpr int kDePlanThreads = 256;
-
 enum : uint32_t
 {
     kDeErrShift = 1u,   // more than kDeShiftMax draws thrown away in one batch
@@ -88,6 +77,7 @@ struct DePlan
     uint32_t m;
     uint32_t shift_after;
 };
+static_assert(sizeof(DePlan) == kDeEventBytes, "de_batch_plan.hpp sizes the records' LDS by it");
 
 // what the resolver leaves for the record lanes
 struct alignas(64) DeBatch

@@ -130,8 +130,7 @@ __device__ __forceinline__ uint32_t de_wave_min(uint32_t v)
 // A bad position p = per * q + res is the start of update q - c / per when c draws have been thrown away and
 // res == c mod per: the positions are kept by residue (a counting sort in LDS), so that an event looks at one residue's
 // handful of positions only.  One workgroup of `threads` lanes sorts, its first wavefront walks.
-// lds: capacity + 2 * per + 2 + kDeSegments uint32.
-__host__ __device__ inline size_t de_resolve_lds_bytes(int capacity, int per) { return sizeof(uint32_t) * ((size_t)capacity + 2 * (size_t)per + 2 + kDeSegments); }
+// lds: capacity + 2 * per + 2 + kDeSegments uint32 (de_resolve_lds_bytes in de_batch_plan.hpp).
 
 __device__ __forceinline__ void de_resolve_block(const DePlanArgs& a, uint32_t* lds, int capacity, int threads)
 {

@@ -158,6 +158,46 @@ def test_device_differential_evolution_matches_the_oracle(W, D, calc, params, dt
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("W,D,steps", [(402, 200, 40), (1020, 509, 30), (2044, 1021, 24), (2050, 1024, 24)])
+def test_device_differential_evolution_smallest_halves_of_wide_walkers(W, D, steps):
+    # The widths at which two walkers per half would cut the planning batch by the resolver's lists, or not be planned at all
+    # (tests/test_de_batch_plan.py).  The library refuses two walkers per half there for a reason of the reference's own
+    # (EnsembleSampler.h:208: more than 2 D walkers), so these are the smallest ensembles it accepts at each width: D + 1
+    # walkers per half, no power of two but the last but one, 1022
+    pos = po.init_positions(po.F64, W, D, salt=8)
+    orc = po.Oracle(W, D, po.CALC_ISO_GAUSSIAN, None, seed=13, mover=po.MOVER_DIFFERENTIAL_EVOLUTION)
+    lp = orc.logp(pos)
+    orc.set_state(pos, lp)
+    want_chain, want_acc = orc.run(steps, 1)
+    s = capi.HipSampler(W, D, capi.CALC_ISO_GAUSSIAN, None, seed=13, mover=capi.MOVER_DIFFERENTIAL_EVOLUTION)
+    s.set_state(pos, lp)
+    got = [s.run(k, 1) for k in (1, steps - 1)]
+    np.testing.assert_array_equal(np.concatenate([g[0] for g in got]), want_chain)
+    np.testing.assert_array_equal(np.concatenate([g[1] for g in got]), want_acc)
+    for have, want in zip(s.get_state(), orc.get_state()):
+        np.testing.assert_array_equal(have, want)
+    c = s.counters()
+    assert c["redraws"] == orc.redraws > 0 and c["near_ties"] == 0
+
+
+@pytest.mark.gpu
+def test_device_differential_evolution_refusals_name_the_bound_that_fired():
+    # two walkers per half at D >= 1022, which the resolver's lists cannot plan, never reach the planner: the reference's own
+    # rule refuses them first (the lists' wording is checked on the CPU, tests/test_de_batch_plan.py)
+    for D in (1022, 1024):
+        with pytest.raises(capi.HipError, match="num_walkers must exceed 2\\*num_params"):
+            capi.HipSampler(4, D, capi.CALC_ISO_GAUSSIAN, None, mover=capi.MOVER_DIFFERENTIAL_EVOLUTION)
+    # what does reach it (refused before anything of the ensemble's size is allocated): a half-step of more than 2^30 stream
+    # positions, and one of more than 8 Mi updates -- each named alone
+    with pytest.raises(capi.HipError) as e:
+        capi.HipSampler(2 * (1 << 20), 1024, capi.CALC_ISO_GAUSSIAN, None, mover=capi.MOVER_DIFFERENTIAL_EVOLUTION)
+    assert "2^30 stream positions" in str(e.value) and "8 Mi updates" not in str(e.value) and "lists" not in str(e.value)
+    with pytest.raises(capi.HipError) as e:
+        capi.HipSampler(2 * ((1 << 23) + 1), 1, capi.CALC_ISO_GAUSSIAN, None, mover=capi.MOVER_DIFFERENTIAL_EVOLUTION)
+    assert "8 Mi updates" in str(e.value) and "2^30" not in str(e.value) and "lists" not in str(e.value)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("batch,scan_run", [(1, 8), (3, 1), (7, 5), (64, 32)])
 def test_device_differential_evolution_planning_batches_of_any_length(monkeypatch, batch, scan_run):
     # the planner's batch length and scan run are free parameters of the device path: the chain must not depend on them
