@@ -657,6 +657,68 @@ int mcmcpp_hip_rank_diagnostics_device(int32_t dtype, int32_t device, const void
                                        int64_t* closed_tail, int64_t* sequence_length, int64_t* num_sequences);
 const char* mcmcpp_hip_rank_diagnostics_last_error(void);
 
+/* The posterior summary of every parameter: mean, sd, quantiles and a highest-density interval, each with its Monte Carlo
+ * standard error and effective sample size (Vehtari et al. 2021, section 4: mcse_mean, mcse_sd, mcse_quantile, ess_quantile; the
+ * row Stan, `posterior` and ArviZ print), an extension.  The sequences, H, L, M, S = M L, the draw order and the total order
+ * x_(0) <= ... <= x_(S-1) are those of mcmcpp_hip_normal_scores.  All arithmetic is fp64, each + - x / sqrt rounded on its own, no
+ * fma, no floating-point atomics.  "The ESS call" below is mcmcpp_hip_effective_sample_size_device(MCMCPP_HIP_F64, ...) with the
+ * same split and max_lag on an fp64 chain [K][H L][W][P] in device memory whose draw j, parameter p holds the value named: the
+ * figures are that entry point's bits.
+ *   mean, ess_mean  the ESS call's mean and ess on the draws as they are (a float draw converts to double exactly).
+ *   sd              with that call's within and between: var = (((L-1) M) within + (L (M-1)) between) / (S-1), the integer
+ *                   products exact; sd = sqrt(var): the pooled sample variance with one degree of freedom removed.
+ *   mcse_mean       sd / sqrt(ess_mean).
+ *   ess_sd, mcse_sd c = (x - mean) (x - mean) in double.  ess_sd = the ESS call's ess on c, Evar its mean, and with its within_c,
+ *                   between_c: m4c = (((L-1) M) within_c + (L (M-1)) between_c) / S;  mcse_sd = sqrt(((m4c / ess_sd) / Evar) / 4)
+ *                   (`posterior`'s rule).
+ *   quantile        [P][n_probs]: the "quantile q" rule of mcmcpp_hip_normal_scores for q = probs[i].
+ *   ess_quantile    [P][n_probs]: the ESS call's ess on the indicators 1.0 / 0.0 of x <= quantile[p][i], compared in double.
+ *   mcse_quantile, rank_lower, rank_upper
+ *                   [P][n_probs]: a = ess_quantile prob + 1, b = ess_quantile (1 - prob) + 1;
+ *                   u_lo = beta_quantile(0.15865525393145707, a, b), u_hi = beta_quantile(0.8413447460685429, a, b);
+ *                   rank_lower = max(floor(u_lo S), 1) - 1, rank_upper = min(ceil(u_hi S), S) - 1, the products in double;
+ *                   mcse_quantile = (x_(rank_upper) - x_(rank_lower)) / 2.  A NaN ess_quantile gives NaN and ranks -1.
+ *   beta_quantile   mcmcpp_hip_beta_quantile below: specified to a relative accuracy of 1e-10, not to bits (it rests on the host
+ *                   libm), so the two ranks are exact wherever u S lies further than S x 1e-10 from an integer.  Everything
+ *                   else in this call is defined to the bit.
+ *   hdi_lower, hdi_upper
+ *                   [P], where hdi_prob != 0: m = floor(hdi_prob S) in double; w_i = x_(i+m) - x_(i) for 0 <= i < S - m; the
+ *                   smallest w_i that is not NaN, among equal widths the lowest i; the bounds are x_(i) and x_(i+m) (ArviZ's
+ *                   rule for one mode).  Every width NaN (inf - inf): both bounds NaN.  hdi_prob = 0: no interval, the two
+ *                   outputs are not written.
+ *   knobs, memory   as for mcmcpp_hip_rank_diagnostics: MCMCPP_HIP_RANK_WORK_MB, MCMCPP_HIP_RHAT_CHUNK_MB and where the chain
+ *                   lies change no bit.  The parameters are sorted once, a tile at a time; where they do not fit one tile,
+ *                   their sorted keys are kept for the ranks of mcse_quantile ((element size) x S P bytes more), and where
+ *                   that exceeds MCMCPP_HIP_SUMMARY_KEEP_MB (read per call; default: no bound) or the device's memory, every
+ *                   tile is sorted a second time instead.  No bit depends on which.
+ *   outputs         mean, sd, mcse_mean, ess_mean, ess_sd, mcse_sd, hdi_lower, hdi_upper [P] double; quantile, ess_quantile,
+ *                   mcse_quantile [P][n_probs] double; rank_lower, rank_upper [P][n_probs] int64; *sequence_length = L,
+ *                   *num_sequences = M.  Any of them may be NULL.
+ * MCMCPP_HIP_E_ARG (with a message), before the device is opened, for everything mcmcpp_hip_rank_diagnostics refuses, and for
+ * n_probs outside 0..16, a NULL probs with n_probs > 0, a prob that is not inside (0, 1), and an hdi_prob that is neither 0
+ * nor inside (0, 1) with 1 <= floor(hdi_prob S) <= S - 1; then for a NaN draw.  Nothing is written to any output of a call
+ * that fails. */
+int mcmcpp_hip_posterior_summary(int32_t dtype, int32_t device, const void* const* steps, int32_t num_chains, int64_t n_steps,
+                                 int32_t num_walkers, int32_t num_params, int32_t split, int64_t max_lag, const double* probs,
+                                 int32_t n_probs, double hdi_prob, double* mean, double* sd, double* mcse_mean, double* ess_mean,
+                                 double* ess_sd, double* mcse_sd, double* quantile, double* ess_quantile, double* mcse_quantile,
+                                 int64_t* rank_lower, int64_t* rank_upper, double* hdi_lower, double* hdi_upper,
+                                 int64_t* sequence_length, int64_t* num_sequences);
+int mcmcpp_hip_posterior_summary_device(int32_t dtype, int32_t device, const void* device_steps, int32_t num_chains,
+                                        int64_t chain_stride_steps, int64_t n_steps, int64_t slice_interval, int32_t num_walkers,
+                                        int32_t num_params, int32_t split, int64_t max_lag, const double* probs, int32_t n_probs,
+                                        double hdi_prob, double* mean, double* sd, double* mcse_mean, double* ess_mean, double* ess_sd,
+                                        double* mcse_sd, double* quantile, double* ess_quantile, double* mcse_quantile,
+                                        int64_t* rank_lower, int64_t* rank_upper, double* hdi_lower, double* hdi_upper,
+                                        int64_t* sequence_length, int64_t* num_sequences);
+const char* mcmcpp_hip_posterior_summary_last_error(void);
+
+/* The x in (0, 1) with I_x(a, b) = p: the quantile function of the Beta distribution (mcmcpp_amd/csrc/beta_quantile.hpp: a
+ * continued fraction inside a bracketed Newton iteration; its comment has the algorithm and the iteration caps).  Valid for
+ * a, b in [1, 2^31 + 2] and 0 < p < 1, with a relative error below 1e-10.  Deterministic, but specified to that accuracy and
+ * not to bits: it uses the host libm's lgamma, log and exp.  Opens no device. */
+double mcmcpp_hip_beta_quantile(double p, double a, double b);
+
 int mcmcpp_hip_abi_version(void);
 
 #ifdef __cplusplus

@@ -42,6 +42,7 @@ EXPORTS = [
     "mcmcpp_hip_effective_sample_size", "mcmcpp_hip_effective_sample_size_device", "mcmcpp_hip_effective_sample_size_last_error",
     "mcmcpp_hip_normal_scores", "mcmcpp_hip_normal_scores_device", "mcmcpp_hip_rank_diagnostics", "mcmcpp_hip_rank_diagnostics_device",
     "mcmcpp_hip_rank_diagnostics_last_error",
+    "mcmcpp_hip_posterior_summary", "mcmcpp_hip_posterior_summary_device", "mcmcpp_hip_posterior_summary_last_error", "mcmcpp_hip_beta_quantile",
 ]
 
 
@@ -189,6 +190,14 @@ def lib():
             L.mcmcpp_hip_rank_diagnostics_device.argtypes = [i32, i32, vp, i32, i64, i64, i64, i32, i32, i32, i64] + outputs
             L.mcmcpp_hip_rank_diagnostics_last_error.argtypes = []
             L.mcmcpp_hip_rank_diagnostics_last_error.restype = C.c_char_p
+        if hasattr(L, "mcmcpp_hip_posterior_summary"):  # (absent from earlier builds selected with MCMCPP_HIP_LIB)
+            tail = [i32, i64, vp, i32, C.c_double] + [vp] * 15  # split, max_lag, probs, n_probs, hdi_prob; thirteen arrays, *sequence_length, *num_sequences
+            L.mcmcpp_hip_posterior_summary.argtypes = [i32, i32, C.POINTER(vp), i32, i64, i32, i32] + tail
+            L.mcmcpp_hip_posterior_summary_device.argtypes = [i32, i32, vp, i32, i64, i64, i64, i32, i32] + tail
+            L.mcmcpp_hip_posterior_summary_last_error.argtypes = []
+            L.mcmcpp_hip_posterior_summary_last_error.restype = C.c_char_p
+            L.mcmcpp_hip_beta_quantile.argtypes = [C.c_double, C.c_double, C.c_double]
+            L.mcmcpp_hip_beta_quantile.restype = C.c_double
         _lib = L
     return _lib
 
@@ -1005,4 +1014,43 @@ def rank_diagnostics(steps, split=True, max_lag=0, slice_interval=1, chain_strid
     else:
         _rank_check(L_.mcmcpp_hip_rank_diagnostics(dtype, device, source, K, n, W, P, int(bool(split)), max_lag, *outputs))
     out.update(sequence_length=length.value, num_sequences=count.value)
+    return out
+
+
+def beta_quantile(p, a, b):
+    """The x with I_x(a, b) = p, by the library's host function (include/mcmcpp_hip.h, mcmcpp_hip_beta_quantile: specified to a
+    relative accuracy of 1e-10).  Opens no device."""
+    if not (0.0 < p < 1.0) or not (a >= 1.0 and b >= 1.0):
+        raise ValueError("beta_quantile needs 0 < p < 1 and a, b >= 1")
+    return float(lib().mcmcpp_hip_beta_quantile(float(p), float(a), float(b)))
+
+
+POSTERIOR_SUMMARY_KEYS = ("mean", "sd", "mcse_mean", "ess_mean", "ess_sd", "mcse_sd", "quantile", "ess_quantile", "mcse_quantile", "rank_lower", "rank_upper",
+                          "hdi_lower", "hdi_upper")
+
+
+def posterior_summary(steps, probs=(0.05, 0.5, 0.95), hdi_prob=0.94, split=True, max_lag=0, slice_interval=1, chain_stride_steps=None, dtype=None, device=-1):
+    """The summary row of every parameter with its Monte Carlo standard errors (include/mcmcpp_hip.h,
+    mcmcpp_hip_posterior_summary; an extension).  steps: as for gelman_rubin.  probs: up to 16 probabilities inside (0, 1).
+    hdi_prob: 0 for no highest-density interval (hdi_lower and hdi_upper are then NaN).  Returns a dict: mean, sd, mcse_mean,
+    ess_mean, ess_sd, mcse_sd, hdi_lower, hdi_upper [(P,)] float64; quantile, ess_quantile, mcse_quantile [(P, len(probs))]
+    float64; rank_lower, rank_upper [(P, len(probs))] int64; probs, hdi_prob, sequence_length, num_sequences."""
+    if max_lag < 0:
+        raise ValueError("max_lag must not be negative")
+    probs = np.ascontiguousarray(probs, dtype=np.float64).reshape(-1)
+    on_device, dtype, device, source, K, stride, n, W, P, _keep = _rhat_sources(steps, slice_interval, chain_stride_steps, dtype, device)
+    Q = probs.size
+    out = {k: np.zeros((P, Q) if "quantile" in k or k.startswith("rank_") else P, np.int64 if k.startswith("rank_") else np.float64) for k in POSTERIOR_SUMMARY_KEYS}
+    out["hdi_lower"][:] = out["hdi_upper"][:] = np.nan
+    length, count = C.c_int64(0), C.c_int64(0)
+    outputs = [_ptr(a) if a.size else None for a in out.values()] + [C.cast(C.byref(length), C.c_void_p), C.cast(C.byref(count), C.c_void_p)]
+    lead = [int(bool(split)), max_lag, _ptr(probs) if Q else None, Q, float(hdi_prob)]
+    L_ = lib()
+    if on_device:
+        rc = L_.mcmcpp_hip_posterior_summary_device(dtype, device, source, K, stride, n, slice_interval, W, P, *(lead + outputs))
+    else:
+        rc = L_.mcmcpp_hip_posterior_summary(dtype, device, source, K, n, W, P, *(lead + outputs))
+    if rc != OK:
+        raise HipError(rc, (L_.mcmcpp_hip_posterior_summary_last_error() or b"").decode())
+    out.update(probs=probs, hdi_prob=float(hdi_prob), sequence_length=length.value, num_sequences=count.value)
     return out
