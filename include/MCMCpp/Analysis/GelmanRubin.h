@@ -36,7 +36,7 @@
 
 #include "../Chain/ChainStepIterator.h"
 #include "../Device/HipBackend.h"
-#include "Detail/DeviceSpan.h"
+#include "Detail/ChainSet.h"
 
 namespace MCMC
 {
@@ -48,7 +48,7 @@ class GelmanRubin
 public:
     typedef Chain::ChainStepIterator<ParamType> IttType;
 
-    GelmanRubin(int numParams, int numWalkers) : pCount(numParams), wCount(numWalkers), used(0), seqLength(0), seqCount(0), anyDevice(false)
+    GelmanRubin(int numParams, int numWalkers) : pCount(numParams), wCount(numWalkers), chains(numParams, numWalkers), seqLength(0), seqCount(0)
     {
         assert(pCount > 0);
         assert(wCount > 0);
@@ -56,37 +56,11 @@ public:
 
     /// One chain: every sliceInterval'th step of [start, end), beginning with `start`.  Every chain must give the same number
     /// of used steps.
-    void addChain(IttType start, IttType end, int sliceInterval)
-    {
-        assert(sliceInterval >= 1);
-        chains.push_back(ChainSteps());
-        ChainSteps& c = chains.back();
-        c.slice = sliceInterval;
-        if (Detail::deviceSpan(start, end, &c.span) && c.span.steps > 0)
-        {
-            c.onDevice = true;
-            c.used = (c.span.steps + sliceInterval - 1) / sliceInterval;
-            anyDevice = true;
-        }
-        else if (!Detail::pointersStay(start))
-        {
-            c.used = Detail::downloadSteps(start, end, sliceInterval, c.staging);
-            for (std::int64_t k = 0; k < c.used; ++k) c.steps.push_back(c.staging.data() + static_cast<std::size_t>(k) * wCount * pCount);
-        }
-        else
-        {
-            long long index = 0;
-            for (IttType itt(start); itt != end; ++itt, ++index)
-                if (index % sliceInterval == 0) c.steps.push_back(*itt);
-            c.used = static_cast<std::int64_t>(c.steps.size());
-        }
-        assert(chains.size() == 1 || c.used == chains.front().used);
-        used = c.used;
-    }
+    void addChain(IttType start, IttType end, int sliceInterval) { chains.addChain(start, end, sliceInterval); }
 
     void calculate(bool split = true)
     {
-        const int K = static_cast<int>(chains.size()), dt = Device::HipDtype<ParamType>::value;
+        const int K = chains.size(), dt = Device::HipDtype<ParamType>::value;
         assert(K >= 1);
         const std::size_t P = static_cast<std::size_t>(pCount);
         rhat.assign(P, 0.0);
@@ -95,12 +69,10 @@ public:
         between.assign(P, 0.0);
         chainMean.assign(K * P, 0.0);
         chainWithin.assign(K * P, 0.0);
-        if (!anyDevice)
+        if (!chains.anyDevice())
         {
-            std::vector<const void*> all;
-            for (int k = 0; k < K; ++k) all.insert(all.end(), chains[k].steps.begin(), chains[k].steps.end());
             check("mcmcpp_hip_gelman_rubin",
-                  mcmcpp_hip_gelman_rubin(dt, -1, all.empty() ? NULL : all.data(), K, used, wCount, pCount, split ? 1 : 0, rhat.data(), mean.data(), within.data(),
+                  mcmcpp_hip_gelman_rubin(dt, -1, chains.hostPointers(), K, chains.used(), wCount, pCount, split ? 1 : 0, rhat.data(), mean.data(), within.data(),
                                           between.data(), chainMean.data(), chainWithin.data(), NULL, NULL, &seqLength, &seqCount));
             return;
         }
@@ -111,7 +83,7 @@ public:
         std::vector<double> seqMean(K * perChain), seqM2(K * perChain);
         for (int k = 0; k < K; ++k)
         {
-            ChainSteps& c = chains[k];
+            const typename Detail::ChainSet<ParamType>::ChainSteps& c = chains.chain(k);
             std::int64_t count = 0;
             // (a single chain of one walker, unsplit, has one sequence and is refused; so it is for K such chains)
             if (c.onDevice)
@@ -137,21 +109,6 @@ public:
     long long getNumSequences() const { return seqCount; }
 
 private:
-    struct ChainSteps
-    {
-        ChainSteps() : onDevice(false), used(0), slice(1)
-        {
-            span.first = NULL;
-            span.steps = 0;
-        }
-        bool onDevice;
-        std::int64_t used;
-        int slice;
-        Detail::DeviceSpan<ParamType> span;
-        std::vector<const void*> steps;
-        std::vector<ParamType> staging;
-    };
-
     /// sum_fixed of include/mcmcpp_hip.h over f(m), m in [m0, m0 + N): slices of max(1024, ceil(N / 64) rounded up to 64) terms,
     /// each summed in ascending order from +0, the slice sums added in ascending order
     template <class F>
@@ -219,19 +176,14 @@ private:
 
     static void check(const char* what, int rc)
     {
-        if (rc == MCMCPP_HIP_OK) return;
-        const char* msg = mcmcpp_hip_gelman_rubin_last_error();
-        std::fprintf(stderr, "MCMCpp (MI355X): %s failed with code %d: %s\n", what, rc, msg ? msg : "");
-        std::abort();
+        if (rc != MCMCPP_HIP_OK) Detail::ChainSet<ParamType>::fail(what, rc, mcmcpp_hip_gelman_rubin_last_error());
     }
 
     int pCount;
     int wCount;
-    std::int64_t used;
+    Detail::ChainSet<ParamType> chains;
     std::int64_t seqLength;
     std::int64_t seqCount;
-    bool anyDevice;
-    std::vector<ChainSteps> chains;
     std::vector<double> rhat, mean, within, between;  ///< [P]
     std::vector<double> chainMean, chainWithin;       ///< [K][P]
 };

@@ -34,7 +34,7 @@
 
 #include "../Chain/ChainStepIterator.h"
 #include "../Device/HipBackend.h"
-#include "Detail/DeviceSpan.h"
+#include "Detail/ChainSet.h"
 
 namespace MCMC
 {
@@ -46,7 +46,7 @@ class PosteriorSummary
 public:
     typedef Chain::ChainStepIterator<ParamType> IttType;
 
-    PosteriorSummary(int numParams, int numWalkers) : pCount(numParams), wCount(numWalkers), used(0), seqLength(0), seqCount(0), hdiProb(0.0)
+    PosteriorSummary(int numParams, int numWalkers) : pCount(numParams), wCount(numWalkers), chains(numParams, numWalkers), seqLength(0), seqCount(0), hdiProb(0.0)
     {
         assert(pCount > 0);
         assert(wCount > 0);
@@ -54,22 +54,7 @@ public:
 
     /// One chain: every sliceInterval'th step of [start, end), beginning with `start`.  Every chain must give the same number
     /// of used steps.
-    void addChain(IttType start, IttType end, int sliceInterval)
-    {
-        assert(sliceInterval >= 1);
-        chains.push_back(ChainSteps(start, end));
-        ChainSteps& c = chains.back();
-        c.slice = sliceInterval;
-        if (Detail::deviceSpan(start, end, &c.span) && c.span.steps > 0)
-        {
-            c.onDevice = true;
-            c.used = (c.span.steps + sliceInterval - 1) / sliceInterval;
-        }
-        else
-            hostSteps(c);
-        assert(chains.size() == 1 || c.used == chains.front().used);
-        used = c.used;
-    }
+    void addChain(IttType start, IttType end, int sliceInterval) { chains.addChain(start, end, sliceInterval); }
 
     /// The quantiles 0.05, 0.5 and 0.95 and the 94 % highest-density interval
     void calculate(bool split = true, long long maxLag = 0)
@@ -81,7 +66,7 @@ public:
     /// quantileProbs: up to 16 probabilities inside (0, 1).  hdiProbability: 0 for no interval.
     void calculate(const std::vector<double>& quantileProbs, double hdiProbability, bool split = true, long long maxLag = 0)
     {
-        const int K = static_cast<int>(chains.size()), dt = Device::HipDtype<ParamType>::value, Q = static_cast<int>(quantileProbs.size());
+        const int K = chains.size(), dt = Device::HipDtype<ParamType>::value, Q = static_cast<int>(quantileProbs.size());
         assert(K >= 1);
         probs = quantileProbs;
         hdiProb = hdiProbability;
@@ -90,53 +75,25 @@ public:
         for (int i = 0; i < kPerQuantile; ++i) tables[i].assign(P * Q, 0.0);
         rankLower.assign(P * Q, 0);
         rankUpper.assign(P * Q, 0);
-        int onDevice = 0;
-        for (int k = 0; k < K; ++k) onDevice += chains[k].onDevice ? 1 : 0;
-        bool sameSpans = onDevice == K;
-        for (int k = 1; k < K && sameSpans; ++k) sameSpans = chains[k].span.steps == chains[0].span.steps && chains[k].slice == chains[0].slice;
         const double* pr = Q ? probs.data() : NULL;
-        if (sameSpans)
+        if (chains.sameSpans())
         {
-            // one chain is read where it lies; several are gathered into one allocation, chain behind chain
-            const std::int64_t steps = chains[0].span.steps;
-            const std::uint64_t chainBytes = static_cast<std::uint64_t>(steps) * wCount * P * sizeof(ParamType);
-            const void* first = chains[0].span.first;
-            void* gathered = NULL;
-            if (K > 1)
+            int rc;
             {
-                gathered = mcmcpp_hip_device_alloc(-1, chainBytes * K);
-                if (!gathered) fail("mcmcpp_hip_device_alloc", MCMCPP_HIP_E_NOMEM, mcmcpp_hip_device_chain_last_error());
-                for (int k = 0; k < K; ++k)
-                {
-                    const int rc = mcmcpp_hip_device_copy(static_cast<char*>(gathered) + chainBytes * k, chains[k].span.first, chainBytes);
-                    if (rc != MCMCPP_HIP_OK) fail("mcmcpp_hip_device_copy", rc, mcmcpp_hip_device_chain_last_error());
-                }
-                first = gathered;
+                const typename Detail::ChainSet<ParamType>::DeviceSource src(chains);  // one chain where it lies, several gathered
+                rc = mcmcpp_hip_posterior_summary_device(dt, -1, src.first, K, 0, src.steps, src.slice, wCount, pCount, split ? 1 : 0, maxLag, pr, Q, hdiProb, values[0].data(),
+                                                         values[1].data(), values[2].data(), values[3].data(), values[4].data(), values[5].data(), tables[0].data(),
+                                                         tables[1].data(), tables[2].data(), rankLower.data(), rankUpper.data(), values[6].data(), values[7].data(),
+                                                         &seqLength, &seqCount);
             }
-            const int rc = mcmcpp_hip_posterior_summary_device(dt, -1, first, K, 0, steps, chains[0].slice, wCount, pCount, split ? 1 : 0, maxLag, pr, Q, hdiProb,
-                                                               values[0].data(), values[1].data(), values[2].data(), values[3].data(), values[4].data(), values[5].data(),
-                                                               tables[0].data(), tables[1].data(), tables[2].data(), rankLower.data(), rankUpper.data(), values[6].data(),
-                                                               values[7].data(), &seqLength, &seqCount);
-            mcmcpp_hip_device_free(gathered);
-            if (rc != MCMCPP_HIP_OK) fail("mcmcpp_hip_posterior_summary_device", rc, mcmcpp_hip_posterior_summary_last_error());
+            if (rc != MCMCPP_HIP_OK) chains.fail("mcmcpp_hip_posterior_summary_device", rc, mcmcpp_hip_posterior_summary_last_error());
             return;
         }
-        std::vector<const void*> all;
-        for (int k = 0; k < K; ++k)
-        {
-            if (chains[k].onDevice)
-            {
-                chains[k].onDevice = false;
-                chains[k].used = Detail::downloadSteps(chains[k].start, chains[k].end, chains[k].slice, chains[k].staging);
-                stagingPointers(chains[k]);
-            }
-            all.insert(all.end(), chains[k].steps.begin(), chains[k].steps.end());
-        }
-        const int rc = mcmcpp_hip_posterior_summary(dt, -1, all.empty() ? NULL : all.data(), K, used, wCount, pCount, split ? 1 : 0, maxLag, pr, Q, hdiProb, values[0].data(),
-                                                    values[1].data(), values[2].data(), values[3].data(), values[4].data(), values[5].data(), tables[0].data(),
-                                                    tables[1].data(), tables[2].data(), rankLower.data(), rankUpper.data(), values[6].data(), values[7].data(), &seqLength,
-                                                    &seqCount);
-        if (rc != MCMCPP_HIP_OK) fail("mcmcpp_hip_posterior_summary", rc, mcmcpp_hip_posterior_summary_last_error());
+        const void* const* all = chains.hostPointers();
+        const int rc = mcmcpp_hip_posterior_summary(dt, -1, all, K, chains.used(), wCount, pCount, split ? 1 : 0, maxLag, pr, Q, hdiProb, values[0].data(), values[1].data(),
+                                                    values[2].data(), values[3].data(), values[4].data(), values[5].data(), tables[0].data(), tables[1].data(),
+                                                    tables[2].data(), rankLower.data(), rankUpper.data(), values[6].data(), values[7].data(), &seqLength, &seqCount);
+        if (rc != MCMCPP_HIP_OK) chains.fail("mcmcpp_hip_posterior_summary", rc, mcmcpp_hip_posterior_summary_last_error());
     }
 
     double getMean(int pNum) const { return values[0][pNum]; }
@@ -179,60 +136,16 @@ public:
     }
 
 private:
-    struct ChainSteps
-    {
-        ChainSteps(const IttType& s, const IttType& e) : onDevice(false), used(0), slice(1), start(s), end(e)
-        {
-            span.first = NULL;
-            span.steps = 0;
-        }
-        bool onDevice;
-        std::int64_t used;
-        int slice;
-        IttType start, end;
-        Detail::DeviceSpan<ParamType> span;
-        std::vector<const void*> steps;
-        std::vector<ParamType> staging;
-    };
-
     std::size_t at(int pNum, int i) const { return static_cast<std::size_t>(pNum) * probs.size() + i; }
-
-    void stagingPointers(ChainSteps& c) const
-    {
-        c.steps.clear();
-        for (std::int64_t k = 0; k < c.used; ++k) c.steps.push_back(c.staging.data() + static_cast<std::size_t>(k) * wCount * pCount);
-    }
-
-    /// the used steps of a chain that is read through host pointers
-    void hostSteps(ChainSteps& c) const
-    {
-        if (!Detail::pointersStay(c.start))
-        {
-            c.used = Detail::downloadSteps(c.start, c.end, c.slice, c.staging);
-            stagingPointers(c);
-            return;
-        }
-        long long index = 0;
-        for (IttType itt(c.start); itt != c.end; ++itt, ++index)
-            if (index % c.slice == 0) c.steps.push_back(*itt);
-        c.used = static_cast<std::int64_t>(c.steps.size());
-    }
-
-    static void fail(const char* what, int rc, const char* msg)
-    {
-        std::fprintf(stderr, "MCMCpp (MI355X): %s failed with code %d: %s\n", what, rc, msg ? msg : "");
-        std::abort();
-    }
 
     enum { kPerParam = 8, kPerQuantile = 3 };  ///< mean, sd, mcse_mean, ess_mean, ess_sd, mcse_sd, hdi_lower, hdi_upper; quantile, ess_quantile, mcse_quantile
     int pCount;
     int wCount;
-    std::int64_t used;
+    Detail::ChainSet<ParamType> chains;
     std::int64_t seqLength;
     std::int64_t seqCount;
     double hdiProb;
     std::vector<double> probs;
-    std::vector<ChainSteps> chains;
     std::vector<double> values[kPerParam];     ///< [P] each
     std::vector<double> tables[kPerQuantile];  ///< [P][Q] each
     std::vector<std::int64_t> rankLower, rankUpper;

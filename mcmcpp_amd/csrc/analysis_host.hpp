@@ -28,23 +28,37 @@ inline int analysis_fail(std::string& slot, int code, std::string msg, hipError_
         if (e_ != hipSuccess) return mcmcpp::analysis_fail(slot, MCMCPP_HIP_E_HIP, #expr, e_);      \
     } while (0)
 
-// Does [device_steps, device_steps + bytes) lie inside one allocation of device `device`?  (As the samplers ask before
-// run_device launches anything.)
-inline int check_device_steps(std::string& slot, const char* what, const void* p, size_t bytes, int device)
+// Does [p, p + bytes) lie inside one allocation of device `device`?  `name` is the argument's; `too_short` is what its entry
+// point says of a range that ends outside the allocation.
+inline int check_device_range(std::string& slot, const char* what, const char* name, const void* p, size_t bytes, int device, const std::string& too_short)
 {
-    const std::string w(what);
+    const std::string w(what), a(name);
     const DeviceRange r = probe_device_range(p, device);
     switch (r.kind)
     {
-    case DeviceRange::NotDevice: return analysis_fail(slot, MCMCPP_HIP_E_ARG, w + ": device_steps is not device memory");
+    case DeviceRange::NotDevice: return analysis_fail(slot, MCMCPP_HIP_E_ARG, w + ": " + a + " is not device memory");
     case DeviceRange::OtherDevice:
-        return analysis_fail(slot, MCMCPP_HIP_E_ARG, w + ": device_steps is memory of device " + std::to_string(r.device) + ", not of device " + std::to_string(device));
-    case DeviceRange::NoAllocation: return analysis_fail(slot, MCMCPP_HIP_E_ARG, w + ": the runtime does not know the allocation device_steps lies in");
+        return analysis_fail(slot, MCMCPP_HIP_E_ARG, w + ": " + a + " is memory of device " + std::to_string(r.device) + ", not of device " + std::to_string(device));
+    case DeviceRange::NoAllocation: return analysis_fail(slot, MCMCPP_HIP_E_ARG, w + ": the runtime does not know the allocation " + a + " lies in");
     case DeviceRange::Found: break;
     }
-    if (bytes > r.room) return analysis_fail(slot, MCMCPP_HIP_E_ARG, w + ": n_steps steps do not end inside the allocation around device_steps");
+    if (bytes > r.room) return analysis_fail(slot, MCMCPP_HIP_E_ARG, w + ": " + too_short);
     return MCMCPP_HIP_OK;
 }
+
+// The same of stored steps.  (As the samplers ask before run_device launches anything.)
+inline int check_device_steps(std::string& slot, const char* what, const void* p, size_t bytes, int device)
+{
+    return check_device_range(slot, what, "device_steps", p, bytes, device, "n_steps steps do not end inside the allocation around device_steps");
+}
+
+// For a function that works on its caller's stream: declared behind the function's buffers, as a Stream of its own would be,
+// so that the stream is idle when they go
+struct IdleOnReturn
+{
+    hipStream_t stream;
+    ~IdleOnReturn() { (void)hipStreamSynchronize(stream); }
+};
 
 // Steps [k0, k0 + now) into dst, one behind the other; src_of(k) is the address of step k.  Steps that follow each other in
 // memory go in one copy.

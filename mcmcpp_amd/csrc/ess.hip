@@ -16,6 +16,8 @@
 //   * The host divides, forms rho, walks the windows (ess_plan.hpp) and decides whether another round of lags is needed.
 // A device chain is read in place.  Of host chains one (chain, half) is the unit of upload; the units stay in device memory
 // across the rounds where they all fit and are uploaded again in every round where they do not.
+// The entry points check, open the device, probe a device chain's range and make a stream; their body is ess_compute
+// (rhat_state.hpp), which rank.hip and summary.hip call on chains of their own, on their stream and into their message slot.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -183,27 +185,13 @@ ess_slice_join_kernel(const double* __restrict__ part, int P, long long lags, in
 
 thread_local std::string g_ess_error;
 
-int ess_fail(int code, const std::string& msg) { return mcmcpp::analysis_fail(g_ess_error, code, msg); }
-
-struct Outputs
-{
-    double *ess, *tau;
-    int64_t *lags_used, *closed;
-    double *rho, *autocov, *rhat, *mean, *within, *between;
-    int64_t *sequence_length, *num_sequences;
-};
-
-struct Request
-{
-    mcmcpp::RhatRequest in;
-    int64_t max_lag, n_functions;
-    Outputs out;
-};
+using mcmcpp::EssOutputs;
 
 template <class T>
-int run_request(const Request& q, int device, const hipDeviceProp_t& prop, long long n, const mcmcpp::RhatShape& shape)
+int run_request(std::string& slot, const mcmcpp::RhatRequest& r, int64_t max_lag, int64_t n_functions, const hipDeviceProp_t& prop, long long n,
+                const mcmcpp::RhatShape& shape, hipStream_t stream, const EssOutputs& out)
 {
-    const mcmcpp::RhatRequest& r = q.in;
+    const auto ess_fail = [&](int code, const std::string& msg) { return mcmcpp::analysis_fail(slot, code, msg); };
     const std::string w(r.what);
     const int K = r.K, P = r.P, H = shape.H;
     const long long E = (long long)r.W * P, L = shape.L, M = shape.M, series = M * P;
@@ -211,17 +199,17 @@ int run_request(const Request& q, int device, const hipDeviceProp_t& prop, long 
     mcmcpp::RhatState st;
     mcmcpp::DeviceBuffer<T> d_units;
     mcmcpp::DeviceBuffer<double> d_A, d_part, d_S;
-    mcmcpp::Stream stream;  // (behind the buffers: the stream is idle and gone when they go)
-    ANALYSIS_TRY(g_ess_error, hipStreamCreateWithFlags(stream.replace(), hipStreamNonBlocking));
-    if (int rc = mcmcpp::rhat_sequences_state(g_ess_error, r, device, prop, n, shape, stream, st)) return rc;
-    ANALYSIS_TRY(g_ess_error, hipStreamSynchronize(stream));
+    std::vector<double> S;              // [lags done][P]
+    mcmcpp::IdleOnReturn idle{stream};  // (behind the buffers: the stream is idle when they go)
+    if (int rc = mcmcpp::rhat_sequences_state(slot, r, prop, n, shape, stream, st)) return rc;
+    ANALYSIS_TRY(slot, hipStreamSynchronize(stream));
     st.chunk.reset();  // (phase 1's upload buffer and slice state have done their work)
     st.first.reset();
     st.state.reset();
     const double* seq_mean = st.seq.get();
     const double *h_mean = st.h_res.data(), *h_within = h_mean + P, *h_between = h_within + P;
 
-    const long long cap = mcmcpp::ess_cap(L, q.max_lag), kmax = mcmcpp::ess_kmax(cap), F = mcmcpp::ess_function_lags(q.n_functions, cap);
+    const long long cap = mcmcpp::ess_cap(L, max_lag), kmax = mcmcpp::ess_kmax(cap), F = mcmcpp::ess_function_lags(n_functions, cap);
     mcmcpp::EssKnobs knobs = mcmcpp::ess_knobs_from_env();
     const mcmcpp::RhatSumPlan sum = mcmcpp::rhat_sum_plan(M, P, 1);
 
@@ -249,9 +237,8 @@ int run_request(const Request& q, int device, const hipDeviceProp_t& prop, long 
         return mcmcpp::copy_steps(dst, [&](long long s) { return src[s]; }, 0, L, step_bytes, hipMemcpyHostToDevice, stream);
     };
     if (!r.on_device && resident)
-        for (int u = 0; u < units; ++u) ANALYSIS_TRY(g_ess_error, upload(u, d_units.get() + (size_t)u * L * E));
+        for (int u = 0; u < units; ++u) ANALYSIS_TRY(slot, upload(u, d_units.get() + (size_t)u * L * E));
 
-    std::vector<double> S;  // [lags done][P]
     std::vector<mcmcpp::EssWindow> win(P);
     long long done = 0, previous = 0;
     const auto rho_of = [&](int p, long long t) {
@@ -259,7 +246,7 @@ int run_request(const Request& q, int device, const hipDeviceProp_t& prop, long 
     };
     for (bool more = true; more;)
     {
-        long long lags = mcmcpp::ess_round_lags(done, previous, knobs, series, cap, q.n_functions);
+        long long lags = mcmcpp::ess_round_lags(done, previous, knobs, series, cap, n_functions);
         if (lags < B) return ess_fail(MCMCPP_HIP_E_UNSUPPORTED, w + ": a round without lags");
         if (mcmcpp::grow(d_A, 8 * (size_t)lags * series, stream) != hipSuccess)
         {
@@ -276,16 +263,16 @@ int run_request(const Request& q, int device, const hipDeviceProp_t& prop, long 
             const mcmcpp::EssGrid g = mcmcpp::ess_lag_grid(E, blocks, units);
             hipLaunchKernelGGL(ess_lag_kernel<T>, dim3(g.x, g.y, g.z), dim3(kThreads), 0, stream, base, step_stride, chain_stride, half_offset, H, E, L, done, blocks, 0,
                                seq_mean, d_A.get(), series);
-            ANALYSIS_TRY(g_ess_error, hipGetLastError());
+            ANALYSIS_TRY(slot, hipGetLastError());
         }
         else
             for (int u = 0; u < units; ++u)
             {
-                ANALYSIS_TRY(g_ess_error, upload(u, d_units.get()));  // (in stream order behind the kernel that read the unit before)
+                ANALYSIS_TRY(slot, upload(u, d_units.get()));  // (in stream order behind the kernel that read the unit before)
                 const mcmcpp::EssGrid g = mcmcpp::ess_lag_grid(E, blocks, 1);
                 hipLaunchKernelGGL(ess_lag_kernel<T>, dim3(g.x, g.y, g.z), dim3(kThreads), 0, stream, base, step_stride, chain_stride, half_offset, 1, E, L, done, blocks,
                                    u, seq_mean, d_A.get(), series);
-                ANALYSIS_TRY(g_ess_error, hipGetLastError());
+                ANALYSIS_TRY(slot, hipGetLastError());
             }
         const unsigned sum_blocks = (unsigned)(((long long)sum.slices * P + kThreads - 1) / kThreads);
         for (long long l0 = 0; l0 < lags; l0 += mcmcpp::kRhatGridYMax)
@@ -293,14 +280,14 @@ int run_request(const Request& q, int device, const hipDeviceProp_t& prop, long 
             const long long now = lags - l0 < mcmcpp::kRhatGridYMax ? lags - l0 : mcmcpp::kRhatGridYMax;
             hipLaunchKernelGGL(ess_slice_sums_kernel, dim3(sum_blocks, (unsigned)now), dim3(kThreads), 0, stream, (const double*)d_A.get(), P, M, sum.slen, sum.slices, l0,
                                d_part.get());
-            ANALYSIS_TRY(g_ess_error, hipGetLastError());
+            ANALYSIS_TRY(slot, hipGetLastError());
         }
         hipLaunchKernelGGL(ess_slice_join_kernel, dim3((unsigned)((lags * P + kThreads - 1) / kThreads)), dim3(kThreads), 0, stream, (const double*)d_part.get(), P, lags,
                            sum.slices, d_S.get());
-        ANALYSIS_TRY(g_ess_error, hipGetLastError());
+        ANALYSIS_TRY(slot, hipGetLastError());
         S.resize((size_t)(done + lags) * P);
-        ANALYSIS_TRY(g_ess_error, hipMemcpyAsync(S.data() + (size_t)done * P, d_S.get(), 8 * (size_t)lags * P, hipMemcpyDeviceToHost, stream));
-        ANALYSIS_TRY(g_ess_error, hipStreamSynchronize(stream));
+        ANALYSIS_TRY(slot, hipMemcpyAsync(S.data() + (size_t)done * P, d_S.get(), 8 * (size_t)lags * P, hipMemcpyDeviceToHost, stream));
+        ANALYSIS_TRY(slot, hipStreamSynchronize(stream));
         done += lags;
         previous = lags;
         more = done < F;
@@ -312,7 +299,6 @@ int run_request(const Request& q, int device, const hipDeviceProp_t& prop, long 
     }
 
     // the call has succeeded: the outputs
-    const Outputs& out = q.out;
     const double N = (double)(M * L), nan = std::numeric_limits<double>::quiet_NaN();
     for (int p = 0; p < P; ++p)
     {
@@ -321,10 +307,10 @@ int run_request(const Request& q, int device, const hipDeviceProp_t& prop, long 
         if (out.ess) out.ess[p] = N / tau;
         if (out.lags_used) out.lags_used[p] = 2 * win[p].pairs;
         if (out.closed) out.closed[p] = win[p].state == 1;
-        for (long long t = 0; t < q.n_functions; ++t)
+        for (long long t = 0; t < n_functions; ++t)
         {
-            if (out.rho) out.rho[(size_t)p * q.n_functions + t] = t < F ? rho_of(p, t) : nan;
-            if (out.autocov) out.autocov[(size_t)p * q.n_functions + t] = t < F ? mcmcpp::ess_gamma(S[(size_t)t * P + p], (double)M, (double)L) : nan;
+            if (out.rho) out.rho[(size_t)p * n_functions + t] = t < F ? rho_of(p, t) : nan;
+            if (out.autocov) out.autocov[(size_t)p * n_functions + t] = t < F ? mcmcpp::ess_gamma(S[(size_t)t * P + p], (double)M, (double)L) : nan;
         }
         if (out.rhat) out.rhat[p] = std::sqrt(mcmcpp::ess_varplus(h_within[p], h_between[p], (double)L) / h_within[p]);
     }
@@ -336,21 +322,35 @@ int run_request(const Request& q, int device, const hipDeviceProp_t& prop, long 
     return MCMCPP_HIP_OK;
 }
 
-int ess_entry(const Request& q)
+int ess_entry(const mcmcpp::RhatRequest& r, int64_t max_lag, int64_t n_functions, const EssOutputs& out)
 {
-    const std::string w(q.in.what);
+    const auto ess_fail = [](int code, const std::string& msg) { return mcmcpp::analysis_fail(g_ess_error, code, msg); };
+    const std::string w(r.what);
     long long n = 0;
     mcmcpp::RhatShape shape;
-    if (int rc = mcmcpp::rhat_check_request(g_ess_error, q.in, &n, &shape)) return rc;
-    if (q.max_lag < 0) return ess_fail(MCMCPP_HIP_E_ARG, w + ": max_lag >= 0 (0: up to L - 1)");
-    if (q.n_functions < 0) return ess_fail(MCMCPP_HIP_E_ARG, w + ": n_functions >= 0");
+    if (int rc = mcmcpp::rhat_check_request(g_ess_error, r, &n, &shape)) return rc;
+    if (max_lag < 0) return ess_fail(MCMCPP_HIP_E_ARG, w + ": max_lag >= 0 (0: up to L - 1)");
+    if (n_functions < 0) return ess_fail(MCMCPP_HIP_E_ARG, w + ": n_functions >= 0");
     hipDeviceProp_t prop;
     std::string why;
-    int device = q.in.device;
+    int device = r.device;
     if (int rc = mcmcpp::open_gfx950_device(device, &device, &prop, &why)) return ess_fail(rc, w + ": " + why);
-    return q.in.dtype == MCMCPP_HIP_F64 ? run_request<double>(q, device, prop, n, shape) : run_request<float>(q, device, prop, n, shape);
+    if (int rc = mcmcpp::rhat_check_device_steps(g_ess_error, r, device)) return rc;
+    mcmcpp::Stream stream;
+    ANALYSIS_TRY(g_ess_error, hipStreamCreateWithFlags(stream.replace(), hipStreamNonBlocking));
+    return mcmcpp::ess_compute(g_ess_error, r, max_lag, n_functions, prop, n, shape, stream, out);
 }
 }  // namespace
+
+namespace mcmcpp
+{
+int ess_compute(std::string& slot, const RhatRequest& r, int64_t max_lag, int64_t n_functions, const hipDeviceProp_t& prop, long long n, const RhatShape& shape,
+                hipStream_t stream, const EssOutputs& out)
+{
+    return r.dtype == MCMCPP_HIP_F64 ? run_request<double>(slot, r, max_lag, n_functions, prop, n, shape, stream, out)
+                                     : run_request<float>(slot, r, max_lag, n_functions, prop, n, shape, stream, out);
+}
+}  // namespace mcmcpp
 
 extern "C"
 {
@@ -361,8 +361,8 @@ int mcmcpp_hip_effective_sample_size(int32_t dtype, int32_t device, const void* 
                                      int64_t* closed, double* rho, double* autocov, double* rhat, double* mean, double* within, double* between,
                                      int64_t* sequence_length, int64_t* num_sequences)
 {
-    return ess_entry(Request{mcmcpp::RhatRequest{"effective_sample_size", dtype, device, steps, nullptr, false, num_chains, 0, n_steps, 1, num_walkers, num_params, split},
-                             max_lag, n_functions, Outputs{ess, tau, lags_used, closed, rho, autocov, rhat, mean, within, between, sequence_length, num_sequences}});
+    return ess_entry(mcmcpp::rhat_host_request("effective_sample_size", dtype, device, steps, num_chains, n_steps, num_walkers, num_params, split), max_lag, n_functions,
+                     EssOutputs{ess, tau, lags_used, closed, rho, autocov, rhat, mean, within, between, sequence_length, num_sequences});
 }
 
 int mcmcpp_hip_effective_sample_size_device(int32_t dtype, int32_t device, const void* device_steps, int32_t num_chains, int64_t chain_stride_steps, int64_t n_steps,
@@ -370,8 +370,8 @@ int mcmcpp_hip_effective_sample_size_device(int32_t dtype, int32_t device, const
                                             double* ess, double* tau, int64_t* lags_used, int64_t* closed, double* rho, double* autocov, double* rhat, double* mean,
                                             double* within, double* between, int64_t* sequence_length, int64_t* num_sequences)
 {
-    return ess_entry(Request{mcmcpp::RhatRequest{"effective_sample_size_device", dtype, device, nullptr, device_steps, true, num_chains, chain_stride_steps, n_steps,
-                                                 slice_interval, num_walkers, num_params, split},
-                             max_lag, n_functions, Outputs{ess, tau, lags_used, closed, rho, autocov, rhat, mean, within, between, sequence_length, num_sequences}});
+    return ess_entry(mcmcpp::rhat_device_request("effective_sample_size_device", dtype, device, device_steps, num_chains, chain_stride_steps, n_steps, slice_interval,
+                                                 num_walkers, num_params, split),
+                     max_lag, n_functions, EssOutputs{ess, tau, lags_used, closed, rho, autocov, rhat, mean, within, between, sequence_length, num_sequences});
 }
 }

@@ -4,8 +4,9 @@
 //
 // The definition is the header's (include/mcmcpp_hip.h, mcmcpp_hip_normal_scores and mcmcpp_hip_rank_diagnostics).  Ranks are
 // integers, found exactly; the score of a rank is normal_score.hpp's, one value in bits on device and host.  The diagnostics are
-// the existing entry points (mcmcpp_hip_effective_sample_size_device, mcmcpp_hip_gelman_rubin_device) run on fp64 chains this
-// file builds in device memory: their bits, by construction.
+// the bodies of the existing entry points (rhat_state.hpp: ess_compute of mcmcpp_hip_effective_sample_size_device, rhat_compute
+// of mcmcpp_hip_gelman_rubin_device) run on fp64 chains this file builds in device memory, on this call's stream and into this
+// family's message slot: their bits, by construction.
 //
 // The kernels and the Ranker are rank_kernels.hpp's (summary.hip sorts with them too).
 // Per tile of parameters (rank_plan.hpp; blockIdx.y is the parameter of the tile in every kernel):
@@ -54,37 +55,19 @@ struct Request
     DiagOutputs dg;
 };
 
-// the scores' buffer of the device form: memory of this device, and large enough
-int check_scores_buffer(const std::string& w, const void* p, size_t bytes, int device)
-{
-    const mcmcpp::DeviceRange r = mcmcpp::probe_device_range(p, device);
-    switch (r.kind)
-    {
-    case mcmcpp::DeviceRange::NotDevice: return rank_fail(MCMCPP_HIP_E_ARG, w + ": scores is not device memory");
-    case mcmcpp::DeviceRange::OtherDevice:
-        return rank_fail(MCMCPP_HIP_E_ARG, w + ": scores is memory of device " + std::to_string(r.device) + ", not of device " + std::to_string(device));
-    case mcmcpp::DeviceRange::NoAllocation: return rank_fail(MCMCPP_HIP_E_ARG, w + ": the runtime does not know the allocation scores lies in");
-    case mcmcpp::DeviceRange::Found: break;
-    }
-    if (bytes > r.room) return rank_fail(MCMCPP_HIP_E_ARG, w + ": the " + std::to_string(bytes) + " bytes of the scores do not end inside the allocation around scores");
-    return MCMCPP_HIP_OK;
-}
-
 template <class T>
-int run_request(const Request& q, int device, long long n, const mcmcpp::RhatShape& shape)
+int run_request(const Request& q, int device, const hipDeviceProp_t& prop, long long n, const mcmcpp::RhatShape& shape)
 {
     const mcmcpp::RhatRequest& r = q.in;
     const std::string w(r.what);
     const int K = r.K, P = r.P, H = shape.H;
     const long long E = (long long)r.W * P, L = shape.L, HL = (long long)H * L;
-    const size_t step_bytes = sizeof(T) * (size_t)E, chain_elems = (size_t)K * HL * E;
-    const long long chain_stride_steps = r.chain_stride_steps ? r.chain_stride_steps : r.n_steps;
-    if (r.on_device)
-    {
-        if (int rc = mcmcpp::check_device_steps(g_rank_error, r.what, r.device_steps, step_bytes * (size_t)((K - 1) * chain_stride_steps + r.n_steps), device)) return rc;
-        if (!q.diagnostics)
-            if (int rc = check_scores_buffer(w, q.so.scores, 8 * chain_elems, device)) return rc;
-    }
+    const size_t chain_elems = (size_t)K * HL * E;
+    if (int rc = mcmcpp::rhat_check_device_steps(g_rank_error, r, device)) return rc;
+    if (r.on_device && !q.diagnostics)  // the scores' buffer of the device form: memory of this device, and large enough
+        if (int rc = mcmcpp::check_device_range(g_rank_error, r.what, "scores", q.so.scores, 8 * chain_elems, device,
+                                                "the " + std::to_string(8 * chain_elems) + " bytes of the scores do not end inside the allocation around scores"))
+            return rc;
     mcmcpp::DeviceBuffer<T> d_up;
     mcmcpp::DeviceBuffer<double> d_chain, d_q;
     mcmcpp::DeviceBuffer<int> d_nan;
@@ -132,26 +115,29 @@ int run_request(const Request& q, int device, long long n, const mcmcpp::RhatSha
         return MCMCPP_HIP_OK;
     }
 
-    // the diagnostics: the existing entry points on fp64 chains [K][HL][W][P] built here
+    // the diagnostics: the bodies of the existing entry points on fp64 chains [K][HL][W][P] built here, on this call's stream
     if (d_chain.alloc(8 * chain_elems) != hipSuccess || d_q.alloc(8 * (size_t)P) != hipSuccess)
         return rank_fail(MCMCPP_HIP_E_NOMEM, w + ": cannot allocate the " + std::to_string(8 * chain_elems) + " bytes of the score chain");
     std::vector<double> rhat_rank(P), ess_bulk(P), rhat_folded(P), lower(P), upper(P);
     std::vector<int64_t> closed_bulk(P), closed_lower(P), closed_upper(P);
-    int64_t len = 0, count = 0;
+    const mcmcpp::RhatShape chain_shape = mcmcpp::rhat_shape(K, HL, r.W, r.split);
+    const auto chain_request = [&](const char* what) { return mcmcpp::rhat_device_request(what, MCMCPP_HIP_F64, device, d_chain.get(), K, 0, HL, 1, r.W, P, r.split); };
     const auto ess_of_chain = [&](double* ess, int64_t* closed, double* rhat) -> int {
-        ANALYSIS_TRY(g_rank_error, hipStreamSynchronize(stream));
-        const int rc = mcmcpp_hip_effective_sample_size_device(MCMCPP_HIP_F64, device, d_chain.get(), K, 0, HL, 1, r.W, P, r.split, q.max_lag, 0, ess, nullptr, nullptr, closed,
-                                                               nullptr, nullptr, rhat, nullptr, nullptr, nullptr, &len, &count);
-        return rc ? rank_fail(rc, w + ": " + mcmcpp_hip_effective_sample_size_last_error()) : MCMCPP_HIP_OK;
+        mcmcpp::EssOutputs out{};
+        out.ess = ess;
+        out.closed = closed;
+        out.rhat = rhat;
+        return mcmcpp::nested_result(g_rank_error, r.what,
+                                     mcmcpp::ess_compute(g_rank_error, chain_request("effective_sample_size_device"), q.max_lag, 0, prop, HL, chain_shape, stream, out));
     };
     if (int rc = rk.rank_all(false, &quant, d_chain.get())) return rc;
     if (int rc = ess_of_chain(ess_bulk.data(), closed_bulk.data(), rhat_rank.data())) return rc;
     if (int rc = rk.set_fold_center(quant)) return rc;
     if (int rc = rk.rank_all(true, nullptr, d_chain.get())) return rc;
-    ANALYSIS_TRY(g_rank_error, hipStreamSynchronize(stream));
-    if (int rc = mcmcpp_hip_gelman_rubin_device(MCMCPP_HIP_F64, device, d_chain.get(), K, 0, HL, 1, r.W, P, r.split, rhat_folded.data(), nullptr, nullptr, nullptr, nullptr,
-                                                nullptr, nullptr, nullptr, nullptr, nullptr))
-        return rank_fail(rc, w + ": " + mcmcpp_hip_gelman_rubin_last_error());
+    mcmcpp::RhatOutputs folded{};
+    folded.rhat = rhat_folded.data();
+    if (int rc = mcmcpp::nested_result(g_rank_error, r.what, mcmcpp::rhat_compute(g_rank_error, chain_request("gelman_rubin_device"), prop, HL, chain_shape, stream, folded)))
+        return rc;
     for (int tail = 0; tail < 2; ++tail)
     {
         ANALYSIS_TRY(g_rank_error, hipMemcpyAsync(d_q.get(), (tail ? quant.q95 : quant.q05).data(), 8 * (size_t)P, hipMemcpyHostToDevice, stream));
@@ -199,7 +185,7 @@ int rank_entry(const Request& q)
     std::string why;
     int device = q.in.device;
     if (int rc = mcmcpp::open_gfx950_device(device, &device, &prop, &why)) return rank_fail(rc, w + ": " + why);
-    return q.in.dtype == MCMCPP_HIP_F64 ? run_request<double>(q, device, n, shape) : run_request<float>(q, device, n, shape);
+    return q.in.dtype == MCMCPP_HIP_F64 ? run_request<double>(q, device, prop, n, shape) : run_request<float>(q, device, prop, n, shape);
 }
 }  // namespace
 
@@ -210,16 +196,16 @@ const char* mcmcpp_hip_rank_diagnostics_last_error(void) { return g_rank_error.c
 int mcmcpp_hip_normal_scores(int32_t dtype, int32_t device, const void* const* steps, int32_t num_chains, int64_t n_steps, int32_t num_walkers, int32_t num_params,
                              int32_t split, int32_t fold, double* scores, double* median, double* q05, double* q95, int64_t* sequence_length, int64_t* num_sequences)
 {
-    return rank_entry(Request{mcmcpp::RhatRequest{"normal_scores", dtype, device, steps, nullptr, false, num_chains, 0, n_steps, 1, num_walkers, num_params, split}, false, fold,
-                              0, ScoreOutputs{scores, median, q05, q95, sequence_length, num_sequences}, DiagOutputs{}});
+    return rank_entry(Request{mcmcpp::rhat_host_request("normal_scores", dtype, device, steps, num_chains, n_steps, num_walkers, num_params, split), false, fold, 0,
+                              ScoreOutputs{scores, median, q05, q95, sequence_length, num_sequences}, DiagOutputs{}});
 }
 
 int mcmcpp_hip_normal_scores_device(int32_t dtype, int32_t device, const void* device_steps, int32_t num_chains, int64_t chain_stride_steps, int64_t n_steps,
                                     int64_t slice_interval, int32_t num_walkers, int32_t num_params, int32_t split, int32_t fold, double* scores, double* median,
                                     double* q05, double* q95, int64_t* sequence_length, int64_t* num_sequences)
 {
-    return rank_entry(Request{mcmcpp::RhatRequest{"normal_scores_device", dtype, device, nullptr, device_steps, true, num_chains, chain_stride_steps, n_steps, slice_interval,
-                                                  num_walkers, num_params, split},
+    return rank_entry(Request{mcmcpp::rhat_device_request("normal_scores_device", dtype, device, device_steps, num_chains, chain_stride_steps, n_steps, slice_interval,
+                                                          num_walkers, num_params, split),
                               false, fold, 0, ScoreOutputs{scores, median, q05, q95, sequence_length, num_sequences}, DiagOutputs{}});
 }
 
@@ -228,8 +214,8 @@ int mcmcpp_hip_rank_diagnostics(int32_t dtype, int32_t device, const void* const
                                 double* ess_tail_lower, double* ess_tail_upper, double* median, double* q05, double* q95, int64_t* closed_bulk, int64_t* closed_tail,
                                 int64_t* sequence_length, int64_t* num_sequences)
 {
-    return rank_entry(Request{mcmcpp::RhatRequest{"rank_diagnostics", dtype, device, steps, nullptr, false, num_chains, 0, n_steps, 1, num_walkers, num_params, split}, true, 0,
-                              max_lag, ScoreOutputs{},
+    return rank_entry(Request{mcmcpp::rhat_host_request("rank_diagnostics", dtype, device, steps, num_chains, n_steps, num_walkers, num_params, split), true, 0, max_lag,
+                              ScoreOutputs{},
                               DiagOutputs{rhat, rhat_rank, rhat_folded, ess_bulk, ess_tail, ess_tail_lower, ess_tail_upper, median, q05, q95, closed_bulk, closed_tail,
                                           sequence_length, num_sequences}});
 }
@@ -239,8 +225,8 @@ int mcmcpp_hip_rank_diagnostics_device(int32_t dtype, int32_t device, const void
                                        double* rhat_folded, double* ess_bulk, double* ess_tail, double* ess_tail_lower, double* ess_tail_upper, double* median,
                                        double* q05, double* q95, int64_t* closed_bulk, int64_t* closed_tail, int64_t* sequence_length, int64_t* num_sequences)
 {
-    return rank_entry(Request{mcmcpp::RhatRequest{"rank_diagnostics_device", dtype, device, nullptr, device_steps, true, num_chains, chain_stride_steps, n_steps,
-                                                  slice_interval, num_walkers, num_params, split},
+    return rank_entry(Request{mcmcpp::rhat_device_request("rank_diagnostics_device", dtype, device, device_steps, num_chains, chain_stride_steps, n_steps, slice_interval,
+                                                          num_walkers, num_params, split),
                               true, 0, max_lag, ScoreOutputs{},
                               DiagOutputs{rhat, rhat_rank, rhat_folded, ess_bulk, ess_tail, ess_tail_lower, ess_tail_upper, median, q05, q95, closed_bulk, closed_tail,
                                           sequence_length, num_sequences}});

@@ -18,7 +18,8 @@
 //     the means and within-variances first, then the squared deviations from the mean in a second pass.
 // The last step, P square roots, is the host's.  A device chain is read in place; host chains are uploaded chain by chain in
 // chunks of MCMCPP_HIP_RHAT_CHUNK_MB (read per call, default 1024).  The argument check and everything up to the figures in
-// device memory are also the first phase of mcmcpp_hip_effective_sample_size (ess.hip), which calls them through rhat_state.hpp.
+// device memory are also the first phase of mcmcpp_hip_effective_sample_size (ess.hip), which calls them through rhat_state.hpp;
+// the entry points' body behind the checks, the open device and the range probe is rhat_compute there, which rank.hip calls.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -284,13 +285,8 @@ rhat_slice_join_kernel(const double* __restrict__ in_a, const double* __restrict
 thread_local std::string g_rhat_error;
 
 using mcmcpp::RhatRequest;
+using mcmcpp::RhatOutputs;
 using mcmcpp::StepSpan;
-
-struct Outputs
-{
-    double *rhat, *mean, *within, *between, *chain_mean, *chain_within, *sequence_mean, *sequence_m2;
-    int64_t *sequence_length, *num_sequences;
-};
 
 template <class T, int V>
 void launch_series(const mcmcpp::RhatSeriesPlan& plan, hipStream_t stream, const StepSpan<T>& sp, long long chain_stride, long long E, long long n, long long L,
@@ -317,15 +313,12 @@ int sum_over_sequences(std::string& slot, hipStream_t stream, const double* seq_
 }
 
 template <class T>
-int run_state(std::string& slot, const RhatRequest& r, int device, const hipDeviceProp_t& prop, long long n, const mcmcpp::RhatShape& shape, hipStream_t stream,
-              mcmcpp::RhatState& st)
+int run_state(std::string& slot, const RhatRequest& r, const hipDeviceProp_t& prop, long long n, const mcmcpp::RhatShape& shape, hipStream_t stream, mcmcpp::RhatState& st)
 {
     const int K = r.K, P = r.P, H = shape.H;
     const long long E = (long long)r.W * P, L = shape.L, M = shape.M;
     const size_t step_bytes = sizeof(T) * (size_t)E;
     const long long chain_stride_steps = r.chain_stride_steps ? r.chain_stride_steps : r.n_steps;
-    if (r.on_device)
-        if (int rc = mcmcpp::check_device_steps(slot, r.what, r.device_steps, step_bytes * (size_t)((K - 1) * chain_stride_steps + r.n_steps), device)) return rc;
     mcmcpp::DeviceBuffer<>& d_chunk = st.chunk;
     mcmcpp::DeviceBuffer<double>& d_first = st.first;
     mcmcpp::DeviceBuffer<double>& d_state = st.state;
@@ -377,23 +370,40 @@ int run_state(std::string& slot, const RhatRequest& r, int device, const hipDevi
     return MCMCPP_HIP_OK;
 }
 
-int run_request(const RhatRequest& r, const Outputs& out, int device, const hipDeviceProp_t& prop, long long n, const mcmcpp::RhatShape& shape)
+int rhat_entry(const RhatRequest& r, const RhatOutputs& out)
+{
+    long long n = 0;
+    mcmcpp::RhatShape shape;
+    if (int rc = mcmcpp::rhat_check_request(g_rhat_error, r, &n, &shape)) return rc;
+    hipDeviceProp_t prop;
+    std::string why;
+    int device = r.device;
+    if (int rc = mcmcpp::open_gfx950_device(device, &device, &prop, &why)) return mcmcpp::analysis_fail(g_rhat_error, rc, std::string(r.what) + ": " + why);
+    if (int rc = mcmcpp::rhat_check_device_steps(g_rhat_error, r, device)) return rc;
+    mcmcpp::Stream stream;
+    ANALYSIS_TRY(g_rhat_error, hipStreamCreateWithFlags(stream.replace(), hipStreamNonBlocking));
+    return mcmcpp::rhat_compute(g_rhat_error, r, prop, n, shape, stream, out);
+}
+}  // namespace
+
+namespace mcmcpp
+{
+int rhat_compute(std::string& slot, const RhatRequest& r, const hipDeviceProp_t& prop, long long n, const RhatShape& shape, hipStream_t stream, const RhatOutputs& out)
 {
     const int K = r.K, P = r.P;
     const long long L = shape.L, M = shape.M;
     const size_t series = (size_t)M * P;
-    mcmcpp::RhatState st;
-    mcmcpp::Stream stream;  // (behind the buffers: the stream is idle and gone when they go)
-    ANALYSIS_TRY(g_rhat_error, hipStreamCreateWithFlags(stream.replace(), hipStreamNonBlocking));
-    if (int rc = mcmcpp::rhat_sequences_state(g_rhat_error, r, device, prop, n, shape, stream, st)) return rc;
+    RhatState st;
     std::vector<double> h_seq;
+    IdleOnReturn idle{stream};  // (behind the buffers: the stream is idle when they go)
+    if (int rc = rhat_sequences_state(slot, r, prop, n, shape, stream, st)) return rc;
     const std::vector<double>& h_res = st.h_res;
     if (out.sequence_mean || out.sequence_m2)
     {
         h_seq.resize(2 * series);
-        ANALYSIS_TRY(g_rhat_error, hipMemcpyAsync(h_seq.data(), st.seq, 16 * series, hipMemcpyDeviceToHost, stream));
+        ANALYSIS_TRY(slot, hipMemcpyAsync(h_seq.data(), st.seq, 16 * series, hipMemcpyDeviceToHost, stream));
     }
-    ANALYSIS_TRY(g_rhat_error, hipStreamSynchronize(stream));
+    ANALYSIS_TRY(slot, hipStreamSynchronize(stream));
     // the call has succeeded: the outputs
     const double Lm1 = (double)(L - 1);
     const double *h_mean = h_res.data(), *h_within = h_mean + P, *h_between = h_within + P;
@@ -415,21 +425,6 @@ int run_request(const RhatRequest& r, const Outputs& out, int device, const hipD
     return MCMCPP_HIP_OK;
 }
 
-int rhat_entry(const RhatRequest& r, const Outputs& out)
-{
-    long long n = 0;
-    mcmcpp::RhatShape shape;
-    if (int rc = mcmcpp::rhat_check_request(g_rhat_error, r, &n, &shape)) return rc;
-    hipDeviceProp_t prop;
-    std::string why;
-    int device = r.device;
-    if (int rc = mcmcpp::open_gfx950_device(device, &device, &prop, &why)) return mcmcpp::analysis_fail(g_rhat_error, rc, std::string(r.what) + ": " + why);
-    return run_request(r, out, device, prop, n, shape);
-}
-}  // namespace
-
-namespace mcmcpp
-{
 int rhat_check_request(std::string& slot, const RhatRequest& r, long long* n_out, RhatShape* shape_out)
 {
     const std::string w(r.what);
@@ -456,10 +451,9 @@ int rhat_check_request(std::string& slot, const RhatRequest& r, long long* n_out
     return MCMCPP_HIP_OK;
 }
 
-int rhat_sequences_state(std::string& slot, const RhatRequest& r, int device, const hipDeviceProp_t& prop, long long n, const RhatShape& shape, hipStream_t stream,
-                         RhatState& st)
+int rhat_sequences_state(std::string& slot, const RhatRequest& r, const hipDeviceProp_t& prop, long long n, const RhatShape& shape, hipStream_t stream, RhatState& st)
 {
-    return r.dtype == MCMCPP_HIP_F64 ? run_state<double>(slot, r, device, prop, n, shape, stream, st) : run_state<float>(slot, r, device, prop, n, shape, stream, st);
+    return r.dtype == MCMCPP_HIP_F64 ? run_state<double>(slot, r, prop, n, shape, stream, st) : run_state<float>(slot, r, prop, n, shape, stream, st);
 }
 }  // namespace mcmcpp
 
@@ -471,8 +465,8 @@ int mcmcpp_hip_gelman_rubin(int32_t dtype, int32_t device, const void* const* st
                             int32_t split, double* rhat, double* mean, double* within, double* between, double* chain_mean, double* chain_within,
                             double* sequence_mean, double* sequence_m2, int64_t* sequence_length, int64_t* num_sequences)
 {
-    return rhat_entry(RhatRequest{"gelman_rubin", dtype, device, steps, nullptr, false, num_chains, 0, n_steps, 1, num_walkers, num_params, split},
-                      Outputs{rhat, mean, within, between, chain_mean, chain_within, sequence_mean, sequence_m2, sequence_length, num_sequences});
+    return rhat_entry(mcmcpp::rhat_host_request("gelman_rubin", dtype, device, steps, num_chains, n_steps, num_walkers, num_params, split),
+                      RhatOutputs{rhat, mean, within, between, chain_mean, chain_within, sequence_mean, sequence_m2, sequence_length, num_sequences});
 }
 
 int mcmcpp_hip_gelman_rubin_device(int32_t dtype, int32_t device, const void* device_steps, int32_t num_chains, int64_t chain_stride_steps, int64_t n_steps,
@@ -480,8 +474,8 @@ int mcmcpp_hip_gelman_rubin_device(int32_t dtype, int32_t device, const void* de
                                    double* between, double* chain_mean, double* chain_within, double* sequence_mean, double* sequence_m2,
                                    int64_t* sequence_length, int64_t* num_sequences)
 {
-    return rhat_entry(RhatRequest{"gelman_rubin_device", dtype, device, nullptr, device_steps, true, num_chains, chain_stride_steps, n_steps, slice_interval,
-                                  num_walkers, num_params, split},
-                      Outputs{rhat, mean, within, between, chain_mean, chain_within, sequence_mean, sequence_m2, sequence_length, num_sequences});
+    return rhat_entry(mcmcpp::rhat_device_request("gelman_rubin_device", dtype, device, device_steps, num_chains, chain_stride_steps, n_steps, slice_interval, num_walkers,
+                                                  num_params, split),
+                      RhatOutputs{rhat, mean, within, between, chain_mean, chain_within, sequence_mean, sequence_m2, sequence_length, num_sequences});
 }
 }

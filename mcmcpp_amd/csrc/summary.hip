@@ -2,10 +2,11 @@
 // Monte Carlo standard error and effective sample size (Vehtari, Gelman, Simpson, Carpenter and Buerkner 2021, section 4), over
 // the sequences of rhat.hip / ess.hip and the sort of rank.hip.  An extension: the reference has no such class.
 //
-// The definition is the header's (include/mcmcpp_hip.h, mcmcpp_hip_posterior_summary).  Every effective sample size is the
-// existing entry point's (mcmcpp_hip_effective_sample_size_device) on a chain in device memory: the draws themselves, their
-// squared deviations, or the indicators of a quantile.  The order statistics come from rank_kernels.hpp's sort of a tile of
-// parameters (summary_plan.hpp has the host's decisions):
+// The definition is the header's (include/mcmcpp_hip.h, mcmcpp_hip_posterior_summary).  Every effective sample size is that of
+// the existing entry point's body (rhat_state.hpp: ess_compute of mcmcpp_hip_effective_sample_size_device, on this call's stream
+// and into this family's message slot) on a chain in device memory: the draws themselves, their squared deviations, or the
+// indicators of a quantile.  The order statistics come from rank_kernels.hpp's sort of a tile of parameters (summary_plan.hpp
+// has the host's decisions):
 //   * summary_square_kernel: thread (draw, parameter): c = (x - mean)(x - mean) in double, at the draw's place of the fp64 chain.
 //   * summary_pick_kernel: block = parameter of the tile, thread = one rank: the sorted key at that rank, as a double.  The
 //     ranks of the quantiles are the same for every parameter; those of the standard errors are the parameter's own.
@@ -164,17 +165,15 @@ struct Request
 };
 
 template <class T>
-int run_request(const Request& q, int device, long long n, const mcmcpp::RhatShape& shape)
+int run_request(const Request& q, int device, const hipDeviceProp_t& prop, long long n, const mcmcpp::RhatShape& shape)
 {
     typedef typename Ranker<T>::OwnKey Key;
     const mcmcpp::RhatRequest& r = q.in;
     const std::string w(r.what);
     const int K = r.K, P = r.P, Q = q.n_probs;
     const long long E = (long long)r.W * P, L = shape.L, M = shape.M, HL = (long long)shape.H * L, S = M * L;
-    const size_t step_bytes = sizeof(T) * (size_t)E, chain_elems = (size_t)K * HL * E;
-    const long long chain_stride_steps = r.chain_stride_steps ? r.chain_stride_steps : r.n_steps;
-    if (r.on_device)
-        if (int rc = mcmcpp::check_device_steps(g_summary_error, r.what, r.device_steps, step_bytes * (size_t)((K - 1) * chain_stride_steps + r.n_steps), device)) return rc;
+    const size_t chain_elems = (size_t)K * HL * E;
+    if (int rc = mcmcpp::rhat_check_device_steps(g_summary_error, r, device)) return rc;
     mcmcpp::DeviceBuffer<T> d_up;
     mcmcpp::DeviceBuffer<double> d_chain, d_q, d_values, d_bounds, d_part_w;
     mcmcpp::DeviceBuffer<unsigned> d_ranks, d_part_i;
@@ -191,25 +190,31 @@ int run_request(const Request& q, int device, long long n, const mcmcpp::RhatSha
     if (d_chain.alloc(8 * chain_elems) != hipSuccess || d_q.alloc(8 * (size_t)P) != hipSuccess)
         return summary_fail(MCMCPP_HIP_E_NOMEM, w + ": cannot allocate the " + std::to_string(8 * chain_elems) + " bytes of the fp64 chain");
 
-    int64_t len = 0, count = 0;
-    // the ESS call on the fp64 chain
+    // The ESS call (its body: ess_compute of rhat_state.hpp, on this call's stream) on a chain in device memory: the steps of
+    // the sequences [K][HL][W][P], or the device chain of the request where it lies
+    const char* const ess_name = "effective_sample_size_device";
+    const mcmcpp::RhatShape chain_shape = mcmcpp::rhat_shape(K, HL, r.W, r.split);
+    const auto ess_of = [&](const mcmcpp::RhatRequest& chain, long long used, const mcmcpp::RhatShape& sh, double* ess, double* mean, double* within, double* between) -> int {
+        mcmcpp::EssOutputs out{};
+        out.ess = ess;
+        out.mean = mean;
+        out.within = within;
+        out.between = between;
+        return mcmcpp::nested_result(g_summary_error, r.what, mcmcpp::ess_compute(g_summary_error, chain, q.max_lag, 0, prop, used, sh, stream, out));
+    };
     const auto ess_of_chain = [&](double* ess, double* mean, double* within, double* between) -> int {
-        ANALYSIS_TRY(g_summary_error, hipStreamSynchronize(stream));
-        const int rc = mcmcpp_hip_effective_sample_size_device(MCMCPP_HIP_F64, device, d_chain.get(), K, 0, HL, 1, r.W, P, r.split, q.max_lag, 0, ess, nullptr, nullptr, nullptr,
-                                                               nullptr, nullptr, nullptr, mean, within, between, &len, &count);
-        return rc ? summary_fail(rc, w + ": " + mcmcpp_hip_effective_sample_size_last_error()) : MCMCPP_HIP_OK;
+        return ess_of(mcmcpp::rhat_device_request(ess_name, MCMCPP_HIP_F64, device, d_chain.get(), K, 0, HL, 1, r.W, P, r.split), HL, chain_shape, ess, mean, within, between);
     };
 
     // mean, sd: the ESS call on the draws as they are, where they lie (a float draw converts to double exactly, and the call
     // converts first: its results are those of the fp64 chain of the same draws)
     std::vector<double> mean(P), ess_mean(P), within(P), between(P), sd(P), mcse_mean(P);
     {
-        const int rc = r.on_device ? mcmcpp_hip_effective_sample_size_device(r.dtype, device, r.device_steps, K, r.chain_stride_steps, r.n_steps, r.slice, r.W, P, r.split,
-                                                                             q.max_lag, 0, ess_mean.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, mean.data(),
-                                                                             within.data(), between.data(), &len, &count)
-                                   : mcmcpp_hip_effective_sample_size_device(r.dtype, device, d_up.get(), K, 0, HL, 1, r.W, P, r.split, q.max_lag, 0, ess_mean.data(), nullptr,
-                                                                             nullptr, nullptr, nullptr, nullptr, nullptr, mean.data(), within.data(), between.data(), &len, &count);
-        if (rc) return summary_fail(rc, w + ": " + mcmcpp_hip_effective_sample_size_last_error());
+        const int rc = r.on_device ? ess_of(mcmcpp::rhat_device_request(ess_name, r.dtype, device, r.device_steps, K, r.chain_stride_steps, r.n_steps, r.slice, r.W, P, r.split),
+                                            n, shape, ess_mean.data(), mean.data(), within.data(), between.data())
+                                   : ess_of(mcmcpp::rhat_device_request(ess_name, r.dtype, device, d_up.get(), K, 0, HL, 1, r.W, P, r.split), HL, chain_shape, ess_mean.data(),
+                                            mean.data(), within.data(), between.data());
+        if (rc) return rc;
     }
     for (int p = 0; p < P; ++p)
     {
@@ -391,7 +396,7 @@ int summary_entry(const Request& q)
     hipDeviceProp_t prop;
     int device = q.in.device;
     if (int rc = mcmcpp::open_gfx950_device(device, &device, &prop, &why)) return summary_fail(rc, w + ": " + why);
-    return q.in.dtype == MCMCPP_HIP_F64 ? run_request<double>(q, device, n, shape) : run_request<float>(q, device, n, shape);
+    return q.in.dtype == MCMCPP_HIP_F64 ? run_request<double>(q, device, prop, n, shape) : run_request<float>(q, device, prop, n, shape);
 }
 }  // namespace
 
@@ -406,8 +411,8 @@ int mcmcpp_hip_posterior_summary(int32_t dtype, int32_t device, const void* cons
                                  double* ess_mean, double* ess_sd, double* mcse_sd, double* quantile, double* ess_quantile, double* mcse_quantile, int64_t* rank_lower,
                                  int64_t* rank_upper, double* hdi_lower, double* hdi_upper, int64_t* sequence_length, int64_t* num_sequences)
 {
-    return summary_entry(Request{mcmcpp::RhatRequest{"posterior_summary", dtype, device, steps, nullptr, false, num_chains, 0, n_steps, 1, num_walkers, num_params, split},
-                                 max_lag, probs, n_probs, hdi_prob,
+    return summary_entry(Request{mcmcpp::rhat_host_request("posterior_summary", dtype, device, steps, num_chains, n_steps, num_walkers, num_params, split), max_lag, probs,
+                                 n_probs, hdi_prob,
                                  SummaryOutputs{mean, sd, mcse_mean, ess_mean, ess_sd, mcse_sd, quantile, ess_quantile, mcse_quantile, rank_lower, rank_upper, hdi_lower,
                                                 hdi_upper, sequence_length, num_sequences}});
 }
@@ -418,8 +423,8 @@ int mcmcpp_hip_posterior_summary_device(int32_t dtype, int32_t device, const voi
                                         double* quantile, double* ess_quantile, double* mcse_quantile, int64_t* rank_lower, int64_t* rank_upper, double* hdi_lower,
                                         double* hdi_upper, int64_t* sequence_length, int64_t* num_sequences)
 {
-    return summary_entry(Request{mcmcpp::RhatRequest{"posterior_summary_device", dtype, device, nullptr, device_steps, true, num_chains, chain_stride_steps, n_steps,
-                                                     slice_interval, num_walkers, num_params, split},
+    return summary_entry(Request{mcmcpp::rhat_device_request("posterior_summary_device", dtype, device, device_steps, num_chains, chain_stride_steps, n_steps, slice_interval,
+                                                             num_walkers, num_params, split),
                                  max_lag, probs, n_probs, hdi_prob,
                                  SummaryOutputs{mean, sd, mcse_mean, ess_mean, ess_sd, mcse_sd, quantile, ess_quantile, mcse_quantile, rank_lower, rank_upper, hdi_lower,
                                                 hdi_upper, sequence_length, num_sequences}});

@@ -50,12 +50,19 @@ def reshaped(spec, x):
 def place_on_device(spec, x, torch):
     """the device tensor the case reads: its chains more than n steps apart and one step inside a larger allocation ("room",
     the default); behind a burn-in of spec["burn"] steps in a [K][n_saved][W][P] array; from a base that is 8 bytes off a
-    16-byte boundary ("base8"); or as it is ("exact")"""
+    16-byte boundary ("base8"); as chain[:, burn:] of a contiguous [K][burn + n][W][P] tensor, which the last chain ends ("tail");
+    or as it is ("exact")"""
     t = torch.from_numpy(x)
     how = spec.get("place", "room")
     K, n = x.shape[:2]
     if how == "exact":
         return t.cuda()
+    if how == "tail":
+        whole = torch.full((K, spec["burn"] + n) + x.shape[2:], 1.0e30, dtype=t.dtype, device="cuda")
+        whole[:, spec["burn"]:] = t.cuda()
+        d = whole[:, spec["burn"]:]
+        assert whole.is_contiguous() and d.stride(0) == (spec["burn"] + n) * x.shape[2] * x.shape[3]
+        return d
     if how == "base8":
         flat = torch.zeros(x.size + 1, dtype=t.dtype, device="cuda")
         flat[1:] = t.reshape(-1).cuda()

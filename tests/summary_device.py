@@ -108,6 +108,39 @@ def errors(out, torch, capi):
     out["errors/steps"] = x
 
 
+def error_slots(out, torch, capi):
+    """tests/test_analysis_errors.py: what the ESS and the R-hat family's *_last_error say after a failure of their own, before
+    and after a summary and rank diagnostics that succeed and a summary that fails.  Those calls run the two families' code on
+    chains of their own and have a message slot of their own.  (None of these calls fails inside the nested ESS or R-hat
+    code -- the NaN is refused by the summary's own check -- so this would not see a nested failure's message written to the
+    other family's slot; that rank.hip and summary.hip reference no symbol of the two families' C ABI is what rules it out.)"""
+    import ctypes as C
+    L = capi.lib()
+    K, n, W, P = 3, 12, 10, 2
+    x = make_steps(dict(dtype="f64", K=K, n=n, W=W, P=P, seed=11))
+    bad = x.copy()
+    bad[1, 7, 3, 1] = np.nan
+    d, d_bad = torch.from_numpy(x).cuda(), torch.from_numpy(bad).cuda()
+    torch.cuda.synchronize()
+
+    def slots(tag):
+        out["slots/%s_ess" % tag] = np.array((L.mcmcpp_hip_effective_sample_size_last_error() or b"").decode())
+        out["slots/%s_rhat" % tag] = np.array((L.mcmcpp_hip_gelman_rubin_last_error() or b"").decode())
+
+    host = C.c_void_p(x.ctypes.data)  # a host pointer as device_steps
+    out["slots/ess_code"] = np.int32(L.mcmcpp_hip_effective_sample_size_device(capi.F64, -1, host, K, 0, n, 1, W, P, 1, 0, 0, *([None] * 12)))
+    out["slots/rhat_code"] = np.int32(L.mcmcpp_hip_gelman_rubin_device(capi.F64, -1, host, K, 0, n, 1, W, P, 1, *([None] * 10)))
+    slots("first")
+    summary, diag = capi.posterior_summary(d), capi.rank_diagnostics(d)
+    out["slots/ess_mean"], out["slots/ess_bulk"] = summary["ess_mean"], diag["ess_bulk"]
+    slots("after_success")
+    probs = np.array(DEFAULT_PROBS)
+    out["slots/nan_code"] = np.int32(L.mcmcpp_hip_posterior_summary_device(capi.F64, -1, C.c_void_p(d_bad.data_ptr()), K, 0, n, 1, W, P, 1, 0, capi._ptr(probs), 3, 0.94,
+                                                                         *([None] * 15)))
+    out["slots/nan_message"] = np.array((L.mcmcpp_hip_posterior_summary_last_error() or b"").decode())
+    slots("after_failure")
+
+
 def main():
     import torch  # (before the library: two HIP runtimes in one process initialise in this order only)
     from mcmcpp_amd import capi
@@ -121,6 +154,8 @@ def main():
         print("sampler done", flush=True)
     if spec.get("errors"):
         errors(out, torch, capi)
+    if spec.get("error_slots"):
+        error_slots(out, torch, capi)
     np.savez(sys.argv[2], **out)
     print("summary_device OK")
 

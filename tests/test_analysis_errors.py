@@ -1,8 +1,13 @@
-"""What every analysis entry point answers to a bad argument, before it opens a device (CPU test): the return code and the whole
+"""What every analysis entry point answers to a bad argument, before it opens a device (CPU tests): the return code and the whole
 message text, row by row.  The five families (moments, histograms, autocorr, order statistics, device chain) share one host
 layer (mcmcpp_amd/csrc/analysis_host.hpp) and keep a message slot each; users match on these texts, so a change of the host
-code must leave them as they are, to the letter.  The suites of the families pin some of them by substring."""
+code must leave them as they are, to the letter.  The suites of the families pin some of them by substring.  One GPU test at the
+end: the slots of the ESS and R-hat families across the calls of the families that run their code."""
 import ctypes as C
+import json
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -214,3 +219,26 @@ def test_calls_without_a_handle_are_refused_and_leave_the_message_alone(lib, fam
     assert getattr(lib, "mcmcpp_hip_%s_last_error" % family)(None).decode() == text
     assert (OUT == 777.0).all()
     getattr(lib, "mcmcpp_hip_%s_destroy" % family)(None)  # (and destroying nothing is fine)
+
+
+# ---- GPU: the multi-chain families keep their slots to themselves -------------------------------------------------------------------
+
+@pytest.mark.gpu
+def test_summary_and_rank_calls_leave_the_ess_and_rhat_slots_alone(tmp_path):
+    """The posterior summary and the rank diagnostics run the code of the ESS and R-hat families on chains of their own.  A
+    failure of mcmcpp_hip_effective_sample_size_device and of mcmcpp_hip_gelman_rubin_device (a host pointer as device_steps)
+    leaves each family's message; neither a summary and rank diagnostics that succeed nor a summary that fails (a NaN draw)
+    changes a byte of it.  One child process (tests/summary_device.py)."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = str(tmp_path / "slots.npz")
+    r = subprocess.run([sys.executable, "-m", "tests.summary_device", json.dumps(dict(error_slots=True)), out], cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "summary_device OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    got = np.load(out)
+    assert got["slots/ess_code"] == E_ARG and got["slots/rhat_code"] == E_ARG
+    assert str(got["slots/first_ess"]) == "effective_sample_size_device: device_steps is not device memory"
+    assert str(got["slots/first_rhat"]) == "gelman_rubin_device: device_steps is not device memory"
+    assert np.isfinite(got["slots/ess_mean"]).all() and np.isfinite(got["slots/ess_bulk"]).all()  # the calls in between did succeed
+    assert got["slots/nan_code"] == E_ARG and str(got["slots/nan_message"]) == "posterior_summary_device: the draws contain a NaN (it has no place in the order)"
+    for when in ("after_success", "after_failure"):
+        for family in ("ess", "rhat"):
+            assert str(got["slots/%s_%s" % (when, family)]).encode() == str(got["slots/first_%s" % family]).encode(), (when, family)

@@ -62,6 +62,10 @@ CASES = {
     # slice_interval 3 on the device against pre-sliced, scattered host pointers
     "scattered_slice3": _case("f32", 2, 100, 12, 4, slice=3, scattered=True, diag=True),
     "slice3_whole": _case("f64", 3, 50, 5, 3, 0, slice=3, scattered=True),
+    # chain[:, 3:] of a contiguous tensor of 16 stored steps at slice_interval 2: 13 stored steps, 7 used, HL = 6 (the middle
+    # one unranked), chains 16 steps apart.  The ESS and R-hat calls inside get a request that no public check has seen
+    "odd7_slice2_tail_f64": _case("f64", 2, 13, 3, 2, place="tail", burn=3, slice=2, diag=True),
+    "odd7_slice2_tail_f32": _case("f32", 2, 13, 3, 2, place="tail", burn=3, slice=2, diag=True),
     # more than 256 blocks in a pass (S > 524 288): a thread of the scan kernel takes two entries of its digit's row, and the
     # histogram and scatter grids pass 256.  S = 3 x 47 x 3750 = 258 B + 366: 259 blocks, thread 129 of the scan takes one
     # entry and the threads behind it none.  S = 3 x 47 x 3733 = 256 B + B + 17: 258 blocks, two parameters in a tile, 64-bit keys
@@ -97,6 +101,9 @@ def test_the_cases_have_the_sizes_they_are_for():
     assert -(-(258 * B + 366) // B) == 259 and -(-(257 * B + 17) // B) == 258  # blocks of a pass: above the scan kernel's 256 threads
     odd = _want("odd_burn_k3", 0)
     assert odd["scores"].shape == (3, 44, 8, 2) and odd["sequence_length"] == 22 and odd["num_sequences"] == 48  # the middle step is not there
+    for name in ("odd7_slice2_tail_f64", "odd7_slice2_tail_f32"):
+        odd = _want(name, 0)
+        assert odd["scores"].shape == (2, 6, 3, 2) and odd["sequence_length"] == 3 and odd["num_sequences"] == 12  # 7 used steps of 13
 
 
 def test_restatement_on_known_answers():

@@ -63,6 +63,10 @@ CASES = {
     "odd_burn_k3": _case("f64", 3, 45, 8, 2, place="burn", burn=15, max_lag=7),
     # slice_interval 3 on the device against pre-sliced, scattered host pointers
     "scattered_slice3": _case("f32", 2, 100, 12, 4, slice=3, scattered=True),
+    # chain[:, 3:] of a contiguous tensor of 16 stored steps at slice_interval 2: 13 stored steps, 7 used, HL = 6 (the middle
+    # one in no sequence), chains 16 steps apart.  The ESS calls inside get a request that no public check has seen
+    "odd7_slice2_tail_f64": _case("f64", 2, 13, 3, 2, place="tail", burn=3, slice=2),
+    "odd7_slice2_tail_f32": _case("f32", 2, 13, 3, 2, place="tail", burn=3, slice=2),
 }
 assert len({CASES[n]["seed"] for n in CASES if n.startswith("tiles_")}) == 1 and 57600 * 5 * 8 > 1 << 20
 
@@ -87,6 +91,7 @@ def test_the_cases_have_the_sizes_they_are_for():
     sizes = {name: _draw_count(CASES[name]) for name in CASES}
     assert sizes["s32"] == 32 and sizes["sBm1_16probs_m1"] == B - 1 and sizes["sB_1prob_mSm1"] == B and sizes["sBp1_0probs"] == B + 1
     assert sizes["s3B17_f32_w2047"] == sizes["s3B17_f64_w2048"] == sizes["s3B17_f64_w2049"] == 3 * B + 17 and sizes["tiles_default"] == 57600
+    assert sizes["odd7_slice2_tail_f64"] == sizes["odd7_slice2_tail_f32"] == 2 * 6 * 3  # 7 used steps of 13: two halves of 3
     windows = {}
     for name, spec in CASES.items():
         probs, hdi = case_arguments(spec, sizes[name])
