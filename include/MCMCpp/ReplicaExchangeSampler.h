@@ -1,0 +1,217 @@
+/*
+ * ReplicaExchangeSampler.h -- parallel tempering on one MI355X (an extension of this repository; the reference has none).
+ *
+ * K ensembles ("rungs") run on a ladder of targets, one Calculator per rung: rung 0 has the target of interest, the others
+ * flattened versions of it (Device::DenseGaussian with beta_k P, Device::Rosenbrock with beta_k c, a plug-in with beta in its
+ * parameter blob).  All rungs are the chains of ONE handle, stepped by the same launches with the stretch move
+ * (GwDistribution<ParamType, 2, 1>); after every `exchangeEvery` ensemble steps a replica-exchange round proposes to swap
+ * walker w of rung k with walker w of rung k + 1 (mcmcpp_hip_exchange_chains, include/mcmcpp_hip.h: the rule, the random
+ * stream and the numbering of rounds).  Rung k steps with seed randSeed + k, as a sampler of its own would.
+ *
+ * One host Chain per rung: the existing Analysis classes accept rung 0's chain (getStepIttBegin(0) / getStepIttEnd(0)) like
+ * any other.  Device-memory chains are not offered here.
+ */
+#ifndef MCMCPP_REPLICAEXCHANGESAMPLER_H
+#define MCMCPP_REPLICAEXCHANGESAMPLER_H
+
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "Chain/Chain.h"
+#include "Device/Calculators.h"
+#include "Device/HipBackend.h"
+#include "Utility/UserOjbectsTest.h"
+
+namespace MCMC
+{
+
+template <class ParamType, class Calculator>
+class ReplicaExchangeSampler
+{
+public:
+    typedef Chain::Chain<ParamType> ChainType;
+    typedef Chain::ChainStepIterator<ParamType> StepItt;
+
+    static_assert(Utility::CheckDeviceCalculator<Calculator>::value && !Utility::CheckBatchCalculator<Calculator, ParamType>::value,
+                  "ReplicaExchangeSampler: the Calculator names a device functor: 'static const int hipCalcId', 'const ParamType* hipParams() const' "
+                  "and 'int hipParamCount() const' (Device/Calculators.h); batch targets cannot be exchanged");
+
+    /// One Calculator per rung, rung 0 first (2 to 16 rungs, all naming the same device functor with the same number of
+    /// parameters: std::invalid_argument otherwise).  numWalker must be even and exceed 2*numParameter; maxChainSizeBytes
+    /// bounds the host memory of each rung's stored steps.
+    ReplicaExchangeSampler(int randSeed, int numWalker, int numParameter, const std::vector<Calculator>& rungCalculators,
+                           unsigned long long maxChainSizeBytes = 2147483648ULL)
+        : calcs(rungCalculators), numWalkers(numWalker), numParams(numParameter), numRungs(static_cast<int>(rungCalculators.size())), nextRound(0),
+          placed(rungCalculators.size(), false), uploaded(false)
+    {
+        checkRungs(calcs);
+        const std::size_t K = static_cast<std::size_t>(numRungs);
+        for (std::size_t k = 0; k < K; ++k) chains.push_back(std::unique_ptr<ChainType>(new ChainType(numWalkers, numParams, maxChainSizeBytes)));
+        initPos.resize(K * static_cast<std::size_t>(numWalkers) * numParams);
+        initAux.resize(K * static_cast<std::size_t>(numWalkers));
+        swapProposed.assign(K - 1, 0);
+        swapAccepted.assign(K - 1, 0);
+        mcmcpp_hip_config cfg = mcmcpp_hip_config();
+        cfg.struct_size = sizeof(cfg);
+        cfg.dtype = Device::HipDtype<ParamType>::value;
+        cfg.num_walkers = numWalkers;
+        cfg.num_params = numParams;
+        cfg.calc_id = Calculator::hipCalcId;
+        cfg.calc_params = calcs[0].hipParams();
+        cfg.calc_params_len = calcs[0].hipParamCount();
+        cfg.seed = static_cast<std::uint64_t>(static_cast<long long>(randSeed));
+        cfg.stream = 0;
+        cfg.gw_alpha_num = 2;
+        cfg.gw_alpha_den = 1;
+        cfg.mover = MCMCPP_HIP_MOVER_STRETCH;
+        cfg.device = Device::Placement::fromEnvironment().device(0);
+        cfg.num_chains = numRungs;
+        handle.create(cfg);
+        if (cfg.calc_params_len > 0)
+            for (int k = 1; k < numRungs; ++k)
+                handle.check("mcmcpp_hip_set_chain_params",
+                             mcmcpp_hip_set_chain_params(handle.get(), k, calcs[static_cast<std::size_t>(k)].hipParams(), cfg.calc_params_len));
+    }
+    ReplicaExchangeSampler(const ReplicaExchangeSampler&) = delete;
+    ReplicaExchangeSampler& operator=(const ReplicaExchangeSampler&) = delete;
+
+    /// What the constructor checks before it touches the device.
+    static void checkRungs(const std::vector<Calculator>& rungs)
+    {
+        if (rungs.size() < 2 || rungs.size() > 16)
+            throw std::invalid_argument("ReplicaExchangeSampler: a ladder has 2 to 16 rungs, got " + std::to_string(rungs.size()));
+        for (std::size_t k = 1; k < rungs.size(); ++k)
+            if (static_cast<int>(rungs[k].hipCalcId) != static_cast<int>(rungs[0].hipCalcId) || rungs[k].hipParamCount() != rungs[0].hipParamCount())
+                throw std::invalid_argument("ReplicaExchangeSampler: the calculators of all rungs must name the same device functor with the same number of parameters: rung " +
+                                            std::to_string(k) + " has id " + std::to_string(static_cast<int>(rungs[k].hipCalcId)) + " with " +
+                                            std::to_string(rungs[k].hipParamCount()) + " parameters, rung 0 id " + std::to_string(static_cast<int>(rungs[0].hipCalcId)) +
+                                            " with " + std::to_string(rungs[0].hipParamCount()));
+    }
+
+    int getNumRungs() const { return numRungs; }
+
+    /// positions: numWalker*numParameter values, walker-major; auxValues: the log-posterior of each walker under THIS rung's
+    /// calculator.  The initial placement becomes step 0 of the rung's chain.  Every rung is placed before the first runMCMC.
+    void setInitialWalkerPos(int rung, ParamType* positions, ParamType* auxValues)
+    {
+        const std::size_t k = checkedRung(rung), cells = static_cast<std::size_t>(numWalkers) * numParams;
+        std::memcpy(&initPos[k * cells], positions, sizeof(ParamType) * cells);
+        std::memcpy(&initAux[k * static_cast<std::size_t>(numWalkers)], auxValues, sizeof(ParamType) * static_cast<std::size_t>(numWalkers));
+        for (int w = 0; w < numWalkers; ++w) chains[k]->storeWalker(w, positions + static_cast<std::size_t>(w) * numParams);
+        chains[k]->incrementChainStep();
+        placed[k] = true;
+        uploaded = false;
+    }
+
+    /// numSteps more stored steps of every rung, with a replica-exchange round after every exchangeEvery of them (a tail shorter
+    /// than exchangeEvery runs without a trailing exchange).  Each segment costs a synchronisation.  False when a chain's byte
+    /// budget ran out first.
+    bool runMCMC(int numSteps, int exchangeEvery)
+    {
+        if (exchangeEvery < 1) throw std::invalid_argument("ReplicaExchangeSampler::runMCMC: exchangeEvery must be positive");
+        upload();
+        const std::size_t K = static_cast<std::size_t>(numRungs), cells = static_cast<std::size_t>(numWalkers) * numParams;
+        std::int64_t left = numSteps;
+        while (left > 0)
+        {
+            std::int64_t seg = left < exchangeEvery ? left : static_cast<std::int64_t>(exchangeEvery);
+            for (std::size_t k = 0; k < K; ++k)
+                if (chains[k]->remainingSteps() < seg) seg = chains[k]->remainingSteps();
+            if (seg < 1) return false;
+            segment.resize(K * static_cast<std::size_t>(seg) * cells);
+            handle.check("mcmcpp_hip_run", mcmcpp_hip_run(handle.get(), seg, 1, segment.data(), nullptr));
+            for (std::size_t k = 0; k < K; ++k)
+                for (std::int64_t s = 0; s < seg; ++s)
+                {
+                    const ParamType* step = &segment[(k * static_cast<std::size_t>(seg) + static_cast<std::size_t>(s)) * cells];
+                    for (int w = 0; w < numWalkers; ++w) chains[k]->storeWalker(w, step + static_cast<std::size_t>(w) * numParams);
+                    chains[k]->incrementChainStep();
+                }
+            left -= seg;
+            if (seg == exchangeEvery)
+            {
+                std::uint64_t proposed[16] = {0}, accepted[16] = {0};
+                handle.check("mcmcpp_hip_exchange_chains", mcmcpp_hip_exchange_chains(handle.get(), nextRound, proposed, accepted, nullptr));
+                for (std::size_t p = 0; p + 1 < K; ++p)
+                {
+                    swapProposed[p] += proposed[p];
+                    swapAccepted[p] += accepted[p];
+                }
+                ++nextRound;
+            }
+            else if (left > 0)
+                return false;  // (a chain filled up inside a segment)
+        }
+        return true;
+    }
+
+    int getStoredSteps() { return static_cast<int>(chains[0]->getStoredStepCount()); }
+    StepItt getStepIttBegin(int rung) { return chains[checkedRung(rung)]->getStepIteratorBegin(); }
+    StepItt getStepIttEnd(int rung) { return chains[checkedRung(rung)]->getStepIteratorEnd(); }
+    ChainType& chain(int rung) { return *chains[checkedRung(rung)]; }
+
+    /// Accepted stretch proposals of the rung's walkers over its walkers times steps, the initial placement counted as one
+    /// accepted step per walker (as EnsembleSampler::getAcceptanceFraction does).  Swaps are not counted here.
+    ParamType getAcceptanceFraction(int rung)
+    {
+        const std::size_t k = checkedRung(rung);
+        upload();
+        std::vector<std::uint32_t> nacc(static_cast<std::size_t>(numRungs) * numWalkers);
+        std::uint64_t steps = 0;
+        handle.check("mcmcpp_hip_get_state", mcmcpp_hip_get_state(handle.get(), nullptr, nullptr, nacc.data()));
+        handle.check("mcmcpp_hip_get_counters", mcmcpp_hip_get_counters(handle.get(), nullptr, &steps, nullptr, nullptr));
+        unsigned long long acc = static_cast<unsigned long long>(numWalkers);
+        for (int w = 0; w < numWalkers; ++w) acc += nacc[k * static_cast<std::size_t>(numWalkers) + static_cast<std::size_t>(w)];
+        return static_cast<ParamType>(acc) / static_cast<ParamType>(static_cast<unsigned long long>(numWalkers) * (steps + 1ULL));
+    }
+
+    /// Accepted over proposed swaps between rung `pair` and rung `pair + 1` so far (0 before the first round that pairs them).
+    ParamType getSwapFraction(int pair) const
+    {
+        if (pair < 0 || pair + 1 >= numRungs) throw std::out_of_range("ReplicaExchangeSampler::getSwapFraction: pair " + std::to_string(pair) + " out of range");
+        const std::size_t p = static_cast<std::size_t>(pair);
+        return swapProposed[p] ? static_cast<ParamType>(swapAccepted[p]) / static_cast<ParamType>(swapProposed[p]) : static_cast<ParamType>(0);
+    }
+    /// Rounds done so far; the next round has this number.
+    std::uint64_t getExchangeRounds() const { return nextRound; }
+
+    /// Walker positions [K][W][D], log-posteriors [K][W] and per-walker accepted counts [K][W] as they stand on the device.
+    void currentState(ParamType* positions, ParamType* logp, std::uint32_t* nAccept)
+    {
+        upload();
+        handle.check("mcmcpp_hip_get_state", mcmcpp_hip_get_state(handle.get(), positions, logp, nAccept));
+    }
+
+private:
+    std::size_t checkedRung(int rung) const
+    {
+        if (rung < 0 || rung >= numRungs) throw std::out_of_range("ReplicaExchangeSampler: rung " + std::to_string(rung) + " out of range");
+        return static_cast<std::size_t>(rung);
+    }
+    void upload()
+    {
+        if (uploaded) return;
+        for (std::size_t k = 0; k < placed.size(); ++k)
+            if (!placed[k]) throw std::logic_error("ReplicaExchangeSampler: setInitialWalkerPos has not been called for rung " + std::to_string(k));
+        handle.check("mcmcpp_hip_set_state", mcmcpp_hip_set_state(handle.get(), initPos.data(), initAux.data()));
+        uploaded = true;
+    }
+
+    std::vector<Calculator> calcs;  // (the handle's create-time parameters point into calcs[0])
+    int numWalkers, numParams, numRungs;
+    std::uint64_t nextRound;
+    std::vector<bool> placed;
+    bool uploaded;
+    std::vector<std::unique_ptr<ChainType> > chains;
+    std::vector<ParamType> initPos, initAux, segment;
+    std::vector<std::uint64_t> swapProposed, swapAccepted;
+    Device::HipHandle handle;
+};
+
+}  // namespace MCMC
+#endif  // MCMCPP_REPLICAEXCHANGESAMPLER_H

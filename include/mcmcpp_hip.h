@@ -327,6 +327,31 @@ int mcmcpp_hip_calc_logp_chain(mcmcpp_hip_sampler* h, int32_t chain, const void*
 int mcmcpp_hip_calc_logp_device(mcmcpp_hip_sampler* h, int32_t chain, const void* device_positions, int64_t count,
                                 void* device_logp_out);
 
+/* ---- parallel tempering: replica exchange among the chains of one handle ------------------------------- */
+
+/* A ladder of targets is K chains with per-chain parameters (mcmcpp_hip_set_chain_params): chain k's block flattens chain
+ * 0's target (dense Gaussian: P_k = beta_k P; Rosenbrock: c_k = beta_k c; a plug-in: beta in its parameter blob).  Between
+ * runs, one round proposes to exchange the states of neighbouring chains:
+ *   pairs     round r pairs chains (k, k+1) for k = r (mod 2), k+1 < K (pair slot j = k >> 1, at most 8); walker w of chain k
+ *             is paired with walker w of chain k+1, for every w.
+ *   draws     one pcg64 engine seeded (seed, 2^64 - 1 - stream), an increment no step stream of the handle has; the pair
+ *             (round, slot j, walker w) consumes the one raw output at stream position (r*8 + j)*W + w, whatever K is and
+ *             whatever was accepted.  `round` is the caller's: a checkpoint stays get_state plus integers.
+ *   decision  in double, whatever the handle's dtype: u = canonical(draw), ln U = log(1 - u),
+ *             delta = (logp_k(x_{k+1}) - logp_k(x_k)) + (logp_{k+1}(x_k) - logp_{k+1}(x_{k+1})), accept iff ln U < delta, by
+ *             the IEEE comparison alone (a NaN delta rejects, +inf accepts).  logp_k(x_k) and logp_{k+1}(x_{k+1}) are the
+ *             stored log-posteriors, the other two are evaluated by the calculator with the other chain's parameters.
+ *             A near tie: |ln U - delta| <= 1e-12 (|ln U| + the four |logp|) and the margin finite.
+ *   on accept the two rows swap; logp_k[w] <- logp_k(x_{k+1}), logp_{k+1}[w] <- logp_{k+1}(x_k).  n_accept (accepted
+ *             stretch proposals of the slot), the step streams and the step count are not touched.
+ * proposed/accepted/near_ties: [K-1] counters of pair (k, k+1), overwritten (pairs not in this round: 0).  Any pointer may
+ * be NULL.  A round without a pair (K = 2, odd round) succeeds and changes nothing.  Returns when the round is applied.
+ * MCMCPP_HIP_E_UNSUPPORTED for the differential-evolution mover, batch targets, sharded handles, handles with a communicator
+ * and handles with caller-owned positions; MCMCPP_HIP_E_ARG for num_chains < 2 and round >= 2^40; MCMCPP_HIP_E_STATE before
+ * set_state, after a failed run and while an asynchronous run is in progress.  The first round allocates its scratch
+ * (16 W log-posteriors) outside the handle's step buffers. */
+int mcmcpp_hip_exchange_chains(mcmcpp_hip_sampler* h, uint64_t round, uint64_t* proposed, uint64_t* accepted, uint64_t* near_ties);
+
 /* ---- measurement ---------------------------------------------------------------------------------- */
 
 /* GPU time of the last mcmcpp_hip_run between HIP events recorded on the launch stream around the

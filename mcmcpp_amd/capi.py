@@ -30,7 +30,7 @@ EXPORTS = [
     "mcmcpp_hip_device_chain_compact",
     "mcmcpp_hip_run_device", "mcmcpp_hip_run_device_async", "mcmcpp_hip_calc_logp_device", "mcmcpp_hip_moments_add_device_steps_strided",
     "mcmcpp_hip_half_step_async", "mcmcpp_hip_bind_device_chain", "mcmcpp_hip_device_positions",
-    "mcmcpp_hip_shard_span", "mcmcpp_hip_synchronize",
+    "mcmcpp_hip_shard_span", "mcmcpp_hip_synchronize", "mcmcpp_hip_exchange_chains",
     "mcmcpp_hip_moments_create", "mcmcpp_hip_moments_destroy", "mcmcpp_hip_moments_reset", "mcmcpp_hip_moments_add_steps",
     "mcmcpp_hip_moments_add_device_steps", "mcmcpp_hip_moments_finish", "mcmcpp_hip_moments_last_error",
     "mcmcpp_hip_autocorr_times", "mcmcpp_hip_autocorr_times_device", "mcmcpp_hip_autocorr_last_error",
@@ -136,6 +136,8 @@ def lib():
         L.mcmcpp_hip_device_positions.restype = vp
         L.mcmcpp_hip_shard_span.argtypes = [vp, i32, C.POINTER(i64), C.POINTER(i64)]
         L.mcmcpp_hip_synchronize.argtypes = [vp]
+        if hasattr(L, "mcmcpp_hip_exchange_chains"):  # (absent from earlier builds selected with MCMCPP_HIP_LIB)
+            L.mcmcpp_hip_exchange_chains.argtypes = [vp, C.c_uint64, vp, vp, vp]
         if hasattr(L, "mcmcpp_hip_moments_create"):  # (absent only from older experiment builds selected with MCMCPP_HIP_LIB)
             L.mcmcpp_hip_moments_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
             L.mcmcpp_hip_moments_destroy.argtypes = [vp]
@@ -547,6 +549,57 @@ class HipSampler:
         else:
             self._check(lib().mcmcpp_hip_calc_logp_chain(self.h, chain, _ptr(pos), pos.shape[0], _ptr(out)))
         return out
+
+    def exchange_chains(self, round):
+        """One replica-exchange round among the K chains (mcmcpp_hip_exchange_chains): round r proposes to swap walker w of
+        chain k with walker w of chain k + 1 for every k = r (mod 2).  Returns dict(proposed, accepted, near_ties), numpy
+        [K-1]: the counters of pair (k, k + 1), 0 for the pairs that are not in this round."""
+        v = [np.zeros(max(self.K - 1, 1), dtype=np.uint64) for _ in range(3)]
+        self._check(lib().mcmcpp_hip_exchange_chains(self.h, round, *[_ptr(x) for x in v]))
+        return dict(proposed=v[0][:self.K - 1], accepted=v[1][:self.K - 1], near_ties=v[2][:self.K - 1])
+
+    def run_exchanging(self, n_saved, interval=1, exchange_every=1, first_round=0, out=None, device=False):
+        """Parallel tempering: n_saved stored steps (one every `interval` ensemble steps) with a replica-exchange round after
+        every `exchange_every` ensemble steps (a multiple of interval), rounds numbered first_round, first_round + 1, ...
+        A loop of run (device=True: run_device) segments, each followed by exchange_chains; a tail shorter than
+        exchange_every runs without a trailing exchange.  Returns (chain [K][n_saved][W][D] -- a device tensor with
+        device=True --, accepted per step [K][n_saved * interval], the summed swap counters as exchange_chains returns
+        them, the next round number).  out: the array (device: tensor) to store into.
+
+        Each segment costs a synchronisation (the exchange works on the state between runs, the segment's stored steps are
+        copied to their place): choose exchange_every with that in mind."""
+        if self.K < 2:
+            raise ValueError("run_exchanging needs num_chains >= 2")
+        if interval < 1 or exchange_every < 1 or exchange_every % interval:
+            raise ValueError("exchange_every must be a positive multiple of interval")
+        K, per = self.K, exchange_every // interval
+        shape = (K, n_saved, self.W, self.D)
+        if device:
+            _, chain = self._device_out(n_saved, out)
+            if not _is_tensor(chain):
+                raise ValueError("run_exchanging(device=True) stores into a torch tensor")
+        else:
+            if out is not None:
+                assert out.shape == shape and out.dtype == self.np_t and out.flags.c_contiguous
+            chain = out if out is not None else np.empty(shape, dtype=self.np_t)
+        acc = np.zeros((K, n_saved * interval), dtype=np.uint32)
+        swaps = dict(proposed=np.zeros(K - 1, np.uint64), accepted=np.zeros(K - 1, np.uint64), near_ties=np.zeros(K - 1, np.uint64))
+        rnd, done = first_round, 0
+        while done < n_saved:
+            seg = min(per, n_saved - done)
+            c, a = (self.run_device if device else self.run)(seg, interval=interval)
+            chain[:, done:done + seg] = c
+            acc[:, done * interval:(done + seg) * interval] = a
+            done += seg
+            if seg == per:
+                r = self.exchange_chains(rnd)
+                for key in swaps:
+                    swaps[key] += r[key]
+                rnd += 1
+        if device:
+            import torch
+            torch.cuda.current_stream(chain.device).synchronize()  # (the copies into `chain` are the caller's to rely on)
+        return chain, acc, swaps, rnd
 
     def last_run_timing(self):
         ms, n = C.c_double(0), C.c_int64(0)

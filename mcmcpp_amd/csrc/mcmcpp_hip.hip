@@ -26,6 +26,7 @@
 #include "../../include/mcmcpp_hip.h"
 #define MCMCPP_DEFINE_REDUCE_KERNEL
 #include "launch_table.hpp"
+#include "replica_kernels.hpp"
 #include "sampler_host.hpp"
 #include "split_exchange.hpp"
 
@@ -1020,6 +1021,78 @@ public:
         return kernel_calc_logp_device(calc_fn, prm, pos, count, out);
     }
 
+    // One replica-exchange round among the K chains (replica_plan.hpp has the rule).  It works on the home state between
+    // runs: d_pos and logp_of(k)[0..W).  Per pair two `calc` launches of the calculator (chain k's parameters on chain k + 1's
+    // rows and the other way round), then one swap launch for the whole round.  The step streams, half_steps and n_accept stay
+    // as they are; so do the draw records left by the last run: they hold draws and partner indices, nothing of a walker's
+    // row (DrawRec), and begin_run marks every row as moved for the full-step kernels.
+    int exchange_chains(uint64_t round, uint64_t* proposed, uint64_t* accepted, uint64_t* near_ties) override
+    {
+        static_assert(kReplicaMaxSlots * 2 == kMaxChains, "a round has a slot for every second chain");
+        if (int rc = chain_params_supported("exchange_chains")) return rc;
+        if (K < 2) return fail(MCMCPP_HIP_E_ARG, "exchange_chains: the handle has one chain (num_chains must be at least 2)");
+        if (round >= kReplicaMaxRound) return fail(MCMCPP_HIP_E_ARG, "exchange_chains: round %llu is out of range (rounds are below 2^40)", (unsigned long long)round);
+        if (!have_state) return fail(MCMCPP_HIP_E_STATE, "exchange_chains: no walker state (set_state has not been called, or a run failed half way)");
+        for (int k = 0; k + 1 < K; ++k)
+        {
+            if (proposed) proposed[k] = 0;
+            if (accepted) accepted[k] = 0;
+            if (near_ties) near_ties[k] = 0;
+        }
+        const int pairs = replica_pairs(K, round), k0 = replica_first_chain(round);
+        if (pairs == 0) return MCMCPP_HIP_OK;
+        HIP_TRY(hipSetDevice(device));
+        if (!d_replica_table)
+        {
+            // the exchange stream and its jump table: once per handle
+            replica_seed(cfg.seed, cfg.stream, &replica_state0, &replica_inc);
+            std::vector<ReplicaJump> t((size_t)replica_table_entries(W));
+            replica_fill_table(replica_inc, W, t.data());
+            DeviceBuffer<ReplicaJump> table;
+            DeviceBuffer<ReplicaCounts> counts;
+            DeviceBuffer<T> cross;
+            if (table.alloc(sizeof(ReplicaJump) * t.size()) != hipSuccess || counts.alloc(sizeof(ReplicaCounts) * kReplicaMaxSlots) != hipSuccess ||
+                cross.alloc(sizeof(T) * (size_t)kReplicaMaxSlots * 2 * (size_t)W) != hipSuccess)
+                return fail(MCMCPP_HIP_E_NOMEM, "exchange_chains: cannot allocate the scratch of a round (%zu bytes)", sizeof(T) * (size_t)kReplicaMaxSlots * 2 * (size_t)W);
+            HIP_TRY(hipMemcpy(table, t.data(), sizeof(ReplicaJump) * t.size(), hipMemcpyHostToDevice));
+            d_replica_table = std::move(table);
+            d_replica_counts = std::move(counts);
+            d_replica_cross = std::move(cross);
+        }
+        const ReplicaShape shape = replica_shape(W, D, (int)sizeof(T), vec_ok, pairs);
+        ReplicaSwapArgs<T> a;
+        std::memset(&a, 0, sizeof a);
+        a.pos = d_pos, a.logp = d_logp, a.cross = d_replica_cross, a.table = d_replica_table, a.counts = d_replica_counts;
+        a.logp_stride_bytes = logp_chain_stride_bytes<T>(n);
+        a.W = W, a.D = D, a.first_chain = k0, a.lanes = shape.lanes, a.units = shape.units, a.vec_ok = vec_ok;
+        const long long per_block = (long long)(64 / lpw) * kWavesPerBlock;
+        const unsigned calc_grid = (unsigned)((W + per_block - 1) / per_block);
+        const size_t chain_elems = (size_t)W * D;
+        for (int j = 0; j < pairs; ++j)
+        {
+            const int ka = replica_lower_chain(round, j), kb = ka + 1;
+            a.base[j] = replica_slot_base(replica_state0, replica_inc, round, j, W);
+            T* const cross = d_replica_cross + (size_t)j * 2 * (size_t)W;
+            calc_fn(d_pos + chain_elems * kb, cross, params_of(ka), W, D, vec_ok, calc_grid, stream);      // logp_a(x_b)
+            calc_fn(d_pos + chain_elems * ka, cross + W, params_of(kb), W, D, vec_ok, calc_grid, stream);  // logp_b(x_a)
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemsetAsync(d_replica_counts, 0, sizeof(ReplicaCounts) * kReplicaMaxSlots, stream));
+        launch_replica_swap(a, shape, stream);
+        HIP_TRY(hipGetLastError());
+        ReplicaCounts counts[kReplicaMaxSlots];
+        HIP_TRY(hipMemcpyAsync(counts, d_replica_counts, sizeof counts, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        for (int j = 0; j < pairs; ++j)
+        {
+            const int ka = replica_lower_chain(round, j);
+            if (proposed) proposed[ka] = (uint64_t)W;
+            if (accepted) accepted[ka] = counts[j].accepted;
+            if (near_ties) near_ties[ka] = counts[j].near_ties;
+        }
+        return MCMCPP_HIP_OK;
+    }
+
     int half_step_async(int32_t color, int64_t save_slot) override
     {
         if (K > 1) return fail(MCMCPP_HIP_E_UNSUPPORTED, "half_step_async: not with several chains per handle");
@@ -1108,6 +1181,9 @@ private:
         run_info_idle = true;
         return MCMCPP_HIP_OK;
     }
+
+    // chain k's calculator parameters: its own block, or the one all chains share
+    const T* params_of(int k) const { return d_chain_params ? d_chain_params + (size_t)chain_params_stride * (size_t)k : d_params; }
 
     // chain k's arrays (ChainGeometry; k = 0: the arrays themselves)
     T* logp_of(int k) const { return logp_of_chain<T>(d_logp, n, k); }
@@ -1390,6 +1466,12 @@ private:
     uint64_t half_steps = 0, enq_step = 0;
     void* bound_chain = nullptr;
     int64_t bound_slots = 0;
+    // replica exchange (exchange_chains), allocated by the first round: cross log-posteriors [8][2][W], the jump table of the
+    // exchange stream, the counters of a round [8]
+    DeviceBuffer<T> d_replica_cross;
+    DeviceBuffer<ReplicaJump> d_replica_table;
+    DeviceBuffer<ReplicaCounts> d_replica_counts;
+    ReplicaU128 replica_state0 = {}, replica_inc = {};
     // a rank of a split ensemble: the communicator and everything only split runs use (declared last: it goes first, the
     // communicator in front of every buffer)
     SplitExchange<T> xchg;
@@ -1555,6 +1637,12 @@ int mcmcpp_hip_calc_logp_chain(mcmcpp_hip_sampler* h, int32_t chain, const void*
     NEED_H;
     NOT_WHILE_ASYNC("calc_logp_chain");
     return h->calc_logp_chain(chain, pos, count, out);
+}
+int mcmcpp_hip_exchange_chains(mcmcpp_hip_sampler* h, uint64_t round, uint64_t* proposed, uint64_t* accepted, uint64_t* near_ties)
+{
+    NEED_H;
+    NOT_WHILE_ASYNC("exchange_chains");
+    return h->exchange_chains(round, proposed, accepted, near_ties);
 }
 int mcmcpp_hip_run(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step)
 {

@@ -1,0 +1,102 @@
+// replica_kernels.hpp -- the device side of a replica-exchange round (replica_plan.hpp): one launch decides and applies
+// every swap of the round.  The cross log-posteriors are there already (the calculator's own `calc` launches).
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "replica_plan.hpp"
+
+namespace mcmcpp
+{
+
+// [slot]{accepted, near ties}
+struct ReplicaCounts
+{
+    unsigned long long accepted, near_ties;
+};
+
+template <class T>
+struct ReplicaSwapArgs
+{
+    T* pos;                // [K][W][D]: the home rows
+    T* logp;               // chain 0's log-posteriors; chain k's lie logp_stride_bytes * k behind them
+    const T* cross;        // [slots][2][W]: logp_a(x_b), logp_b(x_a)
+    const ReplicaJump* table;  // replica_fill_table
+    ReplicaCounts* counts;     // [slots]
+    unsigned long long logp_stride_bytes;
+    int W, D, first_chain, lanes, units, vec_ok;
+    ReplicaU128 base[kReplicaMaxSlots];  // the engine state in front of each slot's first draw
+};
+
+// one swap launch for a whole round (defined in replica.hip, the kernel's only translation unit)
+void launch_replica_swap(const ReplicaSwapArgs<double>& a, const ReplicaShape& s, hipStream_t stream);
+void launch_replica_swap(const ReplicaSwapArgs<float>& a, const ReplicaShape& s, hipStream_t stream);
+
+#if defined(MCMCPP_DEFINE_REPLICA_KERNEL)
+struct alignas(16) ReplicaPiece
+{
+    uint32_t v[4];
+};
+
+template <class U>
+__device__ __forceinline__ void replica_swap_rows(U* a, U* b, int units, int sub, int lanes)
+{
+    for (int i = sub; i < units; i += lanes)
+    {
+        const U va = a[i], vb = b[i];
+        a[i] = vb;
+        b[i] = va;
+    }
+}
+
+// blockIdx.y: pair slot; a group of a.lanes lanes owns walker w of both chains of the pair (nobody else touches the two rows
+// or the two log-posteriors: the swap is race-free in place).  Every lane of a group repeats the group's decision: no
+// cross-lane traffic in front of the row loads.
+template <class T>
+__global__ void __launch_bounds__(kReplicaBlockThreads) replica_swap_kernel(const ReplicaSwapArgs<T> a)
+{
+    const int slot = (int)blockIdx.y;
+    const int lanes = a.lanes;
+    const int group = (int)threadIdx.x / lanes, sub = (int)threadIdx.x % lanes;
+    const long long w_ll = (long long)blockIdx.x * (kReplicaBlockThreads / lanes) + group;
+    const bool live = w_ll < (long long)a.W;
+    bool accept = false, tie = false;
+    if (live)
+    {
+        const int w = (int)w_ll;
+        const int ka = a.first_chain + 2 * slot, kb = ka + 1;
+        T* const lpa = reinterpret_cast<T*>(reinterpret_cast<char*>(a.logp) + (size_t)ka * a.logp_stride_bytes) + w;
+        T* const lpb = reinterpret_cast<T*>(reinterpret_cast<char*>(a.logp) + (size_t)kb * a.logp_stride_bytes) + w;
+        const T lp_ab = a.cross[((size_t)slot * 2 + 0) * (size_t)a.W + w];
+        const T lp_ba = a.cross[((size_t)slot * 2 + 1) * (size_t)a.W + w];
+        const uint64_t draw = replica_draw(a.table, a.base[slot], w);
+        accept = replica_accept(draw, (double)*lpa, (double)*lpb, (double)lp_ab, (double)lp_ba, &tie);
+        if (accept)
+        {
+            T* const xa = a.pos + ((size_t)ka * a.W + w) * (size_t)a.D;
+            T* const xb = a.pos + ((size_t)kb * a.W + w) * (size_t)a.D;
+            if (a.vec_ok)
+                replica_swap_rows(reinterpret_cast<ReplicaPiece*>(xa), reinterpret_cast<ReplicaPiece*>(xb), a.units, sub, lanes);
+            else
+                replica_swap_rows(xa, xb, a.units, sub, lanes);
+            if (sub == 0)
+            {
+                *lpa = lp_ab;
+                *lpb = lp_ba;
+            }
+        }
+    }
+    // counts: one lane per group votes, one lane per wavefront adds (integer sums: the order does not matter)
+    const unsigned long long acc_votes = __ballot(live && sub == 0 && accept);
+    const unsigned long long tie_votes = __ballot(live && sub == 0 && tie);
+    if ((threadIdx.x & 63u) == 0)
+    {
+        if (acc_votes) atomicAdd(&a.counts[slot].accepted, (unsigned long long)__popcll(acc_votes));
+        if (tie_votes) atomicAdd(&a.counts[slot].near_ties, (unsigned long long)__popcll(tie_votes));
+    }
+}
+
+#endif  // MCMCPP_DEFINE_REPLICA_KERNEL
+
+}  // namespace mcmcpp

@@ -71,6 +71,12 @@ struct mcmcpp_hip_sampler
     {
         return fail(MCMCPP_HIP_E_UNSUPPORTED, "calc_logp_chain: per-chain parameters are for stretch-move handles only (not differential evolution)");
     }
+    // one replica-exchange round among the chains of a handle (mcmcpp_hip_exchange_chains): the fused stretch-move sampler only
+    virtual int exchange_chains(uint64_t, uint64_t*, uint64_t*, uint64_t*)
+    {
+        return fail(MCMCPP_HIP_E_UNSUPPORTED,
+                    "exchange_chains: replica exchange is for stretch-move handles with a device calculator only (not the differential-evolution mover, not a batch target)");
+    }
     // stored steps and log-posteriors that stay in device memory (mcmcpp_hip_run_device, mcmcpp_hip_calc_logp_device): every
     // mover overrides both
     virtual int run_device(int64_t, int32_t, void*, uint32_t*) { return fail(MCMCPP_HIP_E_UNSUPPORTED, "run_device: not available for this handle"); }
