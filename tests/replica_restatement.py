@@ -38,31 +38,61 @@ def decide(draw, lp_aa, lp_bb, lp_ab, lp_ba, flip=False):
     return ln_u < delta, tie, ln_u, delta
 
 
+def _bits(a):
+    """an array of floats seen as unsigned integers of the same size: a swap is a move of bits (NaN payloads included)"""
+    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
+
+
+def swap_arrays(pos, logp, cross, first_chain, pairs, rnd, seed, stream=0, flip=False):
+    """The swap of one round on given cross evaluations.  pos [K][W][D] (floats or their integer views) and logp [K][W] (floats)
+    are edited in place; cross [pairs][2][W] (floats) holds logp_a(x_b) and logp_b(x_a) of slot j's chains a = first_chain + 2 j
+    and b = a + 1; slot j draws from position (rnd * 8 + j) * W on, whatever first_chain is.  Returns dict(accepted, near_ties: [pairs] counters; accept, tie: [pairs][W] flags;
+    draws: [pairs][W] raw outputs; in_band: the list of (slot, walker) decided inside the near-tie band)."""
+    W = logp.shape[1]
+    out = dict(accepted=np.zeros(pairs, np.uint64), near_ties=np.zeros(pairs, np.uint64), accept=np.zeros((pairs, W), bool), tie=np.zeros((pairs, W), bool),
+               draws=np.zeros((pairs, W), np.uint64), in_band=[])
+    pos_bits, logp_bits, cross_bits = _bits(pos), _bits(logp), _bits(cross)
+    for j in range(pairs):
+        a = first_chain + 2 * j
+        b = a + 1
+        g = po.Pcg64(seed, 2**64 - 1 - stream)
+        g.advance((rnd * SLOTS + j) * W)
+        for w in range(W):
+            draw = g.next()
+            acc, tie, _, _ = decide(draw, logp[a, w], logp[b, w], cross[j, 0, w], cross[j, 1, w], flip)
+            out["draws"][j, w], out["accept"][j, w], out["tie"][j, w] = draw, acc, tie
+            if tie:
+                out["near_ties"][j] += 1
+                out["in_band"].append((j, w))
+            if acc:
+                row = pos_bits[a, w].copy()
+                pos_bits[a, w] = pos_bits[b, w]
+                pos_bits[b, w] = row
+                logp_bits[a, w:w + 1] = cross_bits[j, 0, w:w + 1]
+                logp_bits[b, w:w + 1] = cross_bits[j, 1, w:w + 1]
+                out["accepted"][j] += 1
+    return out
+
+
 def exchange_arrays(pos, logp, cross_logp, rnd, seed, stream=0, flip=False):
     """One round on arrays: pos [K][W][D] and logp [K][W] are edited in place.  cross_logp(k, rows) -> chain k's
     log-posteriors of rows.  Returns dict(proposed, accepted, near_ties, in_band): [K-1] counters and the list of
-    (pair, walker) decided inside the near-tie band."""
+    (pair, walker) decided inside the near-tie band.  (The pairs of a round share no chain: all cross evaluations are made in
+    front of the swap, as the device makes them.)"""
     K, W = logp.shape
     out = dict(proposed=np.zeros(K - 1, np.uint64), accepted=np.zeros(K - 1, np.uint64), near_ties=np.zeros(K - 1, np.uint64), in_band=[])
-    for a, b in pairs_of(K, rnd):
-        j = a >> 1
-        g = po.Pcg64(seed, 2**64 - 1 - stream)
-        g.advance((rnd * SLOTS + j) * W)
-        lp_ab = cross_logp(a, pos[b])
-        lp_ba = cross_logp(b, pos[a])
+    chains = pairs_of(K, rnd)
+    if not chains:
+        return out
+    cross = np.stack([np.stack([cross_logp(a, pos[b]), cross_logp(b, pos[a])]) for a, b in chains]).astype(logp.dtype, copy=False)
+    first = chains[0][0]
+    assert first == rnd & 1 and [a for a, _ in chains] == [first + 2 * j for j in range(len(chains))]
+    r = swap_arrays(pos, logp, cross, first, len(chains), rnd, seed, stream, flip)
+    for j, (a, _) in enumerate(chains):
         out["proposed"][a] = W
-        for w in range(W):
-            acc, tie, _, _ = decide(g.next(), logp[a, w], logp[b, w], lp_ab[w], lp_ba[w], flip)
-            if tie:
-                out["near_ties"][a] += 1
-                out["in_band"].append((a, w))
-            if acc:
-                row = pos[a, w].copy()
-                pos[a, w] = pos[b, w]
-                pos[b, w] = row
-                logp[a, w] = lp_ab[w]
-                logp[b, w] = lp_ba[w]
-                out["accepted"][a] += 1
+        out["accepted"][a] = r["accepted"][j]
+        out["near_ties"][a] = r["near_ties"][j]
+    out["in_band"] = [(chains[j][0], w) for j, w in r["in_band"]]
     return out
 
 

@@ -35,17 +35,22 @@ def _ladder(calc, D, K, t=np.float64):
     raise ValueError(calc)
 
 
-def _pair(K, W, D, calc, dtype, seed, env, monkeypatch):
-    """(handle, restatement) of the same ladder in the same initial state"""
-    for key, v in env.items():
-        monkeypatch.setenv(key, v)
-    t = po.np_dtype(dtype)
-    params = _ladder(calc, D, K, t)
-    lad = rr.Ladder(W, D, calc, params, seed, dtype=dtype)
-    hip = capi.HipSampler(W, D, calc, np.stack(params), seed=seed, dtype=dtype, num_chains=K)
+def _restated(K, W, D, calc, dtype, seed, stream=0):
+    """(restatement in its initial state, that state, the ladder's parameters)"""
+    params = _ladder(calc, D, K, po.np_dtype(dtype))
+    lad = rr.Ladder(W, D, calc, params, seed, dtype=dtype, stream=stream)
     pos = np.stack([po.init_positions(dtype, W, D, salt=90 + k) for k in range(K)])
     logp = np.stack([lad.logp(k, pos[k]) for k in range(K)])
     lad.set_state(pos, logp)
+    return lad, pos, logp, params
+
+
+def _pair(K, W, D, calc, dtype, seed, env, monkeypatch, stream=0):
+    """(handle, restatement) of the same ladder in the same initial state"""
+    for key, v in env.items():
+        monkeypatch.setenv(key, v)
+    lad, pos, logp, params = _restated(K, W, D, calc, dtype, seed, stream)
+    hip = capi.HipSampler(W, D, calc, np.stack(params), seed=seed, stream=stream, dtype=dtype, num_chains=K)
     hip.set_state(pos, logp)
     return hip, lad
 
@@ -59,8 +64,7 @@ def _assert_same_state(hip, lad, what):
     assert int(nacc.sum()) == int(onacc.sum())
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("K,W,D,calc,dtype,env,rounds,steps", [
+ROUND_CASES = [
     (4, 600, 17, po.CALC_DENSE_GAUSSIAN, po.F64, {"MCMCPP_HIP_FULL_STEP": "1"}, 4, 3),
     (4, 600, 17, po.CALC_DENSE_GAUSSIAN, po.F64, {"MCMCPP_HIP_FULL_STEP": "0"}, 4, 3),
     (2, 2054, 32, po.CALC_DENSE_GAUSSIAN, po.F64, dict(_MC_ON, MCMCPP_HIP_FULL_STEP="1"), 4, 3),  # W no multiple of 64
@@ -70,14 +74,32 @@ def _assert_same_state(hip, lad, what):
     (4, 600, 9, po.CALC_DENSE_GAUSSIAN, po.F32, {}, 4, 3),  # rows of 36 bytes: no 16-byte pieces
     (2, 66, 1, po.CALC_DENSE_GAUSSIAN, po.F32, {}, 4, 3),  # rows of 4 bytes
     (2, 2050, 1024, po.CALC_ROSENBROCK, po.F64, {}, 1, 1),  # the longest rows: one round, one step in front of it
-])
-def test_exchange_rounds_equal_the_restatement(monkeypatch, K, W, D, calc, dtype, env, rounds, steps):
-    """set_state, then `rounds` times run(steps) and exchange_chains(r): after every exchange the state (positions,
-    log-posteriors, n_accept) equals the restatement's array for array, so do the per-pair counters, and so does a final
-    run(2).  The inputs are first checked on the restatement's own counts: every pair of every round accepts at least W/8
-    swaps and rejects at least W/8, and the f64 cases meet no near tie (so that Python's log against fast_log cannot be a
-    source of disagreement).  A decision inside the near-tie band (f32 cases only) is reported, not compared."""
-    hip, lad = _pair(K, W, D, calc, dtype, 40 + K, env, monkeypatch)
+]
+STREAM_CASE = (4, 320, 7, po.CALC_DENSE_GAUSSIAN, po.F64, {}, 4, 3)  # with STREAM, the handle's own
+STREAM = 2**63 + 5
+
+
+def _seed_of(K):
+    return 40 + K
+
+
+def test_the_fp32_cases_meet_no_decision_inside_the_near_tie_band():
+    """A condition on the inputs, from the restatement alone (CPU): with their seeds the fp32 cases of ROUND_CASES decide nothing
+    inside the near-tie band in any round, so test_exchange_rounds_equal_the_restatement compares every round and the final run
+    of theirs too.  (On the device the steps in front of a round are the restatement's bit for bit: that test asserts it.)"""
+    f32 = [c for c in ROUND_CASES if c[4] == po.F32]
+    assert [(c[0], c[1], c[2]) for c in f32] == [(4, 600, 9), (2, 66, 1)]
+    for K, W, D, calc, dtype, _, rounds, steps in f32:
+        lad = _restated(K, W, D, calc, dtype, _seed_of(K))[0]
+        for r in range(rounds):
+            lad.run(steps)
+            want = lad.exchange(r)
+            assert not want["in_band"] and not want["near_ties"].any(), (K, W, D, r, want["in_band"])
+            assert want["proposed"].sum() == W * len(rr.pairs_of(K, r))
+
+
+def _rounds_equal_the_restatement(monkeypatch, K, W, D, calc, dtype, env, rounds, steps, stream=0):
+    hip, lad = _pair(K, W, D, calc, dtype, _seed_of(K), env, monkeypatch, stream)
     for r in range(rounds):
         hc, ha = hip.run(steps)
         oc, oa = lad.run(steps)
@@ -90,11 +112,8 @@ def test_exchange_rounds_equal_the_restatement(monkeypatch, K, W, D, calc, dtype
             assert len(rr.pairs_of(K, r)) == (7 if r & 1 else 8)
         for a, _ in rr.pairs_of(K, r):  # a condition on the inputs
             assert W // 8 <= want["accepted"][a] <= W - W // 8, (r, a, want["accepted"][a])
-        if dtype == po.F64:
-            assert not want["near_ties"].any() and not got["near_ties"].any()
-        elif want["in_band"]:
-            print("decisions inside the near-tie band (not compared):", want["in_band"])
-            return
+        assert not want["in_band"], want["in_band"]  # a condition on the inputs (fp32: also asserted without a GPU, above)
+        assert not want["near_ties"].any() and not got["near_ties"].any()
         np.testing.assert_array_equal(got["proposed"], want["proposed"])
         np.testing.assert_array_equal(got["accepted"], want["accepted"])
         _assert_same_state(hip, lad, "after round %d" % r)
@@ -106,6 +125,26 @@ def test_exchange_rounds_equal_the_restatement(monkeypatch, K, W, D, calc, dtype
     assert c["redraws"] == 0
     if dtype == po.F64:
         assert c["near_ties"] == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K,W,D,calc,dtype,env,rounds,steps", ROUND_CASES)
+def test_exchange_rounds_equal_the_restatement(monkeypatch, K, W, D, calc, dtype, env, rounds, steps):
+    """set_state, then `rounds` times run(steps) and exchange_chains(r): after every exchange the state (positions,
+    log-posteriors, n_accept) equals the restatement's array for array, so do the per-pair counters, and so does a final
+    run(2).  The inputs are first checked on the restatement's own counts: every pair of every round accepts at least W/8
+    swaps and rejects at least W/8, and no case meets a decision inside the near-tie band of the exchange in any round (so
+    that Python's log against fast_log cannot be a source of disagreement): every round and the final run are compared in
+    every case, the fp32 ones included."""
+    _rounds_equal_the_restatement(monkeypatch, K, W, D, calc, dtype, env, rounds, steps)
+
+
+@pytest.mark.gpu
+def test_exchange_rounds_with_a_handle_stream_of_its_own(monkeypatch):
+    """The same with stream = 2^63 + 5 in the handle and in rr.Ladder: the steps draw from (seed + k, stream), the exchange from
+    (seed, 2^64 - 1 - stream), whose increment has a zero high word (replica_stream_of, replica_seed)."""
+    assert (((2**64 - 1 - STREAM) << 1) | 1) >> 64 == 0 and (((2**64 - 1) << 1) | 1) >> 64 == 1
+    _rounds_equal_the_restatement(monkeypatch, *STREAM_CASE, stream=STREAM)
 
 
 @pytest.mark.gpu
