@@ -34,6 +34,22 @@
 //
 // after which `calc_id = 1000` (or a host Calculator class whose hipCalcId is 1000) selects it.
 //
+// What the kernels promise the functor's hooks (tests/test_plugin_contract.py pins each line at every lane mapping of every
+// kernel family, with tests/cpp/plugin_contract.hip, a functor that uses all of it):
+//   - every hook (block_prefetch, block_commit, preload, eval) receives the chain's own parameter block: for a handle of
+//     several chains, the block given to mcmcpp_hip_set_chain_params for the chain the workgroup steps.
+//   - block_prefetch and block_commit are called once per launch by the `nthreads` updating threads of a workgroup, `tid` in
+//     [0, nthreads), in front of a workgroup barrier; a workgroup's extra (draw) wavefronts do not call them, they only join
+//     the barrier.  block_commit fills `scratch`, block_scratch_elems(D) elements of block-shared LDS; behind the barrier
+//     every lane reads the table through g.block_scratch (nullptr when block_scratch_elems(D) is 0).
+//   - preload is called once per launch and thread, eval possibly several times with the same Regs: the full-step kernel
+//     evaluates up to three proposals.  Regs is the place for what a lane reads from the block for each of them.
+//   - with kNeedsStage, g.publish(v) stores this lane's EPL values to wave-private LDS and g.element(j) then reads element j of
+//     the walker's published vector from any lane of its group; publish may be called again in the next eval.
+//   - a launch asks for stage + table bytes of dynamic LDS: 256 * EPL elements of stage when kNeedsStage, then the table.
+//     Keeping block_scratch_elems(D) * sizeof(T) within mcmcpp::kMaxBlockScratchBytes (calculators.hpp) is the author's
+//     obligation: nothing enforces it.
+//
 // An fp32 functor that takes a logarithm calls mcmcpp::glibc_logf (glibc_logf.hpp, included below) and its host twin the same
 // function through include/MCMCpp/Device/GlibcLogf.h: logf is one function on the host and another on the device.
 #pragma once

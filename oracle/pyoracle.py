@@ -19,6 +19,9 @@ F64, F32 = 0, 1
 CALC_ISO_GAUSSIAN, CALC_DENSE_GAUSSIAN, CALC_ROSENBROCK, CALC_SKEWED_GAUSSIAN_2D = 0, 1, 2, 3
 # test target only (stretch_oracle.h): the isotropic Gaussian inside |x_j| <= half_width, `outside` elsewhere; params = [half_width, outside]
 CALC_BOXED_ISO_GAUSSIAN = 100
+# test target only (stretch_oracle.h): the twin of tests/cpp/plugin_contract.hip, a Gaussian with nearest-neighbour and mirror
+# coupling; params = [mu[D], w[D], c[D], r]
+CALC_COUPLED_TABLE = 101
 MOVER_STRETCH, MOVER_DIFFERENTIAL_EVOLUTION = 0, 1
 MODE_SEQUENTIAL, MODE_COUNTER = 0, 1
 

@@ -215,6 +215,9 @@ static int check_cfg(const so_config* c)
     case SO_CALC_BOXED_ISO_GAUSSIAN:
         if (!c->calc_params || c->calc_params_len != 2) return -5;
         break;
+    case SO_CALC_COUPLED_TABLE:
+        if (!c->calc_params || c->calc_params_len != 3 * c->num_params + 1) return -5;
+        break;
     default: return -6;
     }
     return 0;

@@ -44,7 +44,13 @@ enum {
     /* Test target only, not a MCMCPP_HIP_CALC_* id: the isotropic Gaussian's value (same operation order, same bits)
      * where every |x_j| <= half_width, and `outside` verbatim elsewhere (-inf for a bounded prior; NaN and +inf to
      * test how the accept comparison treats them).                   params: half_width, outside */
-    SO_CALC_BOXED_ISO_GAUSSIAN = 100
+    SO_CALC_BOXED_ISO_GAUSSIAN = 100,
+    /* Test target only, not a MCMCPP_HIP_CALC_* id: the twin of the plug-in functor of tests/cpp/plugin_contract.hip, a
+     * Gaussian with nearest-neighbour and mirror coupling.  With d_j = x_j - mu_j, every operation rounded on its own:
+     *   a_j = w_j (d_j d_j),  b_j = c_j (d_j d_{j+1}) for j + 1 < D,  m_j = r (d_j d_{D-1-j}),
+     *   t_j = (a_j + b_j) + m_j  (a_j + m_j at j = D - 1),  logp = -1/2 tree_sum(t).
+     *                                                                params: mu[D], w[D], c[D], r  (3 D + 1) */
+    SO_CALC_COUPLED_TABLE = 101
 };
 
 /* how the random stream is walked */

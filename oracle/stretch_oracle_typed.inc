@@ -69,6 +69,26 @@ static REAL SFX(calc_logp)(int calc_id, int D, const REAL* prm, const REAL* x)
         for (int j = 0; j < D; ++j) t[j] = x[j] * x[j];
         return (REAL)-0.5 * SFX(tree_sum)(t, 0, n2, D);
     }
+    case SO_CALC_COUPLED_TABLE: {
+        /* test target: a Gaussian with nearest-neighbour and mirror coupling, prm = {mu[D], w[D], c[D], r}; every
+         * operation rounded on its own, in the order written (stretch_oracle.h) */
+        const REAL *mu = prm, *w = prm + D, *c = prm + 2 * (size_t)D;
+        const REAL r = prm[3 * (size_t)D];
+        for (int j = 0; j < D; ++j) {
+            const REAL d = x[j] - mu[j];
+            const REAL dm = x[D - 1 - j] - mu[D - 1 - j];
+            const REAL a = w[j] * (d * d);
+            const REAL m = r * (d * dm);
+            if (j + 1 < D) {
+                const REAL dn = x[j + 1] - mu[j + 1];
+                const REAL b = c[j] * (d * dn);
+                t[j] = (a + b) + m;
+            } else {
+                t[j] = a + m;
+            }
+        }
+        return (REAL)-0.5 * SFX(tree_sum)(t, 0, n2, D);
+    }
     default: return (REAL)0;
     }
 }
