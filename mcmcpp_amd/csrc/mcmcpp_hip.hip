@@ -1101,6 +1101,13 @@ public:
         if (save_slot >= 0 && (!bound_chain || save_slot >= bound_slots))
             return fail(MCMCPP_HIP_E_ARG, "half_step_async: save_slot outside the bound device chain");
         HIP_TRY(hipSetDevice(device));
+        // A run whose launches read records made ahead (fill_batch) leaves the two-buffer records where an earlier step put
+        // them: a step that starts here makes its own.  (Every other way to this point has left this step's records behind.)
+        if (color == 0 && plan.batch_draws > 0 && !(records_valid && records_step == (half_steps >> 1)))
+        {
+            const int rc = write_ctl(half_steps, 0);
+            if (rc) return rc;
+        }
         if (!run_info_idle)
         {
             const int rc = upload_idle_run_info();
