@@ -6,7 +6,7 @@
  * parameter blob).  All rungs are the chains of ONE handle, stepped by the same launches with the stretch move
  * (GwDistribution<ParamType, 2, 1>); after every `exchangeEvery` ensemble steps a replica-exchange round proposes to swap
  * walker w of rung k with walker w of rung k + 1 (mcmcpp_hip_exchange_chains, include/mcmcpp_hip.h: the rule, the random
- * stream and the numbering of rounds).  Rung k steps with seed randSeed + k, as a sampler of its own would.
+ * stream and the numbering of rounds; mcmcpp_hip_run_tempered puts the rounds into the run).  Rung k steps with seed randSeed + k, as a sampler of its own would.
  *
  * One host Chain per rung: the existing Analysis classes accept rung 0's chain (getStepIttBegin(0) / getStepIttEnd(0)) like
  * any other.  Device-memory chains are not offered here.
@@ -109,45 +109,37 @@ public:
     }
 
     /// numSteps more stored steps of every rung, with a replica-exchange round after every exchangeEvery of them (a tail shorter
-    /// than exchangeEvery runs without a trailing exchange).  Each segment costs a synchronisation.  False when a chain's byte
-    /// budget ran out first.
+    /// than exchangeEvery runs without a trailing exchange).  One mcmcpp_hip_run_tempered call: the rounds lie inside the run's
+    /// launch sequence.  False when a chain's byte budget ran out first (the steps that fit are run and stored).  The call's
+    /// stored steps of all rungs pass through one host staging vector on their way into the Chains.
     bool runMCMC(int numSteps, int exchangeEvery)
     {
         if (exchangeEvery < 1) throw std::invalid_argument("ReplicaExchangeSampler::runMCMC: exchangeEvery must be positive");
         upload();
+        if (numSteps < 1) return true;
         const std::size_t K = static_cast<std::size_t>(numRungs), cells = static_cast<std::size_t>(numWalkers) * numParams;
-        std::int64_t left = numSteps;
-        while (left > 0)
-        {
-            std::int64_t seg = left < exchangeEvery ? left : static_cast<std::int64_t>(exchangeEvery);
-            for (std::size_t k = 0; k < K; ++k)
-                if (chains[k]->remainingSteps() < seg) seg = chains[k]->remainingSteps();
-            if (seg < 1) return false;
-            segment.resize(K * static_cast<std::size_t>(seg) * cells);
-            handle.check("mcmcpp_hip_run", mcmcpp_hip_run(handle.get(), seg, 1, segment.data(), nullptr));
-            for (std::size_t k = 0; k < K; ++k)
-                for (std::int64_t s = 0; s < seg; ++s)
-                {
-                    const ParamType* step = &segment[(k * static_cast<std::size_t>(seg) + static_cast<std::size_t>(s)) * cells];
-                    for (int w = 0; w < numWalkers; ++w) chains[k]->storeWalker(w, step + static_cast<std::size_t>(w) * numParams);
-                    chains[k]->incrementChainStep();
-                }
-            left -= seg;
-            if (seg == exchangeEvery)
+        std::int64_t steps = numSteps;
+        for (std::size_t k = 0; k < K; ++k)
+            if (chains[k]->remainingSteps() < steps) steps = chains[k]->remainingSteps();
+        if (steps < 1) return false;
+        segment.resize(K * static_cast<std::size_t>(steps) * cells);
+        std::uint64_t proposed[16] = {0}, accepted[16] = {0}, rounds = 0;
+        handle.check("mcmcpp_hip_run_tempered",
+                     mcmcpp_hip_run_tempered(handle.get(), steps, 1, exchangeEvery, nextRound, segment.data(), nullptr, proposed, accepted, nullptr, &rounds));
+        for (std::size_t k = 0; k < K; ++k)
+            for (std::int64_t s = 0; s < steps; ++s)
             {
-                std::uint64_t proposed[16] = {0}, accepted[16] = {0};
-                handle.check("mcmcpp_hip_exchange_chains", mcmcpp_hip_exchange_chains(handle.get(), nextRound, proposed, accepted, nullptr));
-                for (std::size_t p = 0; p + 1 < K; ++p)
-                {
-                    swapProposed[p] += proposed[p];
-                    swapAccepted[p] += accepted[p];
-                }
-                ++nextRound;
+                const ParamType* step = &segment[(k * static_cast<std::size_t>(steps) + static_cast<std::size_t>(s)) * cells];
+                for (int w = 0; w < numWalkers; ++w) chains[k]->storeWalker(w, step + static_cast<std::size_t>(w) * numParams);
+                chains[k]->incrementChainStep();
             }
-            else if (left > 0)
-                return false;  // (a chain filled up inside a segment)
+        for (std::size_t p = 0; p + 1 < K; ++p)
+        {
+            swapProposed[p] += proposed[p];
+            swapAccepted[p] += accepted[p];
         }
-        return true;
+        nextRound += rounds;
+        return steps == numSteps;
     }
 
     int getStoredSteps() { return static_cast<int>(chains[0]->getStoredStepCount()); }

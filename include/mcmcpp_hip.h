@@ -352,6 +352,30 @@ int mcmcpp_hip_calc_logp_device(mcmcpp_hip_sampler* h, int32_t chain, const void
  * (16 W log-posteriors) outside the handle's step buffers. */
 int mcmcpp_hip_exchange_chains(mcmcpp_hip_sampler* h, uint64_t round, uint64_t* proposed, uint64_t* accepted, uint64_t* near_ties);
 
+/* A tempered run in one call: mcmcpp_hip_run (run_tempered_device: mcmcpp_hip_run_device) of n_saved * interval ensemble
+ * steps with a round of mcmcpp_hip_exchange_chains behind every exchange_every-th ensemble step, counted from the start of the
+ * run: rounds first_round, first_round + 1, ...  A run that ends on a multiple of exchange_every ends with a round; a shorter
+ * tail has none behind it.  exchange_every need not be a multiple of interval.  It computes, bit for bit, what the loop
+ * "run exchange_every steps, exchange_chains(round++)" computes -- chain, accepted_per_step, walker state, n_accept, the step
+ * streams, every counter -- but the rounds lie inside the run's launch sequence: two launches per round (the cross
+ * evaluations of all pairs, then the swaps), no host synchronisation, no copy between the segments.  The stored steps reach
+ * chain_out / device_chain by the paths of mcmcpp_hip_run / mcmcpp_hip_run_device, laid out as there; a stored step that is
+ * an exchange point holds the state in front of its round, as in the loop.
+ *   proposed/accepted/near_ties  [K-1] counters of pair (k, k+1), summed over the rounds of this run, overwritten
+ *   rounds_done                  the rounds of this run: n_saved * interval / exchange_every (the next run continues the same
+ *                                tempered run with first_round + *rounds_done when this run's length is a multiple of
+ *                                exchange_every)
+ * Any of the four and accepted_per_step may be NULL.  n_saved == 0 succeeds with zero rounds.  Refusals: those of
+ * mcmcpp_hip_run (run_tempered_device: mcmcpp_hip_run_device) and of mcmcpp_hip_exchange_chains with their codes;
+ * MCMCPP_HIP_E_ARG for exchange_every < 1 and for first_round + rounds > 2^40; MCMCPP_HIP_E_STATE while an asynchronous run is
+ * in progress.  The first tempered run allocates the scratch of a round (16 W log-posteriors) outside the step buffers. */
+int mcmcpp_hip_run_tempered(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, int64_t exchange_every, uint64_t first_round,
+                            void* chain_out, uint32_t* accepted_per_step, uint64_t* proposed, uint64_t* accepted, uint64_t* near_ties,
+                            uint64_t* rounds_done);
+int mcmcpp_hip_run_tempered_device(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, int64_t exchange_every,
+                                   uint64_t first_round, void* device_chain, uint32_t* accepted_per_step, uint64_t* proposed,
+                                   uint64_t* accepted, uint64_t* near_ties, uint64_t* rounds_done);
+
 /* ---- measurement ---------------------------------------------------------------------------------- */
 
 /* GPU time of the last mcmcpp_hip_run between HIP events recorded on the launch stream around the

@@ -31,6 +31,7 @@ EXPORTS = [
     "mcmcpp_hip_run_device", "mcmcpp_hip_run_device_async", "mcmcpp_hip_calc_logp_device", "mcmcpp_hip_moments_add_device_steps_strided",
     "mcmcpp_hip_half_step_async", "mcmcpp_hip_bind_device_chain", "mcmcpp_hip_device_positions",
     "mcmcpp_hip_shard_span", "mcmcpp_hip_synchronize", "mcmcpp_hip_exchange_chains",
+    "mcmcpp_hip_run_tempered", "mcmcpp_hip_run_tempered_device",
     "mcmcpp_hip_moments_create", "mcmcpp_hip_moments_destroy", "mcmcpp_hip_moments_reset", "mcmcpp_hip_moments_add_steps",
     "mcmcpp_hip_moments_add_device_steps", "mcmcpp_hip_moments_finish", "mcmcpp_hip_moments_last_error",
     "mcmcpp_hip_autocorr_times", "mcmcpp_hip_autocorr_times_device", "mcmcpp_hip_autocorr_last_error",
@@ -138,6 +139,9 @@ def lib():
         L.mcmcpp_hip_synchronize.argtypes = [vp]
         if hasattr(L, "mcmcpp_hip_exchange_chains"):  # (absent from earlier builds selected with MCMCPP_HIP_LIB)
             L.mcmcpp_hip_exchange_chains.argtypes = [vp, C.c_uint64, vp, vp, vp]
+        if hasattr(L, "mcmcpp_hip_run_tempered"):  # (likewise)
+            L.mcmcpp_hip_run_tempered.argtypes = [vp, i64, i32, i64, C.c_uint64, vp, vp, vp, vp, vp, u64p]
+            L.mcmcpp_hip_run_tempered_device.argtypes = [vp, i64, i32, i64, C.c_uint64, vp, vp, vp, vp, vp, u64p]
         if hasattr(L, "mcmcpp_hip_moments_create"):  # (absent only from older experiment builds selected with MCMCPP_HIP_LIB)
             L.mcmcpp_hip_moments_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
             L.mcmcpp_hip_moments_destroy.argtypes = [vp]
@@ -600,6 +604,28 @@ class HipSampler:
             import torch
             torch.cuda.current_stream(chain.device).synchronize()  # (the copies into `chain` are the caller's to rely on)
         return chain, acc, swaps, rnd
+
+    def run_tempered(self, n_saved, interval=1, exchange_every=1, first_round=0, out=None, device=False):
+        """run_exchanging in one call (mcmcpp_hip_run_tempered; device=True: mcmcpp_hip_run_tempered_device): the rounds lie
+        inside the run's launch sequence, two launches each, with no synchronisation and no copy between the segments.
+        exchange_every counts ensemble steps and need not be a multiple of interval.  Returns what run_exchanging returns,
+        bit for bit.  out: the array -- pageable or pinned_empty -- (device: tensor, or (address, nbytes)) to store into."""
+        K = self.K
+        acc = np.zeros((K, n_saved * interval), dtype=np.uint32)
+        v = [np.zeros(max(K - 1, 1), dtype=np.uint64) for _ in range(3)]
+        rounds = C.c_uint64(0)
+        if device:
+            ptr, chain = self._device_out(n_saved, out)
+            fn, dst = lib().mcmcpp_hip_run_tempered_device, C.c_void_p(ptr)
+        else:
+            shape = (K, n_saved, self.W, self.D)
+            if out is not None:
+                assert out.shape == shape and out.dtype == self.np_t and out.flags.c_contiguous
+            chain = out if out is not None else np.empty(shape, dtype=self.np_t)
+            fn, dst = lib().mcmcpp_hip_run_tempered, _ptr(chain)
+        self._check(fn(self.h, n_saved, interval, exchange_every, first_round, dst, _ptr(acc), *[_ptr(x) for x in v], C.byref(rounds)))
+        swaps = dict(proposed=v[0][:K - 1], accepted=v[1][:K - 1], near_ties=v[2][:K - 1])
+        return chain, acc, swaps, first_round + rounds.value
 
     def last_run_timing(self):
         ms, n = C.c_double(0), C.c_int64(0)

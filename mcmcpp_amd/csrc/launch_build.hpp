@@ -103,6 +103,16 @@ void launch_calc(const T* pos, T* out, const T* prm, long long count, int dims, 
                        count, dims, vec_ok);
 }
 
+// (grid: the walker blocks of one chain, as for launch_calc with count = W)
+template <class T, class Calc, int EPL, int LPW>
+void launch_replica_cross(const T* pos, T* cross, const T* prm, int params_chain_stride, int W, int dims, int vec_ok, int first_chain, int pairs, unsigned grid,
+                          hipStream_t st)
+{
+    const size_t lds = LdsLayout<T, Calc, EPL>::bytes(dims);
+    hipLaunchKernelGGL((replica_cross_kernel<T, Calc, EPL, LPW>), dim3(grid, (unsigned)(2 * pairs)), dim3(64 * kWavesPerBlock), lds, st, pos, cross, prm,
+                       params_chain_stride, W, dims, vec_ok, first_chain);
+}
+
 template <class T, class Calc, int EPL, int LPW>
 void launch_de(const typename LaunchTable<T>::DeLaunch& l, const DeArgs<T>& a, unsigned grid, hipStream_t st)
 {
@@ -139,6 +149,7 @@ void put(LaunchTable<T>& t)
     }
     t.calc[LPWLOG][EPLSHIFT] = &launch_calc<T, Calc, (kBase << EPLSHIFT), (1 << LPWLOG)>;
     t.de_update[LPWLOG][EPLSHIFT] = &launch_de<T, Calc, (kBase << EPLSHIFT), (1 << LPWLOG)>;
+    t.replica_cross[LPWLOG][EPLSHIFT] = &launch_replica_cross<T, Calc, (kBase << EPLSHIFT), (1 << LPWLOG)>;
 }
 
 // OnlyLpw1: only the single-lane mapping is meaningful (a fixed low-dimensional target such as D = 2)

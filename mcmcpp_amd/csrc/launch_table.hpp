@@ -14,7 +14,7 @@ namespace mcmcpp
 constexpr int kMaxEplShift = 4;
 constexpr int kLpwLevels = 7;  // LPW = 1,2,4,...,64
 
-constexpr uint32_t kLaunchTableAbi = 0x4D430019u;  // bumped whenever HalfStepArgs or the launcher signatures change
+constexpr uint32_t kLaunchTableAbi = 0x4D43001Au;  // bumped whenever HalfStepArgs or the launcher signatures change
 
 template <class T>
 struct LaunchTable
@@ -50,6 +50,11 @@ struct LaunchTable
     DeFn de_update[kLpwLevels][kMaxEplShift];
     // matrix-core variants (nullptr where the calculator has none): 8 ([0]) / 16 ([1]) walkers per wavefront, even D only
     DeFn de_update_mc[2][kLpwLevels][kMaxEplShift];
+    // the cross evaluations of a replica-exchange round inside a run (replica_cross_kernel): chain first_chain + 2 j's
+    // parameters on chain first_chain + 2 j + 1's rows and the other way round, for j in 0..pairs-1, into cross[pairs][2][W]
+    typedef void (*CrossFn)(const T* pos, T* cross, const T* params, int params_chain_stride, int W, int dims, int vec_ok, int first_chain, int pairs,
+                            unsigned grid, hipStream_t);
+    CrossFn replica_cross[kLpwLevels][kMaxEplShift];
 };
 
 // red_base != nullptr: black records, with partner2 (see DrawRec)

@@ -29,6 +29,7 @@
 #include "replica_kernels.hpp"
 #include "sampler_host.hpp"
 #include "split_exchange.hpp"
+#include "temper_plan.hpp"
 
 using namespace mcmcpp;
 
@@ -501,6 +502,7 @@ public:
         const ChainPlan cp = plan_chain(want, direct_stage != nullptr);
         int rc = ensure_run_buffers(cp.acc_entries, cp.half_bytes, cp.ring_bytes, cp.need_host_ring);
         if (rc) return rc;
+        if (tempering && (rc = prepare_tempering())) return rc;
         if ((rc = begin_run(cp.acc_entries, nullptr))) return rc;
         if ((rc = ensure_graphs())) return rc;
 
@@ -1042,23 +1044,7 @@ public:
         const int pairs = replica_pairs(K, round), k0 = replica_first_chain(round);
         if (pairs == 0) return MCMCPP_HIP_OK;
         HIP_TRY(hipSetDevice(device));
-        if (!d_replica_table)
-        {
-            // the exchange stream and its jump table: once per handle
-            replica_seed(cfg.seed, cfg.stream, &replica_state0, &replica_inc);
-            std::vector<ReplicaJump> t((size_t)replica_table_entries(W));
-            replica_fill_table(replica_inc, W, t.data());
-            DeviceBuffer<ReplicaJump> table;
-            DeviceBuffer<ReplicaCounts> counts;
-            DeviceBuffer<T> cross;
-            if (table.alloc(sizeof(ReplicaJump) * t.size()) != hipSuccess || counts.alloc(sizeof(ReplicaCounts) * kReplicaMaxSlots) != hipSuccess ||
-                cross.alloc(sizeof(T) * (size_t)kReplicaMaxSlots * 2 * (size_t)W) != hipSuccess)
-                return fail(MCMCPP_HIP_E_NOMEM, "exchange_chains: cannot allocate the scratch of a round (%zu bytes)", sizeof(T) * (size_t)kReplicaMaxSlots * 2 * (size_t)W);
-            HIP_TRY(hipMemcpy(table, t.data(), sizeof(ReplicaJump) * t.size(), hipMemcpyHostToDevice));
-            d_replica_table = std::move(table);
-            d_replica_counts = std::move(counts);
-            d_replica_cross = std::move(cross);
-        }
+        if (int rc = ensure_replica_scratch("exchange_chains")) return rc;
         const ReplicaShape shape = replica_shape(W, D, (int)sizeof(T), vec_ok, pairs);
         ReplicaSwapArgs<T> a;
         std::memset(&a, 0, sizeof a);
@@ -1090,6 +1076,36 @@ public:
             if (accepted) accepted[ka] = counts[j].accepted;
             if (near_ties) near_ties[ka] = counts[j].near_ties;
         }
+        return MCMCPP_HIP_OK;
+    }
+
+    // A run with its replica-exchange rounds inside the launch sequence (temper_plan.hpp has the schedule).  It is a run like
+    // any other -- run_entry, run_whole, whichever way the stored steps travel -- whose enqueue_steps cuts the step launches at
+    // the exchange points and puts a round's two launches there (enqueue_round).  The counters of the rounds stay on the device
+    // until the run is over.
+    int run_tempered(int64_t n_saved, int32_t interval, int64_t exchange_every, uint64_t first_round, void* chain, uint32_t* accepted_per_step,
+                     uint64_t* proposed, uint64_t* accepted, uint64_t* near_ties, uint64_t* rounds_done, bool to_device) override
+    {
+        if (int rc = chain_params_supported("run_tempered")) return rc;
+        TemperSchedule s = {};
+        s.total = n_saved > 0 && interval >= 1 ? n_saved * (int64_t)interval : 0;  // (bad arguments: the run refuses them below)
+        s.every = exchange_every, s.first_round = first_round, s.K = K;
+        const TemperRefusal refusal = temper_refusal(s);
+        if (refusal != TemperRefusal::None) return fail(MCMCPP_HIP_E_ARG, "run_tempered: %s", temper_refusal_text(refusal));
+        temper = s;
+        tempering = true;
+        const int rc = Host::run_entry(n_saved, interval, chain, accepted_per_step, to_device);
+        tempering = false;
+        if (rc) return rc;
+        ReplicaCounts counts[kMaxChains - 1] = {};
+        if (temper_rounds(s) > 0) HIP_TRY(hipMemcpy(counts, d_temper_counts, sizeof counts, hipMemcpyDeviceToHost));  // (the run has synchronised the stream)
+        for (int k = 0; k + 1 < K; ++k)
+        {
+            if (proposed) proposed[k] = (uint64_t)W * (uint64_t)temper_rounds_pairing(s, k);
+            if (accepted) accepted[k] = counts[k].accepted;
+            if (near_ties) near_ties[k] = counts[k].near_ties;
+        }
+        if (rounds_done) *rounds_done = (uint64_t)temper_rounds(s);
         return MCMCPP_HIP_OK;
     }
 
@@ -1152,6 +1168,63 @@ private:
         if (shard_count != n || shard_begin != 0) return fail(MCMCPP_HIP_E_UNSUPPORTED, "%s: not for a sharded handle", what);
         if (cfg.comm_world >= 1) return fail(MCMCPP_HIP_E_UNSUPPORTED, "%s: not for a handle with a communicator", what);
         if (!own_pos) return fail(MCMCPP_HIP_E_UNSUPPORTED, "%s: not for a handle with caller-owned positions", what);
+        return MCMCPP_HIP_OK;
+    }
+
+    // the exchange stream, its jump table and the scratch of a round: once per handle, by the first round or tempered run
+    int ensure_replica_scratch(const char* what)
+    {
+        if (d_replica_table) return MCMCPP_HIP_OK;
+        replica_seed(cfg.seed, cfg.stream, &replica_state0, &replica_inc);
+        std::vector<ReplicaJump> t((size_t)replica_table_entries(W));
+        replica_fill_table(replica_inc, W, t.data());
+        DeviceBuffer<ReplicaJump> table;
+        DeviceBuffer<ReplicaCounts> counts;
+        DeviceBuffer<T> cross;
+        if (table.alloc(sizeof(ReplicaJump) * t.size()) != hipSuccess || counts.alloc(sizeof(ReplicaCounts) * kReplicaMaxSlots) != hipSuccess ||
+            cross.alloc(sizeof(T) * (size_t)kReplicaMaxSlots * 2 * (size_t)W) != hipSuccess)
+            return fail(MCMCPP_HIP_E_NOMEM, "%s: cannot allocate the scratch of a round (%zu bytes)", what, sizeof(T) * (size_t)kReplicaMaxSlots * 2 * (size_t)W);
+        HIP_TRY(hipMemcpy(table, t.data(), sizeof(ReplicaJump) * t.size(), hipMemcpyHostToDevice));
+        d_replica_table = std::move(table);
+        d_replica_counts = std::move(counts);
+        d_replica_cross = std::move(cross);
+        return MCMCPP_HIP_OK;
+    }
+
+    // in front of the first launch of a tempered run: the scratch of its rounds, the run's counters zeroed
+    int prepare_tempering()
+    {
+        static_assert(kReplicaMaxSlots * 2 == kMaxChains, "a round has a slot for every second chain");
+        if (int rc = ensure_replica_scratch("run_tempered")) return rc;
+        if (!d_temper_counts && d_temper_counts.alloc(sizeof(ReplicaCounts) * (kMaxChains - 1)) != hipSuccess)
+            return fail(MCMCPP_HIP_E_NOMEM, "run_tempered: cannot allocate the counters of the rounds");
+        cross_fn = table->replica_cross[ilog2(lpw)][ilog2(epl / Vec16<T>::N)];
+        if (!cross_fn) return fail(MCMCPP_HIP_E_UNSUPPORTED, "run_tempered: no cross-evaluation kernel for D=%d with this calculator", D);
+        HIP_TRY(hipMemsetAsync(d_temper_counts, 0, sizeof(ReplicaCounts) * (kMaxChains - 1), stream));
+        return MCMCPP_HIP_OK;
+    }
+
+    // Round `round` behind the steps enqueued so far: the cross evaluations of all its pairs in one launch, the swaps in another,
+    // on the position buffer and the log-posterior half that hold the ensemble now (ensemble_in_alt)
+    int enqueue_round(uint64_t round)
+    {
+        const int pairs = replica_pairs(K, round), k0 = replica_first_chain(round);
+        if (pairs == 0) return MCMCPP_HIP_OK;
+        const bool alt = ensemble_in_alt();
+        const ReplicaShape shape = replica_shape(W, D, (int)sizeof(T), vec_ok, pairs);
+        ReplicaSwapRunArgs<T> a;
+        std::memset(&a, 0, sizeof a);
+        a.pos = alt ? d_pos_alt : d_pos, a.logp = d_logp + (alt ? W : 0);
+        a.cross = d_replica_cross, a.table = d_replica_table, a.counts = d_temper_counts;
+        a.logp_stride_bytes = logp_chain_stride_bytes<T>(n);
+        a.nacc_behind_logp_bytes = sizeof(T) * (size_t)(alt ? W : 2 * W);  // (nacc_of(k) = logp_of(k) + 2 W)
+        a.moved_bit = full_fn ? kRowMovedBit : 0u;
+        a.W = W, a.D = D, a.first_chain = k0, a.lanes = shape.lanes, a.units = shape.units, a.vec_ok = vec_ok;
+        for (int j = 0; j < pairs; ++j) a.base[j] = replica_slot_base(replica_state0, replica_inc, round, j, W);
+        const long long per_block = (long long)(64 / lpw) * kWavesPerBlock;
+        cross_fn(a.pos, d_replica_cross, d_params, chain_params_stride, W, D, vec_ok, k0, pairs, (unsigned)((W + per_block - 1) / per_block), stream);
+        launch_replica_swap_run(a, shape, stream);
+        HIP_TRY(hipGetLastError());
         return MCMCPP_HIP_OK;
     }
 
@@ -1368,8 +1441,24 @@ private:
     // full-step launches alternate with the position buffers
     const StepCtl* ctl_after(int64_t pos_parity_after) const { return d_ctl + (full_fn ? (pos_parity_after & 1) : 0); }
 
-    // enqueue `steps` ensemble steps on the launch stream (graph replays, or plain launches when graphs are off)
+    // enqueue `steps` ensemble steps on the launch stream; a tempered run: in pieces that end at the exchange points, each
+    // followed by its round (plain launches between the replays)
     int enqueue_steps(int64_t steps)
+    {
+        if (!tempering) return enqueue_step_launches(steps);
+        while (steps > 0)
+        {
+            const TemperPiece piece = temper_next_piece(temper, (int64_t)run_step, steps);
+            if (int rc = enqueue_step_launches(piece.steps)) return rc;
+            if (piece.round_follows)
+                if (int rc = enqueue_round(piece.round)) return rc;
+            steps -= piece.steps;
+        }
+        return MCMCPP_HIP_OK;
+    }
+
+    // `steps` ensemble steps: graph replays, or plain launches when graphs are off
+    int enqueue_step_launches(int64_t steps)
     {
         // enq_step: ensemble steps enqueued since set_state/seek (its low bit selects the record buffer)
         int64_t left = steps;
@@ -1479,6 +1568,12 @@ private:
     DeviceBuffer<ReplicaJump> d_replica_table;
     DeviceBuffer<ReplicaCounts> d_replica_counts;
     ReplicaU128 replica_state0 = {}, replica_inc = {};
+    // a tempered run (run_tempered): its schedule while it is in hand, the counters of its rounds [K - 1], the launcher of the
+    // cross evaluations
+    bool tempering = false;
+    TemperSchedule temper = {};
+    DeviceBuffer<ReplicaCounts> d_temper_counts;
+    typename LaunchTable<T>::CrossFn cross_fn = nullptr;
     // a rank of a split ensemble: the communicator and everything only split runs use (declared last: it goes first, the
     // communicator in front of every buffer)
     SplitExchange<T> xchg;
@@ -1650,6 +1745,20 @@ int mcmcpp_hip_exchange_chains(mcmcpp_hip_sampler* h, uint64_t round, uint64_t* 
     NEED_H;
     NOT_WHILE_ASYNC("exchange_chains");
     return h->exchange_chains(round, proposed, accepted, near_ties);
+}
+int mcmcpp_hip_run_tempered(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, int64_t exchange_every, uint64_t first_round, void* chain_out,
+                            uint32_t* accepted_per_step, uint64_t* proposed, uint64_t* accepted, uint64_t* near_ties, uint64_t* rounds_done)
+{
+    NEED_H;
+    NOT_WHILE_ASYNC("run_tempered");
+    return h->run_tempered(n_saved, interval, exchange_every, first_round, chain_out, accepted_per_step, proposed, accepted, near_ties, rounds_done, false);
+}
+int mcmcpp_hip_run_tempered_device(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, int64_t exchange_every, uint64_t first_round, void* device_chain,
+                                   uint32_t* accepted_per_step, uint64_t* proposed, uint64_t* accepted, uint64_t* near_ties, uint64_t* rounds_done)
+{
+    NEED_H;
+    NOT_WHILE_ASYNC("run_tempered_device");
+    return h->run_tempered(n_saved, interval, exchange_every, first_round, device_chain, accepted_per_step, proposed, accepted, near_ties, rounds_done, true);
 }
 int mcmcpp_hip_run(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step)
 {

@@ -1,5 +1,6 @@
 // replica_kernels.hpp -- the device side of a replica-exchange round (replica_plan.hpp): one launch decides and applies
-// every swap of the round.  The cross log-posteriors are there already (the calculator's own `calc` launches).
+// every swap of the round.  The cross log-posteriors are there already (the calculator's own `calc` launches; inside a tempered
+// run, replica_cross_kernel of stretch_kernel.hpp).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -32,6 +33,24 @@ struct ReplicaSwapArgs
 // one swap launch for a whole round (defined in replica.hip, the kernel's only translation unit)
 void launch_replica_swap(const ReplicaSwapArgs<double>& a, const ReplicaShape& s, hipStream_t stream);
 void launch_replica_swap(const ReplicaSwapArgs<float>& a, const ReplicaShape& s, hipStream_t stream);
+
+// A round inside a run (replica_swap_run_kernel): the buffers that hold the ensemble at that point of the run
+template <class T>
+struct ReplicaSwapRunArgs
+{
+    T* pos;                    // [K][W][D]: the position buffer in use
+    T* logp;                   // chain 0's log-posteriors in use; chain k's lie logp_stride_bytes * k behind them
+    const T* cross;            // [slots][2][W]: logp_a(x_b), logp_b(x_a) (replica_cross_kernel)
+    const ReplicaJump* table;  // replica_fill_table
+    ReplicaCounts* counts;     // [K - 1], by the lower chain of a pair: summed over the rounds of the run
+    unsigned long long logp_stride_bytes;
+    unsigned long long nacc_behind_logp_bytes;  // from a chain's `logp` to its n_accept
+    uint32_t moved_bit;        // set in n_accept[w] of both chains for a swapped walker w (0: nothing is set)
+    int W, D, first_chain, lanes, units, vec_ok;
+    ReplicaU128 base[kReplicaMaxSlots];  // the engine state in front of each slot's first draw
+};
+void launch_replica_swap_run(const ReplicaSwapRunArgs<double>& a, const ReplicaShape& s, hipStream_t stream);
+void launch_replica_swap_run(const ReplicaSwapRunArgs<float>& a, const ReplicaShape& s, hipStream_t stream);
 
 #if defined(MCMCPP_DEFINE_REPLICA_KERNEL)
 struct alignas(16) ReplicaPiece
@@ -94,6 +113,64 @@ __global__ void __launch_bounds__(kReplicaBlockThreads) replica_swap_kernel(cons
     {
         if (acc_votes) atomicAdd(&a.counts[slot].accepted, (unsigned long long)__popcll(acc_votes));
         if (tie_votes) atomicAdd(&a.counts[slot].near_ties, (unsigned long long)__popcll(tie_votes));
+    }
+}
+
+// The round of a tempered run (temper_plan.hpp): the same decision, draw and row swap, applied in the middle of a run to the
+// buffers that hold the ensemble at that point.  A swapped walker's row in the other position buffer of the full-step kernels
+// is then out of date: the walker gets moved_bit (kRowMovedBit; 0 with half-step kernels, which have one buffer) in both
+// chains' n_accept, and the next launch writes the row whatever it decides.  Counts are summed per lower chain of a pair over
+// all rounds of the run.
+template <class T>
+__global__ void __launch_bounds__(kReplicaBlockThreads) replica_swap_run_kernel(const ReplicaSwapRunArgs<T> a)
+{
+    const int slot = (int)blockIdx.y;
+    const int lanes = a.lanes;
+    const int group = (int)threadIdx.x / lanes, sub = (int)threadIdx.x % lanes;
+    const long long w_ll = (long long)blockIdx.x * (kReplicaBlockThreads / lanes) + group;
+    const bool live = w_ll < (long long)a.W;
+    const int ka = a.first_chain + 2 * slot, kb = ka + 1;
+    bool accept = false, tie = false;
+    if (live)
+    {
+        const int w = (int)w_ll;
+        char* const mine_a = reinterpret_cast<char*>(a.logp) + (size_t)ka * a.logp_stride_bytes;
+        char* const mine_b = reinterpret_cast<char*>(a.logp) + (size_t)kb * a.logp_stride_bytes;
+        T* const lpa = reinterpret_cast<T*>(mine_a) + w;
+        T* const lpb = reinterpret_cast<T*>(mine_b) + w;
+        const T lp_ab = a.cross[((size_t)slot * 2 + 0) * (size_t)a.W + w];
+        const T lp_ba = a.cross[((size_t)slot * 2 + 1) * (size_t)a.W + w];
+        const uint64_t draw = replica_draw(a.table, a.base[slot], w);
+        accept = replica_accept(draw, (double)*lpa, (double)*lpb, (double)lp_ab, (double)lp_ba, &tie);
+        if (accept)
+        {
+            T* const xa = a.pos + ((size_t)ka * a.W + w) * (size_t)a.D;
+            T* const xb = a.pos + ((size_t)kb * a.W + w) * (size_t)a.D;
+            if (a.vec_ok)
+                replica_swap_rows(reinterpret_cast<ReplicaPiece*>(xa), reinterpret_cast<ReplicaPiece*>(xb), a.units, sub, lanes);
+            else
+                replica_swap_rows(xa, xb, a.units, sub, lanes);
+            if (sub == 0)
+            {
+                *lpa = lp_ab;
+                *lpb = lp_ba;
+                if (a.moved_bit)
+                {
+                    // (n_accept lies a.nacc_behind_logp_bytes behind the chain's log-posteriors in use: ChainGeometry)
+                    uint32_t* const na = reinterpret_cast<uint32_t*>(mine_a + a.nacc_behind_logp_bytes) + w;
+                    uint32_t* const nb = reinterpret_cast<uint32_t*>(mine_b + a.nacc_behind_logp_bytes) + w;
+                    *na |= a.moved_bit;
+                    *nb |= a.moved_bit;
+                }
+            }
+        }
+    }
+    const unsigned long long acc_votes = __ballot(live && sub == 0 && accept);
+    const unsigned long long tie_votes = __ballot(live && sub == 0 && tie);
+    if ((threadIdx.x & 63u) == 0)
+    {
+        if (acc_votes) atomicAdd(&a.counts[ka].accepted, (unsigned long long)__popcll(acc_votes));
+        if (tie_votes) atomicAdd(&a.counts[ka].near_ties, (unsigned long long)__popcll(tie_votes));
     }
 }
 

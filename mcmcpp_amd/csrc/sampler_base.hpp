@@ -77,6 +77,12 @@ struct mcmcpp_hip_sampler
         return fail(MCMCPP_HIP_E_UNSUPPORTED,
                     "exchange_chains: replica exchange is for stretch-move handles with a device calculator only (not the differential-evolution mover, not a batch target)");
     }
+    // a run with the rounds inside its launch sequence (mcmcpp_hip_run_tempered, mcmcpp_hip_run_tempered_device): likewise
+    virtual int run_tempered(int64_t, int32_t, int64_t, uint64_t, void*, uint32_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, bool)
+    {
+        return fail(MCMCPP_HIP_E_UNSUPPORTED,
+                    "run_tempered: replica exchange is for stretch-move handles with a device calculator only (not the differential-evolution mover, not a batch target)");
+    }
     // stored steps and log-posteriors that stay in device memory (mcmcpp_hip_run_device, mcmcpp_hip_calc_logp_device): every
     // mover overrides both
     virtual int run_device(int64_t, int32_t, void*, uint32_t*) { return fail(MCMCPP_HIP_E_UNSUPPORTED, "run_device: not available for this handle"); }

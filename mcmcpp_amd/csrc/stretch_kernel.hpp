@@ -1417,10 +1417,9 @@ accepted_reduce_kernel(const uint32_t* partials, int partial_slots, int partial_
 }
 #endif
 
-// Calculator evaluated on arbitrary rows (mcmcpp_hip_calc_logp): same functor, same lane mapping.
+// The calculator on `count` rows, one workgroup's share (blockIdx.x): the body of the two kernels below.
 template <class T, class Calc, int EPL, int LPW>
-__global__ void __launch_bounds__(64 * kWavesPerBlock)
-calc_logp_kernel(const T* pos, T* out, const T* calc_params, long long count, int dims, int vec_ok)
+__device__ __forceinline__ void calc_logp_rows(const T* pos, T* out, const T* calc_params, long long count, int dims, int vec_ok)
 {
     constexpr int WPP = 64 / LPW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1450,6 +1449,31 @@ calc_logp_kernel(const T* pos, T* out, const T* calc_params, long long count, in
     Calc::template preload<EPL, LPW>(ctx, calc_params, cregs);
     const T lp = Calc::template eval<EPL, LPW>(ctx, calc_params, cregs, x);
     if (active && sub == 0) out[w] = lp;
+}
+
+// Calculator evaluated on arbitrary rows (mcmcpp_hip_calc_logp): same functor, same lane mapping.
+template <class T, class Calc, int EPL, int LPW>
+__global__ void __launch_bounds__(64 * kWavesPerBlock)
+calc_logp_kernel(const T* pos, T* out, const T* calc_params, long long count, int dims, int vec_ok)
+{
+    calc_logp_rows<T, Calc, EPL, LPW>(pos, out, calc_params, count, dims, vec_ok);
+}
+
+// The cross evaluations of a replica-exchange round inside a run (temper_plan.hpp), all pairs in one launch.  blockIdx.y = 2 j:
+// chain a = first_chain + 2 j's parameters on chain b = a + 1's rows, into cross[j][0][.]; 2 j + 1: chain b's parameters on
+// chain a's rows, into cross[j][1][.].  `pos` [chains][W][dims] is the position buffer that holds the ensemble; the parameter
+// row is chosen as the multi-chain step kernels choose it (params_chain_stride 0: shared).  A workgroup evaluates for ONE
+// chain, whose block the calculator's hooks receive (the plug-in contract), through calc_logp_kernel's own lines: the values
+// are that kernel's bit for bit.
+template <class T, class Calc, int EPL, int LPW>
+__global__ void __launch_bounds__(64 * kWavesPerBlock)
+replica_cross_kernel(const T* pos, T* cross, const T* calc_params, int params_chain_stride, int W, int dims, int vec_ok, int first_chain)
+{
+    const int j = (int)(blockIdx.y >> 1), dir = (int)(blockIdx.y & 1u);
+    const int ka = first_chain + 2 * j, kb = ka + 1;
+    const int params_chain = dir ? kb : ka, rows_chain = dir ? ka : kb;
+    calc_logp_rows<T, Calc, EPL, LPW>(pos + (size_t)rows_chain * (size_t)W * (size_t)dims, cross + (size_t)blockIdx.y * (size_t)W,
+                                      calc_params + (size_t)params_chain * (size_t)params_chain_stride, (long long)W, dims, vec_ok);
 }
 
 }  // namespace mcmcpp
