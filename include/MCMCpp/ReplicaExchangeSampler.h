@@ -10,6 +10,9 @@
  *
  * One host Chain per rung: the existing Analysis classes accept rung 0's chain (getStepIttBegin(0) / getStepIttEnd(0)) like
  * any other.  Device-memory chains are not offered here.
+ *
+ * evidenceRatios() estimates the ratios of normalising constants between neighbouring rungs from the stored steps
+ * (mcmcpp_hip_evidence_ratios): their chain is the evidence of rung 0 when the top rung is a normalised density.
  */
 #ifndef MCMCPP_REPLICAEXCHANGESAMPLER_H
 #define MCMCPP_REPLICAEXCHANGESAMPLER_H
@@ -29,6 +32,19 @@
 
 namespace MCMC
 {
+
+/// What ReplicaExchangeSampler::evidenceRatios returns (mcmcpp_hip_evidence_ratios, include/mcmcpp_hip.h): every vector is
+/// [2][numRungs - 1], direction-major -- at(d, p): d = 0 the stepping-stone direction (draws of the flatter rung p + 1), d = 1 the
+/// reverse; both estimate log(Z_p / Z_{p+1}).
+struct EvidenceRatios
+{
+    int numPairs;
+    std::int64_t numDraws;  ///< draws per rung: used steps times walkers
+    std::vector<double> logRatio, mcse, ess, kish, maxU;
+    std::vector<std::int64_t> nonfinite;
+    double logRatioTotal[2], mcseTotal[2];  ///< log(Z_0 / Z_{numRungs-1}) by each direction, and its standard error
+    std::size_t at(int direction, int pair) const { return static_cast<std::size_t>(direction) * static_cast<std::size_t>(numPairs) + static_cast<std::size_t>(pair); }
+};
 
 template <class ParamType, class Calculator>
 class ReplicaExchangeSampler
@@ -171,6 +187,39 @@ public:
     }
     /// Rounds done so far; the next round has this number.
     std::uint64_t getExchangeRounds() const { return nextRound; }
+
+    /// The ratios of normalising constants between neighbouring rungs, from every sliceInterval'th stored step of every rung
+    /// behind the first burnIn (the initial placement is stored step 0), through the host-pointer entry.  At least four used
+    /// steps; the walker state is not touched.
+    EvidenceRatios evidenceRatios(int burnIn = 0, int sliceInterval = 1)
+    {
+        if (burnIn < 0 || sliceInterval < 1) throw std::invalid_argument("ReplicaExchangeSampler::evidenceRatios: burnIn >= 0 and sliceInterval >= 1");
+        const std::size_t K = static_cast<std::size_t>(numRungs);
+        std::vector<const void*> steps;
+        std::int64_t used = 0;
+        for (std::size_t k = 0; k < K; ++k)
+        {
+            StepItt itt = chains[k]->getStepIteratorBegin(), end = chains[k]->getStepIteratorEnd();
+            std::int64_t index = 0, mine = 0;
+            for (; itt != end; ++itt, ++index)
+                if (index >= burnIn && (index - burnIn) % sliceInterval == 0)
+                {
+                    steps.push_back(*itt);
+                    ++mine;
+                }
+            if (k > 0 && mine != used) throw std::logic_error("ReplicaExchangeSampler::evidenceRatios: the rungs hold different numbers of steps");
+            used = mine;
+        }
+        EvidenceRatios r;
+        r.numPairs = numRungs - 1;
+        r.numDraws = 0;
+        const std::size_t outs = 2 * (K - 1);
+        r.logRatio.resize(outs), r.mcse.resize(outs), r.ess.resize(outs), r.kish.resize(outs), r.maxU.resize(outs), r.nonfinite.resize(outs);
+        handle.check("mcmcpp_hip_evidence_ratios",
+                     mcmcpp_hip_evidence_ratios(handle.get(), steps.empty() ? nullptr : steps.data(), used, 1, r.logRatio.data(), r.mcse.data(), r.ess.data(),
+                                                r.kish.data(), r.maxU.data(), r.nonfinite.data(), r.logRatioTotal, r.mcseTotal, &r.numDraws));
+        return r;
+    }
 
     /// Walker positions [K][W][D], log-posteriors [K][W] and per-walker accepted counts [K][W] as they stand on the device.
     void currentState(ParamType* positions, ParamType* logp, std::uint32_t* nAccept)

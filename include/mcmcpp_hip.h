@@ -376,6 +376,55 @@ int mcmcpp_hip_run_tempered_device(mcmcpp_hip_sampler* h, int64_t n_saved, int32
                                    uint64_t first_round, void* device_chain, uint32_t* accepted_per_step, uint64_t* proposed,
                                    uint64_t* accepted, uint64_t* near_ties, uint64_t* rounds_done);
 
+/* ---- evidence from a ladder: ratios of normalising constants between neighbouring chains ----------------- */
+
+/* A handle has K = num_chains >= 2 rungs (chains with per-chain parameters); Z_k = integral of exp(logp_k) is the normalising
+ * constant of rung k's target.  From stored steps of the K chains -- a tempered run's, or any draws of the rungs -- the call
+ * estimates log(Z_p / Z_{p+1}) of every pair of neighbours by importance weights, in both directions.  The chain of the
+ * ratios is the evidence of rung 0 only when the top rung is a normalised density (its Z is 1, or known).
+ *   draws      n used steps per rung (every slice_interval-th of n_steps, from the first on), N = n W draws per rung in the
+ *              order i = s W + w.  Pair p is the rungs (a, b) = (p, p + 1), 0 <= p < K - 1.  Direction d = 0, the stepping-stone
+ *              direction, takes the draws x_i of rung b (the flatter one): u_i = logp_a(x_i) - logp_b(x_i).  Direction d = 1,
+ *              the reverse, takes the draws of rung a: u_i = logp_b(x_i) - logp_a(x_i).  Every output is [2][K - 1], d-major.
+ *   logp       the two log-posteriors of a draw are what mcmcpp_hip_calc_logp_device returns for that row with that chain's
+ *              parameters, bit for bit, in the handle's dtype, widened to double exactly; u is one double subtraction.
+ *   nonfinite  counts the i whose u_i is not finite.  If any u_i is NaN or +inf, then log_ratio, mcse, ess, kish and max_u are
+ *              NaN for that (d, p) and for nothing else.  A u_i of -inf (a draw outside the other rung's support) has weight 0.
+ *   estimate   m = max u_i (of -0 and +0, +0); e_i = evidence_exp(u_i - m) (mcmcpp_amd/csrc/evidence_exp.hpp: exp with one
+ *              value in bits; evidence_exp(0) = 1, evidence_exp(-inf) = 0); S1 = sum_fixed(e), S2 = sum_fixed(e e) over i, with
+ *              sum_fixed the shape of mcmcpp_hip_gelman_rubin (slices of rhat_slice_len(N) terms); wbar = S1 / N, a positive
+ *              normal number since 1/N <= wbar <= 1; lme = m + normal_score_log(wbar) (normal_score.hpp's logarithm).
+ *              log_ratio[0][p] = lme, log_ratio[1][p] = -lme: both estimate log(Z_p / Z_{p+1}).  max_u = m.  If every u_i is
+ *              -inf: lme = -inf (log_ratio[1][p] = +inf), and mcse, ess and kish are NaN.
+ *   kish       (S1 S1) / S2, Kish's size of the weights.  rel2 = max(S2 / N - wbar wbar, 0) / (wbar wbar).
+ *   ess        the `ess` output of mcmcpp_hip_effective_sample_size_device on the weights e seen as a chain of one rung: n
+ *              steps, W walkers, one parameter, fp64, split = 1, max_lag = 0 (that call's own body, so its bits): n >= 4.
+ *   mcse       0 when rel2 == 0 (constant weights), else sqrt(rel2 / ess): the standard error of lme.
+ *   totals     log_ratio_total[d] = the sum of log_ratio[d][.] in ascending p from +0: log(Z_0 / Z_{K-1});
+ *              mcse_total[d] = sqrt(the sum of mcse mcse in ascending p from +0).
+ * Everything is fp64, every + - * / rounded on its own; no fused operation, no floating-point atomic.  No output depends on
+ * the CU count, the chunk size (MCMCPP_HIP_EVIDENCE_CHUNK_MB, read per call, default 1024: host steps are uploaded, and rows
+ * evaluated, a chunk at a time) or where a chain lies.
+ *   steps         K * n_steps host pointers to steps [W][D] of the handle's dtype, rung k's step s at steps[k * n_steps + s]
+ *   device_steps  the chains in memory of the handle's device, laid out as for mcmcpp_hip_gelman_rubin_device: rung k's step s
+ *                 at device_steps + (k * chain_stride_steps + s) * W * D elements; chain_stride_steps 0: n_steps.  Read where
+ *                 they lie; the rows must satisfy mcmcpp_hip_calc_logp_device's alignment rule.
+ *   outputs       log_ratio, mcse, ess, kish, max_u [2][K-1] double; nonfinite [2][K-1] int64; log_ratio_total, mcse_total [2];
+ *                 *num_draws = N.  Any may be NULL.  Nothing is written to the outputs of a call that fails.
+ * The call reads the calculators only: it needs no set_state, and leaves the walker state, the step streams and every counter
+ * as they are.  The weights take 8 N bytes of device memory per (d, p) in flight (two at most), freed when the call returns:
+ * MCMCPP_HIP_E_NOMEM with a message where they cannot be had.  Returns MCMCPP_HIP_E_UNSUPPORTED for the differential-evolution
+ * mover, batch targets, sharded handles, handles with a communicator and handles with caller-owned positions;
+ * MCMCPP_HIP_E_ARG for num_chains < 2, fewer than 4 used steps, slice_interval < 1, 0 < chain_stride_steps < n_steps, NULL steps,
+ * a device pointer that is not memory of the handle's device or whose chains end outside its allocation; MCMCPP_HIP_E_STATE
+ * while an asynchronous run is in progress. */
+int mcmcpp_hip_evidence_ratios(mcmcpp_hip_sampler* h, const void* const* steps, int64_t n_steps, int64_t slice_interval, double* log_ratio,
+                               double* mcse, double* ess, double* kish, double* max_u, int64_t* nonfinite, double* log_ratio_total,
+                               double* mcse_total, int64_t* num_draws);
+int mcmcpp_hip_evidence_ratios_device(mcmcpp_hip_sampler* h, const void* device_steps, int64_t chain_stride_steps, int64_t n_steps,
+                                      int64_t slice_interval, double* log_ratio, double* mcse, double* ess, double* kish, double* max_u,
+                                      int64_t* nonfinite, double* log_ratio_total, double* mcse_total, int64_t* num_draws);
+
 /* ---- measurement ---------------------------------------------------------------------------------- */
 
 /* GPU time of the last mcmcpp_hip_run between HIP events recorded on the launch stream around the

@@ -1079,6 +1079,17 @@ public:
         return MCMCPP_HIP_OK;
     }
 
+    // The ratios of normalising constants between neighbouring chains, from stored steps (evidence.hip): the refusals of
+    // exchange_chains that concern the handle; the walker state is neither needed nor touched
+    int evidence_ratios(EvidenceRequest q) override
+    {
+        if (int rc = chain_params_supported(q.what)) return rc;
+        if (K < 2) return fail(MCMCPP_HIP_E_ARG, "%s: the handle has one chain (num_chains must be at least 2)", q.what);
+        q.dtype = sizeof(T) == 8 ? MCMCPP_HIP_F64 : MCMCPP_HIP_F32;
+        q.device = device, q.K = K, q.W = W, q.D = D;
+        return evidence_compute(*this, q);
+    }
+
     // A run with its replica-exchange rounds inside the launch sequence (temper_plan.hpp has the schedule).  It is a run like
     // any other -- run_entry, run_whole, whichever way the stored steps travel -- whose enqueue_steps cuts the step launches at
     // the exchange points and puts a round's two launches there (enqueue_round).  The counters of the rounds stay on the device
@@ -1759,6 +1770,23 @@ int mcmcpp_hip_run_tempered_device(mcmcpp_hip_sampler* h, int64_t n_saved, int32
     NEED_H;
     NOT_WHILE_ASYNC("run_tempered_device");
     return h->run_tempered(n_saved, interval, exchange_every, first_round, device_chain, accepted_per_step, proposed, accepted, near_ties, rounds_done, true);
+}
+int mcmcpp_hip_evidence_ratios(mcmcpp_hip_sampler* h, const void* const* steps, int64_t n_steps, int64_t slice_interval, double* log_ratio, double* mcse, double* ess,
+                               double* kish, double* max_u, int64_t* nonfinite, double* log_ratio_total, double* mcse_total, int64_t* num_draws)
+{
+    NEED_H;
+    NOT_WHILE_ASYNC("evidence_ratios");
+    return h->evidence_ratios(mcmcpp::EvidenceRequest{"evidence_ratios", steps, nullptr, false, 0, n_steps, slice_interval,
+                                                      mcmcpp::EvidenceOutputs{log_ratio, mcse, ess, kish, max_u, nonfinite, log_ratio_total, mcse_total, num_draws}});
+}
+int mcmcpp_hip_evidence_ratios_device(mcmcpp_hip_sampler* h, const void* device_steps, int64_t chain_stride_steps, int64_t n_steps, int64_t slice_interval,
+                                      double* log_ratio, double* mcse, double* ess, double* kish, double* max_u, int64_t* nonfinite, double* log_ratio_total,
+                                      double* mcse_total, int64_t* num_draws)
+{
+    NEED_H;
+    NOT_WHILE_ASYNC("evidence_ratios_device");
+    return h->evidence_ratios(mcmcpp::EvidenceRequest{"evidence_ratios_device", nullptr, device_steps, true, chain_stride_steps, n_steps, slice_interval,
+                                                      mcmcpp::EvidenceOutputs{log_ratio, mcse, ess, kish, max_u, nonfinite, log_ratio_total, mcse_total, num_draws}});
 }
 int mcmcpp_hip_run(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step)
 {

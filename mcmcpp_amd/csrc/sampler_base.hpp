@@ -19,6 +19,29 @@
 #include "../../include/mcmcpp_hip.h"
 #include "step_plan.hpp"
 
+namespace mcmcpp
+{
+// What mcmcpp_hip_evidence_ratios writes (any pointer may be null), and one call as its entry point received it.  The handle
+// fills in its own shape (dtype .. D) behind its refusals; evidence.hip does the rest.
+struct EvidenceOutputs
+{
+    double *log_ratio, *mcse, *ess, *kish, *max_u;
+    int64_t* nonfinite;
+    double *log_ratio_total, *mcse_total;
+    int64_t* num_draws;
+};
+struct EvidenceRequest
+{
+    const char* what;
+    const void* const* steps;
+    const void* device_steps;
+    bool on_device;
+    int64_t chain_stride_steps, n_steps, slice;
+    EvidenceOutputs out;
+    int32_t dtype = 0, device = -1, K = 0, W = 0, D = 0;
+};
+}  // namespace mcmcpp
+
 struct mcmcpp_hip_sampler
 {
     std::string error;
@@ -82,6 +105,12 @@ struct mcmcpp_hip_sampler
     {
         return fail(MCMCPP_HIP_E_UNSUPPORTED,
                     "run_tempered: replica exchange is for stretch-move handles with a device calculator only (not the differential-evolution mover, not a batch target)");
+    }
+    // the ratios of normalising constants between the rungs of a ladder (mcmcpp_hip_evidence_ratios): likewise
+    virtual int evidence_ratios(mcmcpp::EvidenceRequest q)
+    {
+        return fail(MCMCPP_HIP_E_UNSUPPORTED,
+                    "%s: evidence ratios are for stretch-move handles with a device calculator only (not the differential-evolution mover, not a batch target)", q.what);
     }
     // stored steps and log-posteriors that stay in device memory (mcmcpp_hip_run_device, mcmcpp_hip_calc_logp_device): every
     // mover overrides both
@@ -336,4 +365,7 @@ const void* launch_table_lookup(int dtype, int calc_id);
 // Mover::DifferentialEvolution (diffevo.hip) and StretchMove with a batched log-posterior callback (batch.hip): see make_handle
 mcmcpp_hip_sampler* make_de_sampler(const mcmcpp_hip_config& cfg, int* rc);
 mcmcpp_hip_sampler* make_batch_sampler(const mcmcpp_hip_config& cfg, int* rc);
+// the body of mcmcpp_hip_evidence_ratios behind the handle's refusals (evidence.hip): q's shape is the handle's, whose
+// calc_logp_device evaluates the draws and whose message slot takes a failure's words
+int evidence_compute(mcmcpp_hip_sampler& h, const EvidenceRequest& q);
 }  // namespace mcmcpp
