@@ -26,7 +26,7 @@
 #include "../../include/mcmcpp_hip.h"
 #define MCMCPP_DEFINE_REDUCE_KERNEL
 #include "launch_table.hpp"
-#include "replica_kernels.hpp"
+#include "replica_round.hpp"
 #include "sampler_host.hpp"
 #include "split_exchange.hpp"
 #include "temper_plan.hpp"
@@ -1024,13 +1024,12 @@ public:
     }
 
     // One replica-exchange round among the K chains (replica_plan.hpp has the rule).  It works on the home state between
-    // runs: d_pos and logp_of(k)[0..W).  Per pair two `calc` launches of the calculator (chain k's parameters on chain k + 1's
-    // rows and the other way round), then one swap launch for the whole round.  The step streams, half_steps and n_accept stay
+    // runs: d_pos and logp_of(k)[0..W).  Two launches (ReplicaRound::enqueue): the cross evaluations of all pairs (chain k's
+    // parameters on chain k + 1's rows and the other way round), then the swaps.  The step streams, half_steps and n_accept stay
     // as they are; so do the draw records left by the last run: they hold draws and partner indices, nothing of a walker's
     // row (DrawRec), and begin_run marks every row as moved for the full-step kernels.
     int exchange_chains(uint64_t round, uint64_t* proposed, uint64_t* accepted, uint64_t* near_ties) override
     {
-        static_assert(kReplicaMaxSlots * 2 == kMaxChains, "a round has a slot for every second chain");
         if (int rc = chain_params_supported("exchange_chains")) return rc;
         if (K < 2) return fail(MCMCPP_HIP_E_ARG, "exchange_chains: the handle has one chain (num_chains must be at least 2)");
         if (round >= kReplicaMaxRound) return fail(MCMCPP_HIP_E_ARG, "exchange_chains: round %llu is out of range (rounds are below 2^40)", (unsigned long long)round);
@@ -1041,40 +1040,20 @@ public:
             if (accepted) accepted[k] = 0;
             if (near_ties) near_ties[k] = 0;
         }
-        const int pairs = replica_pairs(K, round), k0 = replica_first_chain(round);
+        const int pairs = replica_pairs(K, round);
         if (pairs == 0) return MCMCPP_HIP_OK;
         HIP_TRY(hipSetDevice(device));
-        if (int rc = ensure_replica_scratch("exchange_chains")) return rc;
-        const ReplicaShape shape = replica_shape(W, D, (int)sizeof(T), vec_ok, pairs);
-        ReplicaSwapArgs<T> a;
-        std::memset(&a, 0, sizeof a);
-        a.pos = d_pos, a.logp = d_logp, a.cross = d_replica_cross, a.table = d_replica_table, a.counts = d_replica_counts;
-        a.logp_stride_bytes = logp_chain_stride_bytes<T>(n);
-        a.W = W, a.D = D, a.first_chain = k0, a.lanes = shape.lanes, a.units = shape.units, a.vec_ok = vec_ok;
-        const long long per_block = (long long)(64 / lpw) * kWavesPerBlock;
-        const unsigned calc_grid = (unsigned)((W + per_block - 1) / per_block);
-        const size_t chain_elems = (size_t)W * D;
-        for (int j = 0; j < pairs; ++j)
-        {
-            const int ka = replica_lower_chain(round, j), kb = ka + 1;
-            a.base[j] = replica_slot_base(replica_state0, replica_inc, round, j, W);
-            T* const cross = d_replica_cross + (size_t)j * 2 * (size_t)W;
-            calc_fn(d_pos + chain_elems * kb, cross, params_of(ka), W, D, vec_ok, calc_grid, stream);      // logp_a(x_b)
-            calc_fn(d_pos + chain_elems * ka, cross + W, params_of(kb), W, D, vec_ok, calc_grid, stream);  // logp_b(x_a)
-        }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemsetAsync(d_replica_counts, 0, sizeof(ReplicaCounts) * kReplicaMaxSlots, stream));
-        launch_replica_swap(a, shape, stream);
-        HIP_TRY(hipGetLastError());
-        ReplicaCounts counts[kReplicaMaxSlots];
-        HIP_TRY(hipMemcpyAsync(counts, d_replica_counts, sizeof counts, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
+        if (int rc = ensure_replica("exchange_chains")) return rc;
+        if (int rc = rounds.clear_counts(stream)) return rc;
+        if (int rc = rounds.enqueue(replica_ensemble(false, 0u), round, stream)) return rc;
+        ReplicaCounts counts[kReplicaCountRecords];
+        if (int rc = rounds.read_counts(counts, stream)) return rc;
         for (int j = 0; j < pairs; ++j)
         {
             const int ka = replica_lower_chain(round, j);
             if (proposed) proposed[ka] = (uint64_t)W;
-            if (accepted) accepted[ka] = counts[j].accepted;
-            if (near_ties) near_ties[ka] = counts[j].near_ties;
+            if (accepted) accepted[ka] = counts[ka].accepted;
+            if (near_ties) near_ties[ka] = counts[ka].near_ties;
         }
         return MCMCPP_HIP_OK;
     }
@@ -1092,7 +1071,7 @@ public:
 
     // A run with its replica-exchange rounds inside the launch sequence (temper_plan.hpp has the schedule).  It is a run like
     // any other -- run_entry, run_whole, whichever way the stored steps travel -- whose enqueue_steps cuts the step launches at
-    // the exchange points and puts a round's two launches there (enqueue_round).  The counters of the rounds stay on the device
+    // the exchange points and puts a round's two launches there (ReplicaRound::enqueue).  The counters of the rounds stay on the device
     // until the run is over.
     int run_tempered(int64_t n_saved, int32_t interval, int64_t exchange_every, uint64_t first_round, void* chain, uint32_t* accepted_per_step,
                      uint64_t* proposed, uint64_t* accepted, uint64_t* near_ties, uint64_t* rounds_done, bool to_device) override
@@ -1108,8 +1087,8 @@ public:
         const int rc = Host::run_entry(n_saved, interval, chain, accepted_per_step, to_device);
         tempering = false;
         if (rc) return rc;
-        ReplicaCounts counts[kMaxChains - 1] = {};
-        if (temper_rounds(s) > 0) HIP_TRY(hipMemcpy(counts, d_temper_counts, sizeof counts, hipMemcpyDeviceToHost));  // (the run has synchronised the stream)
+        ReplicaCounts counts[kReplicaCountRecords] = {};
+        if (temper_rounds(s) > 0 && rounds.read_counts(counts, stream)) return MCMCPP_HIP_E_HIP;
         for (int k = 0; k + 1 < K; ++k)
         {
             if (proposed) proposed[k] = (uint64_t)W * (uint64_t)temper_rounds_pairing(s, k);
@@ -1182,61 +1161,32 @@ private:
         return MCMCPP_HIP_OK;
     }
 
-    // the exchange stream, its jump table and the scratch of a round: once per handle, by the first round or tempered run
-    int ensure_replica_scratch(const char* what)
+    // the scratch of a round and the launcher of its cross evaluations: once per handle, by the first round or tempered run
+    int ensure_replica(const char* what)
     {
-        if (d_replica_table) return MCMCPP_HIP_OK;
-        replica_seed(cfg.seed, cfg.stream, &replica_state0, &replica_inc);
-        std::vector<ReplicaJump> t((size_t)replica_table_entries(W));
-        replica_fill_table(replica_inc, W, t.data());
-        DeviceBuffer<ReplicaJump> table;
-        DeviceBuffer<ReplicaCounts> counts;
-        DeviceBuffer<T> cross;
-        if (table.alloc(sizeof(ReplicaJump) * t.size()) != hipSuccess || counts.alloc(sizeof(ReplicaCounts) * kReplicaMaxSlots) != hipSuccess ||
-            cross.alloc(sizeof(T) * (size_t)kReplicaMaxSlots * 2 * (size_t)W) != hipSuccess)
-            return fail(MCMCPP_HIP_E_NOMEM, "%s: cannot allocate the scratch of a round (%zu bytes)", what, sizeof(T) * (size_t)kReplicaMaxSlots * 2 * (size_t)W);
-        HIP_TRY(hipMemcpy(table, t.data(), sizeof(ReplicaJump) * t.size(), hipMemcpyHostToDevice));
-        d_replica_table = std::move(table);
-        d_replica_counts = std::move(counts);
-        d_replica_cross = std::move(cross);
-        return MCMCPP_HIP_OK;
+        return rounds.ensure(this, what, table->replica_cross[ilog2(lpw)][ilog2(epl / Vec16<T>::N)], cfg.seed, cfg.stream, W, D);
     }
 
     // in front of the first launch of a tempered run: the scratch of its rounds, the run's counters zeroed
     int prepare_tempering()
     {
-        static_assert(kReplicaMaxSlots * 2 == kMaxChains, "a round has a slot for every second chain");
-        if (int rc = ensure_replica_scratch("run_tempered")) return rc;
-        if (!d_temper_counts && d_temper_counts.alloc(sizeof(ReplicaCounts) * (kMaxChains - 1)) != hipSuccess)
-            return fail(MCMCPP_HIP_E_NOMEM, "run_tempered: cannot allocate the counters of the rounds");
-        cross_fn = table->replica_cross[ilog2(lpw)][ilog2(epl / Vec16<T>::N)];
-        if (!cross_fn) return fail(MCMCPP_HIP_E_UNSUPPORTED, "run_tempered: no cross-evaluation kernel for D=%d with this calculator", D);
-        HIP_TRY(hipMemsetAsync(d_temper_counts, 0, sizeof(ReplicaCounts) * (kMaxChains - 1), stream));
-        return MCMCPP_HIP_OK;
+        if (int rc = ensure_replica("run_tempered")) return rc;
+        return rounds.clear_counts(stream);
     }
 
-    // Round `round` behind the steps enqueued so far: the cross evaluations of all its pairs in one launch, the swaps in another,
-    // on the position buffer and the log-posterior half that hold the ensemble now (ensemble_in_alt)
-    int enqueue_round(uint64_t round)
+    // what a round works on: the home buffers, or (alt) the second position buffer and log-posterior half
+    ReplicaEnsemble<T> replica_ensemble(bool alt, uint32_t moved_bit) const
     {
-        const int pairs = replica_pairs(K, round), k0 = replica_first_chain(round);
-        if (pairs == 0) return MCMCPP_HIP_OK;
-        const bool alt = ensemble_in_alt();
-        const ReplicaShape shape = replica_shape(W, D, (int)sizeof(T), vec_ok, pairs);
-        ReplicaSwapRunArgs<T> a;
-        std::memset(&a, 0, sizeof a);
-        a.pos = alt ? d_pos_alt : d_pos, a.logp = d_logp + (alt ? W : 0);
-        a.cross = d_replica_cross, a.table = d_replica_table, a.counts = d_temper_counts;
-        a.logp_stride_bytes = logp_chain_stride_bytes<T>(n);
-        a.nacc_behind_logp_bytes = sizeof(T) * (size_t)(alt ? W : 2 * W);  // (nacc_of(k) = logp_of(k) + 2 W)
-        a.moved_bit = full_fn ? kRowMovedBit : 0u;
-        a.W = W, a.D = D, a.first_chain = k0, a.lanes = shape.lanes, a.units = shape.units, a.vec_ok = vec_ok;
-        for (int j = 0; j < pairs; ++j) a.base[j] = replica_slot_base(replica_state0, replica_inc, round, j, W);
+        ReplicaEnsemble<T> e = {};
+        e.pos = alt ? d_pos_alt : d_pos, e.logp = d_logp + (alt ? W : 0);
+        e.logp_stride_bytes = logp_chain_stride_bytes<T>(n);
+        e.nacc_behind_logp_bytes = sizeof(T) * (size_t)(alt ? W : 2 * W);  // (nacc_of(k) = logp_of(k) + 2 W)
+        e.moved_bit = moved_bit;
+        e.params = d_params, e.params_chain_stride = chain_params_stride;
+        e.K = K, e.W = W, e.D = D, e.vec_ok = vec_ok;
         const long long per_block = (long long)(64 / lpw) * kWavesPerBlock;
-        cross_fn(a.pos, d_replica_cross, d_params, chain_params_stride, W, D, vec_ok, k0, pairs, (unsigned)((W + per_block - 1) / per_block), stream);
-        launch_replica_swap_run(a, shape, stream);
-        HIP_TRY(hipGetLastError());
-        return MCMCPP_HIP_OK;
+        e.cross_grid = (unsigned)((W + per_block - 1) / per_block);
+        return e;
     }
 
     // the instantiated graphs (their kernel nodes hold the launch arguments of the time of capture); the stream is idle
@@ -1462,7 +1412,7 @@ private:
             const TemperPiece piece = temper_next_piece(temper, (int64_t)run_step, steps);
             if (int rc = enqueue_step_launches(piece.steps)) return rc;
             if (piece.round_follows)
-                if (int rc = enqueue_round(piece.round)) return rc;
+                if (int rc = rounds.enqueue(replica_ensemble(ensemble_in_alt(), full_fn ? kRowMovedBit : 0u), piece.round, stream)) return rc;
             steps -= piece.steps;
         }
         return MCMCPP_HIP_OK;
@@ -1573,18 +1523,10 @@ private:
     uint64_t half_steps = 0, enq_step = 0;
     void* bound_chain = nullptr;
     int64_t bound_slots = 0;
-    // replica exchange (exchange_chains), allocated by the first round: cross log-posteriors [8][2][W], the jump table of the
-    // exchange stream, the counters of a round [8]
-    DeviceBuffer<T> d_replica_cross;
-    DeviceBuffer<ReplicaJump> d_replica_table;
-    DeviceBuffer<ReplicaCounts> d_replica_counts;
-    ReplicaU128 replica_state0 = {}, replica_inc = {};
-    // a tempered run (run_tempered): its schedule while it is in hand, the counters of its rounds [K - 1], the launcher of the
-    // cross evaluations
+    // replica exchange: the scratch of a round (exchange_chains, run_tempered); a tempered run's schedule while it is in hand
+    ReplicaRound<T> rounds;
     bool tempering = false;
     TemperSchedule temper = {};
-    DeviceBuffer<ReplicaCounts> d_temper_counts;
-    typename LaunchTable<T>::CrossFn cross_fn = nullptr;
     // a rank of a split ensemble: the communicator and everything only split runs use (declared last: it goes first, the
     // communicator in front of every buffer)
     SplitExchange<T> xchg;

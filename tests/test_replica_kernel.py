@@ -3,7 +3,8 @@
 tests/test_replica_exchange.py reaches the kernel through a sampler handle, which fixes W (even, above 2 D), the alignment and the
 padding, and makes every log-posterior the calculator's own finite value.  Here tests/cpp/replica_device.hip -- a program of its
 own, linked with the production replica.hip -- launches the kernel once per case on inputs this module writes, and everything it
-writes back (positions with a guard in front and behind, log-posteriors with their padding, all 8 count records) is compared with
+writes back (positions with a guard in front and behind, log-posteriors with their padding, all 15 count records, which lie
+by the lower chain of a pair) is compared with
 tests/replica_restatement.swap_arrays as integer views, bit for bit.  There is no tolerance anywhere.
 
 How the crafted cases work.  The restatement's stream gives every (slot, walker) its draw and Python's ln U; the stored
@@ -11,6 +12,10 @@ log-posteriors and lp_ba are random, and lp_ab is set so that delta lies a chose
 the margins spread from 1e-6 (fp32 elements: 1e-3, above the rounding of lp_ab) to 2.  The wanted decisions are random bits with
 the last walker and walker 1 accepting and walker 0 rejecting, so accepted and rejected walkers interleave inside a wavefront
 and a device draw that is not the stream's flips about half of the decisions of its slot.
+
+The kernel is the one of the rounds between runs and of the rounds inside a tempered run.  The moved cases give it what only
+the latter pass: a moved_bit, and every chain's n_accept words behind its log-posteriors at the two offsets of a sampler's buffers
+(ChainGeometry: [W | W | W words], the ensemble in the first half or in the second).
 
   CPU   the driver compiles for gfx950; the row table against replica_shape (tests/cpp/replica_plan_cases.cpp); the conditions
         on the inputs, from the restatement alone; the restatement's split into swap_arrays and exchange_arrays.
@@ -37,6 +42,10 @@ PATTERN = 0xA5
 GUARD = 16384       # bytes in front of and behind the positions: two of the longest rows (1024 x 8 bytes)
 BLOCK = 256         # kReplicaBlockThreads
 CHILD_LIMIT = 60    # seconds for the child run of all cases; measured on an MI355X: 0.2 to 0.7 s in the program, 0.3 s around it
+RECORDS = 15        # kReplicaCountRecords: a count record per lower chain of a pair
+MOVED_BIT = 0x80000000  # kRowMovedBit
+NACC_GUARD = 64     # bytes of BLOCK_PATTERN behind a chain's n_accept words
+BLOCK_PATTERN = 0x5A  # around the log-posteriors and n_accept of a moved case: no word of it has MOVED_BIT, so a stray `|=` shows
 UINT = {4: np.uint32, 8: np.uint64}
 FLOAT = {4: np.float32, 8: np.float64}
 FILL = {4: 0xA5A5A5A5, 8: 0xA5A5A5A5A5A5A5A5}
@@ -137,12 +146,39 @@ def make_case(name, elem, K, W, D, first_chain=0, pairs=None, vec_ok=None, offse
                 if digits[i]:
                     arr[at] = (None, -math.inf, math.inf, nan)[digits[i]]
     c = dict(name=name, elem=elem, K=K, W=W, D=D, first_chain=first_chain, pairs=pairs, vec_ok=vec_ok, offset=offset, stride=(W + pad) * elem, seed=seed,
-             stream=stream, rnd=rnd, kind=kind, planted=sorted(planted), pos=pos, logp=logp, cross=cross.view(u), want=want, draws=draws)
+             stream=stream, rnd=rnd, kind=kind, planted=sorted(planted), pos=pos, logp=logp, cross=cross.view(u), want=want, draws=draws,
+             logp_offset=0, nacc_behind=0, moved_bit=0)
     # the restatement, once
     after_pos, after_logp = pos.copy(), logp.copy()
     c["restated"] = rr.swap_arrays(after_pos, after_logp.view(t)[:, :W], cross.copy(), first_chain, pairs, rnd, seed, stream)
     c["after_pos"], c["after_logp"] = after_pos, after_logp
     return c
+
+
+def in_sampler_layout(c, parity, moved_bit):
+    """The case with its log-posteriors inside chain blocks laid out as a sampler's: [W | W] log-posteriors, the ensemble in half
+    `parity` and the other half BLOCK_PATTERN, [W] n_accept words pre-filled with distinct low counts, NACC_GUARD bytes of BLOCK_PATTERN.
+    c["block"] [K][stride] bytes goes to the driver in place of c["logp"]."""
+    assert c["stride"] == c["W"] * c["elem"] and not c["planted"]
+    K, W, elem = c["K"], c["W"], c["elem"]
+    c = dict(c, name="%s_parity%d_bit%x" % (c["name"], parity, moved_bit), moved_bit=moved_bit, logp_offset=parity * W * elem, nacc_behind=(2 - parity) * W * elem)
+    stride = -(-(2 * W * elem + 4 * W + NACC_GUARD) // 8) * 8
+    block = np.full((K, stride), BLOCK_PATTERN, np.uint8)
+    block[:, c["logp_offset"]:c["logp_offset"] + W * elem] = c["logp"].view(np.uint8)
+    c["nacc"] = (np.arange(K * W, dtype=np.uint32) * 7 + 1).reshape(K, W)
+    block[:, 2 * W * elem:2 * W * elem + 4 * W] = c["nacc"].view(np.uint8)
+    c["block"], c["stride"] = block, stride
+    return c
+
+
+def split_block(c, block):
+    """a case's log-posterior buffer [K][stride / elem] -> (log-posteriors in use [K][W], n_accept [K][W], every other byte)"""
+    raw = np.ascontiguousarray(block).view(np.uint8).reshape(c["K"], c["stride"])
+    W, elem, lo = c["W"], c["elem"], c["logp_offset"]
+    logp = raw[:, lo:lo + W * elem].copy().view(UINT[elem])
+    nacc = raw[:, 2 * W * elem:2 * W * elem + 4 * W].copy().view(np.uint32)
+    rest = np.concatenate([raw[:, :lo], raw[:, lo + W * elem:2 * W * elem], raw[:, 2 * W * elem + 4 * W:]], axis=1)
+    return logp, nacc, rest
 
 
 def shape_of(c):
@@ -170,7 +206,17 @@ PAIR_CASES = ["pairs_K16_first0", "pairs_K16_first1", "pairs_K4_first1"]
 NONFINITE_CASES = ["nonfinite_f64", "nonfinite_f32"]
 TIE_PLANTS = {"ties_f64": [(0, 3), (0, 70), (0, 130), (0, 199), (1, 5), (1, 64), (1, 191)], "ties_f32": [(0, 0), (0, 63), (0, 64), (1, 129), (1, 199)]}
 STREAM_CASES = ["stream_last_round_slot7", "stream_3", "stream_2p63_5"]
-ALL_CASES = ROW_CASES + COUNT_CASES + PAIR_CASES + NONFINITE_CASES + list(TIE_PLANTS) + STREAM_CASES
+# (K, first_chain) x element bytes x the half that holds the ensemble: one test each, over every W, D and moved_bit
+MOVED_GROUPS = [(K, first, e, parity) for K, first in ((2, 0), (3, 1)) for e in (8, 4) for parity in (0, 1)]
+MOVED_W, MOVED_D = (1, 63, 64, 65), (1, 3, 2, 32)  # D: the element path twice, 16-byte pieces twice (fp32: D = 32 alone)
+
+
+def moved_names(K, first, e, parity):
+    return ["moved_K%d_first%d_W%d_D%d_%s_parity%d_bit%x" % (K, first, W, D, _t(e), parity, bit) for W in MOVED_W for D in MOVED_D for bit in (MOVED_BIT, 0)]
+
+
+MOVED_CASES = [n for g in MOVED_GROUPS for n in moved_names(*g)]
+ALL_CASES = ROW_CASES + COUNT_CASES + PAIR_CASES + NONFINITE_CASES + list(TIE_PLANTS) + STREAM_CASES + MOVED_CASES
 
 
 @functools.lru_cache(maxsize=None)
@@ -198,6 +244,11 @@ def suite():
     cases.append(make_case("stream_last_round_slot7", 8, 16, 600, 1, seed=2**64 - 3, rnd=2**40 - 1))
     cases.append(make_case("stream_3", 8, 2, 130, 2, seed=41, stream=3, rnd=6))
     cases.append(make_case("stream_2p63_5", 4, 2, 130, 4, seed=42, stream=2**63 + 5, rnd=7))
+    for K, first, e, parity in MOVED_GROUPS:
+        for W in MOVED_W:
+            for D in MOVED_D:
+                plain = make_case("moved_K%d_first%d_W%d_D%d_%s" % (K, first, W, D, _t(e)), e, K, W, D, first_chain=first, seed=500 + 10 * W + D, rnd=first)
+                cases += [in_sampler_layout(plain, parity, bit) for bit in (MOVED_BIT, 0)]
     by_name = {c["name"]: c for c in cases}
     assert list(by_name) == ALL_CASES
     return by_name
@@ -230,13 +281,14 @@ def write_cases(path, cases):
     with open(path, "wb") as f:
         f.write(np.array([len(cases)], np.uint64).tobytes())
         for c in cases:
-            f.write(np.array([c[k] for k in ("elem", "K", "W", "D", "first_chain", "pairs", "vec_ok", "offset", "stride", "seed", "stream", "rnd")], np.uint64).tobytes())
-            for a in (c["pos"], c["logp"], c["cross"]):
+            f.write(np.array([c[k] for k in ("elem", "K", "W", "D", "first_chain", "pairs", "vec_ok", "offset", "stride", "seed", "stream", "rnd", "logp_offset",
+                                             "nacc_behind", "moved_bit")], np.uint64).tobytes())
+            for a in (c["pos"], c.get("block", c["logp"]), c["cross"]):
                 f.write(np.ascontiguousarray(a).tobytes())
 
 
 def read_results(path, cases):
-    """name -> (positions with their guards as bytes, log-posteriors [K][stride / elem], counts [8][2])"""
+    """name -> (positions with their guards as bytes, the log-posterior buffer [K][stride / elem], counts [RECORDS][2] by lower chain)"""
     raw = np.fromfile(path, np.uint8)
     out, at = {}, 0
     for c in cases:
@@ -244,9 +296,9 @@ def read_results(path, cases):
         n_logp = c["K"] * c["stride"]
         pos = raw[at:at + n_pos]
         logp = raw[at + n_pos:at + n_pos + n_logp].view(UINT[c["elem"]]).reshape(c["K"], -1)
-        counts = raw[at + n_pos + n_logp:at + n_pos + n_logp + 128].view(np.uint64).reshape(8, 2)
+        counts = raw[at + n_pos + n_logp:at + n_pos + n_logp + 16 * RECORDS].view(np.uint64).reshape(RECORDS, 2)
         out[c["name"]] = (pos, logp, counts)
-        at += n_pos + n_logp + 128
+        at += n_pos + n_logp + 16 * RECORDS
     assert at == raw.size
     return out
 
@@ -301,9 +353,11 @@ def check_case(c, got):
     assert bad.size == 0, (name, "positions differ at (chain, walker, column)", bad[:8].tolist())
     bad = np.argwhere(got_logp != want_logp)
     assert bad.size == 0, (name, "log-posteriors differ at (chain, cell)", bad[:8].tolist())
-    assert counts[:pairs, 0].tolist() == accepted.tolist(), (name, "accepted", counts[:, 0].tolist(), accepted.tolist())
-    assert counts[:pairs, 1].tolist() == [len(planted.get(j, [])) for j in range(pairs)], (name, "near ties", counts[:, 1].tolist())
-    assert not counts[pairs:].any(), (name, "count records of unused slots", counts.tolist())
+    lower = [first + 2 * j for j in range(pairs)]
+    assert counts.shape == (RECORDS, 2)
+    assert counts[lower, 0].tolist() == accepted.tolist(), (name, "accepted", counts[:, 0].tolist(), accepted.tolist())
+    assert counts[lower, 1].tolist() == [len(planted.get(j, [])) for j in range(pairs)], (name, "near ties", counts[:, 1].tolist())
+    assert not np.delete(counts, lower, axis=0).any(), (name, "count records outside the round's pairs", counts.tolist())
     # without the restatement: chains outside the pairs and the padding are the input's, a crafted walker moved as wanted
     outside = [k for k in range(K) if k < first or k >= first + 2 * pairs]
     assert np.array_equal(pos[outside], c["pos"][outside]) and np.array_equal(got_logp[outside], c["logp"][outside]), (name, "chains outside the pairs")
@@ -544,7 +598,8 @@ def test_pairs_slots_and_what_lies_outside_them(device, name):
     c = suite()[name]
     check_case(c, device[name])
     _, logp, counts = device[name]
-    assert counts[:c["pairs"], 0].tolist() == c["restated"]["accepted"].tolist() and not counts[c["pairs"]:].any()
+    lower = [c["first_chain"] + 2 * j for j in range(c["pairs"])]
+    assert counts[lower, 0].tolist() == c["restated"]["accepted"].tolist() and not np.delete(counts, lower, axis=0).any()
     assert logp.shape == (c["K"], c["W"] + 3) and np.all(logp[:, c["W"]:] == FILL[c["elem"]])
 
 
@@ -567,10 +622,35 @@ def test_planted_near_ties_are_counted(device, name):
     c = suite()[name]
     check_case(c, device[name])
     counts = device[name][2]
-    assert counts[:, 1].tolist() == [sum(1 for j, _ in TIE_PLANTS[name] if j == s) for s in range(8)]
+    assert counts[:, 1].tolist() == [0 if k % 2 else sum(1 for j, _ in TIE_PLANTS[name] if 2 * j == k) for k in range(RECORDS)]  # (first_chain = 0)
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", STREAM_CASES)
 def test_the_stream_on_the_device(device, name):
     check_case(suite()[name], device[name])
+
+
+def check_moved(c, got):
+    """a moved case: rows, log-posteriors in use and counts as without the bit; the bit in n_accept, and nothing else anywhere"""
+    name, K, first = c["name"], c["K"], c["first_chain"]
+    got_pos, block, counts = got
+    logp, nacc, rest = split_block(c, block)
+    check_case(c, (got_pos, logp, counts))
+    assert np.all(rest == BLOCK_PATTERN), (name, "the other log-posterior half or the guard behind n_accept", np.argwhere(rest != BLOCK_PATTERN)[:8].tolist())
+    swapped = np.zeros((K, c["W"]), bool)
+    swapped[first] = swapped[first + 1] = c["restated"]["accept"][0]
+    assert np.array_equal(nacc & np.uint32(MOVED_BIT - 1), c["nacc"]), (name, "low bits of n_accept")
+    if c["moved_bit"]:
+        assert np.array_equal((nacc & np.uint32(MOVED_BIT)) != 0, swapped), (name, "moved_bit", np.argwhere(((nacc >> 31) != 0) != swapped)[:8].tolist())
+    else:
+        assert np.array_equal(nacc, c["nacc"]), (name, "n_accept with moved_bit = 0")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("K,first,e,parity", MOVED_GROUPS, ids=["K%d_first%d_%s_parity%d" % (K, first, _t(e), parity) for K, first, e, parity in MOVED_GROUPS])
+def test_moved_bit_in_n_accept_behind_the_log_posteriors(device, K, first, e, parity):
+    """What a round inside a run of the full-step kernels adds: the bit in both chains' n_accept for exactly the swapped walkers,
+    the counts in the low bits and every byte around the words as they were; with moved_bit = 0 no byte of n_accept changes."""
+    for name in moved_names(K, first, e, parity):
+        check_moved(suite()[name], device[name])

@@ -52,9 +52,9 @@ def measure(K, W, D, calc, out):
         hip.run(20, save_chain=False, want_accepted=False)
     line = ("K=%d W=%d D=%d calc=%d: one ensemble step (all chains, last_run_timing over %d steps) %.2f us [%.2f..%.2f]; one exchange round "
             "(HIP events around 50 rounds, each ending in a synchronise) %.1f us [%.1f..%.1f], host wall %.1f us [%.1f..%.1f]; "
-            "launches of a round: %d calc + 1 swap (even) / %d calc + 1 swap (odd); last swap fraction %.2f"
+            "launches of a round: 1 cross (%d pairs) + 1 swap (even) / 1 cross (%d pairs) + 1 swap (odd); last swap fraction %.2f"
             % (K, W, D, calc, steps, np.median(step_us), min(step_us), max(step_us), np.median(ev), min(ev), max(ev), np.median(wall), min(wall), max(wall),
-               2 * (K // 2), 2 * ((K - 1) // 2), frac[-1]))
+               K // 2, (K - 1) // 2, frac[-1]))
     print(line, flush=True)
     out.write(line + "\n")
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """What a tempered run costs per ensemble step: HipSampler.run_exchanging (the segment loop: a run, a synchronisation and a
-round of 2 pairs + 2 launches per segment) against HipSampler.run_tempered (one call, two launches per round), DESIGN.md section 6.
+round with its counters' clearing, copy and synchronisation per segment) against HipSampler.run_tempered (one call).  A round is
+the same two launches on both sides.  DESIGN.md section 6.
 
 K = 4 and K = 16 chains of 16 384 walkers x 32 dims, dense fp64, ladder P_k = 0.9^k P, device=True, 2 000 ensemble steps, for
 exchange_every in {1, 10, 100}.  One stored step per exchange_every steps (the loop needs exchange_every to be a multiple of the
@@ -9,7 +10,7 @@ stays at 200 stored steps (12.5 GiB with 16 chains) -- for both sides alike.  Fi
 and maximum of the wall time per ensemble step.  Every (K, exchange_every, side) runs in a process of its own.
 
 Also the GPU time of one round, between events on the handle's stream, warm:
-  loop      events around exchange_chains(r): 2 pairs calc launches, a memset, the swap launch, the counters' copy; the medians
+  loop      events around exchange_chains(r): a memset, the cross launch, the swap launch, the counters' copy; the medians
             of ten even and of ten odd rounds, averaged
   tempered  (events around run_tempered(200, exchange_every=1)) - (events around run_device(200)), medians of 20 each, over
             the 200 rounds
@@ -119,7 +120,7 @@ def main():
             fmt = lambda xs: "%9.2f (%8.2f .. %8.2f)" % (statistics.median(xs), min(xs), max(xs))  # noqa: E731
             lines.append("%3d %6d %28s %28s %8.2f" % (K, every, fmt(loop), fmt(temp), statistics.median(loop) / statistics.median(temp)))
             print(lines[-1], flush=True)
-    lines += ["", "GPU time of one round, us (events on the handle's stream, warm): the loop's 2 pairs + 2 launches | the two launches inside a run | one ensemble step"]
+    lines += ["", "GPU time of one round, us (events on the handle's stream, warm): a round of the loop (memset, two launches, copy) | the two launches inside a run | one ensemble step"]
     for K in (4, 16):
         r = child("round", K)
         lines.append("%3d %10.1f %10.1f %10.2f" % (K, r["loop_round_us"], r["tempered_round_us"], r["plain_step_us"]))
