@@ -13,6 +13,8 @@
  *
  * evidenceRatios() estimates the ratios of normalising constants between neighbouring rungs from the stored steps
  * (mcmcpp_hip_evidence_ratios): their chain is the evidence of rung 0 when the top rung is a normalised density.
+ * evidenceBridge() gives the bridge estimate of the same ratios, one per pair from the draws of both rungs
+ * (mcmcpp_hip_evidence_bridge).
  */
 #ifndef MCMCPP_REPLICAEXCHANGESAMPLER_H
 #define MCMCPP_REPLICAEXCHANGESAMPLER_H
@@ -43,6 +45,21 @@ struct EvidenceRatios
     std::vector<double> logRatio, mcse, ess, kish, maxU;
     std::vector<std::int64_t> nonfinite;
     double logRatioTotal[2], mcseTotal[2];  ///< log(Z_0 / Z_{numRungs-1}) by each direction, and its standard error
+    std::size_t at(int direction, int pair) const { return static_cast<std::size_t>(direction) * static_cast<std::size_t>(numPairs) + static_cast<std::size_t>(pair); }
+};
+
+/// What ReplicaExchangeSampler::evidenceBridge returns (mcmcpp_hip_evidence_bridge, include/mcmcpp_hip.h): the bridge estimate
+/// (Bennett's acceptance ratio) of log(Z_p / Z_{p+1}) per pair p, from the draws of both rungs.  ess and nonfinite are
+/// [2][numRungs - 1], direction-major -- at(d, p): d = 0 the draws of rung p + 1, d = 1 those of rung p.
+struct EvidenceBridge
+{
+    int numPairs;
+    std::int64_t numDraws;  ///< draws per rung: used steps times walkers
+    std::vector<double> logRatio, mcse, overlap;  ///< [numRungs - 1]; overlap: 1 for identical rungs, towards 0 for disjoint ones
+    std::vector<std::int64_t> passes, converged;  ///< [numRungs - 1]: the solver's passes, and whether it stopped on its rule
+    std::vector<double> ess;
+    std::vector<std::int64_t> nonfinite;
+    double logRatioTotal, mcseTotal;  ///< log(Z_0 / Z_{numRungs-1}) and its standard error
     std::size_t at(int direction, int pair) const { return static_cast<std::size_t>(direction) * static_cast<std::size_t>(numPairs) + static_cast<std::size_t>(pair); }
 };
 
@@ -193,23 +210,9 @@ public:
     /// steps; the walker state is not touched.
     EvidenceRatios evidenceRatios(int burnIn = 0, int sliceInterval = 1)
     {
-        if (burnIn < 0 || sliceInterval < 1) throw std::invalid_argument("ReplicaExchangeSampler::evidenceRatios: burnIn >= 0 and sliceInterval >= 1");
-        const std::size_t K = static_cast<std::size_t>(numRungs);
-        std::vector<const void*> steps;
         std::int64_t used = 0;
-        for (std::size_t k = 0; k < K; ++k)
-        {
-            StepItt itt = chains[k]->getStepIteratorBegin(), end = chains[k]->getStepIteratorEnd();
-            std::int64_t index = 0, mine = 0;
-            for (; itt != end; ++itt, ++index)
-                if (index >= burnIn && (index - burnIn) % sliceInterval == 0)
-                {
-                    steps.push_back(*itt);
-                    ++mine;
-                }
-            if (k > 0 && mine != used) throw std::logic_error("ReplicaExchangeSampler::evidenceRatios: the rungs hold different numbers of steps");
-            used = mine;
-        }
+        const std::vector<const void*> steps = usedSteps("evidenceRatios", burnIn, sliceInterval, used);
+        const std::size_t K = static_cast<std::size_t>(numRungs);
         EvidenceRatios r;
         r.numPairs = numRungs - 1;
         r.numDraws = 0;
@@ -221,6 +224,25 @@ public:
         return r;
     }
 
+    /// The bridge estimate of the same ratios (mcmcpp_hip_evidence_bridge): one per pair, from the draws of both rungs; the
+    /// steps are chosen as for evidenceRatios.
+    EvidenceBridge evidenceBridge(int burnIn = 0, int sliceInterval = 1)
+    {
+        std::int64_t used = 0;
+        const std::vector<const void*> steps = usedSteps("evidenceBridge", burnIn, sliceInterval, used);
+        const std::size_t pairs = static_cast<std::size_t>(numRungs - 1);
+        EvidenceBridge r;
+        r.numPairs = numRungs - 1;
+        r.numDraws = 0;
+        r.logRatioTotal = r.mcseTotal = 0.0;
+        r.logRatio.resize(pairs), r.mcse.resize(pairs), r.overlap.resize(pairs), r.passes.resize(pairs), r.converged.resize(pairs);
+        r.ess.resize(2 * pairs), r.nonfinite.resize(2 * pairs);
+        handle.check("mcmcpp_hip_evidence_bridge",
+                     mcmcpp_hip_evidence_bridge(handle.get(), steps.empty() ? nullptr : steps.data(), used, 1, r.logRatio.data(), r.mcse.data(), r.overlap.data(),
+                                                r.ess.data(), r.passes.data(), r.converged.data(), r.nonfinite.data(), &r.logRatioTotal, &r.mcseTotal, &r.numDraws));
+        return r;
+    }
+
     /// Walker positions [K][W][D], log-posteriors [K][W] and per-walker accepted counts [K][W] as they stand on the device.
     void currentState(ParamType* positions, ParamType* logp, std::uint32_t* nAccept)
     {
@@ -229,6 +251,29 @@ public:
     }
 
 private:
+    /// every sliceInterval'th stored step of every rung behind the first burnIn, rung-major; used: their number per rung
+    std::vector<const void*> usedSteps(const char* caller, int burnIn, int sliceInterval, std::int64_t& used)
+    {
+        const std::string who = std::string("ReplicaExchangeSampler::") + caller;
+        if (burnIn < 0 || sliceInterval < 1) throw std::invalid_argument(who + ": burnIn >= 0 and sliceInterval >= 1");
+        std::vector<const void*> steps;
+        used = 0;
+        for (std::size_t k = 0; k < static_cast<std::size_t>(numRungs); ++k)
+        {
+            StepItt itt = chains[k]->getStepIteratorBegin(), end = chains[k]->getStepIteratorEnd();
+            std::int64_t index = 0, mine = 0;
+            for (; itt != end; ++itt, ++index)
+                if (index >= burnIn && (index - burnIn) % sliceInterval == 0)
+                {
+                    steps.push_back(*itt);
+                    ++mine;
+                }
+            if (k > 0 && mine != used) throw std::logic_error(who + ": the rungs hold different numbers of steps");
+            used = mine;
+        }
+        return steps;
+    }
+
     std::size_t checkedRung(int rung) const
     {
         if (rung < 0 || rung >= numRungs) throw std::out_of_range("ReplicaExchangeSampler: rung " + std::to_string(rung) + " out of range");

@@ -425,6 +425,59 @@ int mcmcpp_hip_evidence_ratios_device(mcmcpp_hip_sampler* h, const void* device_
                                       int64_t slice_interval, double* log_ratio, double* mcse, double* ess, double* kish, double* max_u,
                                       int64_t* nonfinite, double* log_ratio_total, double* mcse_total, int64_t* num_draws);
 
+/* The bridge estimate of the same ratios (Bennett's acceptance ratio; Meng & Wong 1996; Fruehwirth-Schnatter 2004): one estimate
+ * of log(Z_p / Z_{p+1}) per pair from the draws of BOTH rungs, where mcmcpp_hip_evidence_ratios gives one per direction.
+ *   draws      as for mcmcpp_hip_evidence_ratios: pair p = rungs (a, b) = (p, p + 1), N = n W draws per rung in the order
+ *              i = s W + w.  u0_j = logp_a(x_j) - logp_b(x_j) on the draws x_j of b, u1_i = logp_b(y_i) - logp_a(y_i) on the draws
+ *              y_i of a: that call's u of d = 0 and d = 1, the same calc_logp_device bits widened to double, one subtraction.
+ *   sigma      sigma(x) = 1 / (1 + evidence_exp(-x)) for x >= 0 (-0 included); sigma(x) = e / (1 + e) with e = evidence_exp(x)
+ *              for x < 0: evidence_exp is called with arguments <= 0 only, and has one value in bits on host and device.
+ *              sigma(-inf) = 0, sigma(+inf) = 1.
+ *   sums       h0_j(c) = sigma(u0_j - c), h1_i(c) = sigma(u1_i + c); S_d(c) = sum_tree(h_d), Q_d(c) = sum_tree(h_d (1 - h_d));
+ *              g(c) = S_0(c) - S_1(c).  g does not increase with c; the estimate is its root c*.
+ *   sum_tree   sum_tree(v, N): tiles of 1024 consecutive terms; the missing terms of the last tile are +0.  In a tile, lane t of
+ *              256 forms ((v[2t] + v[2t+1]) + v[2t+512]) + v[2t+513]; then for s = 128, 64, ..., 1: p_t = p_t + p_{t+s} for t < s;
+ *              the tile's sum is p_0.  Tile sums are added in ascending order from +0 within a slice of 64 tiles (the last slice
+ *              may be short); slice sums are added in ascending order from +0.  The shape is a function of N alone; its longest
+ *              chain of dependent additions is 11 in a tile, 64 in a slice and ceil(N / 65536) over the slices.
+ *   solver     A pass evaluates S_0, S_1, Q_0, Q_1 at one c; `passes` counts the passes.
+ *              1. c = +0; a pass.  If g == 0: stop.
+ *              2. up = g > 0 (the root lies above); step = 1.  Repeat: prev = c; c = prev + step if up, else prev - step, and
+ *                 +-DBL_MAX where that is infinite; step = step + step; a pass.  If g == 0: stop.  If (g > 0) != up: lo = the
+ *                 smaller and hi = the larger of prev and c, go to 3.  If 1100 passes are done: stop with converged = 0.
+ *              3. Repeat, 200 times at the most: mid = 0.5 lo + 0.5 hi.  If S_0 > 0 and S_1 > 0 at c:
+ *                 f = normal_score_log(S_0) - normal_score_log(S_1) (normal_score.hpp's logarithm), f' = -(Q_0 / S_0 + Q_1 / S_1),
+ *                 and next = c - f / f' unless f' == 0: a Newton step on ln S_0 - ln S_1, which has the root of g and is linear in
+ *                 c where the rungs barely overlap.  In every other case, and if not lo < next < hi: next = mid.  If next == lo or
+ *                 next == hi: stop.  If |next - c| <= 2^-40 max(1, |next|): c = next, stop.  Otherwise c = next; a pass; if
+ *                 g == 0: stop; if g > 0: lo = c, else hi = c.  Behind the 200th such pass: stop with converged = 0.
+ *              4. Every stop but the two named has converged = 1.  The final pass is at the c of the stop, c*: it gives the S_d of
+ *                 the outputs, forms H_d = sum_tree(h_d h_d) and keeps h_d(c*).  It is counted: passes <= 1301.
+ *              The result is a function of the two u arrays alone.
+ *   outputs    log_ratio [K-1] = c*.  overlap [K-1] = (S_0 + S_1) / N at c*: 1 for identical rungs, towards 0 for disjoint ones.
+ *              passes, converged [K-1] int64.  ess [2][K-1], d-major: the `ess` output of
+ *              mcmcpp_hip_effective_sample_size_device on h_d(c*) seen as a chain of one rung: n steps, W walkers, one parameter,
+ *              fp64, split = 1, max_lag = 0, as mcmcpp_hip_evidence_ratios calls it on its weights.  mean_d = S_d / N;
+ *              rel2_d = max(H_d / N - mean_d mean_d, 0) / (mean_d mean_d); t_d = 0 when rel2_d == 0, else rel2_d / ess_d;
+ *              mcse [K-1] = sqrt(t_0 + t_1): the delta-method error of Fruehwirth-Schnatter 2004 with the autocorrelation in the
+ *              ESS.  nonfinite [2][K-1] int64 as for mcmcpp_hip_evidence_ratios.  *log_ratio_total = the sum of log_ratio in
+ *              ascending p from +0; *mcse_total = sqrt(the sum of mcse mcse in ascending p from +0).  *num_draws = N.
+ *   edges      A NaN or +inf among the u of either direction: log_ratio, overlap, mcse and both ess of that pair are NaN, passes
+ *              and converged 0, and nothing else changes.  A u of -inf has h = 0.  S_0 == 0 or S_1 == 0 at c* (no mass is
+ *              shared at double precision): log_ratio, mcse and ess are NaN and overlap is 0.
+ * Everything is fp64, every + - * / rounded on its own; no fused operation, no floating-point atomic.  No output depends on the
+ * CU count, the chunk size (MCMCPP_HIP_EVIDENCE_CHUNK_MB, as above) or where a chain lies.  steps, device_steps,
+ * chain_stride_steps, n_steps and slice_interval are those of mcmcpp_hip_evidence_ratios, and so are the refusals and argument
+ * checks with their codes.  Any output may be NULL; nothing is written to the outputs of a call that fails.  The raw u take
+ * 8 N bytes of device memory per pair and direction in flight, three at most and two for K = 2, freed when the call returns:
+ * MCMCPP_HIP_E_NOMEM with the byte count where they cannot be had.  The walker state is neither needed nor touched. */
+int mcmcpp_hip_evidence_bridge(mcmcpp_hip_sampler* h, const void* const* steps, int64_t n_steps, int64_t slice_interval, double* log_ratio,
+                               double* mcse, double* overlap, double* ess, int64_t* passes, int64_t* converged, int64_t* nonfinite,
+                               double* log_ratio_total, double* mcse_total, int64_t* num_draws);
+int mcmcpp_hip_evidence_bridge_device(mcmcpp_hip_sampler* h, const void* device_steps, int64_t chain_stride_steps, int64_t n_steps,
+                                      int64_t slice_interval, double* log_ratio, double* mcse, double* overlap, double* ess, int64_t* passes,
+                                      int64_t* converged, int64_t* nonfinite, double* log_ratio_total, double* mcse_total, int64_t* num_draws);
+
 /* ---- measurement ---------------------------------------------------------------------------------- */
 
 /* GPU time of the last mcmcpp_hip_run between HIP events recorded on the launch stream around the

@@ -32,6 +32,7 @@ EXPORTS = [
     "mcmcpp_hip_half_step_async", "mcmcpp_hip_bind_device_chain", "mcmcpp_hip_device_positions",
     "mcmcpp_hip_shard_span", "mcmcpp_hip_synchronize", "mcmcpp_hip_exchange_chains",
     "mcmcpp_hip_run_tempered", "mcmcpp_hip_run_tempered_device", "mcmcpp_hip_evidence_ratios", "mcmcpp_hip_evidence_ratios_device",
+    "mcmcpp_hip_evidence_bridge", "mcmcpp_hip_evidence_bridge_device",
     "mcmcpp_hip_moments_create", "mcmcpp_hip_moments_destroy", "mcmcpp_hip_moments_reset", "mcmcpp_hip_moments_add_steps",
     "mcmcpp_hip_moments_add_device_steps", "mcmcpp_hip_moments_finish", "mcmcpp_hip_moments_last_error",
     "mcmcpp_hip_autocorr_times", "mcmcpp_hip_autocorr_times_device", "mcmcpp_hip_autocorr_last_error",
@@ -146,6 +147,10 @@ def lib():
             outputs = [vp] * 9  # log_ratio, mcse, ess, kish, max_u, nonfinite, log_ratio_total, mcse_total, *num_draws
             L.mcmcpp_hip_evidence_ratios.argtypes = [vp, C.POINTER(vp), i64, i64] + outputs
             L.mcmcpp_hip_evidence_ratios_device.argtypes = [vp, vp, i64, i64, i64] + outputs
+        if hasattr(L, "mcmcpp_hip_evidence_bridge"):  # (likewise)
+            outputs = [vp] * 10  # log_ratio, mcse, overlap, ess, passes, converged, nonfinite, log_ratio_total, mcse_total, *num_draws
+            L.mcmcpp_hip_evidence_bridge.argtypes = [vp, C.POINTER(vp), i64, i64] + outputs
+            L.mcmcpp_hip_evidence_bridge_device.argtypes = [vp, vp, i64, i64, i64] + outputs
         if hasattr(L, "mcmcpp_hip_moments_create"):  # (absent only from older experiment builds selected with MCMCPP_HIP_LIB)
             L.mcmcpp_hip_moments_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
             L.mcmcpp_hip_moments_destroy.argtypes = [vp]
@@ -631,6 +636,29 @@ class HipSampler:
         swaps = dict(proposed=v[0][:K - 1], accepted=v[1][:K - 1], near_ties=v[2][:K - 1])
         return chain, acc, swaps, first_round + rounds.value
 
+    def _evidence_call(self, host_fn, device_fn, steps, slice_interval, chain_stride_steps, outputs):
+        """the steps of evidence_ratios and evidence_bridge, checked, through the host-pointer or the device entry point"""
+        K = self.K
+        if _is_tensor(steps):
+            if steps.dim() != 4 or tuple(steps.shape[0:1] + steps.shape[2:]) != (K, self.W, self.D):
+                raise ValueError("device steps must have shape (%d, n, %d, %d), not %s" % (K, self.W, self.D, tuple(steps.shape)))
+            if steps.dtype != _torch_dtype(self.dtype) or not steps.is_cuda:
+                raise ValueError("device steps must be a device tensor of dtype %s" % _torch_dtype(self.dtype))
+            E = self.W * self.D
+            if not steps[0].is_contiguous() or (K > 1 and steps.stride(0) % E):
+                raise ValueError("every chain of the device steps must be contiguous, and the chains a whole number of steps apart")
+            stride = steps.stride(0) // E if chain_stride_steps is None else chain_stride_steps
+            _after_torch(steps)
+            self._check(device_fn(self.h, C.c_void_p(steps.data_ptr()), stride, steps.shape[1], slice_interval, *outputs))
+        else:
+            x = np.asarray(steps)
+            if x.ndim != 4 or x.shape[0] != K or x.shape[2:] != (self.W, self.D) or x.dtype != self.np_t:
+                raise ValueError("steps must be a %s array (%d, n, %d, %d)" % (np.dtype(self.np_t).name, K, self.W, self.D))
+            n = x.shape[1]
+            rows = [np.ascontiguousarray(x[k, s]) for k in range(K) for s in range(n)]  # (a contiguous step is not copied)
+            ptrs = (C.c_void_p * max(len(rows), 1))(*[r.ctypes.data for r in rows])
+            self._check(host_fn(self.h, ptrs, n, slice_interval, *outputs))
+
     def evidence_ratios(self, steps, slice_interval=1, chain_stride_steps=None):
         """The ratios of normalising constants between neighbouring chains of a ladder, from stored steps of the K chains
         (mcmcpp_hip_evidence_ratios): steps a numpy array [K][n][W][D], or the device tensor run_tempered(device=True) returned
@@ -646,27 +674,32 @@ class HipSampler:
         out["log_ratio_total"], out["mcse_total"] = np.full(2, np.nan), np.full(2, np.nan)
         draws = C.c_int64(0)
         outputs = [_ptr(out[key]) for key in ("log_ratio", "mcse", "ess", "kish", "max_u", "nonfinite", "log_ratio_total", "mcse_total")] + [C.byref(draws)]
-        if _is_tensor(steps):
-            if steps.dim() != 4 or tuple(steps.shape[0:1] + steps.shape[2:]) != (K, self.W, self.D):
-                raise ValueError("device steps must have shape (%d, n, %d, %d), not %s" % (K, self.W, self.D, tuple(steps.shape)))
-            if steps.dtype != _torch_dtype(self.dtype) or not steps.is_cuda:
-                raise ValueError("device steps must be a device tensor of dtype %s" % _torch_dtype(self.dtype))
-            E = self.W * self.D
-            if not steps[0].is_contiguous() or (K > 1 and steps.stride(0) % E):
-                raise ValueError("every chain of the device steps must be contiguous, and the chains a whole number of steps apart")
-            stride = steps.stride(0) // E if chain_stride_steps is None else chain_stride_steps
-            _after_torch(steps)
-            self._check(lib().mcmcpp_hip_evidence_ratios_device(self.h, C.c_void_p(steps.data_ptr()), stride, steps.shape[1], slice_interval, *outputs))
-        else:
-            x = np.asarray(steps)
-            if x.ndim != 4 or x.shape[0] != K or x.shape[2:] != (self.W, self.D) or x.dtype != self.np_t:
-                raise ValueError("steps must be a %s array (%d, n, %d, %d)" % (np.dtype(self.np_t).name, K, self.W, self.D))
-            n = x.shape[1]
-            rows = [np.ascontiguousarray(x[k, s]) for k in range(K) for s in range(n)]  # (a contiguous step is not copied)
-            ptrs = (C.c_void_p * max(len(rows), 1))(*[r.ctypes.data for r in rows])
-            self._check(lib().mcmcpp_hip_evidence_ratios(self.h, ptrs, n, slice_interval, *outputs))
+        self._evidence_call(lib().mcmcpp_hip_evidence_ratios, lib().mcmcpp_hip_evidence_ratios_device, steps, slice_interval, chain_stride_steps, outputs)
         for key in ("log_ratio", "mcse", "ess", "kish", "max_u", "nonfinite"):
             out[key] = out[key][:, :K - 1]
+        out["num_draws"] = draws.value
+        return out
+
+    def evidence_bridge(self, steps, slice_interval=1, chain_stride_steps=None):
+        """The bridge estimate (Bennett's acceptance ratio) of the same ratios, one per pair from the draws of both rungs
+        (mcmcpp_hip_evidence_bridge; steps, slice_interval and chain_stride_steps as for evidence_ratios).  Returns a dict of
+        numpy arrays: log_ratio, mcse, overlap [K-1] float64, passes, converged [K-1] int64, ess [2][K-1] float64 and nonfinite
+        [2][K-1] int64 (row d: the draws of rung p + 1 for d = 0, of rung p for d = 1), the floats log_ratio_total and mcse_total,
+        and num_draws."""
+        K, P = self.K, max(self.K - 1, 1)
+        out = {key: np.full(P, np.nan) for key in ("log_ratio", "mcse", "overlap")}
+        out["ess"] = np.full((2, P), np.nan)
+        out["passes"], out["converged"], out["nonfinite"] = np.zeros(P, np.int64), np.zeros(P, np.int64), np.zeros((2, P), np.int64)
+        totals = np.full(2, np.nan)
+        draws = C.c_int64(0)
+        outputs = [_ptr(out[key]) for key in ("log_ratio", "mcse", "overlap", "ess", "passes", "converged", "nonfinite")]
+        outputs += [C.c_void_p(totals.ctypes.data), C.c_void_p(totals.ctypes.data + 8), C.byref(draws)]
+        self._evidence_call(lib().mcmcpp_hip_evidence_bridge, lib().mcmcpp_hip_evidence_bridge_device, steps, slice_interval, chain_stride_steps, outputs)
+        for key in ("log_ratio", "mcse", "overlap", "passes", "converged"):
+            out[key] = out[key][:K - 1]
+        for key in ("ess", "nonfinite"):
+            out[key] = out[key][:, :K - 1]
+        out["log_ratio_total"], out["mcse_total"] = np.float64(totals[0]), np.float64(totals[1])
         out["num_draws"] = draws.value
         return out
 

@@ -7,10 +7,9 @@
 // decisions: at most three calls per chunk of a rung); the effective sample size is that of the existing entry point's body
 // (rhat_state.hpp: ess_compute of mcmcpp_hip_effective_sample_size_device, on this call's stream and into the handle's message
 // slot) on the weights, a chain of one rung in device memory.
-//   * evidence_diff_kernel: thread = a draw of the chunk: u = (double)logp_other - (double)logp_own, stored at the draw's place
-//     of the weights buffer [N]; the block's largest u that is neither NaN nor +inf (as a key whose unsigned order is the
-//     doubles' order, -0 below +0) and its counts of non-finite u and of NaN or +inf among them, first in LDS, then one
-//     integer atomic each per block: a maximum and two integer sums, which no order of arrival changes.
+//   * evidence_diff_kernel (evidence_kernels.hpp, shared with bridge.hip): thread = a draw of the chunk: u = (double)logp_other -
+//     (double)logp_own, stored at the draw's place of the weights buffer [N]; the largest u that is neither NaN nor +inf and the
+//     counts of non-finite u and of NaN or +inf among them, by integer atomics, which no order of arrival changes.
 //   * evidence_weights_kernel: block = slice t of sum_fixed over the N draws: e = evidence_exp(u - m) written over u, a tile of
 //     kEvidenceTile draws at a time through LDS, from which thread 0 adds e and thread 1 adds e e in ascending order from +0.
 //     The slice sums [slices][2] are added in ascending order by the host.
@@ -28,62 +27,18 @@
 #include <vector>
 
 #include "evidence_exp.hpp"
+#include "evidence_kernels.hpp"
 #include "evidence_plan.hpp"
 #include "normal_score.hpp"
 #include "rhat_state.hpp"
 
 namespace
 {
+using mcmcpp::evidence_diff_kernel;
+using mcmcpp::evidence_key_value;
+using mcmcpp::EvidenceState;
 using mcmcpp::kEvidenceThreads;
 using mcmcpp::kEvidenceTile;
-
-// per (d, p) in flight: the running maximum's key (0: none yet), the non-finite u, the NaN or +inf among them
-struct EvidenceState
-{
-    unsigned long long max_key, nonfinite, bad;
-};
-
-__host__ __device__ inline unsigned long long evidence_key(double u)
-{
-    unsigned long long b;
-    memcpy(&b, &u, 8);
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ULL);
-}
-inline double evidence_key_value(unsigned long long key)
-{
-    const unsigned long long b = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFULL) : ~key;
-    double u;
-    memcpy(&u, &b, 8);
-    return u;
-}
-
-template <class T>
-__global__ void __launch_bounds__(kEvidenceThreads)
-evidence_diff_kernel(const T* __restrict__ lp_other, const T* __restrict__ lp_own, long long count, double* __restrict__ u_out, EvidenceState* __restrict__ state)
-{
-    __shared__ unsigned long long s_max, s_nonfinite, s_bad;
-    if (threadIdx.x == 0) s_max = 0, s_nonfinite = 0, s_bad = 0;
-    __syncthreads();
-    const long long i = (long long)blockIdx.x * kEvidenceThreads + threadIdx.x;
-    if (i < count)
-    {
-        const double u = (double)lp_other[i] - (double)lp_own[i];
-        u_out[i] = u;
-        const bool nan = u != u, pinf = u == __builtin_inf(), ninf = u == -__builtin_inf();
-        if (nan || pinf || ninf) atomicAdd(&s_nonfinite, 1ULL);
-        if (nan || pinf)
-            atomicAdd(&s_bad, 1ULL);
-        else
-            atomicMax(&s_max, evidence_key(u));
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        if (s_max) atomicMax(&state->max_key, s_max);
-        if (s_nonfinite) atomicAdd(&state->nonfinite, s_nonfinite);
-        if (s_bad) atomicAdd(&state->bad, s_bad);
-    }
-}
 
 __global__ void __launch_bounds__(kEvidenceThreads) evidence_weights_kernel(double* __restrict__ w, long long N, long long slen, double m, double* __restrict__ part)
 {
@@ -263,9 +218,8 @@ int run_request(mcmcpp_hip_sampler& h, const mcmcpp::EvidenceRequest& q, long lo
 
 namespace mcmcpp
 {
-int evidence_compute(mcmcpp_hip_sampler& h, const EvidenceRequest& q)
+int evidence_check(mcmcpp_hip_sampler& h, const EvidenceRequest& q, long long* used_steps)
 {
-    // every check that needs no device
     const std::string w(q.what);
     const auto fail = [&](const std::string& msg) { return analysis_fail(h.error, MCMCPP_HIP_E_ARG, w + ": " + msg); };
     if (q.slice < 1) return fail("slice_interval >= 1");
@@ -278,6 +232,15 @@ int evidence_compute(mcmcpp_hip_sampler& h, const EvidenceRequest& q)
         for (int64_t k = 0; k < q.K; ++k)
             for (int64_t s = 0; s < q.n_steps; s += q.slice)
                 if (!q.steps[k * q.n_steps + s]) return fail("a step pointer is NULL");
+    *used_steps = n;
+    return MCMCPP_HIP_OK;
+}
+
+int evidence_compute(mcmcpp_hip_sampler& h, const EvidenceRequest& q)
+{
+    // every check that needs no device
+    long long n = 0;
+    if (int rc = evidence_check(h, q, &n)) return rc;
     return q.dtype == MCMCPP_HIP_F64 ? run_request<double>(h, q, n) : run_request<float>(h, q, n);
 }
 }  // namespace mcmcpp

@@ -1068,6 +1068,15 @@ public:
         q.device = device, q.K = K, q.W = W, q.D = D;
         return evidence_compute(*this, q);
     }
+    // The bridge estimate of the same ratios (bridge.hip): the same refusals
+    int evidence_bridge(BridgeRequest b) override
+    {
+        if (int rc = chain_params_supported(b.q.what)) return rc;
+        if (K < 2) return fail(MCMCPP_HIP_E_ARG, "%s: the handle has one chain (num_chains must be at least 2)", b.q.what);
+        b.q.dtype = sizeof(T) == 8 ? MCMCPP_HIP_F64 : MCMCPP_HIP_F32;
+        b.q.device = device, b.q.K = K, b.q.W = W, b.q.D = D;
+        return bridge_compute(*this, b);
+    }
 
     // A run with its replica-exchange rounds inside the launch sequence (temper_plan.hpp has the schedule).  It is a run like
     // any other -- run_entry, run_whole, whichever way the stored steps travel -- whose enqueue_steps cuts the step launches at
@@ -1729,6 +1738,25 @@ int mcmcpp_hip_evidence_ratios_device(mcmcpp_hip_sampler* h, const void* device_
     NOT_WHILE_ASYNC("evidence_ratios_device");
     return h->evidence_ratios(mcmcpp::EvidenceRequest{"evidence_ratios_device", nullptr, device_steps, true, chain_stride_steps, n_steps, slice_interval,
                                                       mcmcpp::EvidenceOutputs{log_ratio, mcse, ess, kish, max_u, nonfinite, log_ratio_total, mcse_total, num_draws}});
+}
+int mcmcpp_hip_evidence_bridge(mcmcpp_hip_sampler* h, const void* const* steps, int64_t n_steps, int64_t slice_interval, double* log_ratio, double* mcse,
+                               double* overlap, double* ess, int64_t* passes, int64_t* converged, int64_t* nonfinite, double* log_ratio_total, double* mcse_total,
+                               int64_t* num_draws)
+{
+    NEED_H;
+    NOT_WHILE_ASYNC("evidence_bridge");
+    return h->evidence_bridge(mcmcpp::BridgeRequest{mcmcpp::EvidenceRequest{"evidence_bridge", steps, nullptr, false, 0, n_steps, slice_interval, mcmcpp::EvidenceOutputs{}},
+                                                    mcmcpp::BridgeOutputs{log_ratio, mcse, overlap, ess, passes, converged, nonfinite, log_ratio_total, mcse_total, num_draws}});
+}
+int mcmcpp_hip_evidence_bridge_device(mcmcpp_hip_sampler* h, const void* device_steps, int64_t chain_stride_steps, int64_t n_steps, int64_t slice_interval,
+                                      double* log_ratio, double* mcse, double* overlap, double* ess, int64_t* passes, int64_t* converged, int64_t* nonfinite,
+                                      double* log_ratio_total, double* mcse_total, int64_t* num_draws)
+{
+    NEED_H;
+    NOT_WHILE_ASYNC("evidence_bridge_device");
+    return h->evidence_bridge(
+        mcmcpp::BridgeRequest{mcmcpp::EvidenceRequest{"evidence_bridge_device", nullptr, device_steps, true, chain_stride_steps, n_steps, slice_interval, mcmcpp::EvidenceOutputs{}},
+                              mcmcpp::BridgeOutputs{log_ratio, mcse, overlap, ess, passes, converged, nonfinite, log_ratio_total, mcse_total, num_draws}});
 }
 int mcmcpp_hip_run(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step)
 {

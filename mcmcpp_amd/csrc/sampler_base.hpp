@@ -40,6 +40,20 @@ struct EvidenceRequest
     EvidenceOutputs out;
     int32_t dtype = 0, device = -1, K = 0, W = 0, D = 0;
 };
+// What mcmcpp_hip_evidence_bridge writes (any pointer may be null), and one call: the request of the ratios with these outputs
+// (q.out is not used).  bridge.hip does the rest.
+struct BridgeOutputs
+{
+    double *log_ratio, *mcse, *overlap, *ess;
+    int64_t *passes, *converged, *nonfinite;
+    double *log_ratio_total, *mcse_total;
+    int64_t* num_draws;
+};
+struct BridgeRequest
+{
+    EvidenceRequest q;
+    BridgeOutputs out;
+};
 }  // namespace mcmcpp
 
 struct mcmcpp_hip_sampler
@@ -111,6 +125,12 @@ struct mcmcpp_hip_sampler
     {
         return fail(MCMCPP_HIP_E_UNSUPPORTED,
                     "%s: evidence ratios are for stretch-move handles with a device calculator only (not the differential-evolution mover, not a batch target)", q.what);
+    }
+    // the bridge estimate of the same ratios (mcmcpp_hip_evidence_bridge): likewise
+    virtual int evidence_bridge(mcmcpp::BridgeRequest b)
+    {
+        return fail(MCMCPP_HIP_E_UNSUPPORTED,
+                    "%s: evidence ratios are for stretch-move handles with a device calculator only (not the differential-evolution mover, not a batch target)", b.q.what);
     }
     // stored steps and log-posteriors that stay in device memory (mcmcpp_hip_run_device, mcmcpp_hip_calc_logp_device): every
     // mover overrides both
@@ -368,4 +388,8 @@ mcmcpp_hip_sampler* make_batch_sampler(const mcmcpp_hip_config& cfg, int* rc);
 // the body of mcmcpp_hip_evidence_ratios behind the handle's refusals (evidence.hip): q's shape is the handle's, whose
 // calc_logp_device evaluates the draws and whose message slot takes a failure's words
 int evidence_compute(mcmcpp_hip_sampler& h, const EvidenceRequest& q);
+// its checks that need no device, shared with the bridge: the used steps of a rung, or the refusal
+int evidence_check(mcmcpp_hip_sampler& h, const EvidenceRequest& q, long long* used_steps);
+// the body of mcmcpp_hip_evidence_bridge, likewise (bridge.hip)
+int bridge_compute(mcmcpp_hip_sampler& h, const BridgeRequest& b);
 }  // namespace mcmcpp
