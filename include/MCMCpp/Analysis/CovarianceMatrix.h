@@ -42,7 +42,7 @@ public:
 
     CovarianceMatrix(int numParams, int numWalkers)
         : pCount(numParams), wCount(numWalkers), covarMat(static_cast<size_t>(numParams) * numParams, ParamType(0)),
-          corrMat(static_cast<size_t>(numParams) * numParams, ParamType(0)), handle(nullptr)
+          corrMat(static_cast<size_t>(numParams) * numParams, ParamType(0)), meanVec(static_cast<size_t>(numParams), ParamType(0)), handle(nullptr)
     {
         assert(pCount > 0);
         assert(wCount > 0);
@@ -68,7 +68,7 @@ public:
             const std::int64_t used = (span.steps + sliceInterval - 1) / sliceInterval;
             if (used == 0) return;
             check("mcmcpp_hip_moments_add_device_steps_strided", mcmcpp_hip_moments_add_device_steps_strided(handle, span.first, used, sliceInterval));
-            check("mcmcpp_hip_moments_finish", mcmcpp_hip_moments_finish(handle, nullptr, nullptr, covarMat.data(), corrMat.data()));
+            check("mcmcpp_hip_moments_finish", mcmcpp_hip_moments_finish(handle, nullptr, meanVec.data(), covarMat.data(), corrMat.data()));
             return;
         }
         if (!Detail::pointersStay(start))  // a device chain with the device path switched off: the selected steps, downloaded
@@ -77,7 +77,7 @@ public:
             const std::int64_t used = Detail::downloadSteps(start, end, sliceInterval, staging);
             if (used == 0) return;
             check("mcmcpp_hip_moments_add_steps", mcmcpp_hip_moments_add_steps(handle, staging.data(), used, 1));
-            check("mcmcpp_hip_moments_finish", mcmcpp_hip_moments_finish(handle, nullptr, nullptr, covarMat.data(), corrMat.data()));
+            check("mcmcpp_hip_moments_finish", mcmcpp_hip_moments_finish(handle, nullptr, meanVec.data(), covarMat.data(), corrMat.data()));
             return;
         }
         // gather runs of selected steps that lie sliceInterval steps apart in memory: one upload call per run
@@ -101,11 +101,13 @@ public:
         }
         if (runLength > 0) check("mcmcpp_hip_moments_add_steps", mcmcpp_hip_moments_add_steps(handle, runStart, runLength, sliceInterval));
         if (used == 0) return;  // (the reference would divide by zero here)
-        check("mcmcpp_hip_moments_finish", mcmcpp_hip_moments_finish(handle, nullptr, nullptr, covarMat.data(), corrMat.data()));
+        check("mcmcpp_hip_moments_finish", mcmcpp_hip_moments_finish(handle, nullptr, meanVec.data(), covarMat.data(), corrMat.data()));
     }
 
     ParamType getCovarianceMatrixElement(int row, int col) { return covarMat[static_cast<size_t>(row) * pCount + col]; }
     ParamType getCorrelationMatrixElement(int row, int col) { return corrMat[static_cast<size_t>(row) * pCount + col]; }
+    /// The mean of parameter `param` over the samples of the last calculateCovar (not in the reference, which keeps it private).
+    ParamType getMean(int param) { return meanVec[static_cast<size_t>(param)]; }
 
 private:
     void check(const char* what, int rc) const
@@ -122,6 +124,7 @@ private:
     int wCount;
     std::vector<ParamType> covarMat;
     std::vector<ParamType> corrMat;
+    std::vector<ParamType> meanVec;
     mcmcpp_hip_moments* handle;
 };
 

@@ -31,6 +31,7 @@
 #include "../Utility/NoAction.h"
 #include "../Utility/UserOjbectsTest.h"
 #include "Calculators.h"
+#include "GaussianBridge.h"
 #include "HipBackend.h"
 
 namespace MCMC
@@ -278,6 +279,14 @@ public:
         if (redraws) *redraws = r;
     }
     int deviceCount() const { return static_cast<int>(ranks.size()); }
+
+    /// The log-evidence of the sampled target from the chain as it stands (Device/GaussianBridge.h): a Gaussian fitted to the
+    /// first half of every sliceInterval'th stored step behind the first burnIn, bridged with the second half against proposals
+    /// from pcg64(seed, 0).  A device chain is read in place.  One device only: the library refuses a split ensemble.
+    GaussianBridgeEvidence gaussianBridgeEvidence(int burnIn = 0, int sliceInterval = 1, std::uint64_t seed = 0)
+    {
+        return Device::gaussianBridgeEvidence(ranks[0], 0, markovChain, numWalkers, numParams, burnIn, sliceInterval, seed);
+    }
 
     ChainType& chain() { return markovChain; }
 

@@ -81,6 +81,8 @@ public:
     using Core::diagnostics;
     /// The chain itself: memoryKind(), deviceSteps() and hostBytesFetched() of a device chain (MCMCPP_CHAIN_MEMORY=device).
     using Core::chain;
+    /// The log-evidence of the target by a bridge to a Gaussian fitted to the chain: gaussianBridgeEvidence(burnIn, sliceInterval, seed)
+    using Core::gaussianBridgeEvidence;
 
 private:
     int subSamplingInterval;

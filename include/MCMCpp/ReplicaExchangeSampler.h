@@ -29,6 +29,7 @@
 
 #include "Chain/Chain.h"
 #include "Device/Calculators.h"
+#include "Device/GaussianBridge.h"
 #include "Device/HipBackend.h"
 #include "Utility/UserOjbectsTest.h"
 
@@ -241,6 +242,15 @@ public:
                      mcmcpp_hip_evidence_bridge(handle.get(), steps.empty() ? nullptr : steps.data(), used, 1, r.logRatio.data(), r.mcse.data(), r.overlap.data(),
                                                 r.ess.data(), r.passes.data(), r.converged.data(), r.nonfinite.data(), &r.logRatioTotal, &r.mcseTotal, &r.numDraws));
         return r;
+    }
+
+    /// The log-evidence of ONE rung's target from that rung's chain alone (Device/GaussianBridge.h, mcmcpp_hip_evidence_gaussian):
+    /// a Gaussian fitted to the first half of the rung's used steps, bridged with the second half.  Where the top rung is not a
+    /// normalised density, this closes the chain of evidenceBridge's ratios.
+    GaussianBridgeEvidence gaussianBridgeEvidence(int rung, int burnIn = 0, int sliceInterval = 1, std::uint64_t seed = 0)
+    {
+        const std::size_t k = checkedRung(rung);
+        return Device::gaussianBridgeEvidence(handle, rung, *chains[k], numWalkers, numParams, burnIn, sliceInterval, seed);
     }
 
     /// Walker positions [K][W][D], log-posteriors [K][W] and per-walker accepted counts [K][W] as they stand on the device.

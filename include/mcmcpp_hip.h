@@ -478,6 +478,64 @@ int mcmcpp_hip_evidence_bridge_device(mcmcpp_hip_sampler* h, const void* device_
                                       int64_t slice_interval, double* log_ratio, double* mcse, double* overlap, double* ess, int64_t* passes,
                                       int64_t* converged, int64_t* nonfinite, double* log_ratio_total, double* mcse_total, int64_t* num_draws);
 
+/* The evidence of ONE chain's target from an ordinary run: the bridge between the target and a Gaussian q = N(mean, L L^T)
+ * fitted to its draws (Overstall & Forster 2010; Gronau et al. 2017).  q is normalised, so the bridge's log-ratio is
+ * log Z = log of the integral of exp(logp) itself.  No ladder is needed: num_chains may be 0 or 1.
+ *   draws      every slice_interval-th of the n_steps steps [W][D] of one chain, from the first on: n used steps, N = n W draws y_i
+ *              in the order i = s W + w.  `chain` selects the parameters, 0 <= chain < max(num_chains, 1).  Which part of a run
+ *              the steps are is the caller's choice: a Gaussian fitted to one part is bridged with the draws of another.
+ *   Gaussian   mean [D] and chol [D * D], row-major, the lower triangle L of which alone is read; double whatever the handle's
+ *              dtype.  MCMCPP_HIP_E_ARG for an entry that is read and is not finite, and for a diagonal entry that is not a
+ *              positive normal number.  MCMCPP_HIP_E_UNSUPPORTED for D > 64.
+ *   proposals  as many as draws.  Proposal j = 0 .. N - 1, coordinate d, takes the raw output r at position j D + d of the pcg64
+ *              engine seeded (seed, stream) as the samplers seed theirs: the caller's seed and stream, not the handle's -- no
+ *              stream of the handle is touched.  p = ((r >> 12) + 0.5) 2^-52, both operations exact; z_d = normal_score(p)
+ *              (mcmcpp_amd/csrc/normal_score.hpp).  x_i = mean_i + acc_i, where acc_i starts at +0 and takes + L[i][d] z[d] for
+ *              d = 0 .. i in ascending order, every product and every sum rounded on its own; x_i is then rounded once to the
+ *              handle's dtype.  The proposals are seen as n steps of W walkers in the same order j = s W + w.
+ *   log q      for a row x of the handle's dtype, widened exactly to double: z_i = ((x_i - mean_i) - t_i) / L[i][i] for
+ *              i = 0 .. D - 1, where t_i starts at +0 and takes + L[i][d] z[d] for d < i in ascending order; s starts at +0 and
+ *              takes + z_i z_i in ascending i; log q(x) = (-0.5 s) + k with k = -(the sum from +0, in ascending i, of
+ *              normal_score_log(L[i][i])) - D 0.91893853320467274178.  The rounded proposals and the draws go through the same
+ *              evaluation.
+ *   u          u0_j = logp(x_j) - log q(x_j) on the proposals, u1_i = log q(y_i) - logp(y_i) on the draws; logp is what
+ *              mcmcpp_hip_calc_logp_device returns for that row with that chain's parameters, widened to double exactly; one
+ *              subtraction each.  In the bridge's words the pair is (a, b) = (target, q).
+ *   estimate   From here on the definition is mcmcpp_hip_evidence_bridge's, word for word, on these two arrays: sigma, sum_tree, the
+ *              solver, the edges (a NaN or +inf u; no shared mass; a u of -inf has h = 0), mcse from both ESS calls, overlap,
+ *              passes, converged, nonfinite [2].  *log_evidence = c*.
+ *   outputs    *log_evidence, *mcse, *overlap double; ess [2] double; *passes, *converged int64; nonfinite [2] int64 (index 0:
+ *              the proposals, 1: the draws); *num_draws = N; proposals [N][D] of the handle's dtype: the rows as the calculator
+ *              saw them; log_q [2][N] double: row 0 of the proposals, row 1 of the draws.  Any may be NULL.  Nothing is written
+ *              to the outputs of a call that fails.
+ * Everything is fp64, every + - * / rounded on its own; no fused operation, no floating-point atomic.  No output depends on the
+ * CU count, the chunk size (MCMCPP_HIP_EVIDENCE_CHUNK_MB, as above: steps are uploaded, and proposals made and evaluated, a chunk
+ * at a time) or where the chain lies.  The call is a function of its arguments: it needs no set_state and leaves the walker
+ * state, the step streams and every counter as they are.  It holds 8 N bytes of device memory per u (two), and the proposals
+ * of a chunk, freed when it returns: MCMCPP_HIP_E_NOMEM with the byte count where they cannot be had.
+ *   steps         n_steps host pointers to steps [W][D] of the handle's dtype
+ *   device_steps  the chain in memory of the handle's device, step s at device_steps + s * W * D elements; read where it lies;
+ *                 the rows must satisfy mcmcpp_hip_calc_logp_device's alignment rule
+ * Every handle mcmcpp_hip_calc_logp_device serves is served: stretch-move handles of one or more chains,
+ * differential-evolution handles (chain 0) and batch targets (chain 0; the callback is called on the proposals where they were
+ * made, in a buffer that is 16-byte aligned).  Refusals: those of mcmcpp_hip_calc_logp_device with their codes, and
+ * MCMCPP_HIP_E_UNSUPPORTED for sharded handles, handles with a communicator and handles with caller-owned positions;
+ * MCMCPP_HIP_E_ARG for fewer than 4 used steps, slice_interval < 1, NULL steps, mean or chol, a chain out of range, a device
+ * pointer that is not memory of the handle's device or whose steps end outside its allocation; MCMCPP_HIP_E_STATE while an
+ * asynchronous run is in progress. */
+int mcmcpp_hip_evidence_gaussian(mcmcpp_hip_sampler* h, int32_t chain, const void* const* steps, int64_t n_steps, int64_t slice_interval,
+                                 const double* mean, const double* chol, uint64_t seed, uint64_t stream, double* log_evidence, double* mcse,
+                                 double* overlap, double* ess, int64_t* passes, int64_t* converged, int64_t* nonfinite, int64_t* num_draws,
+                                 void* proposals, double* log_q);
+int mcmcpp_hip_evidence_gaussian_device(mcmcpp_hip_sampler* h, int32_t chain, const void* device_steps, int64_t n_steps,
+                                        int64_t slice_interval, const double* mean, const double* chol, uint64_t seed, uint64_t stream,
+                                        double* log_evidence, double* mcse, double* overlap, double* ess, int64_t* passes, int64_t* converged,
+                                        int64_t* nonfinite, int64_t* num_draws, void* proposals, double* log_q);
+/* GPU time of the calling thread's last successful mcmcpp_hip_evidence_gaussian / _device call in its two own kernels, between HIP
+ * events recorded around every launch on the call's stream and summed over the chunks: the kernel that makes the proposals
+ * and the kernel that evaluates log q (on the proposals and on the draws).  Either pointer may be NULL. */
+void mcmcpp_hip_evidence_gaussian_last_timing(double* rows_ms, double* log_q_ms);
+
 /* ---- measurement ---------------------------------------------------------------------------------- */
 
 /* GPU time of the last mcmcpp_hip_run between HIP events recorded on the launch stream around the

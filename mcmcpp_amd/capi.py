@@ -32,7 +32,8 @@ EXPORTS = [
     "mcmcpp_hip_half_step_async", "mcmcpp_hip_bind_device_chain", "mcmcpp_hip_device_positions",
     "mcmcpp_hip_shard_span", "mcmcpp_hip_synchronize", "mcmcpp_hip_exchange_chains",
     "mcmcpp_hip_run_tempered", "mcmcpp_hip_run_tempered_device", "mcmcpp_hip_evidence_ratios", "mcmcpp_hip_evidence_ratios_device",
-    "mcmcpp_hip_evidence_bridge", "mcmcpp_hip_evidence_bridge_device",
+    "mcmcpp_hip_evidence_bridge", "mcmcpp_hip_evidence_bridge_device", "mcmcpp_hip_evidence_gaussian", "mcmcpp_hip_evidence_gaussian_device",
+    "mcmcpp_hip_evidence_gaussian_last_timing",
     "mcmcpp_hip_moments_create", "mcmcpp_hip_moments_destroy", "mcmcpp_hip_moments_reset", "mcmcpp_hip_moments_add_steps",
     "mcmcpp_hip_moments_add_device_steps", "mcmcpp_hip_moments_finish", "mcmcpp_hip_moments_last_error",
     "mcmcpp_hip_autocorr_times", "mcmcpp_hip_autocorr_times_device", "mcmcpp_hip_autocorr_last_error",
@@ -151,6 +152,13 @@ def lib():
             outputs = [vp] * 10  # log_ratio, mcse, overlap, ess, passes, converged, nonfinite, log_ratio_total, mcse_total, *num_draws
             L.mcmcpp_hip_evidence_bridge.argtypes = [vp, C.POINTER(vp), i64, i64] + outputs
             L.mcmcpp_hip_evidence_bridge_device.argtypes = [vp, vp, i64, i64, i64] + outputs
+        if hasattr(L, "mcmcpp_hip_evidence_gaussian"):  # (likewise)
+            # mean, chol, seed, stream; log_evidence, mcse, overlap, ess, passes, converged, nonfinite, *num_draws, proposals, log_q
+            tail = [vp, vp, C.c_uint64, C.c_uint64] + [vp] * 10
+            L.mcmcpp_hip_evidence_gaussian.argtypes = [vp, i32, C.POINTER(vp), i64, i64] + tail
+            L.mcmcpp_hip_evidence_gaussian_device.argtypes = [vp, i32, vp, i64, i64] + tail
+            L.mcmcpp_hip_evidence_gaussian_last_timing.argtypes = [dp, dp]
+            L.mcmcpp_hip_evidence_gaussian_last_timing.restype = None
         if hasattr(L, "mcmcpp_hip_moments_create"):  # (absent only from older experiment builds selected with MCMCPP_HIP_LIB)
             L.mcmcpp_hip_moments_create.argtypes = [i32, i32, i32, i32, C.POINTER(vp)]
             L.mcmcpp_hip_moments_destroy.argtypes = [vp]
@@ -701,6 +709,60 @@ class HipSampler:
             out[key] = out[key][:, :K - 1]
         out["log_ratio_total"], out["mcse_total"] = np.float64(totals[0]), np.float64(totals[1])
         out["num_draws"] = draws.value
+        return out
+
+    def evidence_gaussian(self, steps, chain=0, mean=None, chol=None, fit_fraction=0.5, slice_interval=1, seed=0, stream=0, want_proposals=False):
+        """The log-evidence of chain `chain`'s target from stored steps of that chain, by the bridge estimate between the target
+        and a Gaussian N(mean, chol chol^T) (mcmcpp_hip_evidence_gaussian): no ladder is needed.  steps: a numpy array [n][W][D],
+        or a device tensor of that shape (run_device's, or a view behind a burn-in), read in place
+        (mcmcpp_hip_evidence_gaussian_device).  Every slice_interval-th step is used.  With mean and chol given, all used steps are
+        bridged against as many proposals from pcg64(seed, stream).  With both omitted, the Gaussian is fitted to the first
+        fit_fraction of the used steps (HipMoments' mean and covariance, numpy's Cholesky factor) and the rest are bridged.
+        Returns a dict: log_evidence, mcse, overlap (floats), ess [2], nonfinite [2] (index 0: the proposals, 1: the draws), passes,
+        converged, num_draws, log_q [2][N], the mean and chol used and, with want_proposals, proposals [N][D]."""
+        if (mean is None) != (chol is None):
+            raise ValueError("mean and chol go together")
+        tensor = _is_tensor(steps)
+        if not tensor:
+            steps = np.asarray(steps)
+            if steps.ndim != 3 or steps.shape[1:] != (self.W, self.D) or steps.dtype != self.np_t:
+                raise ValueError("steps must be a %s array (n, %d, %d)" % (np.dtype(self.np_t).name, self.W, self.D))
+        if mean is None:
+            used = (steps.shape[0] + slice_interval - 1) // slice_interval
+            head = int(used * fit_fraction) * slice_interval  # the steps the fit takes; the bridge starts behind them
+            if head < 1 or head >= steps.shape[0]:
+                raise ValueError("fit_fraction %r leaves no steps to fit on, or none to bridge on" % (fit_fraction,))
+            m = HipMoments(self.W, self.D, self.dtype, self.cfg.device)
+            try:
+                (m.add_device_steps if tensor else m.add_steps)(steps[:head], slice_interval=slice_interval)
+                _, mean, cov, _ = m.finish()
+            finally:
+                m.close()
+            chol = np.linalg.cholesky(cov.astype(np.float64))
+            steps = steps[head:]
+        mean = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
+        chol = np.ascontiguousarray(chol, dtype=np.float64)
+        if mean.shape != (self.D,) or chol.shape != (self.D, self.D):
+            raise ValueError("mean must have shape (%d,) and chol (%d, %d)" % (self.D, self.D, self.D))
+        n = int(steps.shape[0])
+        N = max((n + slice_interval - 1) // slice_interval, 0) * self.W
+        figures = np.full(3, np.nan)
+        ess, counts, nonfinite = np.full(2, np.nan), np.zeros(3, np.int64), np.zeros(2, np.int64)
+        log_q = np.full((2, N), np.nan)
+        proposals = np.zeros((N, self.D), self.np_t) if want_proposals else None
+        tail = [_ptr(mean), _ptr(chol), C.c_uint64(seed), C.c_uint64(stream)] + [C.c_void_p(figures.ctypes.data + 8 * j) for j in range(3)] + [_ptr(ess)]
+        tail += [C.c_void_p(counts.ctypes.data), C.c_void_p(counts.ctypes.data + 8), _ptr(nonfinite), C.c_void_p(counts.ctypes.data + 16), _ptr(proposals), _ptr(log_q)]
+        if tensor:
+            ptr, n = _device_steps(steps, None, self.W, self.D, self.dtype, self.cfg.device)
+            self._check(lib().mcmcpp_hip_evidence_gaussian_device(self.h, chain, C.c_void_p(ptr), n, slice_interval, *tail))
+        else:
+            rows = [np.ascontiguousarray(steps[s]) for s in range(n)]  # (a contiguous step is not copied)
+            ptrs = (C.c_void_p * max(n, 1))(*[r.ctypes.data for r in rows])
+            self._check(lib().mcmcpp_hip_evidence_gaussian(self.h, chain, ptrs, n, slice_interval, *tail))
+        out = dict(log_evidence=np.float64(figures[0]), mcse=np.float64(figures[1]), overlap=np.float64(figures[2]), ess=ess, passes=np.int64(counts[0]),
+                   converged=np.int64(counts[1]), nonfinite=nonfinite, num_draws=int(counts[2]), log_q=log_q, mean=mean, chol=chol)
+        if want_proposals:
+            out["proposals"] = proposals
         return out
 
     def last_run_timing(self):

@@ -347,6 +347,12 @@ public:
         HIP_TRY(hipStreamSynchronize(stream));
         return MCMCPP_HIP_OK;
     }
+    // (the callback sees the proposals of the Gaussian where gaussian_bridge.hip made them)
+    int evidence_gaussian(GaussianBridgeRequest g) override
+    {
+        if (!fn) return fail(MCMCPP_HIP_E_STATE, "%s: no batch calculator (mcmcpp_hip_set_batch_calculator)", g.q.what);
+        return gaussian_evidence(g, 1);
+    }
 
     int set_chain_params(int32_t, const void*, int32_t) override
     {

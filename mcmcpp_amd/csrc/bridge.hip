@@ -12,6 +12,8 @@
 //     The final pass writes h over u: the chain the effective sample size is computed on.
 //   * bridge_close_kernel: one block: a thread adds the tile sums of a slice of one quantity in ascending order, then one thread
 //     per quantity adds its slice sums in ascending order.  The host reads back four doubles (six behind the final pass).
+// One pair, from its two u arrays to its figures (the solve, the final sums, the two ESS calls, the edges), is
+// bridge_pair_compute (bridge_pair.hpp): this file calls it per pair of rungs, gaussian_bridge.hip on (target, fitted Gaussian).
 // No atomics on doubles, and nothing depends on the CU count, the chunk size or where a chain lies.
 #include <hip/hip_runtime.h>
 
@@ -22,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "bridge_pair.hpp"
 #include "bridge_plan.hpp"
 #include "evidence_kernels.hpp"
 #include "evidence_plan.hpp"
@@ -140,25 +143,20 @@ int run_request(mcmcpp_hip_sampler& h, const mcmcpp::BridgeRequest& b, long long
     if (q.on_device)
         if (int rc = mcmcpp::check_device_steps(slot, q.what, q.device_steps, step_bytes * (size_t)((K - 1) * chain_stride_steps + q.n_steps), q.device)) return rc;
 
-    // h_d(c*) as the ESS call sees it: a chain of one rung, n steps of W walkers of one parameter, split
-    const mcmcpp::RhatRequest ess_request = mcmcpp::rhat_device_request("effective_sample_size_device", MCMCPP_HIP_F64, q.device, nullptr, 1, 0, n, 1, W, 1, 1);
-    const mcmcpp::RhatShape ess_shape = mcmcpp::rhat_shape(1, n, W, 1);
-
     const long long per = mcmcpp::evidence_steps_per_chunk(mcmcpp::chunk_bytes_from_env("MCMCPP_HIP_EVIDENCE_CHUNK_MB", 1024), step_bytes, q.on_device, q.slice);
     const long long chunk_steps = n < per ? n : per, chunk_draws = chunk_steps * W;
-    const mcmcpp::BridgePlan plan = mcmcpp::bridge_plan(N);
     if (!mcmcpp::evidence_grid_fits(chunk_draws)) return fail(MCMCPP_HIP_E_ARG, w + ": too many draws in a chunk for a launch grid (lower MCMCPP_HIP_EVIDENCE_CHUNK_MB)");
     if (!mcmcpp::bridge_grid_fits(N)) return fail(MCMCPP_HIP_E_ARG, w + ": too many draws of a rung for a launch grid");
 
     mcmcpp::DeviceBuffer<> d_chunk;
     mcmcpp::DeviceBuffer<T> d_lp;
-    mcmcpp::DeviceBuffer<double> d_u[3], d_tiles, d_slices, d_out;
+    mcmcpp::DeviceBuffer<double> d_u[3];
+    mcmcpp::BridgePairScratch scratch;
     mcmcpp::DeviceBuffer<EvidenceState> d_state;
     mcmcpp::Stream stream;  // (behind the buffers: the stream is idle and gone when they go)
     ANALYSIS_TRY(slot, hipStreamCreateWithFlags(stream.replace(), hipStreamNonBlocking));
     if (!q.on_device && d_chunk.alloc(step_bytes * (size_t)chunk_steps) != hipSuccess) return fail(MCMCPP_HIP_E_NOMEM, w + ": cannot allocate the upload buffer");
-    if (d_lp.alloc(sizeof(T) * 3 * (size_t)chunk_draws) != hipSuccess || d_tiles.alloc(8 * plan.tile_sum_doubles) != hipSuccess ||
-        d_slices.alloc(8 * plan.slice_sum_doubles) != hipSuccess || d_out.alloc(8 * 6) != hipSuccess || d_state.alloc(2 * sizeof(EvidenceState)) != hipSuccess)
+    if (d_lp.alloc(sizeof(T) * 3 * (size_t)chunk_draws) != hipSuccess || scratch.alloc(N) != hipSuccess || d_state.alloc(2 * sizeof(EvidenceState)) != hipSuccess)
         return fail(MCMCPP_HIP_E_NOMEM, w + ": cannot allocate the log-posteriors of a chunk");
     for (int j = 0; j < mcmcpp::bridge_buffers(K); ++j)
         if (d_u[j].alloc(8 * (size_t)N) != hipSuccess)
@@ -210,47 +208,11 @@ int run_request(mcmcpp_hip_sampler& h, const mcmcpp::BridgeRequest& b, long long
         const size_t at0 = (size_t)mcmcpp::evidence_index(K, 0, p), at1 = (size_t)mcmcpp::evidence_index(K, 1, p);
         if (bad[at0] || bad[at1]) continue;  // a NaN or +inf u: the figures of this pair stay NaN
         double* const u[2] = {d_u[mcmcpp::bridge_buffer_of(0, p)].get(), d_u[mcmcpp::bridge_buffer_of(1, p)].get()};
-        const auto eval = [&](double c, bool final, mcmcpp::BridgeSums* s) -> int {
-            const dim3 grid(plan.grid_x, plan.grid_y), block(kBridgeThreads);
-            if (final)
-                hipLaunchKernelGGL(bridge_pass_kernel<true>, grid, block, 0, stream, u[0], u[1], N, plan.tiles, c, d_tiles.get());
-            else
-                hipLaunchKernelGGL(bridge_pass_kernel<false>, grid, block, 0, stream, u[0], u[1], N, plan.tiles, c, d_tiles.get());
-            hipLaunchKernelGGL(bridge_close_kernel, dim3(1), block, 0, stream, (const double*)d_tiles.get(), plan.tiles, plan.slices, final ? 3 : 2, d_slices.get(), d_out.get());
-            ANALYSIS_TRY(slot, hipGetLastError());
-            double r[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-            ANALYSIS_TRY(slot, hipMemcpyAsync(r, d_out.get(), 8 * (final ? 6 : 4), hipMemcpyDeviceToHost, stream));
-            ANALYSIS_TRY(slot, hipStreamSynchronize(stream));
-            for (int d = 0; d < 2; ++d) s->S[d] = r[d], s->Q[d] = r[2 + d], s->H[d] = r[4 + d];
-            return MCMCPP_HIP_OK;
-        };
-        mcmcpp::BridgeRoot root;
-        if (int src_rc = mcmcpp::bridge_solve(eval, &root)) return src_rc;
-        passes[(size_t)p] = root.passes;
-        converged[(size_t)p] = root.converged;
-        if (root.at.S[0] == 0.0 || root.at.S[1] == 0.0)  // no mass is shared at double precision
-        {
-            overlap[(size_t)p] = 0.0;
-            continue;
-        }
-        const double Nd = (double)N;
-        double sum = 0.0;
-        for (int d = 0; d < 2; ++d)
-        {
-            const double mean = root.at.S[d] / Nd, var = root.at.H[d] / Nd - mean * mean;
-            const double rel2 = (var > 0.0 ? var : 0.0) / (mean * mean);
-            mcmcpp::RhatRequest chain = ess_request;
-            chain.device_steps = u[d];
-            mcmcpp::EssOutputs eo{};
-            double ess_value = nan;
-            eo.ess = &ess_value;
-            if (int erc = mcmcpp::nested_result(slot, q.what, mcmcpp::ess_compute(slot, chain, 0, 0, prop, n, ess_shape, stream, eo))) return erc;
-            ess[d == 0 ? at0 : at1] = ess_value;
-            sum = sum + (rel2 == 0.0 ? 0.0 : rel2 / ess_value);
-        }
-        log_ratio[(size_t)p] = root.c;
-        overlap[(size_t)p] = (root.at.S[0] + root.at.S[1]) / Nd;
-        mcse[(size_t)p] = std::sqrt(sum);
+        mcmcpp::BridgePairFigures f;
+        if (int prc = mcmcpp::bridge_pair_compute(slot, q.what, q.device, prop, stream, scratch, u, n, W, &f)) return prc;
+        log_ratio[(size_t)p] = f.log_ratio, mcse[(size_t)p] = f.mcse, overlap[(size_t)p] = f.overlap;
+        ess[at0] = f.ess[0], ess[at1] = f.ess[1];
+        passes[(size_t)p] = f.passes, converged[(size_t)p] = f.converged;
     }
 
     // the call has succeeded: the outputs
@@ -283,6 +245,62 @@ int run_request(mcmcpp_hip_sampler& h, const mcmcpp::BridgeRequest& b, long long
 
 namespace mcmcpp
 {
+int bridge_pair_compute(std::string& slot, const char* what, int device, const hipDeviceProp_t& prop, hipStream_t stream, const BridgePairScratch& scratch,
+                        double* const u[2], long long n, int W, BridgePairFigures* out)
+{
+    const BridgePlan& plan = scratch.plan;
+    const long long N = n * W;
+    // h_d(c*) as the ESS call sees it: a chain of one rung, n steps of W walkers of one parameter, split
+    const RhatRequest ess_request = rhat_device_request("effective_sample_size_device", MCMCPP_HIP_F64, device, nullptr, 1, 0, n, 1, W, 1, 1);
+    const RhatShape ess_shape = rhat_shape(1, n, W, 1);
+    const auto eval = [&](double c, bool final, BridgeSums* s) -> int {
+        const dim3 grid(plan.grid_x, plan.grid_y), block(kBridgeThreads);
+        if (final)
+            hipLaunchKernelGGL(bridge_pass_kernel<true>, grid, block, 0, stream, u[0], u[1], N, plan.tiles, c, scratch.tiles.get());
+        else
+            hipLaunchKernelGGL(bridge_pass_kernel<false>, grid, block, 0, stream, u[0], u[1], N, plan.tiles, c, scratch.tiles.get());
+        hipLaunchKernelGGL(bridge_close_kernel, dim3(1), block, 0, stream, (const double*)scratch.tiles.get(), plan.tiles, plan.slices, final ? 3 : 2, scratch.slices.get(),
+                           scratch.out.get());
+        ANALYSIS_TRY(slot, hipGetLastError());
+        double r[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        ANALYSIS_TRY(slot, hipMemcpyAsync(r, scratch.out.get(), 8 * (final ? 6 : 4), hipMemcpyDeviceToHost, stream));
+        ANALYSIS_TRY(slot, hipStreamSynchronize(stream));
+        for (int d = 0; d < 2; ++d) s->S[d] = r[d], s->Q[d] = r[2 + d], s->H[d] = r[4 + d];
+        return MCMCPP_HIP_OK;
+    };
+    BridgePairFigures f;
+    BridgeRoot root;
+    if (int rc = bridge_solve(eval, &root)) return rc;
+    f.passes = root.passes;
+    f.converged = root.converged;
+    if (root.at.S[0] == 0.0 || root.at.S[1] == 0.0)  // no mass is shared at double precision
+    {
+        f.overlap = 0.0;
+        *out = f;
+        return MCMCPP_HIP_OK;
+    }
+    const double Nd = (double)N;
+    double sum = 0.0;
+    for (int d = 0; d < 2; ++d)
+    {
+        const double mean = root.at.S[d] / Nd, var = root.at.H[d] / Nd - mean * mean;
+        const double rel2 = (var > 0.0 ? var : 0.0) / (mean * mean);
+        RhatRequest chain = ess_request;
+        chain.device_steps = u[d];
+        EssOutputs eo{};
+        double ess_value = std::numeric_limits<double>::quiet_NaN();
+        eo.ess = &ess_value;
+        if (int erc = nested_result(slot, what, ess_compute(slot, chain, 0, 0, prop, n, ess_shape, stream, eo))) return erc;
+        f.ess[d] = ess_value;
+        sum = sum + (rel2 == 0.0 ? 0.0 : rel2 / ess_value);
+    }
+    f.log_ratio = root.c;
+    f.overlap = (root.at.S[0] + root.at.S[1]) / Nd;
+    f.mcse = std::sqrt(sum);
+    *out = f;
+    return MCMCPP_HIP_OK;
+}
+
 int bridge_compute(mcmcpp_hip_sampler& h, const BridgeRequest& b)
 {
     long long n = 0;  // every check that needs no device: those of the ratios

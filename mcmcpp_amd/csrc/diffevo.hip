@@ -339,6 +339,7 @@ public:
         if (chain != 0) return fail(MCMCPP_HIP_E_ARG, "calc_logp_device: chain %d, but a differential-evolution handle holds one ensemble (chain 0)", chain);
         return kernel_calc_logp_device(calc_fn, d_params, pos, count, out);
     }
+    int evidence_gaussian(GaussianBridgeRequest g) override { return gaussian_evidence(g, 1); }
 
     int half_step_async(int32_t, int64_t) override { return unsupported("half_step_async"); }
     int bind_device_chain(void*, int64_t) override { return unsupported("bind_device_chain"); }

@@ -3,7 +3,8 @@
 //   * evidence_diff_kernel: thread = a draw of the chunk: u = (double)logp_other - (double)logp_own, stored at the draw's place
 //     of the buffer [N]; the block's largest u that is neither NaN nor +inf (as a key whose unsigned order is the
 //     doubles' order, -0 below +0) and its counts of non-finite u and of NaN or +inf among them, first in LDS, then one
-//     integer atomic each per block: a maximum and two integer sums, which no order of arrival changes.
+//     integer atomic each per block: a maximum and two integer sums, which no order of arrival changes (evidence_note_u, which
+//     the differences kernel of gaussian_bridge.hip calls too).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -34,18 +35,15 @@ inline double evidence_key_value(unsigned long long key)
     return u;
 }
 
-template <class T>
-__global__ void __launch_bounds__(kEvidenceThreads)
-evidence_diff_kernel(const T* __restrict__ lp_other, const T* __restrict__ lp_own, long long count, double* __restrict__ u_out, EvidenceState* __restrict__ state)
+// What a block of a differences kernel does with its u (every thread of the block calls it; `live`: the thread has a draw):
+// the block's maximum and counts first in LDS, then one integer atomic each on *state
+__device__ inline void evidence_note_u(double u, bool live, EvidenceState* __restrict__ state)
 {
     __shared__ unsigned long long s_max, s_nonfinite, s_bad;
     if (threadIdx.x == 0) s_max = 0, s_nonfinite = 0, s_bad = 0;
     __syncthreads();
-    const long long i = (long long)blockIdx.x * kEvidenceThreads + threadIdx.x;
-    if (i < count)
+    if (live)
     {
-        const double u = (double)lp_other[i] - (double)lp_own[i];
-        u_out[i] = u;
         const bool nan = u != u, pinf = u == __builtin_inf(), ninf = u == -__builtin_inf();
         if (nan || pinf || ninf) atomicAdd(&s_nonfinite, 1ULL);
         if (nan || pinf)
@@ -60,5 +58,19 @@ evidence_diff_kernel(const T* __restrict__ lp_other, const T* __restrict__ lp_ow
         if (s_nonfinite) atomicAdd(&state->nonfinite, s_nonfinite);
         if (s_bad) atomicAdd(&state->bad, s_bad);
     }
+}
+
+template <class T>
+__global__ void __launch_bounds__(kEvidenceThreads)
+evidence_diff_kernel(const T* __restrict__ lp_other, const T* __restrict__ lp_own, long long count, double* __restrict__ u_out, EvidenceState* __restrict__ state)
+{
+    const long long i = (long long)blockIdx.x * kEvidenceThreads + threadIdx.x;
+    double u = 0.0;
+    if (i < count)
+    {
+        u = (double)lp_other[i] - (double)lp_own[i];
+        u_out[i] = u;
+    }
+    evidence_note_u(u, i < count, state);
 }
 }  // namespace mcmcpp

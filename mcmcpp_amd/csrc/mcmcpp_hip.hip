@@ -1077,6 +1077,12 @@ public:
         b.q.device = device, b.q.K = K, b.q.W = W, b.q.D = D;
         return bridge_compute(*this, b);
     }
+    // The evidence of one chain's target by a bridge to a fitted Gaussian (gaussian_bridge.hip): one chain will do
+    int evidence_gaussian(GaussianBridgeRequest g) override
+    {
+        if (int rc = chain_params_supported(g.q.what)) return rc;
+        return gaussian_evidence(g, K);
+    }
 
     // A run with its replica-exchange rounds inside the launch sequence (temper_plan.hpp has the schedule).  It is a run like
     // any other -- run_entry, run_whole, whichever way the stored steps travel -- whose enqueue_steps cuts the step launches at
@@ -1757,6 +1763,26 @@ int mcmcpp_hip_evidence_bridge_device(mcmcpp_hip_sampler* h, const void* device_
     return h->evidence_bridge(
         mcmcpp::BridgeRequest{mcmcpp::EvidenceRequest{"evidence_bridge_device", nullptr, device_steps, true, chain_stride_steps, n_steps, slice_interval, mcmcpp::EvidenceOutputs{}},
                               mcmcpp::BridgeOutputs{log_ratio, mcse, overlap, ess, passes, converged, nonfinite, log_ratio_total, mcse_total, num_draws}});
+}
+int mcmcpp_hip_evidence_gaussian(mcmcpp_hip_sampler* h, int32_t chain, const void* const* steps, int64_t n_steps, int64_t slice_interval, const double* mean,
+                                 const double* chol, uint64_t seed, uint64_t stream, double* log_evidence, double* mcse, double* overlap, double* ess, int64_t* passes,
+                                 int64_t* converged, int64_t* nonfinite, int64_t* num_draws, void* proposals, double* log_q)
+{
+    NEED_H;
+    NOT_WHILE_ASYNC("evidence_gaussian");
+    return h->evidence_gaussian(mcmcpp::GaussianBridgeRequest{
+        mcmcpp::EvidenceRequest{"evidence_gaussian", steps, nullptr, false, 0, n_steps, slice_interval, mcmcpp::EvidenceOutputs{}}, chain, mean, chol, seed, stream,
+        mcmcpp::GaussianBridgeOutputs{log_evidence, mcse, overlap, ess, passes, converged, nonfinite, num_draws, proposals, log_q}});
+}
+int mcmcpp_hip_evidence_gaussian_device(mcmcpp_hip_sampler* h, int32_t chain, const void* device_steps, int64_t n_steps, int64_t slice_interval, const double* mean,
+                                        const double* chol, uint64_t seed, uint64_t stream, double* log_evidence, double* mcse, double* overlap, double* ess,
+                                        int64_t* passes, int64_t* converged, int64_t* nonfinite, int64_t* num_draws, void* proposals, double* log_q)
+{
+    NEED_H;
+    NOT_WHILE_ASYNC("evidence_gaussian_device");
+    return h->evidence_gaussian(mcmcpp::GaussianBridgeRequest{
+        mcmcpp::EvidenceRequest{"evidence_gaussian_device", nullptr, device_steps, true, 0, n_steps, slice_interval, mcmcpp::EvidenceOutputs{}}, chain, mean, chol, seed,
+        stream, mcmcpp::GaussianBridgeOutputs{log_evidence, mcse, overlap, ess, passes, converged, nonfinite, num_draws, proposals, log_q}});
 }
 int mcmcpp_hip_run(mcmcpp_hip_sampler* h, int64_t n_saved, int32_t interval, void* chain_out, uint32_t* accepted_per_step)
 {

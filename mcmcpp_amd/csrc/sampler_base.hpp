@@ -54,6 +54,23 @@ struct BridgeRequest
     EvidenceRequest q;
     BridgeOutputs out;
 };
+// What mcmcpp_hip_evidence_gaussian writes (any pointer may be null), and one call: the steps of ONE chain in q (q.K is 1 and
+// q.chain_stride_steps 0; q.out is not used), the Gaussian and the proposals' stream.  gaussian_bridge.hip does the rest.
+struct GaussianBridgeOutputs
+{
+    double *log_evidence, *mcse, *overlap, *ess;
+    int64_t *passes, *converged, *nonfinite, *num_draws;
+    void* proposals;
+    double* log_q;
+};
+struct GaussianBridgeRequest
+{
+    EvidenceRequest q;
+    int32_t chain;
+    const double *mean, *chol;
+    uint64_t seed, stream;
+    GaussianBridgeOutputs out;
+};
 }  // namespace mcmcpp
 
 struct mcmcpp_hip_sampler
@@ -132,6 +149,8 @@ struct mcmcpp_hip_sampler
         return fail(MCMCPP_HIP_E_UNSUPPORTED,
                     "%s: evidence ratios are for stretch-move handles with a device calculator only (not the differential-evolution mover, not a batch target)", b.q.what);
     }
+    // the evidence of one chain's target by a bridge to a fitted Gaussian (mcmcpp_hip_evidence_gaussian): every mover overrides it
+    virtual int evidence_gaussian(mcmcpp::GaussianBridgeRequest g) { return fail(MCMCPP_HIP_E_UNSUPPORTED, "%s: not available for this handle", g.q.what); }
     // stored steps and log-posteriors that stay in device memory (mcmcpp_hip_run_device, mcmcpp_hip_calc_logp_device): every
     // mover overrides both
     virtual int run_device(int64_t, int32_t, void*, uint32_t*) { return fail(MCMCPP_HIP_E_UNSUPPORTED, "run_device: not available for this handle"); }
@@ -392,4 +411,7 @@ int evidence_compute(mcmcpp_hip_sampler& h, const EvidenceRequest& q);
 int evidence_check(mcmcpp_hip_sampler& h, const EvidenceRequest& q, long long* used_steps);
 // the body of mcmcpp_hip_evidence_bridge, likewise (bridge.hip)
 int bridge_compute(mcmcpp_hip_sampler& h, const BridgeRequest& b);
+// the body of mcmcpp_hip_evidence_gaussian behind the handle's refusals (gaussian_bridge.hip): g.q's shape is the handle's, whose
+// calc_logp_device evaluates the draws and the proposals with chain g.chain's parameters
+int gaussian_bridge_compute(mcmcpp_hip_sampler& h, const GaussianBridgeRequest& g);
 }  // namespace mcmcpp

@@ -399,6 +399,16 @@ protected:
         return MCMCPP_HIP_OK;
     }
 
+    // mcmcpp_hip_evidence_gaussian behind the mover's own refusals: the handle's shape and its `chains` sets of parameters, then
+    // gaussian_bridge.hip
+    int gaussian_evidence(GaussianBridgeRequest g, int chains)
+    {
+        if (g.chain < 0 || g.chain >= chains) return fail(MCMCPP_HIP_E_ARG, "%s: chain %d outside 0..%d", g.q.what, g.chain, chains - 1);
+        g.q.dtype = sizeof(T) == 8 ? MCMCPP_HIP_F64 : MCMCPP_HIP_F32;
+        g.q.device = device, g.q.K = 1, g.q.W = W, g.q.D = D;
+        return gaussian_bridge_compute(*this, g);
+    }
+
     // calc_logp by the calculator's own kernel (`calc` of its launch table)
     int kernel_calc_logp(typename LaunchTable<T>::CalcFn calc_fn, const T* params, const void* pos, int64_t count, void* out)
     {
@@ -440,7 +450,7 @@ protected:
         Host::last_ms, Host::last_launches, Host::run_touched;                                                                                   \
     using Host::set_shape, Host::open_device, Host::open_stream, Host::quiesce, Host::abandon_state, Host::read_state,         \
         Host::clear_accepted, Host::read_counters, Host::kernel_calc_logp, Host::kernel_calc_logp_device, Host::check_device_range,   \
-        Host::upload_state, Host::refuse_run;                                       \
+        Host::upload_state, Host::refuse_run, Host::gaussian_evidence;                                       \
     using Host::fail, Host::error, Host::publish_stored, Host::host_enqueue_ms, Host::host_wall_ms
 
 }  // namespace mcmcpp
