@@ -14,7 +14,8 @@
  * evidenceRatios() estimates the ratios of normalising constants between neighbouring rungs from the stored steps
  * (mcmcpp_hip_evidence_ratios): their chain is the evidence of rung 0 when the top rung is a normalised density.
  * evidenceBridge() gives the bridge estimate of the same ratios, one per pair from the draws of both rungs
- * (mcmcpp_hip_evidence_bridge).
+ * (mcmcpp_hip_evidence_bridge).  evidenceMbar() solves for all rungs' log-normalising constants at once from every draw of
+ * every rung, with their covariance (mcmcpp_hip_evidence_mbar).
  */
 #ifndef MCMCPP_REPLICAEXCHANGESAMPLER_H
 #define MCMCPP_REPLICAEXCHANGESAMPLER_H
@@ -62,6 +63,22 @@ struct EvidenceBridge
     std::vector<std::int64_t> nonfinite;
     double logRatioTotal, mcseTotal;  ///< log(Z_0 / Z_{numRungs-1}) and its standard error
     std::size_t at(int direction, int pair) const { return static_cast<std::size_t>(direction) * static_cast<std::size_t>(numPairs) + static_cast<std::size_t>(pair); }
+};
+
+/// What ReplicaExchangeSampler::evidenceMbar returns (mcmcpp_hip_evidence_mbar, include/mcmcpp_hip.h): the multistate Bennett
+/// acceptance ratio, one joint solve from every draw of every rung.  logZ [numRungs]: log(Z_k / Z_{numRungs-1}); cov
+/// [numRungs][numRungs], row-major: the covariance of logZ, from which the error of any difference follows.
+struct EvidenceMbar
+{
+    int numRungs;
+    std::int64_t numDraws;  ///< draws per rung: used steps times walkers
+    std::vector<double> logZ, cov;
+    std::vector<double> logRatio, mcse;  ///< [numRungs - 1]: log(Z_p / Z_{p+1}) and its standard error from cov
+    std::vector<double> ess;             ///< [numRungs]
+    std::vector<std::int64_t> nonfinite;  ///< [numRungs][numRungs]: at(r, k) counts the draws of rung r that are not finite under rung k
+    double logRatioTotal, mcseTotal;      ///< log(Z_0 / Z_{numRungs-1}) and its standard error
+    std::int64_t passes, converged;       ///< the solver's passes, and whether it stopped on its rule
+    std::size_t at(int row, int column) const { return static_cast<std::size_t>(row) * static_cast<std::size_t>(numRungs) + static_cast<std::size_t>(column); }
 };
 
 template <class ParamType, class Calculator>
@@ -241,6 +258,24 @@ public:
         handle.check("mcmcpp_hip_evidence_bridge",
                      mcmcpp_hip_evidence_bridge(handle.get(), steps.empty() ? nullptr : steps.data(), used, 1, r.logRatio.data(), r.mcse.data(), r.overlap.data(),
                                                 r.ess.data(), r.passes.data(), r.converged.data(), r.nonfinite.data(), &r.logRatioTotal, &r.mcseTotal, &r.numDraws));
+        return r;
+    }
+
+    /// All rungs' log-normalising constants in one joint solve from every draw of every rung, with their covariance
+    /// (mcmcpp_hip_evidence_mbar); the steps are chosen as for evidenceRatios.
+    EvidenceMbar evidenceMbar(int burnIn = 0, int sliceInterval = 1)
+    {
+        std::int64_t used = 0;
+        const std::vector<const void*> steps = usedSteps("evidenceMbar", burnIn, sliceInterval, used);
+        const std::size_t K = static_cast<std::size_t>(numRungs);
+        EvidenceMbar r;
+        r.numRungs = numRungs;
+        r.numDraws = r.passes = r.converged = 0;
+        r.logRatioTotal = r.mcseTotal = 0.0;
+        r.logZ.resize(K), r.cov.resize(K * K), r.logRatio.resize(K - 1), r.mcse.resize(K - 1), r.ess.resize(K), r.nonfinite.resize(K * K);
+        handle.check("mcmcpp_hip_evidence_mbar",
+                     mcmcpp_hip_evidence_mbar(handle.get(), steps.empty() ? nullptr : steps.data(), used, 1, r.logZ.data(), r.cov.data(), r.logRatio.data(), r.mcse.data(),
+                                              r.ess.data(), r.nonfinite.data(), &r.logRatioTotal, &r.mcseTotal, &r.passes, &r.converged, &r.numDraws));
         return r;
     }
 

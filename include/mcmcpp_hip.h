@@ -478,6 +478,66 @@ int mcmcpp_hip_evidence_bridge_device(mcmcpp_hip_sampler* h, const void* device_
                                       int64_t slice_interval, double* log_ratio, double* mcse, double* overlap, double* ess, int64_t* passes,
                                       int64_t* converged, int64_t* nonfinite, double* log_ratio_total, double* mcse_total, int64_t* num_draws);
 
+/* All K log-normalising constants of the ladder at once (the multistate Bennett acceptance ratio, MBAR: Shirts & Chodera 2008;
+ * Tan 2004's extended bridge; Geyer's reverse logistic regression): one joint solve from every draw of every rung, each
+ * evaluated under every rung's parameters, with the K x K covariance of the estimates -- where mcmcpp_hip_evidence_bridge gives
+ * one estimate per pair of neighbours and an error that takes the pairs for independent.
+ *   draws      as for mcmcpp_hip_evidence_ratios: n used steps per rung, N = n W draws per rung in the order i = s W + w, K
+ *              rungs.  Draw i of rung r has the index j = r N + i among all K N draws.
+ *   l          l[k][j] is the log-posterior of draw j under chain k's parameters: what mcmcpp_hip_calc_logp_device returns for
+ *              that row with that chain's parameters, bit for bit, in the handle's dtype, widened to double exactly.  K K N
+ *              evaluations, kept as K arrays of K N doubles.  nonfinite [K][K] int64: [r][k] counts the draws of rung r whose
+ *              l[k] is not finite.
+ *   weights    zeta is a K-vector with zeta_{K-1} = +0 held fixed.  For draw j: a_k = l[k][j] - zeta_k; m = a_0, then for
+ *              k = 1 .. K - 1: m = a_k if a_k > m; e_k = evidence_exp(a_k - m) (mcmcpp_amd/csrc/evidence_exp.hpp; arguments
+ *              <= 0 only); Dn = ((+0 + e_0) + e_1) + ... in ascending k; w_k(j) = e_k / Dn.  A draw whose K entries are all -inf
+ *              (m = -inf) has every w_k = +0.
+ *   sums       S_k = sum_tree(w_k, K N) and P_kl = sum_tree(w_k w_l, K N) for k <= l (P_lk = P_kl): mcmcpp_hip_evidence_bridge's
+ *              sum_tree over the K N terms in the order of j; every product and every sum rounded on its own.
+ *   equations  G_k(zeta) = S_k - N = 0 for k < K - 1.  A_kk = S_k - P_kk and A_kl = -P_kl (k != l), on the reduced indices
+ *              0 .. K - 2: symmetric and positive semi-definite; -A is the Jacobian of G.
+ *   solve      solve(A, b), the reduced system A x = b of order M = K - 1, in this order.  Factor, for i = 0 .. M - 1: for
+ *              j = 0 .. i - 1: t = A_ij, then t = t - L_ik L_jk for k = 0 .. j - 1 ascending, L_ij = t / L_jj; then d = A_ii, then
+ *              d = d - L_ik L_ik for k = 0 .. i - 1 ascending; unless d > 0 the factor fails (below); L_ii = sqrt(d).  Forward,
+ *              for i = 0 .. M - 1: t = b_i, t = t - L_ik y_k for k = 0 .. i - 1 ascending, y_i = t / L_ii.  Backward, for
+ *              i = M - 1 .. 0: t = y_i, t = t - L_ki x_k for k = i + 1 .. M - 1 ascending, x_i = t / L_ii.
+ *   solver     A pass evaluates every S_k and P_kl at one zeta; `passes` counts the passes.  zeta = +0.  Repeat, 200 times at
+ *              the most: a pass; delta = solve(A, G); mx = max_k |delta_k|; if mx > 4: delta_k = delta_k (4 / mx) (one
+ *              division, then one product each) and mx = max_k |delta_k| anew; zeta_k = zeta_k + delta_k for k < K - 1; if
+ *              mx <= 2^-40 max(1, max_k |zeta_k|): stop with converged = 1.  Behind the 200th such pass: converged = 0.  The
+ *              final pass is at the zeta of the stop; it is counted: passes <= 201.  The result is a function of l alone.
+ *   errors     The final pass gives S and P at the stopped zeta, hence A and its factor, and forms per rung r, over that rung's N
+ *              terms alone (a tree of its own that begins at j = r N): M_rk = sum_tree(w_k, N), P^r_kl = sum_tree(w_k w_l, N)
+ *              (k <= l), C^r_kl = P^r_kl / N - (M_rk / N) (M_rl / N) (not clamped; C^r_lk = C^r_kl).  ess [K]: ess[r] is the
+ *              `ess` output of mcmcpp_hip_effective_sample_size_device on the series w_r(r N + i), i = 0 .. N - 1, seen as a chain
+ *              of one rung: n steps, W walkers, one parameter, fp64, split = 1, max_lag = 0, as the other two evidence calls use
+ *              it.  f_r = (N N) / ess[r].  V_kl = the sum in ascending r from +0 of f_r C^r_kl, where a C^r_kl that is zero
+ *              contributes +0 whatever f_r is (the series of identical rungs is constant and has no ESS).  With Y = the matrix
+ *              whose column c is solve(A, column c of V): row c of cov is solve(A, row c of Y), on the reduced indices: the
+ *              sandwich A^-1 V A^-T of the estimating equations with each rung's autocorrelation in its ESS.  Row and column
+ *              K - 1 of cov are +0.  It is not the delta-method mcse of mcmcpp_hip_evidence_bridge, also not for K = 2.
+ *   outputs    log_z [K] = zeta: log(Z_k / Z_{K-1}).  cov [K][K].  log_ratio [K-1]: zeta_p - zeta_{p+1}, the estimate of
+ *              log(Z_p / Z_{p+1}).  mcse [K-1]: v = (cov_pp + cov_qq) - 2 cov_pq with q = p + 1; sqrt(v), and 0 where v < 0.
+ *              ess [K].  nonfinite [K][K] int64.  *log_ratio_total = zeta_0; *mcse_total = sqrt(cov_00), and 0 where
+ *              cov_00 < 0.  *passes, *converged int64.  *num_draws = N.
+ *   edges      A NaN or +inf anywhere in l: every floating output is NaN, passes = converged = 0 (the solve is joint: nothing can
+ *              be spared); nonfinite stands.  An l of -inf has weight 0 and is counted.  A factor that fails in the solver or
+ *              behind the final pass (a pivot that is not positive: no mass is shared at double precision): every floating
+ *              output is NaN and converged = 1; passes counts the passes made.  Identical rungs: zeta = +0, mcse = 0, passes = 2.
+ * Everything is fp64, every + - * / rounded on its own; no fused operation, no floating-point atomic.  No output depends on the
+ * CU count, the chunk size (MCMCPP_HIP_EVIDENCE_CHUNK_MB, as above: host steps are uploaded, and rows evaluated, a chunk at a
+ * time) or where a chain lies.  steps, device_steps, chain_stride_steps, n_steps and slice_interval are those of
+ * mcmcpp_hip_evidence_ratios, and so are the refusals and argument checks with their codes.  Any output may be NULL; nothing is
+ * written to the outputs of a call that fails.  l takes 8 K K N bytes of device memory, freed when the call returns:
+ * MCMCPP_HIP_E_NOMEM with the byte count where they cannot be had.  The walker state is neither needed nor touched. */
+int mcmcpp_hip_evidence_mbar(mcmcpp_hip_sampler* h, const void* const* steps, int64_t n_steps, int64_t slice_interval, double* log_z, double* cov,
+                             double* log_ratio, double* mcse, double* ess, int64_t* nonfinite, double* log_ratio_total, double* mcse_total,
+                             int64_t* passes, int64_t* converged, int64_t* num_draws);
+int mcmcpp_hip_evidence_mbar_device(mcmcpp_hip_sampler* h, const void* device_steps, int64_t chain_stride_steps, int64_t n_steps,
+                                    int64_t slice_interval, double* log_z, double* cov, double* log_ratio, double* mcse, double* ess,
+                                    int64_t* nonfinite, double* log_ratio_total, double* mcse_total, int64_t* passes, int64_t* converged,
+                                    int64_t* num_draws);
+
 /* The evidence of ONE chain's target from an ordinary run: the bridge between the target and a Gaussian q = N(mean, L L^T)
  * fitted to its draws (Overstall & Forster 2010; Gronau et al. 2017).  q is normalised, so the bridge's log-ratio is
  * log Z = log of the integral of exp(logp) itself.  No ladder is needed: num_chains may be 0 or 1.

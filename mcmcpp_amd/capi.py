@@ -32,7 +32,8 @@ EXPORTS = [
     "mcmcpp_hip_half_step_async", "mcmcpp_hip_bind_device_chain", "mcmcpp_hip_device_positions",
     "mcmcpp_hip_shard_span", "mcmcpp_hip_synchronize", "mcmcpp_hip_exchange_chains",
     "mcmcpp_hip_run_tempered", "mcmcpp_hip_run_tempered_device", "mcmcpp_hip_evidence_ratios", "mcmcpp_hip_evidence_ratios_device",
-    "mcmcpp_hip_evidence_bridge", "mcmcpp_hip_evidence_bridge_device", "mcmcpp_hip_evidence_gaussian", "mcmcpp_hip_evidence_gaussian_device",
+    "mcmcpp_hip_evidence_bridge", "mcmcpp_hip_evidence_bridge_device", "mcmcpp_hip_evidence_mbar", "mcmcpp_hip_evidence_mbar_device",
+    "mcmcpp_hip_evidence_gaussian", "mcmcpp_hip_evidence_gaussian_device",
     "mcmcpp_hip_evidence_gaussian_last_timing",
     "mcmcpp_hip_moments_create", "mcmcpp_hip_moments_destroy", "mcmcpp_hip_moments_reset", "mcmcpp_hip_moments_add_steps",
     "mcmcpp_hip_moments_add_device_steps", "mcmcpp_hip_moments_finish", "mcmcpp_hip_moments_last_error",
@@ -152,6 +153,10 @@ def lib():
             outputs = [vp] * 10  # log_ratio, mcse, overlap, ess, passes, converged, nonfinite, log_ratio_total, mcse_total, *num_draws
             L.mcmcpp_hip_evidence_bridge.argtypes = [vp, C.POINTER(vp), i64, i64] + outputs
             L.mcmcpp_hip_evidence_bridge_device.argtypes = [vp, vp, i64, i64, i64] + outputs
+        if hasattr(L, "mcmcpp_hip_evidence_mbar"):  # (likewise)
+            outputs = [vp] * 11  # log_z, cov, log_ratio, mcse, ess, nonfinite, log_ratio_total, mcse_total, *passes, *converged, *num_draws
+            L.mcmcpp_hip_evidence_mbar.argtypes = [vp, C.POINTER(vp), i64, i64] + outputs
+            L.mcmcpp_hip_evidence_mbar_device.argtypes = [vp, vp, i64, i64, i64] + outputs
         if hasattr(L, "mcmcpp_hip_evidence_gaussian"):  # (likewise)
             # mean, chol, seed, stream; log_evidence, mcse, overlap, ess, passes, converged, nonfinite, *num_draws, proposals, log_q
             tail = [vp, vp, C.c_uint64, C.c_uint64] + [vp] * 10
@@ -645,7 +650,7 @@ class HipSampler:
         return chain, acc, swaps, first_round + rounds.value
 
     def _evidence_call(self, host_fn, device_fn, steps, slice_interval, chain_stride_steps, outputs):
-        """the steps of evidence_ratios and evidence_bridge, checked, through the host-pointer or the device entry point"""
+        """the steps of evidence_ratios, evidence_bridge and evidence_mbar, checked, through the host-pointer or the device entry point"""
         K = self.K
         if _is_tensor(steps):
             if steps.dim() != 4 or tuple(steps.shape[0:1] + steps.shape[2:]) != (K, self.W, self.D):
@@ -709,6 +714,26 @@ class HipSampler:
             out[key] = out[key][:, :K - 1]
         out["log_ratio_total"], out["mcse_total"] = np.float64(totals[0]), np.float64(totals[1])
         out["num_draws"] = draws.value
+        return out
+
+    def evidence_mbar(self, steps, slice_interval=1, chain_stride_steps=None):
+        """All K log-normalising constants of the ladder in one joint solve from every draw of every rung (the multistate Bennett
+        acceptance ratio, mcmcpp_hip_evidence_mbar; steps, slice_interval and chain_stride_steps as for evidence_ratios).  Returns
+        a dict of numpy arrays: log_z [K] (log(Z_k / Z_{K-1})), cov [K][K], log_ratio and mcse [K-1] (log(Z_p / Z_{p+1}) and its
+        standard error from cov), ess [K], nonfinite [K][K] int64 (row r: the draws of rung r, column k: under chain k), the floats
+        log_ratio_total = log_z[0] and mcse_total = sqrt(cov[0][0]), and passes, converged, num_draws."""
+        K = self.K
+        out = dict(log_z=np.full(K, np.nan), cov=np.full((K, K), np.nan), log_ratio=np.full(max(K - 1, 1), np.nan), mcse=np.full(max(K - 1, 1), np.nan),
+                   ess=np.full(K, np.nan), nonfinite=np.zeros((K, K), np.int64))
+        totals = np.full(2, np.nan)
+        counts = np.zeros(3, np.int64)  # passes, converged, num_draws
+        outputs = [_ptr(out[key]) for key in ("log_z", "cov", "log_ratio", "mcse", "ess", "nonfinite")]
+        outputs += [C.c_void_p(totals.ctypes.data), C.c_void_p(totals.ctypes.data + 8)] + [C.c_void_p(counts.ctypes.data + 8 * i) for i in range(3)]
+        self._evidence_call(lib().mcmcpp_hip_evidence_mbar, lib().mcmcpp_hip_evidence_mbar_device, steps, slice_interval, chain_stride_steps, outputs)
+        for key in ("log_ratio", "mcse"):
+            out[key] = out[key][:K - 1]
+        out["log_ratio_total"], out["mcse_total"] = np.float64(totals[0]), np.float64(totals[1])
+        out["passes"], out["converged"], out["num_draws"] = np.int64(counts[0]), np.int64(counts[1]), int(counts[2])
         return out
 
     def evidence_gaussian(self, steps, chain=0, mean=None, chol=None, fit_fraction=0.5, slice_interval=1, seed=0, stream=0, want_proposals=False):

@@ -1077,6 +1077,15 @@ public:
         b.q.device = device, b.q.K = K, b.q.W = W, b.q.D = D;
         return bridge_compute(*this, b);
     }
+    // All K log-normalising constants in one joint solve (mbar.hip): the same refusals
+    int evidence_mbar(MbarRequest m) override
+    {
+        if (int rc = chain_params_supported(m.q.what)) return rc;
+        if (K < 2) return fail(MCMCPP_HIP_E_ARG, "%s: the handle has one chain (num_chains must be at least 2)", m.q.what);
+        m.q.dtype = sizeof(T) == 8 ? MCMCPP_HIP_F64 : MCMCPP_HIP_F32;
+        m.q.device = device, m.q.K = K, m.q.W = W, m.q.D = D;
+        return mbar_compute(*this, m);
+    }
     // The evidence of one chain's target by a bridge to a fitted Gaussian (gaussian_bridge.hip): one chain will do
     int evidence_gaussian(GaussianBridgeRequest g) override
     {
@@ -1763,6 +1772,25 @@ int mcmcpp_hip_evidence_bridge_device(mcmcpp_hip_sampler* h, const void* device_
     return h->evidence_bridge(
         mcmcpp::BridgeRequest{mcmcpp::EvidenceRequest{"evidence_bridge_device", nullptr, device_steps, true, chain_stride_steps, n_steps, slice_interval, mcmcpp::EvidenceOutputs{}},
                               mcmcpp::BridgeOutputs{log_ratio, mcse, overlap, ess, passes, converged, nonfinite, log_ratio_total, mcse_total, num_draws}});
+}
+int mcmcpp_hip_evidence_mbar(mcmcpp_hip_sampler* h, const void* const* steps, int64_t n_steps, int64_t slice_interval, double* log_z, double* cov, double* log_ratio,
+                             double* mcse, double* ess, int64_t* nonfinite, double* log_ratio_total, double* mcse_total, int64_t* passes, int64_t* converged,
+                             int64_t* num_draws)
+{
+    NEED_H;
+    NOT_WHILE_ASYNC("evidence_mbar");
+    return h->evidence_mbar(mcmcpp::MbarRequest{mcmcpp::EvidenceRequest{"evidence_mbar", steps, nullptr, false, 0, n_steps, slice_interval, mcmcpp::EvidenceOutputs{}},
+                                                mcmcpp::MbarOutputs{log_z, cov, log_ratio, mcse, ess, nonfinite, log_ratio_total, mcse_total, passes, converged, num_draws}});
+}
+int mcmcpp_hip_evidence_mbar_device(mcmcpp_hip_sampler* h, const void* device_steps, int64_t chain_stride_steps, int64_t n_steps, int64_t slice_interval, double* log_z,
+                                    double* cov, double* log_ratio, double* mcse, double* ess, int64_t* nonfinite, double* log_ratio_total, double* mcse_total,
+                                    int64_t* passes, int64_t* converged, int64_t* num_draws)
+{
+    NEED_H;
+    NOT_WHILE_ASYNC("evidence_mbar_device");
+    return h->evidence_mbar(
+        mcmcpp::MbarRequest{mcmcpp::EvidenceRequest{"evidence_mbar_device", nullptr, device_steps, true, chain_stride_steps, n_steps, slice_interval, mcmcpp::EvidenceOutputs{}},
+                            mcmcpp::MbarOutputs{log_z, cov, log_ratio, mcse, ess, nonfinite, log_ratio_total, mcse_total, passes, converged, num_draws}});
 }
 int mcmcpp_hip_evidence_gaussian(mcmcpp_hip_sampler* h, int32_t chain, const void* const* steps, int64_t n_steps, int64_t slice_interval, const double* mean,
                                  const double* chol, uint64_t seed, uint64_t stream, double* log_evidence, double* mcse, double* overlap, double* ess, int64_t* passes,

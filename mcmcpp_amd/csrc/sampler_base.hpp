@@ -54,6 +54,20 @@ struct BridgeRequest
     EvidenceRequest q;
     BridgeOutputs out;
 };
+// What mcmcpp_hip_evidence_mbar writes (any pointer may be null), and one call: the request of the ratios with these outputs
+// (q.out is not used).  mbar.hip does the rest.
+struct MbarOutputs
+{
+    double *log_z, *cov, *log_ratio, *mcse, *ess;
+    int64_t* nonfinite;
+    double *log_ratio_total, *mcse_total;
+    int64_t *passes, *converged, *num_draws;
+};
+struct MbarRequest
+{
+    EvidenceRequest q;
+    MbarOutputs out;
+};
 // What mcmcpp_hip_evidence_gaussian writes (any pointer may be null), and one call: the steps of ONE chain in q (q.K is 1 and
 // q.chain_stride_steps 0; q.out is not used), the Gaussian and the proposals' stream.  gaussian_bridge.hip does the rest.
 struct GaussianBridgeOutputs
@@ -148,6 +162,12 @@ struct mcmcpp_hip_sampler
     {
         return fail(MCMCPP_HIP_E_UNSUPPORTED,
                     "%s: evidence ratios are for stretch-move handles with a device calculator only (not the differential-evolution mover, not a batch target)", b.q.what);
+    }
+    // all K log-normalising constants in one joint solve (mcmcpp_hip_evidence_mbar): likewise
+    virtual int evidence_mbar(mcmcpp::MbarRequest m)
+    {
+        return fail(MCMCPP_HIP_E_UNSUPPORTED,
+                    "%s: evidence ratios are for stretch-move handles with a device calculator only (not the differential-evolution mover, not a batch target)", m.q.what);
     }
     // the evidence of one chain's target by a bridge to a fitted Gaussian (mcmcpp_hip_evidence_gaussian): every mover overrides it
     virtual int evidence_gaussian(mcmcpp::GaussianBridgeRequest g) { return fail(MCMCPP_HIP_E_UNSUPPORTED, "%s: not available for this handle", g.q.what); }
@@ -411,6 +431,8 @@ int evidence_compute(mcmcpp_hip_sampler& h, const EvidenceRequest& q);
 int evidence_check(mcmcpp_hip_sampler& h, const EvidenceRequest& q, long long* used_steps);
 // the body of mcmcpp_hip_evidence_bridge, likewise (bridge.hip)
 int bridge_compute(mcmcpp_hip_sampler& h, const BridgeRequest& b);
+// the body of mcmcpp_hip_evidence_mbar, likewise (mbar.hip)
+int mbar_compute(mcmcpp_hip_sampler& h, const MbarRequest& m);
 // the body of mcmcpp_hip_evidence_gaussian behind the handle's refusals (gaussian_bridge.hip): g.q's shape is the handle's, whose
 // calc_logp_device evaluates the draws and the proposals with chain g.chain's parameters
 int gaussian_bridge_compute(mcmcpp_hip_sampler& h, const GaussianBridgeRequest& g);
