@@ -470,9 +470,13 @@ class HipSampler:
         return chain, acc
 
     def run_async(self, n_saved, interval=1, out=None, want_accepted=False):
-        """Start the run on the handle's worker thread; returns (chain, acc) arrays that fill up as it proceeds."""
-        chain = out if out is not None else np.empty((n_saved, self.W, self.D), dtype=self.np_t)
-        acc = np.zeros(n_saved * interval, dtype=np.uint32) if want_accepted else None
+        """Start the run on the handle's worker thread; returns (chain, acc) arrays that fill up as it proceeds
+        (several chains: chain[K][n_saved][W][D], acc[K][steps], as run returns them)."""
+        lead = (self.K,) if self.K > 1 else ()
+        if out is not None:
+            assert out.shape == lead + (n_saved, self.W, self.D) and out.dtype == self.np_t and out.flags.c_contiguous
+        chain = out if out is not None else np.empty(lead + (n_saved, self.W, self.D), dtype=self.np_t)
+        acc = np.zeros(lead + (n_saved * interval,), dtype=np.uint32) if want_accepted else None
         self._async_keep = (chain, acc)
         self._check(lib().mcmcpp_hip_run_async(self.h, n_saved, interval, _ptr(chain), _ptr(acc)))
         return chain, acc

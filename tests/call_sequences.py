@@ -27,6 +27,14 @@ Operations are tuples, the kind first:
   ("calc_logp", count, rows seed, chain or None), ("calc_logp_device", count, rows seed, chain)
   ("refused", "run_negative" | "run_interval_0" | "half_step_out_of_order" | "seek_unsupported")
   ("set_chain_params", chain, index into BETAS), ("exchange_chains", round)
+and on the ladders (family "ladder": K >= 2 chains, a tempered handle):
+  ("run_device_async", n_saved, interval, want_accepted)   run_async into a torch tensor (also a stretch operation)
+  ("run_tempered", n_saved, interval, exchange_every, first_round, "pageable" | "pinned" | "device")
+                                            compared as (chain, accepted per step, swaps dict, next round)
+  ("evidence", "ratios" | "bridge" | "mbar", n, rows seed, "host" | "device")   on draws [K][n][W][D] made from the seed alone
+  ("refused", "run_tempered_every_0" | "half_step_async"), ("refused", "run_tempered_round_out_of_range", n_saved, interval,
+   exchange_every, first_round): a generated tempered run whose last round would pass 2^40 - 1 is this refusal
+  ("refused_in_flight", ... | "run_tempered" | "exchange_chains" | "set_chain_params" | "evidence")
 """
 import collections
 import hashlib
@@ -59,9 +67,10 @@ _LONG_300 = [(300, 1), (3, 100), (301, 1), (4, 100), (7, 50), (600, 1)]
 _LONG_128 = [(128, 1), (64, 2), (129, 1), (2, 128), (100, 2)]
 
 
-def _path(family, calc, dtype, W, D, env, graph_steps, full_step, long_runs, K=1, create=None, directed=()):
+def _path(family, calc, dtype, W, D, env, graph_steps, full_step, long_runs, K=1, create=None, directed=(), weights=None):
+    """weights: the key of WEIGHTS the path draws from (by default its family's)"""
     return dict(family=family, calc=calc, dtype=dtype, W=W, D=D, K=K, env=env, create=create or {}, graph_steps=graph_steps,
-                full_step=full_step, long_runs=long_runs, directed=tuple(directed))
+                full_step=full_step, long_runs=long_runs, directed=tuple(directed), weights=weights or family)
 
 
 PATHS = collections.OrderedDict([
@@ -85,6 +94,24 @@ PATHS = collections.OrderedDict([
     ("batch_f64", _path("batch", ISO, po.F64, 70, 5, {}, -1, False, _LONG_4)),
     ("batch_f32", _path("batch", ISO, po.F32, 70, 5, {}, -1, False, _LONG_4)),
 ])
+OLD_PATHS = tuple(PATHS)  # the fifteen paths of the first version of this module: their sequences stay as they are, byte for byte
+# The ladders: tempered handles.  K = 2 for the rounds without a pair (every odd one), K = 16 for rounds of 8 and of 7 slots.
+_G4 = {"MCMCPP_HIP_GRAPH_STEPS": "4"}
+PATHS.update([
+    ("ladder3_full_step", _path("ladder", DENSE, po.F64, 134, 20, {**_FULL, **_G4}, 4, True, _LONG_4, K=3)),
+    ("ladder3_half_step", _path("ladder", DENSE, po.F64, 134, 20, {**_HALF, **_G4}, 4, False, _LONG_4, K=3,
+                                directed=[("run_tempered", 9, 3, 5, 0, "pageable")])),
+    ("ladder2_full_step_f32", _path("ladder", ROSENBROCK, po.F32, 70, 9, {**_FULL, **_G4}, 4, True, _LONG_4, K=2,
+                                    directed=[("run_tempered", 9, 3, 5, 1, "pinned")], weights="ladder_f32")),
+    ("ladder4_plain_launches", _path("ladder", DENSE, po.F64, 134, 20, _FULL, -1, True, _LONG_4, K=4, create={"graph_steps": -1})),
+    ("ladder3_default_graphs", _path("ladder", DENSE, po.F64, 134, 20, _FULL, 300, True, _LONG_300, K=3,
+                                     directed=[("run_tempered", 301, 1, 150, 0, "device"), ("run", 299, 1, True, True)])),
+    ("ladder16_half_step", _path("ladder", DENSE, po.F64, 70, 5, {**_HALF, **_G4}, 4, False, _LONG_4, K=16,
+                                 directed=[("run_tempered", 9, 4, 7, 3, "pageable")])),
+    # the stretch family's asynchronous run into device memory: a path of its own, with weights of its own
+    ("full_step_device_async", _path("stretch", ISO, po.F64, 70, 5, {**_FULL, **_G4}, 4, True, _LONG_4, weights="stretch_device_async")),
+])
+NEW_PATHS = tuple(p for p in PATHS if p not in OLD_PATHS)
 PATH_INDEX = {name: i for i, name in enumerate(PATHS)}
 
 # The six sequences of each path: the generator seeds 0..5, but for those listed with the input condition the oracle missed
@@ -97,7 +124,9 @@ DIRECTED_AFTER = 20
 LONG_RUN_PROBABILITY = 0.15
 BETAS = (1.0, 0.8, 0.6, 0.5, 0.35, 0.25)          # set_chain_params: chain 0's matrix times one of these
 CHAINS3_START = (0, 3, 5)                          # the ladder a chains3 handle is created with (indices into BETAS)
+LADDER_START = {2: (0, 3), 3: CHAINS3_START, 4: (0, 2, 3, 5)}  # the ladder a handle of K chains is created with; K = 16: geometric
 EXCHANGE_ROUNDS = (0, 1, 2, 3, 4, 5, 6, 7, 2**40 - 2, 2**40 - 1)
+MAX_ROUND = 2**40                                  # temper_plan.hpp refuses a run with first_round + rounds above this
 SPECIAL_64 = (0, M64, 2**63, 2**63 + 1)            # handle seeds and streams: these, or 64 random bits (inc.hi = stream >> 63)
 
 # Weights of the operation kinds while the handle is idle, per family ...
@@ -108,23 +137,59 @@ WEIGHTS = {
                "get_state": 2, "counters": 2, "refused": 2, "set_chain_params": 3, "exchange_chains": 4},
     "diffevo": {"run": 12, "run_device": 5, "set_state": 3, "reset_counters": 3, "get_state": 3, "counters": 2, "calc_logp": 3, "refused": 4},
     "batch": {"run": 12, "seek": 5, "set_state": 3, "reset_counters": 3, "get_state": 3, "counters": 2, "refused": 3},
+    "ladder": {"run_tempered": 10, "run": 5, "run_device": 2.5, "run_async": 5, "run_device_async": 2.5, "evidence": 6.5, "seek": 3.5,
+               "reset_counters": 4, "set_state": 2, "set_chain_params": 5, "exchange_chains": 3, "calc_logp": 2.5, "calc_logp_device": 3.5,
+               "get_state": 3.5, "counters": 5, "refused": 5},
+    # the fp32 ladder's own (its two chains make other sequences of the same weights: these meet its facts)
+    "ladder_f32": {"run_tempered": 12, "run": 5, "run_device": 3, "run_async": 5, "run_device_async": 2.5, "evidence": 6.5, "seek": 3.5,
+                   "reset_counters": 4, "set_state": 2, "set_chain_params": 4, "exchange_chains": 2.5, "calc_logp": 2.5, "calc_logp_device": 4,
+                   "get_state": 4, "counters": 6, "refused": 5},
+    # the stretch family's, with a third of the weight of run_async and run_device each moved to run_device_async
+    "stretch_device_async": {"run": 10, "run_async": 2.5, "run_device_async": 3.5, "run_device": 3, "half_step_async": 5, "synchronize": 2, "seek": 4,
+                             "reset_counters": 3, "set_state": 3, "calc_logp": 3, "calc_logp_device": 3, "get_state": 3, "counters": 3, "refused": 3},
 }
 # ... while an ensemble step is half done (half_step_async(0) went out) ...
 WEIGHTS_HALF_DONE = {"half_step_async": 8, "synchronize": 1, "get_state": 1, "counters": 1, "calc_logp": 1, "refused": 2, "set_state": 0.5,
                      "reset_counters": 0.5}
 # ... and while an asynchronous run is in flight (run_wait: before / after the first wait_stored)
 WEIGHTS_IN_FLIGHT = {"refused_in_flight": 2, "wait_stored": 3, "run_wait": (0.5, 4)}
+WEIGHTS_IN_FLIGHT_LADDER = {"refused_in_flight": 6, "wait_stored": 3, "run_wait": (0.5, 4)}
 # What the last state-changing operation multiplies: a run that left an odd step count, a seek, a reset behind a run
 FOLLOW = {
     "odd_run": {"run_device": 3, "half_step_async": 3, "set_state": 2, "reset_counters": 2},
     "seek": {"run": 3, "run_async": 2},
     "reset_after_run": {"run": 6},
 }
+# ... and on a ladder: the hand-overs into and out of a tempered run (a run_tempered behind a tempered run also takes the round
+# number that one returned as its first_round, CARRY_ROUND_PROBABILITY of the time)
+FOLLOW_LADDER = {
+    "odd_tempered": {"run": 9, "run_device": 14.5, "exchange_chains": 10, "set_state": 3.5, "get_state": 5.5},
+    "tempered": {"run_tempered": 3.5},
+    "odd_run": {"run_tempered": 2.5, "run_device": 2.5, "set_state": 3, "reset_counters": 2},
+    "seek": {"run_tempered": 6, "run": 1.5},
+    "set_chain_params": {"run_tempered": 5.5, "evidence": 6},
+    "reset_counters": {"run_tempered": 6},
+    "reset_after_run": {"run_tempered": 2, "run": 6},
+    "exchange_chains": {"run_tempered": 7},
+}
+CARRY_ROUND_PROBABILITY = 0.6
 REFUSED = {"stretch": ("run_negative", "run_interval_0", "half_step_out_of_order"), "chains": ("run_negative", "run_interval_0"),
-           "diffevo": ("run_negative", "run_interval_0", "seek_unsupported"), "batch": ("run_negative", "run_interval_0")}
-REFUSED_CODE = {"run_negative": E_ARG, "run_interval_0": E_ARG, "half_step_out_of_order": E_ARG, "seek_unsupported": E_UNSUPPORTED}
-RUN_KINDS = ("run", "run_async", "run_device")
-STATE_CHANGING = RUN_KINDS + ("half_step_async", "seek", "reset_counters", "set_state", "set_chain_params", "exchange_chains")
+           "diffevo": ("run_negative", "run_interval_0", "seek_unsupported"), "batch": ("run_negative", "run_interval_0"),
+           "ladder": ("run_negative", "run_interval_0", "run_tempered_every_0", "run_tempered_round_out_of_range", "half_step_async")}
+REFUSED_CODE = {"run_negative": E_ARG, "run_interval_0": E_ARG, "half_step_out_of_order": E_ARG, "seek_unsupported": E_UNSUPPORTED,
+                "run_tempered_every_0": E_ARG, "run_tempered_round_out_of_range": E_ARG, "half_step_async": E_UNSUPPORTED}
+ROUND_OUT_OF_RANGE = (2, 1, 1, 2**40 - 1)          # the run_tempered of a drawn ("refused", "run_tempered_round_out_of_range"): two rounds
+REFUSED_IN_FLIGHT = {"stretch": ("seek", "calc_logp", "get_state"),
+                     "ladder": ("seek", "calc_logp", "get_state") + 2 * ("run_tempered", "exchange_chains", "set_chain_params", "evidence")}
+LADDER_CALLS = ("run_tempered", "exchange_chains", "set_chain_params", "evidence")
+RUN_KINDS = ("run", "run_async", "run_device", "run_device_async")
+ASYNC_KINDS = ("run_async", "run_device_async")
+STATE_CHANGING = RUN_KINDS + ("half_step_async", "seek", "reset_counters", "set_state", "set_chain_params", "exchange_chains", "run_tempered")
+DELIVERIES = ("pageable", "pinned", "device")
+EVIDENCE_KINDS = ("ratios", "bridge", "mbar")      # (K = 16: the first two; the joint solve of 16 rungs is tests/test_evidence_mbar.py's)
+EVIDENCE_PLACES = ("host", "device")
+EXCHANGE_EVERY = (1, 2, 3, 4, 5, 7)                # and the run's length, and one more; 300 steps a replay: EXCHANGE_EVERY_300 too
+EXCHANGE_EVERY_300 = (100, 150, 300, 301)
 
 
 def seek_targets(cfg, step, rng):
@@ -164,50 +229,80 @@ def plan(path, seed):
     """(handle seed, handle stream, operations) of sequence `seed` of `path`"""
     cfg = PATHS[path]
     fam = cfg["family"]
+    ladder = fam == "ladder"
     rng = np.random.default_rng((PATH_INDEX[path], seed))
     handle_seed, stream = _special_64(rng), _special_64(rng)
     ops = [("set_state", int(rng.integers(0, 1000)))]
     # the generator's own view of the handle: enough to tell a legal operation from an illegal one
     step, half_done, in_flight, waited, context = 0, False, None, False, None
+    next_round = None  # the round the last tempered run returned, while nothing has changed the state behind it
+    evidence_at = refused_at = seed
     drawn, directed = 0, list(cfg["directed"])
     while drawn < OPS_PER_SEQUENCE or in_flight is not None:
         if directed and drawn >= DIRECTED_AFTER and not half_done and in_flight is None:
             for op in directed:
                 ops.append(op)
                 step += op[1] * op[2]
-            context = "odd_run" if sum(op[1] * op[2] for op in directed) & 1 else None
+            context, next_round = "odd_run" if sum(op[1] * op[2] for op in directed) & 1 else None, None
+            if directed[-1][0] == "run_tempered":
+                op = directed[-1]
+                context, next_round = "odd_tempered" if (op[1] * op[2]) & 1 else "tempered", op[4] + op[1] * op[2] // op[3]
             directed = []
             continue
         left = OPS_PER_SEQUENCE - drawn
         if in_flight is not None:
-            w = dict(WEIGHTS_IN_FLIGHT)
-            w["run_wait"] = WEIGHTS_IN_FLIGHT["run_wait"][1 if waited else 0]
+            w = dict(WEIGHTS_IN_FLIGHT_LADDER if ladder else WEIGHTS_IN_FLIGHT)
+            w["run_wait"] = w["run_wait"][1 if waited else 0]
             kind = "run_wait" if left <= 1 else _pick(rng, w)
         elif half_done:
             kind = _pick(rng, WEIGHTS_HALF_DONE)
         else:
-            w = dict(WEIGHTS[fam])
-            for k, f in FOLLOW.get(context, {}).items():
+            w = dict(WEIGHTS[cfg["weights"]])
+            for k, f in (FOLLOW_LADDER if ladder else FOLLOW).get(context, {}).items():
                 if k in w:
                     w[k] *= f
             if left < 3:
-                w.pop("run_async", None)  # (an operation that would be illegal is not drawn: the run could not be waited for)
+                for k in ASYNC_KINDS:
+                    w.pop(k, None)  # (an operation that would be illegal is not drawn: the run could not be waited for)
             kind = _pick(rng, w)
         drawn += 1
-        if kind in ("run", "run_device", "run_async"):
+        if kind in RUN_KINDS:
             n_saved, interval = _run_shape(rng, cfg)
             flags = (bool(rng.random() < 0.75), bool(rng.random() < 0.75))
             if kind == "run":
                 ops.append(("run", n_saved, interval) + flags)
             else:
                 ops.append((kind, n_saved, interval, flags[1]))
-            if kind == "run_async":
+            if kind in ASYNC_KINDS:
                 in_flight, waited = n_saved, False
             step += n_saved * interval
             if n_saved > 0:
-                context = "odd_run" if (n_saved * interval) & 1 else "run"
+                context, next_round = "odd_run" if (n_saved * interval) & 1 else "run", None
+        elif kind == "run_tempered":
+            n_saved, interval = _run_shape(rng, cfg)
+            total = n_saved * interval
+            every = EXCHANGE_EVERY + (max(total, 1), total + 1) + (EXCHANGE_EVERY_300 if cfg["graph_steps"] == 300 else ())
+            every = every[int(rng.integers(0, len(every)))]
+            first = EXCHANGE_ROUNDS[int(rng.integers(0, len(EXCHANGE_ROUNDS)))]
+            if next_round is not None and rng.random() < CARRY_ROUND_PROBABILITY:
+                first = next_round
+            delivery = DELIVERIES[int(rng.integers(0, len(DELIVERIES)))]
+            if first + total // every > MAX_ROUND:
+                ops.append(("refused", "run_tempered_round_out_of_range", n_saved, interval, every, first))
+            else:
+                ops.append((kind, n_saved, interval, every, first, delivery))
+                step += total
+                if total > 0:
+                    context, next_round = "odd_tempered" if total & 1 else "tempered", first + total // every
+        elif kind == "evidence":
+            # (which, place) in rotation, sequence `seed` beginning at pair `seed`: the six sequences meet every pair
+            pairs = [(which, place) for which in EVIDENCE_KINDS[:2 if cfg["K"] > 4 else 3] for place in EVIDENCE_PLACES]
+            which, place = pairs[evidence_at % len(pairs)]
+            evidence_at += 1
+            ops.append((kind, which, int(rng.integers(4, 9)), int(rng.integers(0, 2**31)), place))
         elif kind == "refused_in_flight":
-            ops.append((kind, ("seek", "calc_logp", "get_state")[int(rng.integers(0, 3))]))
+            names = REFUSED_IN_FLIGHT[fam]
+            ops.append((kind, names[int(rng.integers(0, len(names)))]))
         elif kind == "wait_stored":
             ops.append((kind, int(rng.integers(0, in_flight + 1))))
             waited = True
@@ -224,17 +319,17 @@ def plan(path, seed):
             targets = seek_targets(cfg, step, rng)
             step = targets[int(rng.integers(0, len(targets)))]
             ops.append((kind, step))
-            context = "seek"
+            context, next_round = "seek", None
         elif kind == "reset_counters":
             ops.append((kind,))
-            context = "reset_after_run" if context in ("run", "odd_run") else None
+            context = "reset_after_run" if context in ("run", "odd_run") else "reset_counters" if ladder else None
         elif kind == "set_state":
             ops.append((kind, int(rng.integers(0, 1000))))
-            step, half_done, context = 0, False, None
+            step, half_done, context, next_round = 0, False, None, None
         elif kind in ("calc_logp", "calc_logp_device"):
             count, rows_seed = int(rng.integers(1, 21)), int(rng.integers(0, 2**31))
             chain = None
-            if fam == "chains":
+            if fam in ("chains", "ladder"):
                 chain = int(rng.integers(0, cfg["K"] + (1 if kind == "calc_logp" else 0)))
                 chain = None if chain == cfg["K"] else chain
             ops.append((kind, count, rows_seed, 0 if kind == "calc_logp_device" and chain is None else chain))
@@ -242,13 +337,17 @@ def plan(path, seed):
             names = REFUSED[fam]
             if half_done:
                 names = ("half_step_out_of_order", "half_step_out_of_order") + names
-            ops.append((kind, names[int(rng.integers(0, len(names)))]))
+            if ladder:  # (in rotation, sequence `seed` beginning at name `seed`: the six sequences meet every name)
+                what, refused_at = names[refused_at % len(names)], refused_at + 1
+            else:
+                what = names[int(rng.integers(0, len(names)))]
+            ops.append((kind, what) + (ROUND_OUT_OF_RANGE if what == "run_tempered_round_out_of_range" else ()))
         elif kind == "set_chain_params":
             ops.append((kind, int(rng.integers(0, cfg["K"])), int(rng.integers(0, len(BETAS)))))
-            context = None
+            context, next_round = kind if ladder else None, None
         elif kind == "exchange_chains":
             ops.append((kind, EXCHANGE_ROUNDS[int(rng.integers(0, len(EXCHANGE_ROUNDS)))]))
-            context = None
+            context, next_round = kind if ladder else None, None
         else:
             ops.append((kind,))  # synchronize, get_state, counters
     return handle_seed, stream, ops
@@ -262,10 +361,11 @@ def render(ops):
     return "\n".join("%3d %r" % (i, op) for i, op in enumerate(ops))
 
 
-def digest():
-    """SHA-256 over every (path, seed) of SEEDS: the handle's seed and stream and the rendered operations"""
+def digest(paths=None):
+    """SHA-256 over every (path, seed) of SEEDS (paths: of these paths, in this order): the handle's seed and stream and the
+    rendered operations"""
     h = hashlib.sha256()
-    for path in PATHS:
+    for path in PATHS if paths is None else paths:
         for seed in SEEDS[path]:
             handle_seed, stream, ops = plan(path, seed)
             h.update(("%s %d %d %d\n%s\n" % (path, seed, handle_seed, stream, render(ops))).encode())
@@ -285,8 +385,34 @@ def base_params(cfg):
     return None
 
 
+def params_at(cfg, beta):
+    """chain 0's parameters flattened by beta: the dense matrix times beta; Rosenbrock: its third parameter times beta"""
+    t = po.np_dtype(cfg["dtype"])
+    if cfg["calc"] == ROSENBROCK:
+        p = base_params(cfg).astype(np.float64)
+        p[2] *= beta
+        return p.astype(t)
+    return (beta * base_params(cfg)).astype(t)
+
+
 def chain_params(cfg, beta_index):
-    return (BETAS[beta_index] * base_params(cfg)).astype(po.np_dtype(cfg["dtype"]))
+    return params_at(cfg, BETAS[beta_index])
+
+
+def start_betas(cfg):
+    """the betas a handle of several chains is created with: spread over BETAS; K = 16: a geometric ladder from 1 down to 0.25"""
+    K = cfg["K"]
+    if K in LADDER_START:
+        return [BETAS[i] for i in LADDER_START[K]]
+    return [float(0.25 ** (k / (K - 1.0))) for k in range(K)]
+
+
+def evidence_draws(cfg, betas, n, rows_seed):
+    """the draws [K][n][W][D] of an evidence operation, from rows_seed alone (tests/evidence_device.make_draws): Gaussian, chain
+    k's wider by 1 / sqrt of its beta"""
+    from tests import evidence_device as ed
+    return ed.make_draws(dict(dtype="f32" if cfg["dtype"] == po.F32 else "f64", calc="rosen" if cfg["calc"] == ROSENBROCK else "dense", K=cfg["K"], n=n,
+                              W=cfg["W"], D=cfg["D"], seed=rows_seed, betas=list(betas)))
 
 
 def rows_for(cfg, count, rows_seed):
@@ -298,8 +424,8 @@ def rows_for(cfg, count, rows_seed):
 SUBCHUNK_BYTES = 32 << 20
 
 
-def launch_chunks(cfg, n_saved, interval, save_chain, to_device):
-    """the step counts a run hands to enqueue_steps, in order"""
+def launch_chunks(cfg, n_saved, interval, save_chain, to_device, pinned=False):
+    """the step counts a run hands to enqueue_steps, in order (pinned: plan_chain's `direct`)"""
     total = n_saved * interval
     if total == 0:
         return []
@@ -309,7 +435,7 @@ def launch_chunks(cfg, n_saved, interval, save_chain, to_device):
         return [total]
     if to_device or (cfg["full_step"] and step_bytes % 16 == 0):
         per = (G if G > 0 else 64) // interval
-        if not to_device:
+        if not to_device and not pinned:
             ring = 4
             while ring < 64 and 2 * ring * step_bytes <= 2 * SUBCHUNK_BYTES:
                 ring *= 2
@@ -317,7 +443,7 @@ def launch_chunks(cfg, n_saved, interval, save_chain, to_device):
         chunk, out, done = max(per, 1) * interval, [], 0
         while done < total:
             now = min(total - done, chunk)
-            if not to_device and now == total - done and now > interval:
+            if not to_device and not pinned and now == total - done and now > interval:
                 now -= interval  # (the trickle window ends a run with a chunk of one interval)
             out.append(now)
             done += now
@@ -349,7 +475,8 @@ class Model:
         cfg = self.cfg
         self.K, self.W, self.D = cfg["K"], cfg["W"], cfg["D"]
         self.mover = DE if cfg["family"] == "diffevo" else STRETCH
-        self.params = [chain_params(cfg, b) for b in CHAINS3_START] if cfg["family"] == "chains" else [base_params(cfg)]
+        self.betas = start_betas(cfg) if self.K > 1 else [1.0]  # what set_chain_params installed last, chain by chain
+        self.params = [params_at(cfg, b) for b in self.betas] if self.K > 1 else [base_params(cfg)]
         self.orcs = [self._oracle(k) for k in range(self.K)]
         self.nacc_off = [np.zeros(self.W, np.int64) for _ in range(self.K)]  # get_state's counts = the oracle's + these
         self.ties_off = self.redraws_off = 0
@@ -362,7 +489,11 @@ class Model:
         self.accepted = self.proposed = self.in_band = 0
         self._last_change, self._prev_op = None, None  # the last state-changing operation, the last operation
         self._reset_behind_run = self._pair_after_odd_run = False
-        self._in_flight_refusals = 0
+        self._in_flight_refusals, self._in_flight_ladder_calls, self._in_flight_device = 0, 0, False
+        # the rounds of a ladder, inside tempered runs and between runs: swaps accepted and refused; the evidence operations
+        self.swaps_accepted = self.swaps_refused = 0
+        self.evidence_nonfinite = self.evidence_unconverged = 0
+        self._next_round = None  # the round the last tempered run returned (while it is the last state-changing operation)
 
     def _oracle(self, k):
         return po.Oracle(self.W, self.D, self.cfg["calc"], self.params[k], seed=(self.seed + k) & M64, stream=self.stream,
@@ -393,6 +524,8 @@ class Model:
     def apply(self, op):
         kind = op[0]
         self.kinds[kind] += 1
+        if self._prev_op and self._prev_op[0] == "evidence" and self._last_change is not None and kind in STATE_CHANGING:
+            self.facts.add("an evidence call between two state-changing operations")
         out = getattr(self, "_" + kind)(*op[1:])
         if kind in STATE_CHANGING:
             self._last_change = op
@@ -420,8 +553,8 @@ class Model:
         logp = [o.logp(p) for o, p in zip(self.orcs, pos)]
         return (pos[0], logp[0]) if self.K == 1 else (np.stack(pos), np.stack(logp))
 
-    def _steps(self, n_saved, interval, save_chain, want_accepted, to_device=False):
-        self._note_run(n_saved, interval, save_chain, to_device)
+    def _steps(self, n_saved, interval, save_chain, want_accepted, to_device=False, kind="run"):
+        self._note_run(n_saved, interval, save_chain, to_device, kind)
         mode = po.MODE_SEQUENTIAL if self.mover == DE else po.MODE_COUNTER
         r = [o.run(n_saved, interval=interval, save_chain=save_chain, mode=mode) for o in self.orcs]
         total = n_saved * interval
@@ -437,23 +570,31 @@ class Model:
         return self._steps(n_saved, interval, save_chain, want_accepted)
 
     def _run_device(self, n_saved, interval, want_accepted):
-        return self._steps(n_saved, interval, True, want_accepted, to_device=True)
+        return self._steps(n_saved, interval, True, want_accepted, to_device=True, kind="run_device")
 
-    def _run_async(self, n_saved, interval, want_accepted):
-        self.pending = self._steps(n_saved, interval, True, want_accepted)
-        self._in_flight_refusals = 0
+    def _run_async(self, n_saved, interval, want_accepted, to_device=False):
+        self.pending = self._steps(n_saved, interval, True, want_accepted, to_device=to_device, kind="run_device_async" if to_device else "run_async")
+        self._in_flight_refusals, self._in_flight_ladder_calls, self._in_flight_device = 0, 0, to_device
+
+    def _run_device_async(self, n_saved, interval, want_accepted):
+        self._run_async(n_saved, interval, want_accepted, to_device=True)
 
     def _refused_in_flight(self, what):
         self._in_flight_refusals += 1
+        self._in_flight_ladder_calls += what in LADDER_CALLS
         return E_STATE
 
     def _wait_stored(self, k):
-        return self.pending[0][:k]
+        return self.pending[0][:k] if self.K == 1 else self.pending[0][:, :k]
 
     def _run_wait(self):
         out, self.pending = self.pending, None
         if self._in_flight_refusals:
             self.facts.add("an asynchronous run with a refused call inside it")
+            if self._in_flight_device:
+                self.facts.add("an asynchronous run into device memory with a refused call inside it")
+        if self._in_flight_ladder_calls:
+            self.facts.add("an asynchronous %s run with a refused ladder call inside it" % ("device" if self._in_flight_device else "host"))
         return out
 
     def _half_step_async(self, colour):
@@ -498,7 +639,8 @@ class Model:
 
     _calc_logp_device = _calc_logp
 
-    def _refused(self, what):
+    def _refused(self, what, *args):
+        self.facts.add("a refused " + what)
         return REFUSED_CODE[what]
 
     def _set_chain_params(self, chain, beta_index):
@@ -507,6 +649,7 @@ class Model:
         self.nacc_off[chain] = self.nacc_off[chain] + nacc.astype(np.int64)
         self.ties_off += old.near_ties
         self.redraws_off += old.redraws
+        self.betas[chain] = BETAS[beta_index]
         self.params[chain] = chain_params(self.cfg, beta_index)
         new = self._oracle(chain)
         new.set_state(pos, logp)  # (the stored log-posteriors are not recomputed, by the library either)
@@ -521,10 +664,73 @@ class Model:
             pos[k][...] = P[k]
             logp[k][...] = L[k]
         self.in_band += len(out["in_band"])
+        self.swaps_accepted += int(out["accepted"].sum())
+        self.swaps_refused += int(out["proposed"].sum()) - int(out["accepted"].sum())
+        if self._prev_op and self._prev_op[0] == "run_tempered" and (self._prev_op[1] * self._prev_op[2]) & 1:
+            self.facts.add("exchange_chains directly behind a tempered run that ended at an odd step")
         return dict(proposed=out["proposed"], accepted=out["accepted"], near_ties=out["near_ties"])
 
+    def _run_tempered(self, n_saved, interval, every, first_round, delivery):
+        """Ladder.run_exchanging's rule on the model's own oracles: steps with interval 1 in pieces that end at the multiples of
+        `every` counted from the start of the run, a round behind each such piece (none behind a shorter tail), every interval-th
+        step kept"""
+        total, K = n_saved * interval, self.K
+        self._note_tempered(n_saved, interval, every, first_round, delivery)
+        chains, accs = [[] for _ in range(K)], [[] for _ in range(K)]
+        swaps = dict(proposed=np.zeros(K - 1, np.uint64), accepted=np.zeros(K - 1, np.uint64), near_ties=np.zeros(K - 1, np.uint64))
+        done, rnd, start, prev = 0, first_round, self.step, self._prev_op
+        self._prev_op = None  # (the rounds inside the run are not "directly behind" the operation in front of it)
+        while done < total:
+            piece = min(every - done % every, total - done)
+            for k, o in enumerate(self.orcs):
+                c, a = o.run(piece, interval=1, save_chain=True, mode=po.MODE_COUNTER)
+                chains[k].append(c)
+                accs[k].append(a)
+                self.accepted += int(a.sum())
+            done += piece
+            if done % every == 0:
+                if self.cfg["full_step"]:
+                    self.facts.add("a round that finds the ensemble %s" % ("in the second buffer" if done & 1 else "at home"))
+                self.facts.add("a round at record-buffer parity %d" % ((start + done) & 1))
+                if not rr.pairs_of(K, rnd):
+                    self.facts.add("a round without a pair inside a tempered run")
+                r = self._exchange_chains(rnd)
+                for key in swaps:
+                    swaps[key] += r[key]
+                rnd += 1
+        self._prev_op = prev
+        self.step += total
+        self.steps_since_reset += total
+        self.proposed += self.W * total * K
+        t = po.np_dtype(self.cfg["dtype"])
+        chain = np.stack([np.concatenate(c)[interval - 1::interval] if c else np.empty((0, self.W, self.D), t) for c in chains])
+        acc = np.stack([np.concatenate(a) if a else np.zeros(0, np.uint32) for a in accs])
+        self._next_round = rnd
+        return chain, acc, swaps, rnd
+
+    def _evidence(self, which, n, rows_seed, place):
+        """the restatements on the model's own log-posteriors of the draws, under the parameters set_chain_params installed last"""
+        from tests import bridge_restatement, evidence_restatement, mbar_restatement
+        K, W = self.K, self.W
+        x = evidence_draws(self.cfg, self.betas, n, rows_seed)
+        if self._prev_op and self._prev_op[0] == "set_chain_params":
+            self.facts.add("an evidence call directly behind set_chain_params")
+        self.facts.add("evidence %s from %s memory" % (which, place))
+        lp = lambda k, r: self.orcs[k].logp(x[r]).reshape(n, W)  # noqa: E731  (chain k's log-posteriors of the draws of rung r)
+        if which == "mbar":
+            out = mbar_restatement.mbar(mbar_restatement.from_logp(np.stack([np.stack([lp(k, r) for r in range(K)]) for k in range(K)])), n, W)
+        else:
+            own = np.stack([lp(k, k) for k in range(K)])
+            lower = np.stack([lp(k - 1, k) if k > 0 else np.zeros_like(own[0]) for k in range(K)])
+            upper = np.stack([lp(k + 1, k) if k + 1 < K else np.zeros_like(own[0]) for k in range(K)])
+            out = (evidence_restatement.evidence_ratios if which == "ratios" else bridge_restatement.evidence_bridge)(own, lower, upper)
+        self.evidence_nonfinite += int(np.asarray(out["nonfinite"]).sum())
+        if which != "ratios":
+            self.evidence_unconverged += int((np.atleast_1d(out["converged"]) != 1).sum())
+        return evidence_result(which, out)
+
     # -- coverage facts of a run, from the model's own numbers
-    def _note_run(self, n_saved, interval, save_chain, to_device):
+    def _note_run(self, n_saved, interval, save_chain, to_device, kind):
         total, cfg, f = n_saved * interval, self.cfg, self.facts
         if total == 0:
             f.add("a zero-step run")
@@ -536,6 +742,8 @@ class Model:
             f.add("reset_counters between two runs")
         if to_device and self._last_was_run(odd=True):
             f.add("run_device after an odd run")
+        if kind in ("run", "run_device") and self._prev_op and self._prev_op[0] == "run_tempered" and (self._prev_op[1] * self._prev_op[2]) & 1:
+            f.add("%s directly behind a tempered run that ended at an odd step" % kind)
         heads = replays(cfg, launch_chunks(cfg, n_saved, interval, save_chain, to_device))
         if cfg["full_step"]:
             for at, _ in heads:
@@ -546,6 +754,83 @@ class Model:
             f.add("a run made of whole replays only" if whole and not rest else
                   "a run made of a remainder only" if rest and not whole else "a run made of whole replays and remainders")
 
+    def _note_tempered(self, n_saved, interval, every, first_round, delivery):
+        total, cfg, f, prev, last = n_saved * interval, self.cfg, self.facts, self._prev_op, self._last_change
+        if total == 0:
+            f.add("a zero-step tempered run")
+            return
+        rounds = total // every
+        f.add("a tempered run that begins at %s steps-since-origin" % ("odd" if self.step & 1 else "even"))
+        f.add("a tempered run delivered %s" % delivery)
+        if rounds and every % interval:
+            f.add("a tempered run whose exchange_every is no multiple of its interval")
+        f.add("a tempered run without any round" if not rounds else "a tempered run that ends on an exchange point" if total % every == 0 else
+              "a tempered run with a tail shorter than exchange_every")
+        if rounds >= 2 and self.K == 16:
+            f.add("a tempered run with both an 8-slot and a 7-slot round")
+        if prev and prev[0] in ("seek", "set_chain_params", "reset_counters", "exchange_chains"):
+            f.add("run_tempered directly behind " + prev[0])
+        if self._last_was_run(odd=True):
+            f.add("run_tempered behind an odd plain run")
+        if last and last[0] == "run_tempered" and last[1] * last[2] >= last[3] and rounds and first_round == self._next_round:
+            f.add("two tempered runs with the round number carried over")
+        # the launches: the run's chunks (launch_chunks), each cut at the exchange points
+        G, at = cfg["graph_steps"], 0
+        for c in launch_chunks(cfg, n_saved, interval, True, delivery == "device", pinned=delivery == "pinned"):
+            end = at + c
+            while at < end:
+                piece = min(every - at % every, end - at)
+                at += piece
+                if G >= 1 and piece < G:
+                    f.add("a tempered piece shorter than a replay")
+                if G >= 1 and piece > G and piece % G:
+                    f.add("a tempered piece made of whole replays and a remainder")
+
+
+# ---- what the sequences of a path must show, and what an evidence operation is compared on ------------------------------------------
+
+# a chunk of a run is longer than a replay only where the stored steps leave through sub-chunks (half-step kernels, or a stored
+# step that is no multiple of 16 bytes): elsewhere no piece of a tempered run is
+def subchunk_delivery(cfg):
+    return not cfg["full_step"] or (cfg["W"] * cfg["D"] * (8 if cfg["dtype"] == po.F64 else 4)) % 16 != 0
+
+
+def facts_wanted_ladder(path):
+    """what a ladder path must show on top of the facts of every multi-chain path"""
+    cfg = PATHS[path]
+    want = {"a tempered run that begins at odd steps-since-origin", "a tempered run that begins at even steps-since-origin",
+            "a round at record-buffer parity 0", "a round at record-buffer parity 1",
+            "a tempered run whose exchange_every is no multiple of its interval", "a tempered run that ends on an exchange point",
+            "a tempered run with a tail shorter than exchange_every", "a tempered run without any round", "a zero-step tempered run",
+            "run_tempered directly behind seek", "run_tempered directly behind set_chain_params", "run_tempered directly behind reset_counters",
+            "run_tempered directly behind exchange_chains", "run_tempered behind an odd plain run",
+            "run directly behind a tempered run that ended at an odd step", "run_device directly behind a tempered run that ended at an odd step",
+            "exchange_chains directly behind a tempered run that ended at an odd step", "two tempered runs with the round number carried over",
+            "an evidence call between two state-changing operations", "an evidence call directly behind set_chain_params",
+            "an asynchronous host run with a refused ladder call inside it", "an asynchronous device run with a refused ladder call inside it"}
+    want |= {"a refused " + name for name in REFUSED["ladder"]}
+    want |= {"a tempered run delivered " + d for d in DELIVERIES}
+    want |= {"evidence %s from %s memory" % (w, p) for w in EVIDENCE_KINDS[:2 if cfg["K"] > 4 else 3] for p in EVIDENCE_PLACES}
+    if cfg["full_step"]:
+        want |= {"a round that finds the ensemble in the second buffer", "a round that finds the ensemble at home"}
+    if cfg["graph_steps"] >= 1:
+        want.add("a tempered piece shorter than a replay")
+        if subchunk_delivery(cfg):
+            want.add("a tempered piece made of whole replays and a remainder")
+    if cfg["K"] == 2:
+        want.add("a round without a pair inside a tempered run")
+    if cfg["K"] == 16:
+        want.add("a tempered run with both an 8-slot and a 7-slot round")
+    return want
+
+
+def evidence_result(which, out):
+    """what an evidence operation is compared on: every key the GPU tests of tests/test_evidence.py, test_evidence_bridge.py and
+    test_evidence_mbar.py compare, each as an array of at least one dimension"""
+    from tests import bridge_device, evidence_device, mbar_device
+    keys = {"ratios": evidence_device.KEYS, "bridge": bridge_device.KEYS, "mbar": mbar_device.KEYS}[which] + ("num_draws",)
+    return {key: np.atleast_1d(np.asarray(out[key])) for key in keys}
+
 
 def facts_wanted(path):
     """the coverage facts the six sequences of a path must show between them"""
@@ -553,6 +838,12 @@ def facts_wanted(path):
     fam = cfg["family"]
     want = {"a run that begins at even steps-since-origin", "a zero-step run", "set_state after an odd number of steps",
             "reset_counters between two runs", "a run that begins at odd steps-since-origin"}
+    if fam == "ladder":
+        # On top of the facts of every path that hold for a plain run and a tempered run alike.  Left out on purpose: what is about
+        # the launches of plain runs alone (replay heads, whole replays and remainders, run_device after an odd run, a seek or a
+        # reset in front of a plain run) -- the chains3 paths show them on handles of several chains, the ladders ask for the same
+        # hand-overs into a tempered run, and 40 operations of which a quarter are plain runs cannot show both sets.
+        return (want - {"reset_counters between two runs"}) | facts_wanted_ladder(path)
     if cfg["full_step"]:
         want |= {"a replay head with start parity %d, position parity %d" % (a, b) for a in (0, 1) for b in (0, 1)}
     if cfg["graph_steps"] >= 1:
@@ -563,6 +854,8 @@ def facts_wanted(path):
         want.add("run_device after an odd run")
     if fam == "stretch":
         want.add("an asynchronous run with a refused call inside it")
+        if "run_device_async" in WEIGHTS[cfg["weights"]]:
+            want.add("an asynchronous run into device memory with a refused call inside it")
         if cfg["full_step"]:
             want.add("a half-step pair after an odd full-step run")
     return want
@@ -570,8 +863,8 @@ def facts_wanted(path):
 
 def kinds_of(path):
     fam = PATHS[path]["family"]
-    kinds = set(WEIGHTS[fam]) | {"set_state"}
-    if fam == "stretch":
+    kinds = set(WEIGHTS[PATHS[path]["weights"]]) | {"set_state"}
+    if fam in ("stretch", "ladder"):
         kinds |= {"refused_in_flight", "wait_stored", "run_wait"}
     return kinds
 
@@ -630,8 +923,8 @@ def open_handle(path, handle_seed, stream, cb_lib=None):
     from mcmcpp_amd import capi
     cfg = PATHS[path]
     fam, kw, keep = cfg["family"], dict(cfg["create"]), None
-    if fam == "chains":
-        return capi.HipSampler(cfg["W"], cfg["D"], cfg["calc"], np.stack([chain_params(cfg, b) for b in CHAINS3_START]), seed=handle_seed,
+    if fam in ("chains", "ladder"):
+        return capi.HipSampler(cfg["W"], cfg["D"], cfg["calc"], np.stack([params_at(cfg, b) for b in start_betas(cfg)]), seed=handle_seed,
                                stream=stream, dtype=cfg["dtype"], num_chains=cfg["K"], **kw), None
     if fam == "batch":
         from tests.test_batch_calc import CTarget
@@ -657,6 +950,20 @@ class Runner:
             return e.code
         return 0
 
+    def _stored(self, k):
+        """the first k stored steps (of every chain) of the run in flight; from device memory on a stream of their own, as a
+        caller of run_device_async reads them"""
+        chain = self.flight[0]
+        lead = (slice(None),) if self.cfg["K"] > 1 else ()
+        if isinstance(chain, np.ndarray):
+            return chain[lead + (slice(0, k),)].copy()
+        import torch
+        mine = torch.cuda.Stream()
+        with torch.cuda.stream(mine):
+            first = chain[lead + (slice(0, k),)].clone()
+        mine.synchronize()
+        return first.cpu().numpy()
+
     def _device_rows(self, rows):
         import torch
         return torch.from_numpy(rows).to("cuda")
@@ -670,19 +977,34 @@ class Runner:
         if kind == "run_device":
             chain, acc = hip.run_device(op[1], interval=op[2], want_accepted=op[3])
             return chain.cpu().numpy(), acc
-        if kind == "run_async":
-            self.flight = hip.run_async(op[1], interval=op[2], want_accepted=op[3])
+        if kind in ASYNC_KINDS:
+            self.flight = (hip.run_async if kind == "run_async" else hip.run_device_async)(op[1], interval=op[2], want_accepted=op[3])
             return None
         if kind == "refused_in_flight":
+            cfg = self.cfg
             return self._code({"seek": lambda: hip.seek(3), "get_state": hip.get_state,
-                               "calc_logp": lambda: hip.calc_logp(rows_for(self.cfg, 2, 1))}[op[1]])
+                               "calc_logp": lambda: hip.calc_logp(rows_for(cfg, 2, 1)),
+                               "run_tempered": lambda: hip.run_tempered(2), "exchange_chains": lambda: hip.exchange_chains(0),
+                               "set_chain_params": lambda: hip.set_chain_params(0, chain_params(cfg, 1)),
+                               "evidence": lambda: hip.evidence_ratios(np.zeros((cfg["K"], 4, cfg["W"], cfg["D"]), po.np_dtype(cfg["dtype"])))}[op[1]])
         if kind == "wait_stored":
             hip.wait_stored(op[1])
-            return self.flight[0][:op[1]].copy()
+            return self._stored(op[1])
         if kind == "run_wait":
             hip.run_wait()
-            out, self.flight = self.flight, None
-            return out
+            (chain, acc), self.flight = self.flight, None
+            return (chain if isinstance(chain, np.ndarray) else chain.cpu().numpy()), acc
+        if kind == "run_tempered":
+            from mcmcpp_amd import capi
+            shape, t = (self.cfg["K"], op[1], self.cfg["W"], self.cfg["D"]), po.np_dtype(self.cfg["dtype"])
+            out = None if op[5] == "device" else np.empty(shape, t) if op[5] == "pageable" else capi.pinned_empty(shape, t)
+            chain, acc, swaps, nxt = hip.run_tempered(op[1], interval=op[2], exchange_every=op[3], first_round=op[4], out=out, device=op[5] == "device")
+            assert out is None or chain is out
+            return (chain.cpu().numpy() if out is None else np.array(chain)), acc, swaps, nxt
+        if kind == "evidence":
+            x = evidence_draws(self.cfg, self.model.betas, op[2], op[3])
+            fn = {"ratios": hip.evidence_ratios, "bridge": hip.evidence_bridge, "mbar": hip.evidence_mbar}[op[1]]
+            return evidence_result(op[1], fn(x if op[4] == "host" else self._device_rows(x)))
         if kind == "half_step_async":
             return hip.half_step_async(op[1])
         if kind == "synchronize":
@@ -704,7 +1026,10 @@ class Runner:
             return self._code({"run_negative": lambda: hip.run(-1, interval=1, save_chain=False, want_accepted=False),
                                "run_interval_0": lambda: hip.run(1, interval=0),
                                "half_step_out_of_order": lambda: hip.half_step_async(0 if self.model.half_done else 1),
-                               "seek_unsupported": lambda: hip.seek(4)}[op[1]])
+                               "seek_unsupported": lambda: hip.seek(4),
+                               "run_tempered_every_0": lambda: hip.run_tempered(2, exchange_every=0),
+                               "run_tempered_round_out_of_range": lambda: hip.run_tempered(op[2], interval=op[3], exchange_every=op[4], first_round=op[5]),
+                               "half_step_async": lambda: hip.half_step_async(0)}[op[1]])
         if kind == "set_chain_params":
             return hip.set_chain_params(op[1], chain_params(self.cfg, op[2]))
         if kind == "exchange_chains":
@@ -741,7 +1066,7 @@ def run_sequence(path, seed, upto=None, cb_lib=None, ops=None, handle=None, log=
             d = differs(hip.get_state(), model.state(), "get_state") or differs(hip.counters(), model.counters(), "counters")
             if d:
                 fail(i, d)
-        if op[0] in ("run", "run_device") and op[1] > 0:
+        if op[0] in ("run", "run_device", "run_tempered") and op[1] > 0:
             steps, launches = op[1] * op[2], hip.last_run_timing()[1]
             per_step = 4 if PATHS[path]["family"] == "batch" else 1 if PATHS[path]["full_step"] else 2
             if launches != per_step * steps:
